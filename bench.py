@@ -18,6 +18,8 @@ one `{"summary": {...}}` line, and LAST the result line the driver parses — th
   roofline      — the dominant kernel of the step (ahc_round_t, one launch per merge): algorithmic bytes per launch / average
                   launch period measured with HIP events around the merge phase, against 8 TB/s; traffic from the committed PMC pass
   cpu_baseline  — the same path on this box's host cores: the reference's linkage build (oracle/_ref) + the C restatements, 1 thread
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last one returned (a seeded sample of the mel chunks, the mel lengths,
+the assignments, the centroids) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 Legs:
   e2e_8h        — the timed region itself (stages, digest checks, start-up TFLOP/s)
   mel           — BASELINE configs[1]: 1024 x 15 s chunks per GPU, its own HBM roofline (HIP events per launch)
@@ -36,12 +38,6 @@ import sys
 import time
 
 import numpy as np
-
-# Hardware queues of the HIP runtime for this process (read when the runtime starts).  Only the optional round-3 leg (--in-flight: four independent chains
-# of dependent launches) wants more than the default four: with the streams the other legs created before it, two chains shared a queue (58 instead of
-# 87 audio-hours/s).  The serving path of round 4 (uniform batches, at most two streams) runs on the runtime's defaults: nothing is set for it.
-if "--in-flight" in sys.argv:
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -818,8 +814,30 @@ def vbx_sharded_leg(fa, ctx, torch, dist, rank, world, hours=64.0):
     return out
 
 
-def headline_leg(fa, ctx, torch, dist, rank, world, steps, warmup, hours=8.0):
-    """The timed region of the bench: K x (mel over the recording's chunks + fa_offline_cluster on its embeddings), inputs resident."""
+DUMP_MEL_CHUNKS = 32               # mel chunks of the last step written by --dump-outputs: 32 x 128 x 1501 fp32, about 25 MB
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dump_dir, torch, d_out, d_len, result):
+    """--dump-outputs: what the last timed step handed its caller, as float32 / float64 .npy files.  The mel tensor of a step is 1.5 GB, so a fixed
+    seeded sample of its chunks (mel_chunk_index.npy) is written; the lengths, assignments and centroids are written whole."""
+    n_chunks = d_out.shape[0]
+    idx = np.sort(np.random.default_rng(0).choice(n_chunks, size=min(DUMP_MEL_CHUNKS, n_chunks), replace=False))
+    arrays = {"mel": d_out[torch.from_numpy(idx).to(d_out.device)].cpu().numpy(),
+              "mel_chunk_index": idx.astype(np.float64),
+              "mel_lengths": d_len.cpu().numpy().astype(np.float64),
+              "assignments": np.asarray(result.assignments, np.float64),
+              "centroids": np.asarray(result.centroids, np.float64)}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs would write {total} bytes"
+    os.makedirs(dump_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dump_dir, f"{name}.npy"), a)
+
+
+def headline_leg(fa, ctx, torch, dist, rank, world, steps, warmup, hours=8.0, dump_dir=None):
+    """The timed region of the bench: K x (mel over the recording's chunks + fa_offline_cluster on its embeddings), inputs resident.
+    dump_dir: rank 0 writes what the last timed step computed there (dump_outputs)."""
     from e2e_inputs import sha256 as sha
     s, gold, aux = e2e_session_for(rank, hours)
     n_chunks15 = int(hours * 3600 / 15)
@@ -865,6 +883,8 @@ def headline_leg(fa, ctx, torch, dist, rank, world, steps, warmup, hours=8.0):
         tt = mine.clone()
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt)
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, torch, d_out, d_len, results[-1])
     # mel share of a step, timed on its own (not part of the timed region above)
     t0 = time.perf_counter()
     plan.execute(d_pcm, d_out, d_len, order=False)
@@ -1269,10 +1289,13 @@ def main():
     ap.add_argument("--only-mel", action="store_true", help="profiling helper: the configs[1] mel leg alone, printed as a reduced line")
     ap.add_argument("--ctc-matrices", type=int, default=10000)
     ap.add_argument("--launch-check", action="store_true", help="start the ranks, form the process group, all-reduce a one per rank, print what was seen; no device work")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))                          # `python bench.py --gpus N` starts its own N ranks
     import torch
@@ -1334,7 +1357,7 @@ def main():
         return
 
     # ---------------- the timed region: K steps of configs[4]
-    h = headline_leg(fa, ctx, torch, dist, rank, world, args.steps, args.warmup, args.hours)
+    h = headline_leg(fa, ctx, torch, dist, rank, world, args.steps, args.warmup, args.hours, args.dump_outputs)
     elapsed = h.pop("elapsed")
     value = world * args.hours * args.steps / elapsed
     roof = h.pop("roofline")

@@ -12,7 +12,6 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import fluidaudio_amd as fa  # noqa: E402
 from e2e_inputs import e2e_session  # noqa: E402
 

@@ -3,6 +3,7 @@ the HIP kernels compile) replayed on the CPU against the reference build (oracle
 mirrored copies, grid-quantised rows (overlapping tied pairs), regular lattices.  Row for row, bit for bit — this is what fixes the
 order among exactly tied distances (fastcluster_internal.hpp:778-935, :1625-1800) that the tie-free device path cannot know."""
 import ctypes as C
+import hashlib
 import os
 import subprocess
 
@@ -10,6 +11,19 @@ import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+GOLDEN = os.path.join(HERE, "golden", "ahc_reforder_golden.npz")
+
+
+@pytest.fixture(scope="module")
+def reference_rows():
+    """rows(key, x): the reference build's dendrogram of x, stored by tests/golden/make_reforder_golden.py (oracle/_ref on every input of
+    this module); the input must be the one the rows were stored for."""
+    g = np.load(GOLDEN)
+
+    def rows(key, x):
+        assert str(g[key + "_sha256"]) == hashlib.sha256(np.ascontiguousarray(x, np.float64).tobytes()).hexdigest(), f"{key}: not the stored input"
+        return g[key]
+    return rows
 
 
 @pytest.fixture(scope="module")
@@ -41,24 +55,8 @@ def tie_inputs():
     yield "all equal", np.ones((40, 4))
 
 
-@pytest.mark.parametrize("name,x", list(tie_inputs()), ids=[n for n, _ in tie_inputs()])
-def test_selection_logic_reproduces_the_reference_row_for_row(oracle_mod, emul, name, x):
-    if not oracle_mod.ref_available():
-        pytest.skip("oracle/_ref not built")
-    x = np.ascontiguousarray(x, np.float64)
-    st, zr = oracle_mod.linkage_ref(x)
-    assert st == 0
-    z = emul(x)
-    bad = np.nonzero((z != zr).any(axis=1))[0]
-    assert bad.size == 0, f"{name}: first differing row {bad[0]} of {len(z)}: emulation {z[bad[0]]} reference {zr[bad[0]]}"
-
-
-@pytest.mark.parametrize("seed", range(24))
-def test_selection_logic_on_random_tie_heavy_inputs(oracle_mod, emul, seed):
-    """Randomised: size, dimension, grid step, duplication rate and a mirror are drawn per seed — low-entropy inputs whose distance
-    multisets are full of exact ties (often overlapping ones).  Row for row against the reference build."""
-    if not oracle_mod.ref_available():
-        pytest.skip("oracle/_ref not built")
+def tie_heavy_input(seed):
+    """Randomised: size, dimension, grid step, duplication rate and a mirror are drawn per seed."""
     rng = np.random.default_rng(1000 + seed)
     n, d = int(rng.integers(3, 260)), int(rng.integers(1, 7))
     step = float(rng.choice([1.0, 0.5, 0.25, 1 / 3, 1 / 64]))
@@ -68,9 +66,61 @@ def test_selection_logic_on_random_tie_heavy_inputs(oracle_mod, emul, seed):
         x[rng.integers(0, n, k)] = x[rng.integers(0, n, k)]
     if rng.random() < 0.3:                                   # a mirrored copy far away: every intra-copy distance occurs twice
         x = np.vstack([x, -x + 50.0])
-    x = np.ascontiguousarray(x[rng.permutation(len(x))], np.float64)
-    st, zr = oracle_mod.linkage_ref(x)
-    assert st == 0
+    return np.ascontiguousarray(x[rng.permutation(len(x))], np.float64), d, step
+
+
+def filtered_input(seed):
+    """Tie-heavy and tie-free inputs by turns."""
+    rng = np.random.default_rng(2000 + seed)
+    n, d = int(rng.integers(3, 300)), int(rng.integers(1, 40))
+    x = rng.standard_normal((n, d))
+    if seed % 2 == 0:
+        step = float(rng.choice([1.0, 0.5, 0.25, 1 / 64]))
+        x = np.round(x * 2 / step) * step
+        k = max(1, n // 3)
+        x[rng.integers(0, n, k)] = x[rng.integers(0, n, k)]
+    else:
+        x /= np.linalg.norm(x, axis=1, keepdims=True)       # the pipeline's input: unit rows
+    return np.ascontiguousarray(x, np.float64)
+
+
+TIE_SEEDS, FILTERED_SEEDS = range(24), range(16)
+
+
+def stored_inputs():
+    """Every input of this module with its key in the golden file."""
+    for i, (_, x) in enumerate(tie_inputs()):
+        yield f"tie_{i}", np.ascontiguousarray(x, np.float64)
+    for seed in TIE_SEEDS:
+        yield f"heavy_{seed}", tie_heavy_input(seed)[0]
+    for seed in FILTERED_SEEDS:
+        yield f"filtered_{seed}", filtered_input(seed)
+
+
+def test_stored_rows_are_the_reference_builds(oracle_mod, reference_rows):
+    if not oracle_mod.ref_available():
+        pytest.skip("oracle/_ref not built")
+    for key, x in stored_inputs():
+        st, zr = oracle_mod.linkage_ref(x)
+        assert st == 0
+        np.testing.assert_array_equal(reference_rows(key, x), zr, err_msg=key)
+
+
+@pytest.mark.parametrize("i,name,x", [(i, n, x) for i, (n, x) in enumerate(tie_inputs())], ids=[n for n, _ in tie_inputs()])
+def test_selection_logic_reproduces_the_reference_row_for_row(reference_rows, emul, i, name, x):
+    x = np.ascontiguousarray(x, np.float64)
+    zr = reference_rows(f"tie_{i}", x)
+    z = emul(x)
+    bad = np.nonzero((z != zr).any(axis=1))[0]
+    assert bad.size == 0, f"{name}: first differing row {bad[0]} of {len(z)}: emulation {z[bad[0]]} reference {zr[bad[0]]}"
+
+
+@pytest.mark.parametrize("seed", TIE_SEEDS)
+def test_selection_logic_on_random_tie_heavy_inputs(reference_rows, emul, seed):
+    """Randomised (tie_heavy_input): low-entropy inputs whose distance multisets are full of exact ties (often overlapping ones).  Row for
+    row against the reference build."""
+    x, d, step = tie_heavy_input(seed)
+    zr = reference_rows(f"heavy_{seed}", x)
     z = emul(x)
     bad = np.nonzero((z != zr).any(axis=1))[0]
     assert bad.size == 0, f"seed {seed} (n {len(x)}, d {d}, step {step}): first differing row {bad[0]}: emulation {z[bad[0]]} reference {zr[bad[0]]}"
@@ -113,38 +163,23 @@ def test_block_heap_equals_the_restated_heap_after_every_operation(rom, n, level
 
 
 @pytest.mark.parametrize("noise", [0.0, 0.45])
-@pytest.mark.parametrize("name,x", list(tie_inputs()), ids=[n for n, _ in tie_inputs()])
-def test_matrix_filtered_run_reproduces_the_reference_row_for_row(oracle_mod, rom, name, x, noise):
-    if not oracle_mod.ref_available():
-        pytest.skip("oracle/_ref not built")
+@pytest.mark.parametrize("i,name,x", [(i, n, x) for i, (n, x) in enumerate(tie_inputs())], ids=[n for n, _ in tie_inputs()])
+def test_matrix_filtered_run_reproduces_the_reference_row_for_row(reference_rows, rom, i, name, x, noise):
     x = np.ascontiguousarray(x, np.float64)
-    st, zr = oracle_mod.linkage_ref(x)
-    assert st == 0
+    zr = reference_rows(f"tie_{i}", x)
     z, stats = rom(x, noise, 7)
     bad = np.nonzero((z != zr).any(axis=1))[0]
     assert bad.size == 0, f"{name}: first differing row {bad[0]} of {len(z)}: emulation {z[bad[0]]} reference {zr[bad[0]]} (stats {stats})"
     assert stats[1] >= stats[0] >= len(x) - 2
 
 
-@pytest.mark.parametrize("seed", range(16))
-def test_matrix_filtered_run_on_random_inputs(oracle_mod, rom, seed):
-    """Tie-heavy and tie-free inputs by turns, the start-up matrix perturbed by up to 0.45 eps per entry: the candidates of a scan then really are
-    several, and the exact evaluation has to pick the reference's."""
-    if not oracle_mod.ref_available():
-        pytest.skip("oracle/_ref not built")
-    rng = np.random.default_rng(2000 + seed)
-    n, d = int(rng.integers(3, 300)), int(rng.integers(1, 40))
-    x = rng.standard_normal((n, d))
-    if seed % 2 == 0:
-        step = float(rng.choice([1.0, 0.5, 0.25, 1 / 64]))
-        x = np.round(x * 2 / step) * step
-        k = max(1, n // 3)
-        x[rng.integers(0, n, k)] = x[rng.integers(0, n, k)]
-    else:
-        x /= np.linalg.norm(x, axis=1, keepdims=True)       # the pipeline's input: unit rows
-    x = np.ascontiguousarray(x, np.float64)
-    st, zr = oracle_mod.linkage_ref(x)
-    assert st == 0
+@pytest.mark.parametrize("seed", FILTERED_SEEDS)
+def test_matrix_filtered_run_on_random_inputs(reference_rows, rom, seed):
+    """Tie-heavy and tie-free inputs by turns (filtered_input), the start-up matrix perturbed by up to 0.45 eps per entry: the candidates of a
+    scan then really are several, and the exact evaluation has to pick the reference's."""
+    x = filtered_input(seed)
+    n, d = x.shape
+    zr = reference_rows(f"filtered_{seed}", x)
     z, stats = rom(x, 0.45, seed)
     bad = np.nonzero((z != zr).any(axis=1))[0]
     assert bad.size == 0, f"seed {seed} (n {n}, d {d}): first differing row {bad[0]}: emulation {z[bad[0]]} reference {zr[bad[0]]} (stats {stats})"

@@ -157,12 +157,10 @@ def test_demo_models_as_arpa_text_and_windows_line_endings(fa, oracle_mod):
 
 
 def test_reference_arpa_fixture_parses_identically(fa, oracle_mod):
-    """Tests/.../CTC/sample_medical.arpa, the reference's ARPA fixture (read where it lies; not copied): 15 unigrams, 12 bigrams in 5
-    contexts; library and restatement give the same float for every (word, context) pair."""
+    """Tests/.../CTC/sample_medical.arpa, the reference's ARPA fixture (test data, kept as tests/golden/sample_medical.arpa): 15 unigrams,
+    12 bigrams in 5 contexts; library and restatement give the same float for every (word, context) pair."""
     import os
-    path = "/root/reference/Tests/FluidAudioTests/ASR/Parakeet/SlidingWindow/CTC/sample_medical.arpa"
-    if not os.path.exists(path):
-        pytest.skip("reference tree not present")
+    path = os.path.join(os.path.dirname(__file__), "golden", "sample_medical.arpa")
     text = open(path, encoding="utf-8").read()
     ref, lib = oracle_mod.ARPALanguageModel.parse(text), fa.ARPALanguageModel.load(path)
     assert len(ref.unigrams) == lib.unigram_count == 15

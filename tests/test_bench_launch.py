@@ -71,11 +71,19 @@ def test_two_ranks_on_the_one_gpu_print_a_whole_line():
     assert full["vbx_sharded"] == legs["vbx_sharded"] and full["n_gpus"] == 2
 
 
+def test_steps_below_one_are_refused():
+    r, line = _run(["--steps", "0"], timeout=120)
+    assert r.returncode == 2 and line is None and "--steps" in r.stderr
+
+
 @pytest.mark.gpu
-def test_single_gpu_run_prints_a_line_the_driver_can_parse():
-    """The driver's own command form, shortened: last line strict JSON < 4 KB with roofline + cpu_baseline, legs on their own lines."""
+def test_single_gpu_run_prints_a_line_the_driver_can_parse(tmp_path):
+    """The driver's own command form, shortened: last line strict JSON < 4 KB with roofline + cpu_baseline, legs on their own lines;
+    --dump-outputs writes what the last timed step returned."""
+    dump = tmp_path / "dump"
     r, line = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--hours", "1", "--mel-steps", "5", "--mel-warmup", "2", "--clock-warm-s", "0",
-                    "--chunks", "64", "--ctc-matrices", "64", "--skip-ahc", "--skip-e2e", "--skip-beam", "--skip-resample"], timeout=900)
+                    "--chunks", "64", "--ctc-matrices", "64", "--skip-ahc", "--skip-e2e", "--skip-beam", "--skip-resample", "--dump-outputs", str(dump)],
+                   timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     last = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     assert len(last) < 4096
@@ -87,6 +95,14 @@ def test_single_gpu_run_prints_a_line_the_driver_can_parse():
     assert {"e2e_8h", "cpu_baseline", "mel", "ctc"} <= set(legs)
     summary = [l for l in r.stdout.splitlines() if l.startswith('{"summary"')]
     assert len(summary) == 1 and _strict(summary[0])["summary"]["errors"] == []
+    import numpy as np
+    out = {f[:-4]: np.load(dump / f) for f in os.listdir(dump)}
+    assert set(out) == {"mel", "mel_chunk_index", "mel_lengths", "assignments", "centroids"}
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values()) and sum(a.nbytes for a in out.values()) <= 64 << 20
+    assert out["mel"].shape[:2] == (32, 128) and out["mel_chunk_index"].shape == (32,) and np.isfinite(out["mel"]).all()
+    assert (out["mel_lengths"] == 1501).all() and out["mel_lengths"].shape == (240,)              # 1 h = 240 chunks of 15 s
+    assert out["assignments"].shape == (5400,) and out["centroids"].shape == (legs["e2e_8h"]["clusters_found"], 256)
+    assert set(out["assignments"].tolist()) <= set(range(legs["e2e_8h"]["clusters_found"]))
 
 
 @pytest.mark.gpu

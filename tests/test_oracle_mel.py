@@ -9,9 +9,7 @@ import os
 
 import numpy as np
 import pytest
-from conftest import REFERENCE, synth_audio
-
-LUX = os.path.join(REFERENCE, "Tests/FluidAudioTests/TTS/LuxTts/Resources")
+from conftest import synth_audio
 
 
 def test_frame_counts(oracle_mod):
@@ -106,11 +104,11 @@ def test_fft_restatement_against_float64(oracle_mod):
         assert np.abs(re + 1j * im - ref).max() < 2e-5 * np.abs(ref).max()
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(LUX, "prompt_mel_f32le.bin")), reason="reference fixtures not present")
 def test_luxtts_golden_fixture(oracle_mod):
-    """The only golden mel in the reference: 103 936 samples -> 406 x 100 log-mel, gate max-abs < 1e-3."""
-    audio = np.fromfile(os.path.join(LUX, "prompt_24k_f32le.bin"), np.float32)
-    gold = np.fromfile(os.path.join(LUX, "prompt_mel_f32le.bin"), np.float32).reshape(-1, 100)
+    """The only golden mel in the reference: 103 936 samples -> 406 x 100 log-mel, gate max-abs < 1e-3
+    (tests/golden/luxtts_prompt.npz holds the reference's prompt_24k_f32le.bin / prompt_mel_f32le.bin as they are)."""
+    g = np.load(os.path.join(os.path.dirname(__file__), "golden", "luxtts_prompt.npz"))
+    audio, gold = g["audio"], g["mel_scaled"]
     assert audio.size == 103936 and gold.shape == (406, 100)
     n_fft, hop, n_mels, sr = 1024, 256, 100, 24000
     win = (0.5 * (1 - np.cos(2 * np.float32(np.pi) * np.arange(n_fft, dtype=np.float32) / np.float32(n_fft)))).astype(np.float32)
