@@ -126,7 +126,7 @@ fa_status ahc_batch_once(fa_ctx *ctx, int count, const double *const *d_data, co
     int2 *d_map = reinterpret_cast<int2 *>(base + o_map);
     FA_HIP_TRY(ctx, hipMemcpyAsync(const_cast<Ws *>(d_table), table.data(), sizeof(Ws) * count, hipMemcpyHostToDevice, ctx->stream));
     const size_t lds = sizeof(double) * d;
-    bool big = fa::sw_on(fa::Sw::AHC_ROUND_BIG);
+    bool big = false;
     for (const Prob &p : probs) if (p.active && p.Np / kBlk > 4 * 64) big = true;
     if (lds > 48 * 1024) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ahc_round_t<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));

@@ -197,9 +197,8 @@ __global__ void ro_finish(RoWs w) {
 }  // namespace
 
 namespace fa_ahc {
-// the three kernels the matrix-filtered run (ahc_rom.hip) shares with this one, on its own view of the same arrays
+// the two kernels the matrix-filtered run (ahc_rom.hip) shares with this one, on its own view of the same arrays
 void ro_launch_init(hipStream_t st, const RoWs &w, size_t threads) { hipLaunchKernelGGL(ro_init, dim3(static_cast<unsigned>((threads + 255) / 256)), dim3(256), 0, st, w); }
-void ro_launch_lower_minima_direct(hipStream_t st, const RoWs &w) { hipLaunchKernelGGL(ro_lower_minima_direct, dim3(static_cast<unsigned>((w.N + kRoT - 1) / kRoT)), dim3(256), 0, st, w); }
 void ro_launch_finish(hipStream_t st, const RoWs &w) { hipLaunchKernelGGL(ro_finish, dim3(static_cast<unsigned>((w.N + 255) / 256)), dim3(256), 0, st, w); }
 
 // The whole problem in the reference's selection order (see the kernels above).  d_data / d_Z: device pointers.

@@ -572,7 +572,7 @@ fa_status rom_run_device(fa_ctx *ctx, const double *d_data, size_t N, size_t d, 
     w.pair_a = reinterpret_cast<double *>(base + L.pa); w.pair_b = reinterpret_cast<double *>(base + L.pb); w.height_sq = reinterpret_cast<double *>(base + L.hs);
     w.C = reinterpret_cast<double *>(base + L.c); w.XT = reinterpret_cast<double *>(base + L.xt); w.M = reinterpret_cast<double *>(base + L.m);
     w.N = static_cast<int32_t>(N); w.Np = static_cast<int32_t>(Np); w.d = static_cast<int32_t>(d); w.nblk = static_cast<int32_t>(nblk);
-    RoWs rw{};   // the kernels shared with the matrix-free run (ro_init, ro_lower_minima_direct, ro_finish) see their own view of the same arrays
+    RoWs rw{};   // the kernels shared with the matrix-free run (ro_init, ro_finish) see their own view of the same arrays
     rw.C = w.C; rw.XT = w.XT; rw.sizes = w.sizes; rw.key = reinterpret_cast<double *>(base + L.key); rw.pair_a = w.pair_a; rw.pair_b = w.pair_b; rw.height_sq = w.height_sq;
     rw.Z = reinterpret_cast<double *>(base + L.z); rw.node = w.node; rw.slot_of = w.slot_of; rw.nghbr = w.nghbr; rw.flags = w.flags;
     rw.N = w.N; rw.Np = w.Np; rw.d = w.d; rw.nblk = w.nblk;
@@ -595,10 +595,8 @@ fa_status rom_run_device(fa_ctx *ctx, const double *d_data, size_t N, size_t d, 
     }
     ro_launch_init(st, rw, std::max(Np, 2 * N));
     if (!matrix_ready) startup_transpose(st, d_data, w.XT, w.N, w.Np, w.d);
-    const bool direct_start = fa::sw_on(fa::Sw::AHC_ROM_DIRECT_START);   // the start-up of the matrix-free run (all N^2 / 2 exact sums) for A/B
-    if (direct_start) ro_launch_lower_minima_direct(st, rw);
     if (!matrix_ready) FA_TRY(startup_gram(ctx, st, gw, d_norms));
-    if (!direct_start) hipLaunchKernelGGL(rom_lower_minima, dim3(static_cast<unsigned>(N - 1)), dim3(kBlk), 0, st, w, gw.state, rw.key);
+    hipLaunchKernelGGL(rom_lower_minima, dim3(static_cast<unsigned>(N - 1)), dim3(kBlk), 0, st, w, gw.state, rw.key);
     FA_HIP_TRY(ctx, hipGetLastError());
     // ---- the heap over points 1 .. N-1, the list, the first pair: host (the selection logic is the same header on both sides)
     std::vector<double> key(2 * N, 0.0), pa(N, 0.0), pb(N, 0.0), hs(N, 0.0);

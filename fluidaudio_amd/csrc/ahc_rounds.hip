@@ -211,8 +211,7 @@ fa_status prob_run_rounds(fa_ctx *ctx, Prob &p) {
     const size_t N = p.N, d = p.d, lds = sizeof(double) * d;
     const bool no_single_block = fa::sw_on(fa::Sw::AHC_NO_SINGLE_BLOCK);
     const Ws w = p.w;
-    const bool env_big = fa::sw_on(fa::Sw::AHC_ROUND_BIG);
-    const bool big = w.nblk > (4 / p.cpt) * 64 || env_big;   // more than 65 536 points (four block records per lane at one slot per thread): the kernel with the many-record reduction
+    const bool big = w.nblk > (4 / p.cpt) * 64;   // more than 65 536 points (four block records per lane at one slot per thread): the kernel with the many-record reduction
     // records a lane of the first reduction owns: the one-slot-per-thread kernel exists per count (ahc_round_body: a request for a record the lane does not own
     // is not free); the forms with 2 / 4 slots per thread hold all 2 / 1 of theirs
     const int kc = p.cpt == 1 && !big ? std::max(1, (w.nblk + 63) / 64) : 4 / p.cpt;
@@ -294,11 +293,7 @@ fa_status fa::ahc_run_device(fa_ctx *ctx, const double *d_data, size_t N, size_t
         if (stats) *stats = fa_ahc_stats{};
         return ro_run_device(ctx, d_data, N, d, d_Z, stats, z_on_host);
     }
-    const bool may_fall_back = !fa::sw_on(fa::Sw::AHC_NO_MATRIX_FREE);
-    if (prob_check_shape(ctx, N, d) != FA_SUCCESS) {   // too many points for the block records (a too large d fails in ro_run_device as well)
-        if (may_fall_back) return without_matrix();
-        return FA_ALLOCATION_FAILURE;
-    }
+    if (prob_check_shape(ctx, N, d) != FA_SUCCESS) return without_matrix();   // too many points for the block records (a too large d fails in ro_run_device as well)
     Prob p;
     p.z_on_host = z_on_host;
     // slots per thread of the round: 1 for a chain of its own (the fewest dependent instructions per round: 5.09 us at 43 200 points against 5.60 / 6.69 with
@@ -313,7 +308,7 @@ fa_status fa::ahc_run_device(fa_ctx *ctx, const double *d_data, size_t N, size_t
     p.L = make_layout(N, p.Np, d, p.Np / cols);
     {
         const fa_status ws = fa::ws_acquire(ctx, p.L.total);
-        if (ws == FA_ALLOCATION_FAILURE && may_fall_back) return without_matrix();
+        if (ws == FA_ALLOCATION_FAILURE) return without_matrix();
         FA_TRY(ws);
     }
     hipEvent_t ev[3];

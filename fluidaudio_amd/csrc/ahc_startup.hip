@@ -575,7 +575,7 @@ void startup_filter(hipStream_t st, const Ws &w, const Layout &L, char *base, in
     if (dev_mode == FA_AHC_MODE_AUTO) {  // Gram form on the fp64 matrix cores (approximate entries, see ahc_gram_mfma)
         double *d_norms = reinterpret_cast<double *>(base + L.norms);
         hipLaunchKernelGGL(ahc_sqnorms, dim3((w.Np + 63) / 64), dim3(256), 0, st, w, d_norms);
-        if (w.d % G2K == 0 && !fa::sw_on(fa::Sw::AHC_GRAM_V1) && gram2_attr<true>() == hipSuccess) {
+        if (w.d % G2K == 0 && gram2_attr<true>() == hipSuccess) {
             double2 *part_vs = reinterpret_cast<double2 *>(base + L.part_vs);
             int *part_ix = reinterpret_cast<int *>(base + L.part_ix);
             hipLaunchKernelGGL(ahc_gram_mfma2_t<true>, FA_GRAM_GRID(w.Np / GT), dim3(256), kGram2LdsBytes, st, w, d_norms, part_vs, part_ix);

@@ -382,7 +382,6 @@ fa_status ro_run_device(fa_ctx *ctx, const double *d_data, size_t N, size_t d, d
                         bool matrix_ready = false);
 size_t rom_total_bytes(size_t N, size_t Np, size_t d);   // workspace of the matrix-filtered reference-order run
 void ro_launch_init(hipStream_t st, const RoWs &w, size_t threads);
-void ro_launch_lower_minima_direct(hipStream_t st, const RoWs &w);
 void ro_launch_finish(hipStream_t st, const RoWs &w);
 // ahc_batch.hip
 bool uniform_eligible(int count, const size_t *n, int mode);

@@ -148,7 +148,6 @@ struct BeamArgs {
     int64_t row_stride, matrix_stride, arena_stride;
     int32_t frames, vocab, blank, beam_width, top_k, use_lm, first;
     float lm_weight, word_bonus;
-    unsigned long long *prof;   // FA_BEAM_PROF (diagnostics): cycles per step of workgroup 0, thread 0
     const TopEntry *top;   // the pre-pass' table (ctc_topk_kernel): [workgroup][frame][top_k + 1]
 };
 
@@ -397,7 +396,7 @@ __device__ __forceinline__ uint32_t slot_of(uint32_t a, uint32_t b) {
 constexpr int kOrdShift = 7;   // candidate order = beam << 7 | slot (slot 0 = the beam itself, 1 + r = its extension by top token r): beam-major, token-minor
 
 // MAXE: extension keys per thread = ceil(top tokens / 2)
-template <int MAXE, bool PROF>   // PROF: FA_BEAM_PROF cycle stamps (their 16 accumulators cost 32 registers)
+template <int MAXE>
 __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(const BeamArgs a) {
     __shared__ Shared s;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -416,8 +415,6 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(const BeamArgs a) {
     }
     __syncthreads();
 
-    unsigned long long t_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, t_prev = clock64();
-#define BEAM_STAMP(i) do { if (PROF) { const unsigned long long t_now = clock64(); t_acc[i] += t_now - t_prev; t_prev = t_now; } } while (0)
     int cur = 0;
     // the frame's top tokens, best first (sorted { frame[$0] > frame[$1] }, stable: ties by index; CtcDecoder.swift:141-144): computed for all
     // frames by ctc_topk_kernel; thread r carries entry r of the frame, requested one frame ahead so that its HBM latency hides behind the frame
@@ -462,7 +459,6 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(const BeamArgs a) {
         s.map_pl_parent[tid] = -4;
         if (tid < kMaxBeam) s.cancel[tid] = 0ull;
         __syncthreads();
-        BEAM_STAMP(0);
         // ---- 2. extension keys (threads 2 i, 2 i + 1: beam i); maps over the live beams (thread i: beam i) ----
         unsigned kh[MAXE + 1], kl[MAXE + 1];                            // this thread's candidate keys: extensions 2 q + h of its beam, then (h = 0) the beam itself
         int r_last = -1;                                                 // the top token equal to the beam's last token (at most one)
@@ -505,7 +501,6 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(const BeamArgs a) {
             r_last = r_last > other ? r_last : other;
         }
         __syncthreads();
-        BEAM_STAMP(2);
         // ---- 3. the beam itself (slot 0): blank + repeated token, merged with the extension of the live beam one token shorter ----
         auto find_node = [&](const int node) {
             for (uint32_t q = slot_of(static_cast<uint32_t>(node), 0x51u);; q = (q + 1) & (kMapSlots - 1)) {
@@ -544,7 +539,6 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(const BeamArgs a) {
             if (total == total) { kh[MAXE] = desc_word(total); kl[MAXE] = ord; }
         }
         __syncthreads();
-        BEAM_STAMP(3);
         // ---- 4. prune: W best totals, earlier candidate first on ties ----
         if (bi < n) {
             const unsigned long long gone = s.cancel[bi] >> h;
@@ -555,17 +549,13 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(const BeamArgs a) {
                 kh[q] = c ? ~0u : kh[q]; kl[q] = c ? ~0u : kl[q];
             }
         }
-        BEAM_STAMP(8);
         {
             const KeyBound bound = wave_bound<MAXE + 1>(kh, kl, W);
-            BEAM_STAMP(9);
             const int cnt = wave_gather<MAXE + 1>(kh, kl, bound, s.wave_sel[wave]);
             if (lane == 0) s.wave_cnt[wave] = cnt;
         }
-        BEAM_STAMP(10);
         if (a.use_lm && tid < ntop) { s.top_mult[tid] = ti_mine.mult; s.top_add[tid] = ti_mine.add; s.top_len[tid] = ti_mine.len; }   // requested in step 1
         __syncthreads();
-        BEAM_STAMP(4);
         if (wave == 0) {
             constexpr int N2 = 2 * (kThreads / 64);
             unsigned h2[N2], l2[N2];
@@ -581,10 +571,8 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(const BeamArgs a) {
             if (lane == 0) s.sel_count = cnt;
         }
         __syncthreads();
-        BEAM_STAMP(5);
         sort_selected(s);
         const int nsel = min(s.sel_count, W);
-        BEAM_STAMP(6);
         // ---- 5. survivors -> new beams (rank = sorted position) ----
         if (tid < nsel) {
             const unsigned ord = static_cast<unsigned>(s.sel_key[tid] & 0xffffffffu);
@@ -623,10 +611,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(const BeamArgs a) {
         if (tid == 0) s.n_beams = nsel;
         cur ^= 1;
         __syncthreads();
-        BEAM_STAMP(7);
     }
-    if (PROF && a.prof && blockIdx.x == 0 && tid == 0 && a.first == 0) for (int i = 0; i < 16; ++i) a.prof[i] = t_acc[i];
-#undef BEAM_STAMP
     resolve_node(s.b[cur]);
     __syncthreads();
 
@@ -840,8 +825,6 @@ fa_status fa_ctc_beam_search_batch_dev(fa_ctx *ctx, const float *d_log_probs, in
     fa::DevBuf d_arena;
     FA_HIP_TRY(ctx, d_arena.alloc(ctx, static_cast<size_t>(per) * chunk));   // the context's buffer cache: a second call pays no hipMalloc
     a.arena = d_arena.as<unsigned long long>();
-    fa::DevBuf d_prof;
-    if (fa::sw(fa::Sw::BEAM_PROF)) { FA_HIP_TRY(ctx, d_prof.alloc(128)); FA_HIP_TRY(ctx, hipMemsetAsync(d_prof.p, 0, 128, ctx->stream)); a.prof = d_prof.as<unsigned long long>(); }
     // the pre-pass' table of one launch: K (token, log-prob) pairs + the blank's log-prob per frame
     fa::DevBuf d_top;
     const size_t rows_max = static_cast<size_t>(chunk) * std::max(frames, 1);
@@ -864,30 +847,19 @@ fa_status fa_ctc_beam_search_batch_dev(fa_ctx *ctx, const float *d_log_probs, in
             FA_HIP_TRY(ctx, hipGetLastError());
         }
         const int ntop = std::min(token_candidates, vocab - (blank_id >= 0 && blank_id < vocab ? 1 : 0));   // extension keys per thread = ceil(ntop / 2)
-        if (a.prof && ntop <= 16) hipLaunchKernelGGL((ctc_beam_kernel<8, true>), dim3(now), dim3(kThreads), 0, ctx->stream, a);
-        else if (a.prof && ntop <= 40) hipLaunchKernelGGL((ctc_beam_kernel<20, true>), dim3(now), dim3(kThreads), 0, ctx->stream, a);
-        else if (a.prof) hipLaunchKernelGGL((ctc_beam_kernel<32, true>), dim3(now), dim3(kThreads), 0, ctx->stream, a);
-        else if (ntop <= 16) hipLaunchKernelGGL((ctc_beam_kernel<8, false>), dim3(now), dim3(kThreads), 0, ctx->stream, a);
-        else if (ntop <= 40) hipLaunchKernelGGL((ctc_beam_kernel<20, false>), dim3(now), dim3(kThreads), 0, ctx->stream, a);
-        else hipLaunchKernelGGL((ctc_beam_kernel<32, false>), dim3(now), dim3(kThreads), 0, ctx->stream, a);
+        if (ntop <= 16) hipLaunchKernelGGL(ctc_beam_kernel<8>, dim3(now), dim3(kThreads), 0, ctx->stream, a);
+        else if (ntop <= 40) hipLaunchKernelGGL(ctc_beam_kernel<20>, dim3(now), dim3(kThreads), 0, ctx->stream, a);
+        else hipLaunchKernelGGL(ctc_beam_kernel<32>, dim3(now), dim3(kThreads), 0, ctx->stream, a);
         FA_HIP_TRY(ctx, hipGetLastError());
     }
     if (ctx->timing) FA_HIP_TRY(ctx, hipEventRecord(ctx->tim_ev[1], ctx->stream));
     FA_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // the arena and the tables go back to the context's cache on return
     if (ctx->timing) { float ms = -1.0f; FA_HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->tim_ev[0], ctx->tim_ev[1])); ctx->last_device_ms = ms; }
-    if (a.prof) {
-        unsigned long long h[16];
-        FA_HIP_TRY(ctx, hipMemcpy(h, d_prof.p, 128, hipMemcpyDeviceToHost));
-        const double f = frames > 0 ? frames : 1;
-        fprintf(stderr, "beam profile (cycles per frame, workgroup 0): top-token table + empty maps %.0f | maps + extension keys %.0f | slot 0 of the beams %.0f | "
-                        "selection level 1 %.0f (cancelled extensions %.0f, bound %.0f, gather %.0f, barrier %.0f) | level 2 %.0f | rank sort %.0f | new beams %.0f\n",
-                h[0] / f, h[2] / f, h[3] / f, (h[4] + h[8] + h[9] + h[10]) / f, h[8] / f, h[9] / f, h[10] / f, h[4] / f, h[5] / f, h[6] / f, h[7] / f);
-    }
     return FA_SUCCESS;
 }
 
 // What a call of these shapes launches (bench.py prints it next to its timing): out = { trie slots per utterance (arena_stride), utterances
-// per launch (the ~2 GiB arena cap), launches, extension keys per thread of the ctc_beam_kernel<MAXE, false> instance (8 / 20 / 32) }.
+// per launch (the ~2 GiB arena cap), launches, extension keys per thread of the ctc_beam_kernel<MAXE> instance (8 / 20 / 32) }.
 fa_status fa_ctc_beam_plan(int32_t batch, int32_t frames, int32_t vocab, int32_t beam_width, int32_t blank_id, int32_t token_candidates, int64_t out[4]) {
     if (!out || batch < 0 || frames < 0 || vocab < 1 || beam_width < 1 || beam_width > kMaxBeam || token_candidates < 0 || token_candidates > kMaxTop) return FA_INVALID_ARGUMENT;
     const int64_t stride = static_cast<int64_t>(pow2_at_least(static_cast<size_t>(2) * frames * beam_width + 2));

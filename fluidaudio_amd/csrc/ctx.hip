@@ -52,7 +52,7 @@ std::atomic<int32_t> g_fault[FA_FAULT_SITES];
 constexpr int kSwCount = static_cast<int>(fa::Sw::kCount);
 const char *const kSwName[kSwCount] = {
 #define FA_SW_NAME(id, name) name,
-    FA_SWITCHES(FA_SW_NAME, FA_SW_NAME)
+    FA_SWITCHES(FA_SW_NAME)
 #undef FA_SW_NAME
 };
 std::atomic<const char *> g_sw[kSwCount];
@@ -134,7 +134,7 @@ bool fault_hit(const int site) {
 }
 
 // ---- switches (fa_common.h): the process environment, read once
-const char *sw_lookup(const Sw s) {
+const char *sw(const Sw s) {
     std::call_once(g_sw_once, sw_read_environment);
     return g_sw[static_cast<int>(s)].load(std::memory_order_acquire);
 }
@@ -216,9 +216,6 @@ fa_status fa_debug_set_switch(const char *name, const char *value) {
     if (!debug_hooks()) return FA_RUNTIME_ERROR;
     for (int i = 0; i < kSwCount; ++i)
         if (strcmp(name, kSwName[i]) == 0) {
-#ifndef FA_AB_SWITCHES
-            if (fa::sw_is_ab(static_cast<fa::Sw>(i))) return FA_INVALID_ARGUMENT;   // compiled out of this build
-#endif
             const char *c = sw_copy(value);
             if (value && !c) return FA_ALLOCATION_FAILURE;
             g_sw[i].store(c, std::memory_order_release);

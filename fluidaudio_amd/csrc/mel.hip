@@ -14,7 +14,6 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <mutex>
 #include <vector>
 
 #include "fa_common.h"
@@ -58,8 +57,10 @@ struct MelArgs {
     int32_t floor_clamped;
     unsigned long long *queue;       // mel_kernel_v4: tile counter (never reset) ...
     unsigned long long queue_base;   // ... and the first value that belongs to this launch
-    unsigned long long *prof;  // FA_MEL_PROF env (diagnostics): per-phase cycle sums of one workgroup's wave 0
-    int32_t prio_lo, prio_hi, prio_pw, prio_rd;  // wave priorities: FFT / filterbank..store / power / sample reads (FA_MEL_PRIO=a,b,c,d)
+    // mel_kernel_v4's per-phase cycle stamps (an experiment build sets it): the library leaves it null.  The stamps stay because their
+    // branches shape the kernel's code generation: without them the mel leg of bench.py measured 0.8 % slower (636 against 631 us).
+    unsigned long long *prof;
+    int32_t prio_lo, prio_hi, prio_pw, prio_rd;  // wave priorities: FFT / filterbank..store / power / sample reads
 };
 
 // lane l <- lane (16 - l) & 15 inside every row of 16 lanes: row_mirror (l <- 15 - l), then row_ror:1 (l <- l - 1)
@@ -279,14 +280,6 @@ __global__ __launch_bounds__(kThreads, 2) void mel_kernel(const MelArgs a) {
         }
     };
 
-    unsigned long long t_seg[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long t_prev = clock64();
-#define MEL_STAMP(i) do { if (a.prof) { const unsigned long long t_now = clock64(); t_seg[i] += t_now - t_prev; t_prev = t_now; } } while (0)
-#ifdef FA_MEL_PROF_FINE   // diagnostics build: split the packed pass (slots 8..11; slot 3 keeps the remainder)
-#define MEL_STAMP_FINE(i) MEL_STAMP(i)
-#else
-#define MEL_STAMP_FINE(i) do { } while (0)
-#endif
     // All table / constant loads are complete from here on (vmcnt(0), expcnt/lgkmcnt untouched).  Without this explicit
     // instruction the wait-count pass keeps them "possibly pending" around the tile loop and guards the first LDS reads of
     // every pass with s_waitcnt vmcnt(<=3), which also drains the next tile's prefetch loads (vmcnt retires in order) and
@@ -319,7 +312,6 @@ __global__ __launch_bounds__(kThreads, 2) void mel_kernel(const MelArgs a) {
     // tile); in this order the only VMEM operations in flight are the loads issued a whole pass earlier.
     for (int64_t tl = first; tl < stop; ++tl) {
         __syncthreads();
-        MEL_STAMP(1);
         if (PK && cur.stage) {  // workgroup-uniform; group g computes the frames 2 g and 2 g + 1 of the tile in one pass
             using namespace fa::melpk;
             const int f = 2 * grp;
@@ -329,11 +321,9 @@ __global__ __launch_bounds__(kThreads, 2) void mel_kernel(const MelArgs a) {
 #pragma unroll
             for (int q = 0; q < 8; ++q) w4[q] = reinterpret_cast<const float4 *>(wtab)[q * kGroup + l];
             load_frame_pair<PK == 2>(samples + f * kPkHop + 2 * l, v);
-            MEL_STAMP_FINE(8);
             f2 *P2 = reinterpret_cast<f2 *>(__builtin_assume_aligned(regions + grp * kRegionFloatsPk, 8));
             set_prio(a.prio_lo);   // VALU-bound stretch: yield issue slots to the co-resident wave's short latency-bound bursts
             fft256<PK == 2>(l, v, w4, kp, P2);
-            MEL_STAMP_FINE(9);
             set_prio(a.prio_pw);
             // power bins of both frames, pair k at P2[k], over the transpose buffer (its last reads are already issued)
 #pragma unroll
@@ -347,7 +337,6 @@ __global__ __launch_bounds__(kThreads, 2) void mel_kernel(const MelArgs a) {
                 P2[kHalf - (l + 16 * j)] = phi;
             }
             if (l == 0) P2[128] = 4.0f * (v.re[8] * v.re[8] + v.im[8] * v.im[8]);  // k = 128: X = conj(Z[128])
-            MEL_STAMP_FINE(10);
             set_prio(a.prio_hi);   // LDS-latency-bound from here to the next pass: issue as soon as data arrives
             // sparse triangular filterbank (vDSP_mmul row, :270-283, zeros skipped): lane l owns the mels l + 16 i; weights are
             // fetched two global slots (2 p, 2 p + 1) per register pair, so a pair may straddle two mel groups
@@ -390,7 +379,6 @@ __global__ __launch_bounds__(kThreads, 2) void mel_kernel(const MelArgs a) {
             // :542-549: log(acc + floor) or log(max(acc, floor)) as log(max(acc + add, clamp)) with wave-uniform add / clamp.
             // The argument is >= floor > 0 and far from the denormal range, so the hardware log2 (1 ulp) times ln 2 replaces
             // logf's denormal pre-scaling and two-term ln 2 product: 2 instructions instead of 11.
-            MEL_STAMP_FINE(11);
             const float add_floor = a.floor_clamped ? 0.0f : a.log_floor, clamp_floor = a.floor_clamped ? a.log_floor : 0.0f;
 #pragma unroll
             for (int i = 0; i < kFastGroups; ++i) {
@@ -476,11 +464,8 @@ __global__ __launch_bounds__(kThreads, 2) void mel_kernel(const MelArgs a) {
                 }
             }
         }
-        MEL_STAMP(3);
         __syncthreads();
-        MEL_STAMP(4);
         stage_tile(nxt);   // `samples` has no reader left after the barrier
-        MEL_STAMP(0);
 
         const bool full_tile = cur.t0 + kTileFrames <= cur.T && cur.t0 + kTileFrames <= a.frame_stride;
         if (LAYOUT == FA_MEL_LAYOUT_MEL_MAJOR && FAST && full_tile && n_mels == kFastGroups * kGroup) {
@@ -516,17 +501,10 @@ __global__ __launch_bounds__(kThreads, 2) void mel_kernel(const MelArgs a) {
             }
         }
         // the barrier at the top of the next iteration orders these `outs` reads before the next tile's writes
-        MEL_STAMP(5);
         cur = nxt;
         // the loads of the tile after the next travel from HBM during the barrier wait and the whole next pass
         nxt = info_and_fetch(tl + 2);
-        MEL_STAMP(2);
     }
-    if (a.prof && blockIdx.x == gridDim.x / 2 && tid == 0) {
-        for (int i = 0; i < 12; ++i) if (i != 7) atomicAdd(&a.prof[i], t_seg[i]);
-        atomicAdd(&a.prof[7], static_cast<unsigned long long>(stop - first));
-    }
-#undef MEL_STAMP
 }
 
 #include "mel_v4.inc"
@@ -689,7 +667,6 @@ struct fa_mel_plan {
     bool edge_zero = false;  // the zero-extended window vanishes on positions [0, 32) and [480, 512) of the frame
     int v4_wps = 0;          // > 0: mel_kernel_v4 with that many workgroups per CU (packed kernel, 128 mels, hop 160)
     unsigned long long launches = 0;   // v4 launches made so far (spaces the tile-queue ranges)
-    bool v4_deep = true;               // tile queue two tiles ahead: the next tile's samples travel during the second pass (FA_MEL_V4_DEEP=0: one ahead)
     bool generic = false;    // mel_generic_kernel (any n_fft, magnitude, reflect padding, replicated tail)
     fa::melgen::GenArgs gargs{};
 };
@@ -839,7 +816,7 @@ fa_status fa_mel_plan_create(fa_ctx *ctx, const fa_mel_config *cfg, const int64_
         }
         std::vector<float> windowz(kNfft, 0.0f);
         for (int i = 0; i < cfg->win; ++i) windowz[off + i] = hann[i];
-        p->edge_zero = !fa::sw_on(fa::Sw::MEL_NO_EZ);
+        p->edge_zero = true;
         for (int i = 0; i < 32; ++i) if (windowz[i] != 0.0f || windowz[kNfft - 32 + i] != 0.0f) p->edge_zero = false;
         std::vector<float2> tw256(256), tw512(129);
         for (int k = 0; k < 256; ++k) { const double a = -2.0 * M_PI * k / 256.0; tw256[k] = make_float2((float)cos(a), (float)sin(a)); }
@@ -923,25 +900,11 @@ fa_status fa_mel_plan_create(fa_ctx *ctx, const fa_mel_config *cfg, const int64_
         a.log_floor = cfg->log_floor;
         a.floor_clamped = cfg->floor_mode == FA_MEL_FLOOR_CLAMPED;
         a.prio_lo = 0; a.prio_hi = 3; a.prio_pw = 1; a.prio_rd = 2;   // measured best of the sweep in DESIGN.md §3.1
-        if (const char *pe = fa::sw(fa::Sw::MEL_PRIO)) {   // diagnostics
-            int v4[4] = {0, 3, 1, 2};
-            const int got = sscanf(pe, "%d,%d,%d,%d", &v4[0], &v4[1], &v4[2], &v4[3]);
-            if (got == 2) { v4[2] = v4[0]; v4[3] = v4[1]; }
-            if (got >= 2) { a.prio_lo = v4[0] & 3; a.prio_hi = v4[1] & 3; a.prio_pw = v4[2] & 3; a.prio_rd = v4[3] & 3; }
-        }
-        p->pk = fast && cfg->hop == kPkHop && !fa::sw_on(fa::Sw::MEL_SCALAR);   // FA_MEL_SCALAR: diagnostics, one frame per lane
-        if (p->pk && cfg->n_mels == kFastGroups * kGroup) {   // FA_MEL_V4=0: the v3 kernel (diagnostics); FA_MEL_V4=4: four workgroups per CU
-            const char *ve = fa::sw(fa::Sw::MEL_V4);
-            p->v4_wps = ve ? atoi(ve) : 3;
-            if (p->v4_wps != 3) p->v4_wps = 0;
-            if (const char *de = fa::sw(fa::Sw::MEL_V4_DEEP)) p->v4_deep = atoi(de) != 0;
-        }
+        p->pk = fast && cfg->hop == kPkHop;
+        if (p->pk && cfg->n_mels == kFastGroups * kGroup) p->v4_wps = 3;
         p->lds_bytes = sizeof(float) * (a.stage_alloc + kRegions * (p->pk ? kRegionFloatsPk : kRegionFloats) + a.out_alloc) + sizeof(int32_t) * kMaxMels +
                        sizeof(float) * (static_cast<size_t>(a.n_weights) + 24 + 4 + (p->pk ? fa::melpk::kWindowTableFloats : 0));   // the paired weight reads of the packed kernel touch one slot row past the table
-        if (p->v4_wps) {
-            p->lds_bytes = kV4LdsBytes;
-            if (const char *pe = fa::sw(fa::Sw::MEL_V4_LDS_PAD)) p->lds_bytes += static_cast<size_t>(atoi(pe));   // diagnostics: fewer resident workgroups per CU
-        }
+        if (p->v4_wps) p->lds_bytes = kV4LdsBytes;
         if (p->lds_bytes > 160 * 1024) { (void)hipFree(p->dev); delete p; return fa::set_error(ctx, FA_INVALID_ARGUMENT, "mel: hop too large for LDS staging"); }
         if (p->lds_bytes > 64 * 1024) {
             const int lb = static_cast<int>(p->lds_bytes);
@@ -953,23 +916,20 @@ fa_status fa_mel_plan_create(fa_ctx *ctx, const fa_mel_config *cfg, const int64_
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(mel_kernel<0, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, lb);
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(mel_kernel<1, true, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, lb);
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(mel_kernel<1, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, lb);
-#define FA_V4_ATTR(L, E) do { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(mel_kernel_v4<L, E, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lb); \
-                              (void)hipFuncSetAttribute(reinterpret_cast<const void *>(mel_kernel_v4<L, E, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lb); \
-                              (void)hipFuncSetAttribute(reinterpret_cast<const void *>(mel_kernel_v4<L, E, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lb); \
-                              (void)hipFuncSetAttribute(reinterpret_cast<const void *>(mel_kernel_v4<L, E, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lb); } while (0)
+#define FA_V4_ATTR(L, E) do { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(mel_kernel_v4<L, E, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lb); \
+                              (void)hipFuncSetAttribute(reinterpret_cast<const void *>(mel_kernel_v4<L, E, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lb); } while (0)
             FA_V4_ATTR(0, true); FA_V4_ATTR(0, false); FA_V4_ATTR(1, true); FA_V4_ATTR(1, false);
 #undef FA_V4_ATTR
         }
         hipDeviceProp_t prop;
         e = hipGetDeviceProperties(&prop, ctx->device);
         const int cus = e == hipSuccess ? prop.multiProcessorCount : 256;
-        const char *rounds_env = fa::sw(fa::Sw::MEL_ROUNDS);  // diagnostics
         // Equal-length batches: one persistent round (the per-workgroup prologue — tables, lane constants — is paid once:
         // 0.663 vs 0.685 ms with four rounds on the bench workload).  Ragged batches keep four rounds, so that the hardware
         // scheduler evens out ranges that hold many empty tiles of short utterances.
         bool uniform = true;
         for (int b = 1; b < batch; ++b) if (frames[b] != frames[0]) { uniform = false; break; }
-        const int rounds = rounds_env && atoi(rounds_env) > 0 ? atoi(rounds_env) : (uniform ? 1 : 4);
+        const int rounds = uniform ? 1 : 4;
         const int64_t want = static_cast<int64_t>(cus) * (p->v4_wps ? p->v4_wps : 2) * rounds;  // resident workgroups per CU, `rounds` rounds of them
         p->grid = static_cast<int>(a.total_tiles < want ? a.total_tiles : want);
         if (p->grid < 1) p->grid = 1;
@@ -1005,71 +965,17 @@ fa_status fa_mel_execute_dev(fa_mel_plan *p, const float *d_pcm, const float *d_
     }
     MelArgs a = p->args;
     a.pcm = d_pcm; a.last = d_last; a.out = d_mel; a.lengths = d_lengths;
-    static unsigned long long *s_prof = nullptr;
-    static int s_prof_calls = 0;
-    static unsigned long long s_last_span[4] = {0, 0, 0, 0};
-    static std::mutex s_prof_mutex;   // the diagnostics state is process-wide; entries of different contexts may run concurrently
-    std::unique_lock<std::mutex> prof_lock(s_prof_mutex, std::defer_lock);
-    if (fa::sw(fa::Sw::MEL_PROF)) {  // diagnostics only: per-phase cycles of one workgroup, printed every 10 launches
-        prof_lock.lock();
-        if (!s_prof) { (void)hipMalloc(&s_prof, 128 + 4 * 8192); (void)hipMemset(s_prof, 0, 128 + 4 * 8192); }
-        a.prof = s_prof;
-        {   // slots 2..5: min / max of the workgroup start and end times of the launch about to be made
-            const unsigned long long init[4] = {~0ull, 0ull, ~0ull, 0ull};
-            unsigned long long keep[4];
-            (void)hipMemcpy(keep, s_prof + 2, 32, hipMemcpyDeviceToHost);
-            (void)hipMemcpy(s_prof + 2, init, 32, hipMemcpyHostToDevice);
-            if (s_prof_calls % 10 == 9) memcpy(s_last_span, keep, 32);
-        }
-        if (++s_prof_calls % 10 == 0) {
-            unsigned long long h[16];
-            (void)hipMemcpy(h, s_prof, 128, hipMemcpyDeviceToHost);
-            const double n = h[7] ? static_cast<double>(h[7]) : 1.0;
-            if (p->v4_wps) {
-                fprintf(stderr, "mel v4 profile (cycles per tile, wave 0 of one workgroup, %llu tiles): stage %.0f | B1 %.0f | reads+pass1 %.0f | B2 %.0f | pass2..log %.0f | B3 %.0f | loads+stores %.0f | B4 %.0f\n",
-                        h[7], h[8] / n, h[9] / n, h[10] / n, h[11] / n, h[12] / n, h[13] / n, h[14] / n, h[15] / n);
-                fprintf(stderr, "mel v4 profile: workgroup starts spread over %.1f us, ends over %.1f us, first start -> last end %.1f us (last launch)\n",
-                        (s_last_span[1] - s_last_span[0]) / 100.0, (s_last_span[3] - s_last_span[2]) / 100.0, (s_last_span[3] - s_last_span[0]) / 100.0);
-                {
-                    std::vector<unsigned> dur(p->grid);
-                    (void)hipMemcpy(dur.data(), s_prof + 16, sizeof(unsigned) * dur.size(), hipMemcpyDeviceToHost);
-                    std::vector<unsigned> srt(dur);
-                    std::sort(srt.begin(), srt.end());
-                    fprintf(stderr, "mel v4 profile: workgroup durations (us): min %.1f | p10 %.1f | median %.1f | p90 %.1f | max %.1f ; slowest blocks:", srt.front() / 100.0,
-                            srt[srt.size() / 10] / 100.0, srt[srt.size() / 2] / 100.0, srt[srt.size() * 9 / 10] / 100.0, srt.back() / 100.0);
-                    int shown = 0;
-                    for (size_t b = 0; b < dur.size() && shown < 12; ++b) if (dur[b] >= srt[srt.size() - 12]) { fprintf(stderr, " %zu", b); ++shown; }
-                    double byx[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-                    for (size_t b = 0; b < dur.size(); ++b) byx[b & 7] += dur[b];
-                    fprintf(stderr, "\n   mean by 64-block bucket (us):");
-                    for (size_t b0 = 0; b0 < dur.size(); b0 += 64) { double m = 0; size_t c = 0; for (size_t b = b0; b < b0 + 64 && b < dur.size(); ++b, ++c) m += dur[b]; fprintf(stderr, " %.0f", m / c / 100.0); }
-                    fprintf(stderr, "\n   mean by blockIdx %% 8 (us):");
-                    for (int x = 0; x < 8; ++x) fprintf(stderr, " %.1f", byx[x] / (dur.size() / 8.0) / 100.0);
-                    fprintf(stderr, "\n");
-                }
-                if (h[1]) fprintf(stderr, "mel v4 profile: shader clock during the kernel %.0f MHz (clock64 / wall_clock64 at 100 MHz)\n", 100.0 * static_cast<double>(h[0]) / static_cast<double>(h[1]));
-            } else {
-            fprintf(stderr, "mel profile (cycles per tile, wave 0 of one workgroup, %llu tiles): stage-write %.0f | barrier1 %.0f | prefetch issue %.0f | passes %.0f | barrier2 %.0f | store %.0f\n",
-                    h[7], h[0] / n, h[1] / n, (h[2] + h[6]) / n, (h[3] + h[8] + h[9] + h[10] + h[11]) / n, h[4] / n, h[5] / n);
-            if (h[8]) fprintf(stderr, "mel profile, packed pass: sample reads %.0f | fft256 %.0f | partner + power %.0f | filterbank %.0f | log + stage %.0f\n",
-                              h[8] / n, h[9] / n, h[10] / n, h[11] / n, h[3] / n);
-            }
-        }
-    } else a.prof = nullptr;
     const bool mm = p->cfg.layout == FA_MEL_LAYOUT_MEL_MAJOR;
     const bool pk = p->pk;
     const dim3 grid(p->grid), block(kThreads);
     if (p->v4_wps) {
-        // every workgroup draws one index per tile it processes plus the one that tells it to stop: a launch advances the
-        // counter by exactly total_tiles + grid
-        a.queue_base = p->launches++ * (static_cast<unsigned long long>(a.total_tiles) + static_cast<unsigned long long>(p->v4_deep ? 2 : 1) * static_cast<unsigned long long>(p->grid));
-        const bool ez = p->edge_zero, w4 = p->v4_deep;   // w4: the deep-queue variant
-#define FA_V4(L, E, D) do { if (p->cfg.floor_mode == FA_MEL_FLOOR_CLAMPED) hipLaunchKernelGGL((mel_kernel_v4<L, E, D, true>), grid, block, p->lds_bytes, ctx->stream, a); \
-                             else hipLaunchKernelGGL((mel_kernel_v4<L, E, D, false>), grid, block, p->lds_bytes, ctx->stream, a); } while (0)
-        if (mm) { if (ez) { if (w4) FA_V4(FA_MEL_LAYOUT_MEL_MAJOR, true, true); else FA_V4(FA_MEL_LAYOUT_MEL_MAJOR, true, false); }
-                  else { if (w4) FA_V4(FA_MEL_LAYOUT_MEL_MAJOR, false, true); else FA_V4(FA_MEL_LAYOUT_MEL_MAJOR, false, false); } }
-        else { if (ez) { if (w4) FA_V4(FA_MEL_LAYOUT_FRAME_MAJOR, true, true); else FA_V4(FA_MEL_LAYOUT_FRAME_MAJOR, true, false); }
-               else { if (w4) FA_V4(FA_MEL_LAYOUT_FRAME_MAJOR, false, true); else FA_V4(FA_MEL_LAYOUT_FRAME_MAJOR, false, false); } }
+        // every workgroup draws one index per tile it processes plus the two it holds when it stops (the queue runs two tiles
+        // ahead): a launch advances the counter by exactly total_tiles + 2 grid
+        a.queue_base = p->launches++ * (static_cast<unsigned long long>(a.total_tiles) + 2ull * static_cast<unsigned long long>(p->grid));
+#define FA_V4(L, E) do { if (p->cfg.floor_mode == FA_MEL_FLOOR_CLAMPED) hipLaunchKernelGGL((mel_kernel_v4<L, E, true>), grid, block, p->lds_bytes, ctx->stream, a); \
+                          else hipLaunchKernelGGL((mel_kernel_v4<L, E, false>), grid, block, p->lds_bytes, ctx->stream, a); } while (0)
+        if (mm) { if (p->edge_zero) FA_V4(FA_MEL_LAYOUT_MEL_MAJOR, true); else FA_V4(FA_MEL_LAYOUT_MEL_MAJOR, false); }
+        else { if (p->edge_zero) FA_V4(FA_MEL_LAYOUT_FRAME_MAJOR, true); else FA_V4(FA_MEL_LAYOUT_FRAME_MAJOR, false); }
 #undef FA_V4
         FA_HIP_TRY(ctx, hipGetLastError());
         return FA_SUCCESS;

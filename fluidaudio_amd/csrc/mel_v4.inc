@@ -95,9 +95,9 @@ __device__ __forceinline__ void load_frame_pair_eo(const float *e, const float *
     }
 }
 
-// DEEP: the tile queue runs two tiles ahead, so that the loads of the next tile are issued right behind B2 and travel during the
+// The tile queue runs two tiles ahead, so that the loads of the next tile are issued right behind B2 and travel during the
 // whole second pass (30 more live registers there) instead of only during the store phase.
-template <int LAYOUT, bool EZ, bool DEEP, bool CLAMPED>
+template <int LAYOUT, bool EZ, bool CLAMPED>
 __global__ __launch_bounds__(kThreads, 3) void mel_kernel_v4(const MelArgs a) {
     constexpr bool AHEAD = true;   // the next tile's loads are issued before the store phase of the current one (measured equal to issuing them at the top of their own iteration)
     using namespace fa::melpk;
@@ -143,8 +143,8 @@ __global__ __launch_bounds__(kThreads, 3) void mel_kernel_v4(const MelArgs a) {
     __syncthreads();
 
     // Tiles are handed out dynamically: one atomic per tile on a counter that never resets.  Every workgroup draws one index
-    // per tile it processes plus the one (>= total_tiles) that stops it, so a launch advances the counter by exactly
-    // total_tiles + gridDim.x and launch k owns the values from queue_base = k (total_tiles + gridDim.x).  Static ranges lose a third of the machine here: the
+    // per tile it processes plus the two (>= total_tiles) it holds when it stops (the queue runs two tiles ahead), so a launch advances the counter
+    // by exactly total_tiles + 2 gridDim.x and launch k owns the values from queue_base = k (total_tiles + 2 gridDim.x).  Static ranges lose a third of the machine here: the
     // workgroups of a CU are served by age (the oldest issues first), so the first-dispatched workgroup of every CU finishes
     // its range in 0.47 ms, the second in 0.58 ms, the third in 0.69 ms (profiles/r02_mel_v4_static_ranges.txt).  The next
     // index is requested right after B1 and consumed after B3: its latency hides behind the pass.
@@ -229,27 +229,22 @@ __global__ __launch_bounds__(kThreads, 3) void mel_kernel_v4(const MelArgs a) {
     };
 
     __builtin_amdgcn_s_waitcnt(0x0F70);   // table loads complete: vmcnt(0) once, outside the tile loop
-    if (tid == 0) { qslot[0] = grab(); if (DEEP) qslot[1] = grab(); }
+    if (tid == 0) { qslot[0] = grab(); qslot[1] = grab(); }
     __syncthreads();
     int tl = __builtin_amdgcn_readfirstlane(qslot[0]);
-    int tl_n = DEEP ? __builtin_amdgcn_readfirstlane(qslot[1]) : 0;   // DEEP: the tile after `tl`, known one iteration ahead
-    __syncthreads();                                                   // (both slots are reused below)
+    int tl_n = __builtin_amdgcn_readfirstlane(qslot[1]);   // the tile after `tl`, known one iteration ahead
+    __syncthreads();                                       // (both slots are reused below)
     int par = 1;
     TileInfo cur{};
     cur.stage = false;
     if (tl < total_tiles) { cur = tile_info(tl); if (AHEAD && cur.stage) fetch(cur); }
     long long n_done = 0;
 
-    unsigned long long t_seg[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // FA_MEL_PROF (diagnostics): stage | B1 | reads + first pass | B2 | rest of the pass | B3 | loads + stores | B4
+    unsigned long long t_seg[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // cycle stamps, inert while a.prof is null (MelArgs::prof): stage | B1 | reads + first pass | B2 | rest of the pass | B3 | loads + stores | B4
     unsigned long long t_prev = a.prof ? clock64() : 0;
     const unsigned long long t_begin = t_prev, w_begin = a.prof ? wall_clock64() : 0;   // wall_clock64: constant 100 MHz
-#ifdef FA_MEL_PROF_FINE
-#define V4_FINE(i) V4_STAMP_(i)
-#define V4_STAMP(i) do { if ((i) % 2 == 0) V4_STAMP_(i); } while (0)
-#else
 #define V4_FINE(i) do { } while (0)
 #define V4_STAMP(i) V4_STAMP_(i)
-#endif
 #define V4_STAMP_(i) do { if (a.prof) { const unsigned long long t_now = clock64(); t_seg[i] += t_now - t_prev; t_prev = t_now; } } while (0)
     while (tl < total_tiles) {
         ++n_done;
@@ -263,8 +258,8 @@ __global__ __launch_bounds__(kThreads, 3) void mel_kernel_v4(const MelArgs a) {
             }
             if (tid == 0) qslot[par] = grab();
             __syncthreads();
-            if (DEEP) { tl = tl_n; tl_n = __builtin_amdgcn_readfirstlane(qslot[par]); }
-            else tl = __builtin_amdgcn_readfirstlane(qslot[par]);
+            tl = tl_n;
+            tl_n = __builtin_amdgcn_readfirstlane(qslot[par]);
             par ^= 1;
             if (tl < total_tiles) { cur = tile_info(tl); if (AHEAD && cur.stage) fetch(cur); }
             continue;
@@ -310,7 +305,7 @@ __global__ __launch_bounds__(kThreads, 3) void mel_kernel_v4(const MelArgs a) {
         V4_STAMP(3);
         TileInfo nxt{};
         nxt.stage = false;
-        if (DEEP && tl_n < total_tiles) { nxt = tile_info(tl_n); if (nxt.stage) fetch(nxt); }   // in flight during the second pass
+        if (tl_n < total_tiles) { nxt = tile_info(tl_n); if (nxt.stage) fetch(nxt); }   // in flight during the second pass
         V4_FINE(1);
         {
             FA_V4_LANE();
@@ -407,7 +402,6 @@ __global__ __launch_bounds__(kThreads, 3) void mel_kernel_v4(const MelArgs a) {
         V4_STAMP(5);
         const int tl_next = __builtin_amdgcn_readfirstlane(qslot[par]);
         par ^= 1;
-        if (!DEEP && tl_next < total_tiles) { nxt = tile_info(tl_next); if (AHEAD && nxt.stage) fetch(nxt); }   // in flight during the stores below
         const f2 *R = reinterpret_cast<const f2 *>(area);
         constexpr int kRegF2 = kV4RegionFloats / 2;
         const bool full_tile = cur.t0 + kTileFrames <= cur.T && cur.t0 + kTileFrames <= a.frame_stride;
@@ -445,8 +439,8 @@ __global__ __launch_bounds__(kThreads, 3) void mel_kernel_v4(const MelArgs a) {
         __syncthreads();                                   // B4: the regions are free for the next tile's samples
         V4_STAMP(7);
         cur = nxt;
-        if (DEEP) { tl = tl_n; tl_n = tl_next; }
-        else tl = tl_next;
+        tl = tl_n;
+        tl_n = tl_next;
     }
     if (a.prof && blockIdx.x == gridDim.x / 2 && threadIdx.x == 0) {
         for (int i = 0; i < 8; ++i) atomicAdd(&a.prof[8 + i], t_seg[i]);

@@ -420,7 +420,7 @@ __global__ __launch_bounds__(kRowsThreads) FA_ROWS_ATTR void poly_rows_kernel(co
 constexpr int wide_row_floats(int rows, int waves, int nv) { return rows == 32 ? (waves == 10 ? (nv == 32 ? 576 : 288) : 512) : (nv == 32 ? 576 : 512); }
 template <int ROWS, int WAVES, int NV, int SHARE, int CH>
 __device__ __forceinline__ void poly_rows_wide_body(const float *__restrict__ x, const float *__restrict__ tt, float *__restrict__ y, const PolyRowsGeom g_,
-                                                    const int2 *__restrict__ gtab, const int tiles_, const int64_t m_end_, const int64_t k_lim_, const int vec_ok_, const int dbg_, const int rot) {
+                                                    const int2 *__restrict__ gtab, const int tiles_, const int64_t m_end_, const int64_t k_lim_, const int vec_ok_, const int rot) {
     constexpr int kWideBuf = ROWS * wide_row_floats(ROWS, WAVES, NV), PU = 4 * 64 / ROWS;     // floats per LDS buffer; phases per unit
     __shared__ float buf_a[kWideBuf];
     __shared__ float buf_b[kWideBuf];
@@ -433,10 +433,10 @@ __device__ __forceinline__ void poly_rows_wide_body(const float *__restrict__ x,
     // group (b >> 3) % groups, tiles (b & 7) + 8 ((b >> 3) / groups) + k n_chains — the workgroups that stage the overlapping spans of a tile's groups are 8
     // apart: the same XCD's L2, at about the same time
     const int groups = g_.groups, qb = static_cast<int>(blockIdx.x) >> 3, grp = qb % groups;
-    int up = g_.up, down = g_.down, sld = g_.sld, tiles = tiles_, vec_ok = vec_ok_, dbg = dbg_, smin = reinterpret_cast<const int *>(gtab)[2 * grp];
+    int up = g_.up, down = g_.down, sld = g_.sld, tiles = tiles_, vec_ok = vec_ok_, smin = reinterpret_cast<const int *>(gtab)[2 * grp];
     int n_chains = 8 * (static_cast<int>(gridDim.x) / (8 * groups)), ph0 = grp * g_.ppg, ph1 = ph0 + g_.ppg < up ? ph0 + g_.ppg : up;
     int tile = (static_cast<int>(blockIdx.x) & 7) + 8 * (qb / groups);
-    asm volatile("" : "+s"(m_end), "+s"(k_lim), "+s"(k_begin), "+s"(m_begin), "+s"(up), "+s"(down), "+s"(sld), "+s"(tiles), "+s"(vec_ok), "+s"(dbg), "+s"(smin), "+s"(n_chains),
+    asm volatile("" : "+s"(m_end), "+s"(k_lim), "+s"(k_begin), "+s"(m_begin), "+s"(up), "+s"(down), "+s"(sld), "+s"(tiles), "+s"(vec_ok), "+s"(smin), "+s"(n_chains),
                  "+s"(ph0), "+s"(ph1), "+s"(tile));
     struct { int64_t k_begin, m_begin; int up, down, sld; } g{k_begin, m_begin, up, down, sld};
     const int n_units = (ph1 - ph0 + PU - 1) / PU;
@@ -530,16 +530,16 @@ __device__ __forceinline__ void poly_rows_wide_body(const float *__restrict__ x,
     // one tile: computed from `mine` while the next one travels into `other`
     auto step = [&](const float *mine, float *other) {
         const int tile_n = tile + n_chains;
-        // (dbg = FA_RESAMPLE_WIDE_PART, 0 in production: 1 = staging only, 2 = everything but staging, 3 = arithmetic and stores without the period's wait and
-        // barrier, 4 = arithmetic alone — the decomposition of profiles/r05_resample_wide_steps.json; wave-uniform branches on a scalar)
-        if (dbg < 3) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wavefront's pieces of the present tile have landed ...
-            __builtin_amdgcn_s_barrier();                       // ... everybody's have, and nobody reads the other buffer any more
-            asm volatile("" ::: "memory");
-        }
-        if (dbg < 4) flush();
-        if (tile_n < tiles && dbg < 2) stage(tile_n, other);
-        if (dbg != 1) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wavefront's pieces of the present tile have landed ...
+        __builtin_amdgcn_s_barrier();                       // ... everybody's have, and nobody reads the other buffer any more
+        asm volatile("" ::: "memory");
+        flush();
+        if (tile_n < tiles) stage(tile_n, other);
+        // the arithmetic in a block of its own, behind a branch the compiler cannot resolve: in one block with the staging above, the
+        // short-window forms (<8, 4, *>) spill twice as much to scratch (11.025 kHz: 237 -> 259 us per audio hour, 7.35 kHz: 249 -> 309)
+        int own_block = 1;
+        asm volatile("" : "+s"(own_block));
+        if (own_block) {
             // a software pipeline over PIECES of a window (four 16-byte LDS reads = 16 window positions): the reads of piece i + AHEAD are issued before the
             // multiply-adds of piece i, through a ring of AHEAD + 1 register quarters.  A CU holds ONE workgroup here, two wavefronts per SIMD: nobody else covers a
             // read's latency (first build, whole windows read and then used: 4.5 us of arithmetic per tile where the multiply-adds need 2.4 —
@@ -602,8 +602,8 @@ __device__ __forceinline__ void poly_rows_wide_body(const float *__restrict__ x,
 #define FA_WIDE_KERNEL(NAME, ROWS_, WAVES_, MINW)                                                                                                     \
     template <int NV, int SHARE, int CH>                                                                                                              \
     __global__ __launch_bounds__(64 * WAVES_, MINW) void NAME(const float *__restrict__ x, const float *__restrict__ tt, float *__restrict__ y, const PolyRowsGeom g, \
-                                                              const int2 *__restrict__ gtab, const int tiles, const int64_t m_end, const int64_t k_lim, const int vec_ok, const int dbg, const int rot) { \
-        poly_rows_wide_body<ROWS_, WAVES_, NV, SHARE, CH>(x, tt, y, g, gtab, tiles, m_end, k_lim, vec_ok, dbg, rot);                                        \
+                                                              const int2 *__restrict__ gtab, const int tiles, const int64_t m_end, const int64_t k_lim, const int vec_ok, const int rot) { \
+        poly_rows_wide_body<ROWS_, WAVES_, NV, SHARE, CH>(x, tt, y, g, gtab, tiles, m_end, k_lim, vec_ok, rot);                                             \
     }
 FA_WIDE_KERNEL(poly_rows_wide32_kernel, 32, 8, 2)        // one workgroup per CU: 2 wavefronts per SIMD, 256 registers
 FA_WIDE_KERNEL(poly_rows_wide16_kernel, 16, 8, 4)        // two per CU: 4 per SIMD, 128 registers
@@ -729,8 +729,6 @@ __global__ __launch_bounds__(kThreads) void poly_decim_tile_kernel(const float *
 struct PolyRows {
     bool wide = false;              // served by poly_rows_wide_kernel (32-row tiles, every phase in one item, two LDS buffers)
     int ch = 0, wide_rows = 0, wide_waves = 0;   // its units per wavefront; rows per tile (32: units of 8 phases, 16: of 16); wavefronts per workgroup
-    bool wide_no_rot = false;
-    int wide_part = 0;              // FA_RESAMPLE_WIDE_PART (read when the tables are built): time PARTS of the kernel — results are wrong for any value but 0
     PolyRowsGeom g{};
     int nv = 0;                     // 16-byte reads per phase window
     size_t lds = 0;
@@ -744,14 +742,10 @@ bool wide_instance(int rows, int waves, int nv, int share, int ch);
 
 // Geometry + tables (resample_geom.h); false when the pair does not suit the kernel (then poly_lds_kernel serves it).
 bool poly_rows_build(PolyRows &R, const std::vector<float> &h, int up, int down, int64_t pre_remove, std::vector<int> &gtab, std::vector<float> &tt) {
-    size_t budget = 0;                                                  // automatic (resample_geom.h); FA_RESAMPLE_ROWS_LDS_KB: measurements (r04_rows_lds_probe.json)
-    if (const char *e = fa::sw(fa::Sw::RESAMPLE_ROWS_LDS_KB)) { const int v = atoi(e); if (v >= 16 && v <= 150) budget = static_cast<size_t>(v) * 1024; }
-    int share_max = 4;                                                  // FA_RESAMPLE_ROWS_SHARE = 1 | 2 | 4: measurements (1 = every phase its own window, round 4's reads)
-    if (const char *e = fa::sw(fa::Sw::RESAMPLE_ROWS_SHARE)) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) share_max = v; }
     // the persistent kernel with two buffers (FA_RESAMPLE_NO_WIDE=1: the one-tile-per-workgroup kernel): one phase group — an unbounded LDS budget keeps
     // rows_geometry from splitting —, rows of at most 512 floats, and one of the instantiated (window, sharing, units per wavefront) combinations
     R.wide = false;
-    if (budget == 0 && !fa::sw_on(fa::Sw::RESAMPLE_NO_WIDE)) {
+    if (!fa::sw_on(fa::Sw::RESAMPLE_NO_WIDE)) {
         // candidates, in order: {rows, wavefronts, LDS budget of rows_geometry (per 64 rows: it decides the phase groups)}.  FA_RESAMPLE_WIDE = "rows:waves" picks
         // one.  Measured per audio hour (profiles/r05_resample_wide_steps.json): 16-row tiles, 8 wavefronts, two workgroups per CU — 44.1 kHz 233 - 250 us,
         // 22.05 kHz 128, 11.025 kHz 116; 32-row tiles with one workgroup per CU 243 - 262 / 152 / (no instance); 32-row tiles of one phase GROUP (80 k phases:
@@ -773,7 +767,7 @@ bool poly_rows_build(PolyRows &R, const std::vector<float> &h, int up, int down,
             int nv2 = 0;
             std::vector<int> gtab2;
             std::vector<float> tt2;
-            if (!fa::rows_geometry(g2, nv2, h, up, down, pre_remove, gtab2, tt2, c.budget, share_max)) continue;
+            if (!fa::rows_geometry(g2, nv2, h, up, down, pre_remove, gtab2, tt2, c.budget)) continue;
             if (c.rows == 32 && c.waves == 10 && c.budget > group_budget && nv2 != 32) continue;   // the ungrouped ten-wavefront form exists for the long windows only
             if (g2.sld > wide_row_floats(c.rows, c.waves, nv2) || g2.groups > 8) continue;
             if (!(c.rows == 32 && c.waves == 10) && g2.groups != 1) continue;
@@ -782,14 +776,12 @@ bool poly_rows_build(PolyRows &R, const std::vector<float> &h, int up, int down,
             if (!wide_instance(c.rows, c.waves, nv2, g2.share, ch)) continue;
             R.g = g2; R.nv = nv2; R.ch = ch; R.wide_rows = c.rows; R.wide_waves = c.waves; gtab.swap(gtab2); tt.swap(tt2);
             R.wide = true;
-            if (const char *e = fa::sw(fa::Sw::RESAMPLE_WIDE_PART)) R.wide_part = atoi(e);
-            R.wide_no_rot = fa::sw_on(fa::Sw::RESAMPLE_WIDE_NO_ROT);
             R.lds = 0; R.up = up; R.down = down;     // (static LDS)
             return true;
         }
     }
-    if (!fa::rows_geometry(R.g, R.nv, h, up, down, pre_remove, gtab, tt, budget, share_max)) return false;
-    if (R.g.sld > 64 * 5 && R.g.share != 1 && !fa::rows_geometry(R.g, R.nv, h, up, down, pre_remove, gtab, tt, budget, 1)) return false;   // the long-row build is instantiated for share = 1 only
+    if (!fa::rows_geometry(R.g, R.nv, h, up, down, pre_remove, gtab, tt)) return false;   // the automatic LDS budget (resample_geom.h)
+    if (R.g.sld > 64 * 5 && R.g.share != 1 && !fa::rows_geometry(R.g, R.nv, h, up, down, pre_remove, gtab, tt, 0, 1)) return false;   // the long-row build is instantiated for share = 1 only
     R.lds = static_cast<size_t>(R.g.sld) * 64 * sizeof(float); R.up = up; R.down = down;
     return true;
 }
@@ -823,19 +815,17 @@ void poly_rows_wide_launch(fa_ctx *ctx, const PolyRows &R, const float *d_x, flo
     int64_t sets = 256 * per_cu / set;
     sets = std::max<int64_t>(1, std::min<int64_t>(sets, (tiles + 7) / 8));
     const unsigned grid = static_cast<unsigned>(sets * set);
-    const int dbg = R.wide_part;
-    int rot = 0;                                                     // (sld / 4)^-1 mod 16 (sld / 4 is odd); FA_RESAMPLE_WIDE_NO_ROT (tables' build time): rows unrotated
+    int rot = 0;                                                     // (sld / 4)^-1 mod 16 (sld / 4 is odd)
     for (int c = 1; c < 16; c += 2) if ((c * (R.g.sld / 4)) % 16 == 1) rot = c;
-    if (R.wide_no_rot) rot = 0;
     const int n_tiles = static_cast<int>(tiles);
     const int64_t k_lim = frames - 4;
 #define FA_WIDE_GO(R_, W_, V, S, C)                                                                                                                 \
     if (R.wide_rows == R_ && R.wide_waves == W_ && R.nv == V && R.g.share == S && R.ch == C) {                                                     \
-        if constexpr (R_ == 32 && W_ == 8) hipLaunchKernelGGL((poly_rows_wide32_kernel<V, S, C>), dim3(grid), dim3(64 * W_), 0, ctx->stream, d_x, tt, d_y, R.g, gtab, n_tiles, m_end, k_lim, vec_ok, dbg, rot);   \
-        else if constexpr (R_ == 32 && V == 32) hipLaunchKernelGGL((poly_rows_wide32w10l_kernel<V, S, C>), dim3(grid), dim3(64 * W_), 0, ctx->stream, d_x, tt, d_y, R.g, gtab, n_tiles, m_end, k_lim, vec_ok, dbg, rot); \
-        else if constexpr (R_ == 32) hipLaunchKernelGGL((poly_rows_wide32w10_kernel<V, S, C>), dim3(grid), dim3(64 * W_), 0, ctx->stream, d_x, tt, d_y, R.g, gtab, n_tiles, m_end, k_lim, vec_ok, dbg, rot); \
-        else if constexpr (W_ == 8) hipLaunchKernelGGL((poly_rows_wide16_kernel<V, S, C>), dim3(grid), dim3(64 * W_), 0, ctx->stream, d_x, tt, d_y, R.g, gtab, n_tiles, m_end, k_lim, vec_ok, dbg, rot); \
-        else hipLaunchKernelGGL((poly_rows_wide16w10_kernel<V, S, C>), dim3(grid), dim3(64 * W_), 0, ctx->stream, d_x, tt, d_y, R.g, gtab, n_tiles, m_end, k_lim, vec_ok, dbg, rot); \
+        if constexpr (R_ == 32 && W_ == 8) hipLaunchKernelGGL((poly_rows_wide32_kernel<V, S, C>), dim3(grid), dim3(64 * W_), 0, ctx->stream, d_x, tt, d_y, R.g, gtab, n_tiles, m_end, k_lim, vec_ok, rot);   \
+        else if constexpr (R_ == 32 && V == 32) hipLaunchKernelGGL((poly_rows_wide32w10l_kernel<V, S, C>), dim3(grid), dim3(64 * W_), 0, ctx->stream, d_x, tt, d_y, R.g, gtab, n_tiles, m_end, k_lim, vec_ok, rot); \
+        else if constexpr (R_ == 32) hipLaunchKernelGGL((poly_rows_wide32w10_kernel<V, S, C>), dim3(grid), dim3(64 * W_), 0, ctx->stream, d_x, tt, d_y, R.g, gtab, n_tiles, m_end, k_lim, vec_ok, rot); \
+        else if constexpr (W_ == 8) hipLaunchKernelGGL((poly_rows_wide16_kernel<V, S, C>), dim3(grid), dim3(64 * W_), 0, ctx->stream, d_x, tt, d_y, R.g, gtab, n_tiles, m_end, k_lim, vec_ok, rot); \
+        else hipLaunchKernelGGL((poly_rows_wide16w10_kernel<V, S, C>), dim3(grid), dim3(64 * W_), 0, ctx->stream, d_x, tt, d_y, R.g, gtab, n_tiles, m_end, k_lim, vec_ok, rot); \
         return;                                                                                                                                    \
     }
     FA_WIDE_INSTANCES(FA_WIDE_GO)
@@ -996,11 +986,11 @@ fa_status fa_resample_poly_dev(fa_ctx *ctx, const float *d_x, int64_t frames, in
             }
         }
         float *d_h = static_cast<float *>(ctx->poly_taps);
-        // the kernel-choice switches of the tests and probes, read ONCE per call, here (the forms fixed with a context's tables — FA_RESAMPLE_WIDE*, _ROWS_* —
+        // the kernel-choice switches of the tests, read ONCE per call, here (the forms fixed with a context's tables — FA_RESAMPLE_WIDE, _NO_WIDE —
         // are read when the tables are built)
-        struct { bool simple, no_decim, no_decim_tiles, no_interp, no_rows; } const sw = {
+        struct { bool simple, no_decim, no_decim_tiles, no_rows; } const sw = {
             fa::sw_on(fa::Sw::RESAMPLE_SIMPLE), fa::sw_on(fa::Sw::RESAMPLE_NO_DECIM), fa::sw_on(fa::Sw::RESAMPLE_NO_DECIM_TILES),
-            fa::sw_on(fa::Sw::RESAMPLE_NO_INTERP), fa::sw_on(fa::Sw::RESAMPLE_NO_ROWS)};
+            fa::sw_on(fa::Sw::RESAMPLE_NO_ROWS)};
         const bool simple = sw.simple;
         auto edges = [&](const int64_t m_lo, const int64_t m_hi) {   // outputs [m_lo, m_hi) by the one-thread-per-output kernel (clamps at the signal's ends)
             if (m_hi <= m_lo) return;
@@ -1062,7 +1052,7 @@ fa_status fa_resample_poly_dev(fa_ctx *ctx, const float *d_x, int64_t frames, in
             }
         }
         // small interpolation factors: register-tiled kernel on the outputs whose inputs all exist, poly_kernel on the two ends
-        if (!decim && !simple && u >= 2 && u <= 4 && !sw.no_interp) {
+        if (!decim && !simple && u >= 2 && u <= 4) {
             int64_t lo = 0, hi = 0;
             if (u == 2 && dn == 1 && n_taps == 42) poly_interp_launch<2, 1, 42>(ctx, d_x, d_h, d_y, frames, n_out, pre_remove, lo, hi);
             else if (u == 2 && dn == 3 && n_taps == 64) poly_interp_launch<2, 3, 64>(ctx, d_x, d_h, d_y, frames, n_out, pre_remove, lo, hi);
