@@ -30,7 +30,7 @@ FAULT_VBX, FAULT_THREAD_START, FAULT_DEVBUF_MALLOC, FAULT_WS_MALLOC, FAULT_AHC =
 
 # Every symbol include/fluidaudio_hip.h + include/FastClusterWrapper.h declare (checked by tests/test_abi.py).
 EXPORTED_SYMBOLS = [
-    "fa_version", "fa_debug_inject_fault", "fa_debug_set_switch", "fa_debug_hooks_enabled", "fa_ctx_set_timing", "fa_ctx_last_device_ms", "fa_debug_sclk_mhz", "fa_ctc_beam_plan", "fa_host_alloc", "fa_host_free", "fa_ctx_create", "fa_ctx_destroy", "fa_ctx_synchronize", "fa_ctx_stream", "fa_ctx_last_error",
+    "fa_version", "fa_debug_inject_fault", "fa_debug_set_switch", "fa_debug_hooks_enabled", "fa_debug_ahc_adopted", "fa_ctx_set_timing", "fa_ctx_last_device_ms", "fa_debug_sclk_mhz", "fa_ctc_beam_plan", "fa_host_alloc", "fa_host_free", "fa_ctx_create", "fa_ctx_destroy", "fa_ctx_synchronize", "fa_ctx_stream", "fa_ctx_last_error",
     "fa_ctx_set_workspace_limit", "fa_ctx_set_workspace_cap", "fa_ctx_trim", "fa_ctx_workspace_bytes", "fa_ctx_reserve",
     "fa_mel_default_config", "fa_mel_num_frames", "fa_mel_padded_frames", "fa_mel_plan_create", "fa_mel_plan_destroy",
     "fa_mel_plan_utt_stride", "fa_mel_plan_frame_stride", "fa_mel_plan_total_frames", "fa_mel_execute_dev",
@@ -127,6 +127,7 @@ def lib() -> C.CDLL:
     L.fa_debug_inject_fault.restype = None
     L.fa_debug_set_switch.argtypes = [C.c_char_p, C.c_char_p]
     L.fa_debug_hooks_enabled.restype = i32
+    L.fa_debug_ahc_adopted.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp]
     L.fa_ctx_set_timing.argtypes = [vp, i32]
     L.fa_ctx_last_device_ms.argtypes = [vp]
     L.fa_ctx_last_device_ms.restype = f64
@@ -351,6 +352,21 @@ class Context:
     def check(self, status: int, where: str):
         if status != SUCCESS:
             raise FluidAudioHipError(status, where, self.last_error())
+
+    def ahc_adopted(self):
+        """What the filter-based rounds adopted at the last hand-over of AUTO's tie route on this context (fa_debug_ahc_adopted; recorded while
+        FA_AHC_RO_HANDOVER_AT is set): dict of row, kind, eps and per-slot arrays node, d1, nn, nnnode, e2 — or None when nothing was recorded."""
+        import numpy as np
+        row, kind, eps, slots = C.c_int64(), C.c_int32(), C.c_double(), C.c_size_t()
+        f = lib().fa_debug_ahc_adopted
+        self.check(f(self._h, C.byref(row), C.byref(kind), C.byref(eps), C.byref(slots), 0, None, None, None, None, None), "fa_debug_ahc_adopted")
+        if row.value < 0:
+            return None
+        n = slots.value
+        a = {"node": np.zeros(n, np.int32), "d1": np.zeros(n), "nn": np.zeros(n, np.int32), "nnnode": np.zeros(n, np.int32), "e2": np.zeros(n)}
+        self.check(f(self._h, C.byref(row), C.byref(kind), C.byref(eps), C.byref(slots), n, *(a[k].ctypes.data for k in ("node", "d1", "nn", "nnnode", "e2"))),
+                   "fa_debug_ahc_adopted")
+        return dict(row=row.value, kind=kind.value, eps=eps.value, **a)
 
     def sclk_mhz(self, spin_us: int = 200) -> float:
         """The shader clock right now (fa_debug_sclk_mhz): latency-bound legs print it next to their timing."""

@@ -552,10 +552,43 @@ size_t rom_total_bytes(size_t N, size_t Np, size_t d) { return rom_layout(N, Np,
 // slower than never having tried, never different from the reference.  Inputs that tie at distances > 0 (quantised embeddings) stay in reference order.
 constexpr int kRomQuiet = 1024, kRomMinRest = 4096;
 
+// A switch holding a positive integer (the test hooks FA_AHC_RO_HANDOVER_AT / FA_AHC_RO_REPLAY_PAIRS): 0 when unset, -1 when not a positive integer.
+static long long rom_switch_value(const fa::Sw s) {
+    const char *v = fa::sw(s);
+    if (!v) return 0;
+    char *end = nullptr;
+    const long long x = strtoll(v, &end, 10);
+    return (end != v && *end == '\0' && x > 0 && x <= (1LL << 30)) ? x : -1;
+}
+
+// fa_debug_ahc_adopted: the state prob_adopt has just built (row records, e2, node ids of every slot) copied to the context (one synchronisation)
+static fa_status rom_record_adopted(fa_ctx *ctx, const Prob &p, const int merges, const int kind, const double eps) {
+    const size_t Np = p.Np;
+    std::vector<RowSt> rows(Np);
+    fa_ctx::AhcAdopted &a = ctx->ahc_adopted;
+    a.node.resize(Np); a.e2.resize(Np);
+    FA_HIP_TRY(ctx, hipMemcpyAsync(rows.data(), p.w.row, sizeof(RowSt) * Np, hipMemcpyDeviceToHost, ctx->stream));
+    FA_HIP_TRY(ctx, hipMemcpyAsync(a.node.data(), p.w.node, sizeof(int32_t) * Np, hipMemcpyDeviceToHost, ctx->stream));
+    FA_HIP_TRY(ctx, hipMemcpyAsync(a.e2.data(), p.w.e2, sizeof(double) * Np, hipMemcpyDeviceToHost, ctx->stream));
+    FA_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    a.d1.resize(Np); a.nn.resize(Np); a.nnnode.resize(Np);
+    for (size_t i = 0; i < Np; ++i) { a.d1[i] = rows[i].d1; a.nn[i] = rows[i].nn; a.nnnode[i] = rows[i].nnnode; }
+    a.row = merges; a.kind = kind; a.eps = eps;
+    return FA_SUCCESS;
+}
+
 fa_status rom_run_device(fa_ctx *ctx, const double *d_data, size_t N, size_t d, double *d_Z, fa_ahc_stats *stats, bool z_on_host, bool &declined, bool may_hand_over,
                          bool &tie_after_hand_over, bool matrix_ready = false) {
     tie_after_hand_over = false;
     declined = true;
+    // test hooks (include/fluidaudio_hip.h): the hand-over at the first replay boundary at or behind a chosen row; the launch pairs per replay.  A replay must be
+    // a multiple of 4 pairs (the boundary state is in dev[0]: the parity rule below), anything else is refused.
+    const long long force_at = rom_switch_value(fa::Sw::AHC_RO_HANDOVER_AT), replay_pairs = rom_switch_value(fa::Sw::AHC_RO_REPLAY_PAIRS);
+    if (force_at < 0 || replay_pairs < 0 || replay_pairs % 4 != 0) {
+        declined = false;
+        return fa::set_error(ctx, FA_INVALID_ARGUMENT, "ahc: FA_AHC_RO_HANDOVER_AT must be a positive integer, FA_AHC_RO_REPLAY_PAIRS a positive multiple of 4");
+    }
+    if (may_hand_over && force_at > 0) ctx->ahc_adopted.row = -1;
     if (N < 2 || d * sizeof(double) > 60 * 1024) return FA_SUCCESS;
     const size_t Np = (N + kBlk - 1) / kBlk * kBlk, nblk = Np / kBlk;
     if (nblk > static_cast<size_t>(kMaxBlocks)) return FA_SUCCESS;
@@ -650,7 +683,7 @@ fa_status rom_run_device(fa_ctx *ctx, const double *d_data, size_t N, size_t d, 
         hipLaunchKernelGGL(rom_select, dim3(1 + w.nblk), dim3(64), 0, st, w, ph4 & 1);
     };
     RoundGraph rg;
-    rg.capture(ctx, launch, static_cast<int>(std::min<size_t>(256, (N + 3) & ~static_cast<size_t>(3))));
+    rg.capture(ctx, launch, replay_pairs > 0 ? static_cast<int>(replay_pairs) : static_cast<int>(std::min<size_t>(256, (N + 3) & ~static_cast<size_t>(3))));
     const long long max_replays = 16 + 16 * static_cast<long long>(N) / rg.rounds;   // rows + re-scans + exact re-evaluations
     for (long long it = 0; it < max_replays && !hd.done; ++it) {
         FA_TRY(rg.replay(ctx, launch));
@@ -658,17 +691,21 @@ fa_status rom_run_device(fa_ctx *ctx, const double *d_data, size_t N, size_t d, 
         FA_HIP_TRY(ctx, hipStreamSynchronize(st));
         if (fa::sw(fa::Sw::AHC_DEBUG) && (it % 8 == 0 || hd.done))
             fprintf(stderr, "ahc (reference order): replay %lld rows %d last tie at %d nonzero %d scans %lld exact %lld\n", it, hd.merges, hd.last_tie, hd.tie_nonzero, hd.scans, hd.exact_scans);
-        if (may_hand_over && !hd.done && !hd.nan_seen && !hd.tie_nonzero && hd.merges >= 1 && hd.merges - hd.last_tie >= kRomQuiet &&
-            static_cast<long long>(N) - 1 - hd.merges >= kRomMinRest && hd.kind != ROM_EXACT) {
+        const bool quiet = force_at > 0 ? hd.merges >= force_at
+                                        : hd.merges - hd.last_tie >= kRomQuiet && static_cast<long long>(N) - 1 - hd.merges >= kRomMinRest;
+        if (may_hand_over && !hd.done && !hd.nan_seen && !hd.tie_nonzero && hd.merges >= 1 && quiet && hd.kind != ROM_EXACT) {
             // the state of a replay boundary sits in dev[0] (a replay is an even number of launch pairs).  A merge that is decided but not applied yet (ROM_NEW
-            // pending: its row, node id, size and centroid are the next scan's work) is applied by that scan; its column copies stay unwritten, which is
-            // what prob_adopt's sym_limit says.
+            // pending: its row, node id, size and centroid are the next scan's work) is applied by that scan; its column copies M[x][sa] are NOT written (no
+            // rom_select behind it, whose mirror workgroups would) and still hold d(x, a).  prob_adopt's sym_limit (N + merges - 1) says so: every reader of
+            // the rounds takes the pairs of the newest node from its row (pair_entry), ahc_adopt_rows included.  (Mirroring here instead would cost one more
+            // launch over all rows and leave the adopting kernel reading the matrix differently from the rounds.)
             if (hd.kind == ROM_NEW) hipLaunchKernelGGL(rom_scan, dim3(w.nblk + 1), dim3(kBlk), lds, st, w, 0);
             Prob p;
             p.N = N; p.d = d; p.Np = Np; p.cpt = 1; p.d_data = d_data; p.d_Z = d_Z; p.mode = FA_AHC_MODE_AUTO; p.z_on_host = z_on_host;
             p.L = L.core;
             prob_bind(p, base);
             FA_TRY(prob_adopt(ctx, p, hd.merges, hd.eps, w.pair_a, w.pair_b));
+            if (force_at > 0) FA_TRY(rom_record_adopted(ctx, p, hd.merges, hd.kind, hd.eps));
             FA_TRY(prob_run_rounds(ctx, p));
             if (p.needs_ro) { tie_after_hand_over = true; return FA_SUCCESS; }   // an exact tie after all: the caller runs the problem again, in reference order to the end
             FA_HIP_TRY(ctx, hipEventRecord(ev[2], st));

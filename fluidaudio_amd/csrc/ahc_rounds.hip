@@ -124,19 +124,19 @@ fa_status ctx_events(fa_ctx *ctx, hipEvent_t (&ev)[3]) {
 // ---- adopting a clustering in progress (prob_adopt): what the start-up leaves for the rounds, from a matrix some of whose slots are dead already
 namespace {
 // Row minimum, lowest-slot argmin and second minimum of every live row over its LIVE columns (the start-up's ahc_row_minima reads a fresh matrix whose dead
-// columns hold +inf; here merged-away slots hold whatever their last row was).  One workgroup per row.
+// columns hold +inf; here merged-away slots hold whatever their last row was).  One workgroup per row.  Every entry is read as the rounds read it (pair_entry
+// under the sym_limit ahc_adopt_state has just written): the column copies of the newest node may be stale (ahc_rom.hip, the hand-over).
 __global__ __launch_bounds__(kBlk) void ahc_adopt_rows(Ws w) {
     __shared__ double s_val[kWaves], s_second[kWaves];
     __shared__ int s_idx[kWaves];
     __shared__ int s_win;
-    const int i = blockIdx.x;
+    const int i = blockIdx.x, ni = w.node[i], sym_limit = w.state[0].sym_limit;
     double v = dinf(), v2 = dinf();
     int ix = INT_MAX;
-    const bool live_row = w.node[i] != kDead;
-    if (live_row) {
-        const double *row = w.M + static_cast<size_t>(i) * w.Np;
+    if (ni != kDead) {
         for (int x = threadIdx.x; x < w.Np; x += kBlk) {
-            const double m = (x != i && w.node[x] != kDead) ? row[x] : dinf();
+            const int nx = w.node[x];
+            const double m = (x != i && nx != kDead) ? pair_entry(w.M, w.Np, i, ni, x, nx, sym_limit) : dinf();
             if (m < v) { v2 = v; v = m; ix = x; }   // x ascending per thread: the lowest index of equal values is kept
             else if (m < v2) v2 = m;
         }

@@ -226,6 +226,22 @@ fa_status fa_debug_set_switch(const char *name, const char *value) {
 
 int32_t fa_debug_hooks_enabled(void) { return debug_hooks() ? 1 : 0; }
 
+fa_status fa_debug_ahc_adopted(const fa_ctx *ctx, int64_t *row, int32_t *kind, double *eps, size_t *slots, size_t capacity, int32_t *node, double *d1,
+                               int32_t *nn, int32_t *nnnode, double *e2) {
+    if (!ctx || !row || !kind || !eps || !slots) return FA_INVALID_ARGUMENT;
+    if (!debug_hooks()) return FA_RUNTIME_ERROR;
+    const fa_ctx::AhcAdopted &a = ctx->ahc_adopted;
+    *row = a.row; *kind = a.kind; *eps = a.eps;
+    *slots = a.row >= 0 ? a.node.size() : 0;
+    const size_t n = *slots < capacity ? *slots : capacity;
+    if (n && node) memcpy(node, a.node.data(), sizeof(int32_t) * n);
+    if (n && d1) memcpy(d1, a.d1.data(), sizeof(double) * n);
+    if (n && nn) memcpy(nn, a.nn.data(), sizeof(int32_t) * n);
+    if (n && nnnode) memcpy(nnnode, a.nnnode.data(), sizeof(int32_t) * n);
+    if (n && e2) memcpy(e2, a.e2.data(), sizeof(double) * n);
+    return FA_SUCCESS;
+}
+
 fa_status fa_ctx_create(int device, void *stream, fa_ctx **out) {
     if (!out) return FA_INVALID_ARGUMENT;
     *out = nullptr;

@@ -62,6 +62,15 @@ struct fa_ctx {
     double last_device_ms = -1.0;
     // fa_offline_cluster_batch prepares / finishes its recordings on worker contexts (own stream each); kept between calls since round 4
     fa_ctx *workers[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // test hook (fa_debug_ahc_adopted): what the filter-based rounds adopted at the last hand-over of AUTO's tie route on this context — recorded only
+    // while FA_AHC_RO_HANDOVER_AT is set (ahc_rom.hip); per slot: node id, row record (d1, nn, nnnode), e2
+    struct AhcAdopted {
+        int64_t row = -1;                      // dendrogram rows done at the hand-over (-1: none recorded)
+        int32_t kind = -1;                     // what was pending at that replay boundary (0: a new row, 1: a re-scan)
+        double eps = 0.0;
+        std::vector<int32_t> node, nn, nnnode;
+        std::vector<double> d1, e2;
+    } ahc_adopted;
 };
 
 namespace fa {
@@ -120,6 +129,7 @@ bool fault_hit(int site);
     ROUTE(HIP_WORKSPACE_LIMIT, "FLUIDAUDIO_HIP_WORKSPACE_LIMIT") ROUTE(HIP_DEVICES, "FLUIDAUDIO_HIP_DEVICES") ROUTE(HIP_DEVICE, "FLUIDAUDIO_HIP_DEVICE") \
     ROUTE(AHC_CPT, "FA_AHC_CPT") ROUTE(AHC_NO_SINGLE_BLOCK, "FA_AHC_NO_SINGLE_BLOCK") ROUTE(AHC_NO_UNIFORM, "FA_AHC_NO_UNIFORM")      \
     ROUTE(AHC_RO_NO_MATRIX, "FA_AHC_RO_NO_MATRIX") ROUTE(AHC_RO_NO_HANDOVER, "FA_AHC_RO_NO_HANDOVER") ROUTE(AHC_UNI_CPT, "FA_AHC_UNI_CPT") ROUTE(AHC_UNI_GROUPS, "FA_AHC_UNI_GROUPS")    \
+    ROUTE(AHC_RO_HANDOVER_AT, "FA_AHC_RO_HANDOVER_AT") ROUTE(AHC_RO_REPLAY_PAIRS, "FA_AHC_RO_REPLAY_PAIRS")                           \
     ROUTE(AHC_UNI_WAVES, "FA_AHC_UNI_WAVES") ROUTE(AHC_IN_FLIGHT, "FA_AHC_IN_FLIGHT") ROUTE(AHC_DEBUG, "FA_AHC_DEBUG")                \
     ROUTE(MEL_GENERIC, "FA_MEL_GENERIC") ROUTE(MEL_SLICE_MB, "FA_MEL_SLICE_MB") ROUTE(VBX_NO_TILED, "FA_VBX_NO_TILED")                \
     ROUTE(RESAMPLE_SIMPLE, "FA_RESAMPLE_SIMPLE") ROUTE(RESAMPLE_NO_DECIM, "FA_RESAMPLE_NO_DECIM")                                     \

@@ -86,6 +86,12 @@ const char *fa_version(void);
  *   FA_AHC_NO_UNIFORM, FA_AHC_IN_FLIGHT, FA_AHC_UNI_GROUPS=1..4, FA_AHC_UNI_WAVES=6|8   how a batch of problems is laid over launches / streams
  *   FA_AHC_RO_NO_MATRIX                      the reference-order run without the N x N filter matrix (O(N d) memory, like the reference)
  *   FA_AHC_RO_NO_HANDOVER                    AUTO's tie route stays in reference order to the last row (no hand-over to the rounds once the ties have stopped)
+ *   FA_AHC_RO_HANDOVER_AT=row                AUTO's tie route hands over at the first replay boundary with >= row rows done, whatever the ties did before
+ *                                            (the other conditions stay: no tie above height 0 seen, no exact re-scan pending); fa_debug_ahc_adopted
+ *                                            records what the rounds adopt there
+ *   FA_AHC_RO_REPLAY_PAIRS=k                 (scan, select) launch pairs per graph replay of the reference-order run (default min(256, N rounded up
+ *                                            to 4)); a positive multiple of 4, anything else fails a call that runs in reference order with
+ *                                            INVALID_ARGUMENT.  4: a hand-over lands within 4 rows of any chosen row
  *   FA_AHC_DEBUG                             one line of statistics per linkage call on stderr
  *   FA_MEL_GENERIC, FA_MEL_SLICE_MB=n        the generic mel kernel; slice size of host-pointer batches
  *   FA_VBX_NO_TILED                          the untiled VBx iteration
@@ -94,6 +100,15 @@ const char *fa_version(void);
  * on other threads).  RUNTIME_ERROR without FLUIDAUDIO_HIP_DEBUG_HOOKS=1, INVALID_ARGUMENT for an unknown name. */
 fa_status fa_debug_set_switch(const char *name, const char *value);
 int32_t fa_debug_hooks_enabled(void);
+/* Test hook: the state the filter-based rounds adopted at the last hand-over of AUTO's tie route on this context, recorded only while
+ * FA_AHC_RO_HANDOVER_AT is set (one synchronisation and a copy of O(slots) values per hand-over; nothing without the switch).
+ * *row: dendrogram rows done at the hand-over (-1: none recorded, or the last tie route run under the switch did not hand over),
+ * *kind: what was pending at that replay boundary (0: a merge decided, its row not yet written; 1: a re-scan), *eps: the bound of
+ * |matrix entry - exact squared distance| the rounds certify with, *slots: matrix slots.  The arrays (nullable) take the first min(capacity, slots) slots: node id (INT32_MAX: empty slot),
+ * the row record (d1: smallest entry over the other live slots, nn: its slot, lowest on ties, nnnode: that slot's node id) and e2 (smallest
+ * entry other than column nn).  RUNTIME_ERROR without FLUIDAUDIO_HIP_DEBUG_HOOKS=1. */
+fa_status fa_debug_ahc_adopted(const fa_ctx *ctx, int64_t *row, int32_t *kind, double *eps, size_t *slots, size_t capacity, int32_t *node, double *d1,
+                               int32_t *nn, int32_t *nnnode, double *e2);
 /* Test hook: the next `count` passes through `site` fail the way the real failure would (count 0 disarms).  Process-wide; one relaxed
  * atomic load on the paths that carry a site.  Inert unless the process was started with FLUIDAUDIO_HIP_DEBUG_HOOKS=1.  Used by the
  * fault-injection tests of the degrade contracts:
