@@ -11,9 +11,11 @@ from .ctc import (LogitsArgmax, ctc_greedy_decode, ctc_greedy_ids_batch, ctc_gre
 from .formats import AudioWAV, RTTMParser, RTTMParserError, TimedSpeakerSegment, export_embeddings_json  # noqa: F401
 from .kmeans import KMeansClustering, SeededRNG, SpeakerCountConstraints  # noqa: F401
 from .mel import AudioMelSpectrogram, LuxTtsMelExtractor, MelPlan, UnifiedMelExtractor  # noqa: F401
-from .pipeline import (ClusteringResult, OfflineClusteringConfig, cluster_embeddings, cluster_embeddings_batch, cluster_embeddings_stagewise,  # noqa: F401
+from .pipeline import (ClusteringResult, OfflineClusteringConfig, cluster_embeddings, cluster_embeddings_batch, cluster_embeddings_stagewise, diarize_segments,  # noqa: F401
                        select_training_embeddings)
 from .pool import Pool, device_count  # noqa: F401
+from .reconstruct import (OfflineReconstruction, ReconstructionConfig, SegmentationOutput, chunk_assignments, finalize_segments,  # noqa: F401
+                          powerset_decode)
 from .post import (ConstrainedClusterAssignment, HungarianAssignment, assign_embeddings, centroid_scores,  # noqa: F401
                    compute_centroids)
 from .resample import linear_resample, poly_taps, resample_poly  # noqa: F401

@@ -51,6 +51,8 @@ EXPORTED_SYMBOLS = [
     "fa_resample_linear_frames", "fa_resample_linear", "fa_resample_poly_frames", "fa_resample_poly_taps", "fa_resample_poly", "fa_resample_poly_dev",
     "fa_device_count", "fa_pool_create", "fa_pool_destroy", "fa_pool_size", "fa_pool_context", "fa_ctx_device", "fa_pool_acquire", "fa_pool_release",
     "fa_mel_batch_sharded", "fa_ctc_greedy_batch_sharded", "fa_ahc_linkage_many",
+    "fa_powerset_decode_dev", "fa_powerset_decode", "fa_offline_chunk_assignments", "fa_reconstruct_default_config",
+    "fa_offline_reconstruct", "fa_offline_reconstruct_dev", "fa_segments_finalize",
 ]
 
 
@@ -92,6 +94,19 @@ class OfflineClusterInfo(C.Structure):
                 ("was_adjusted", C.c_int32), ("constrained", C.c_int32), ("vbx_degraded", C.c_int32), ("ahc_degraded", C.c_int32),
                 ("inputs_s", C.c_double), ("ahc_s", C.c_double),
                 ("vbx_s", C.c_double), ("assign_s", C.c_double), ("total_s", C.c_double), ("ahc", AhcStats)]
+
+
+class ReconstructConfig(C.Structure):
+    _fields_ = [("window_duration", C.c_double), ("frame_duration", C.c_double), ("min_duration_on", C.c_double),
+                ("min_duration_off", C.c_double), ("min_segment_duration", C.c_double), ("min_gap_duration", C.c_double),
+                ("exclusive", C.c_int32), ("zero_vote_enabled", C.c_int32), ("zero_vote_min_duration", C.c_double)]
+
+
+class ReconstructInfo(C.Structure):
+    _fields_ = [("total_frames", C.c_int64), ("raw_segments", C.c_int64), ("frame_duration", C.c_double),
+                ("zero_vote_run_count", C.c_int64), ("zero_vote_runs", C.c_void_p), ("zero_vote_capacity", C.c_int64),
+                ("speaker_counts", C.c_void_p), ("speaker_counts_capacity", C.c_int64), ("frame_capacity", C.c_int64),
+                ("frame_clusters", C.c_void_p), ("frame_averages", C.c_void_p), ("expected_count_sums", C.c_void_p), ("frame_slots", C.c_int32)]
 
 
 def build(force: bool = False) -> str:
@@ -281,6 +296,15 @@ def lib() -> C.CDLL:
     L.fa_mel_batch_sharded.argtypes = [vp, C.POINTER(MelConfig), vp, vp, i32, vp, vp, i32, vp, vp]
     L.fa_ctc_greedy_batch_sharded.argtypes = [vp, vp, i32, i32, i32, i32, i64, i64, vp, i32, vp, vp, vp]
     L.fa_ahc_linkage_many.argtypes = [vp, i32, vp, vp, sz, vp, i32, vp, vp]
+    L.fa_powerset_decode_dev.argtypes = [vp, vp, i64, i32, i32, vp, vp]
+    L.fa_powerset_decode.argtypes = [vp, vp, i64, i32, i32, vp, vp]
+    L.fa_offline_chunk_assignments.argtypes = [i64, vp, vp, vp, i32, i32, i32, vp]
+    L.fa_reconstruct_default_config.argtypes = [C.POINTER(ReconstructConfig)]
+    L.fa_reconstruct_default_config.restype = None
+    L.fa_offline_reconstruct.argtypes = [vp, C.POINTER(ReconstructConfig), vp, i64, i32, i32, vp, i64, vp, i32, vp, i64, vp, i64,
+                                         C.POINTER(i64), C.POINTER(ReconstructInfo)]
+    L.fa_offline_reconstruct_dev.argtypes = L.fa_offline_reconstruct.argtypes
+    L.fa_segments_finalize.argtypes = [C.POINTER(ReconstructConfig), vp, i64, vp, i64, C.POINTER(i64)]
     _lib = L
     return L
 

@@ -268,3 +268,30 @@ def cluster_embeddings_stagewise(embedding256, rho128, chunk_indices, phi, confi
         assignments = assign_embeddings(emb, centroids, ctx=ctx)
     t["assign_s"] = time.perf_counter() - t0
     return ClusteringResult(assignments, centroids, list(initial), vbx, train, t)
+
+
+@dataclass
+class DiarizationSegments:
+    segments: list
+    speaker_database: dict
+    clustering: ClusteringResult
+    hard_clusters: np.ndarray
+    info: dict = field(default_factory=dict)
+
+
+def diarize_segments(embedding256, rho128, chunk_indices, speaker_indices, phi, segmentation, config: OfflineClusteringConfig | None = None,
+                     reconstruction=None, span_embedder=None, ctx: L.Context | None = None) -> DiarizationSegments:
+    """The rest of OfflineDiarizerManager.cluster (:377-467) behind ``cluster_embeddings``: chunk assignments (buildChunkAssignments,
+    :885-911) -> OfflineReconstruction.buildSegments -> buildSpeakerDatabase, i.e. DiarizationResult.segments / .speakerDatabase.
+    ``segmentation`` is a ``reconstruct.SegmentationOutput`` (speaker weights [chunks, frames, speakers], numpy or a torch CUDA tensor:
+    ``powerset_decode`` of the segmentation logits); ``speaker_indices`` is each embedding's local speaker slot in its chunk;
+    ``reconstruction`` a ``reconstruct.ReconstructionConfig``."""
+    from .reconstruct import OfflineReconstruction, chunk_assignments
+    ctx = ctx or L.default_context()
+    res = cluster_embeddings(embedding256, rho128, chunk_indices, phi, config, ctx=ctx)
+    nc, _, ns = segmentation.shape
+    k = int(res.centroids.shape[0])
+    hard = chunk_assignments(chunk_indices, speaker_indices, res.assignments, k, nc, ns)
+    rec = OfflineReconstruction(reconstruction, ctx=ctx)
+    segs = rec.build_segments(segmentation, hard, res.centroids, span_embedder)
+    return DiarizationSegments(segs, rec.build_speaker_database(segs, res.centroids), res, hard, dict(rec.last_info))

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <map>
 #include <optional>
 #include <stdexcept>
@@ -521,6 +522,77 @@ struct RTTMParser {
         if (count) fa_rttm_parse(text.data(), static_cast<int64_t>(text.size()), 1, segs.data(), count, &count, bad, sizeof(bad));
         return segs;
     }
+};
+
+
+// ------------------------------------------------------------------------------------------------------------------ speaker segments
+// OfflineReconstruction (Sources/FluidAudio/Diarizer/Offline/Utils/OfflineReconstruction.swift:24-357) over fa_offline_reconstruct:
+// speakerWeights [chunks][frames][speakers] (powerset decode output), hardClusters [chunks][speakers] (chunk assignments, -2 = none),
+// centroids [K][d].  buildSegments runs on the device; buildSpeakerDatabase is the host fp32 average of the segments' centroids.
+// The zero-vote re-embed pass is the caller's (fa_reconstruct_info.zero_vote_runs + overrides, include/fluidaudio_hip.h).
+class OfflineReconstruction {
+public:
+    struct Result { std::vector<fa_rttm_segment> segments; std::map<std::string, std::vector<float>> speakerDatabase; };
+    explicit OfflineReconstruction(fa_reconstruct_config config = defaultConfig()) : cfg_(config) {}
+    static fa_reconstruct_config defaultConfig() { fa_reconstruct_config c; fa_reconstruct_default_config(&c); return c; }
+    std::vector<fa_rttm_segment> buildSegments(Context &ctx, const std::vector<std::vector<std::vector<float>>> &speakerWeights,
+                                               const std::vector<double> &chunkOffsets, const std::vector<std::vector<int>> &hardClusters,
+                                               int32_t clusterCount) const {
+        const int64_t C = static_cast<int64_t>(speakerWeights.size());
+        const int32_t F = C ? static_cast<int32_t>(speakerWeights[0].size()) : 0;
+        const int32_t S = F ? static_cast<int32_t>(speakerWeights[0][0].size()) : 0;
+        std::vector<float> w;
+        w.reserve(static_cast<size_t>(C * F * S));
+        for (const auto &chunk : speakerWeights) {
+            if (static_cast<int32_t>(chunk.size()) != F) throw Error(FA_INVALID_ARGUMENT, "OfflineReconstruction: ragged frames");
+            for (const auto &frame : chunk) {
+                if (static_cast<int32_t>(frame.size()) != S) throw Error(FA_INVALID_ARGUMENT, "OfflineReconstruction: ragged speakers");
+                w.insert(w.end(), frame.begin(), frame.end());
+            }
+        }
+        std::vector<int32_t> hard(static_cast<size_t>(C * S), -2);   // chunks past hardClusters.count: -2 (:65-67)
+        for (size_t c = 0; c < hardClusters.size() && static_cast<int64_t>(c) < C; ++c)
+            for (size_t s = 0; s < hardClusters[c].size() && static_cast<int32_t>(s) < S; ++s) hard[c * S + s] = hardClusters[c][s];
+        int64_t n = 0;
+        fa_reconstruct_info info{};
+        const auto call = [&](fa_rttm_segment *out, int64_t cap) {
+            return fa_offline_reconstruct(ctx.handle(), &cfg_, w.data(), C, F, S, chunkOffsets.data(), static_cast<int64_t>(chunkOffsets.size()), hard.data(),
+                                          clusterCount, nullptr, 0, out, cap, &n, &info);
+        };
+        std::vector<fa_rttm_segment> segs(4096);
+        fa_status st = call(segs.data(), static_cast<int64_t>(segs.size()));
+        if (st == FA_OUTPUT_TOO_SMALL) { segs.resize(static_cast<size_t>(n)); st = call(segs.data(), n); }
+        ctx.check(st, "fa_offline_reconstruct");
+        segs.resize(static_cast<size_t>(n));
+        return segs;
+    }
+    // buildSpeakerDatabase (:300-357): per speaker the fp32 sum of Float(centroid) over its segments, in segment order, times 1 / Float(count)
+    static std::map<std::string, std::vector<float>> buildSpeakerDatabase(const std::vector<fa_rttm_segment> &segments, const Matrix &centroids) {
+        std::map<std::string, std::vector<float>> sums;
+        std::map<std::string, int> counts;
+        const size_t dim = centroids.empty() ? 0 : centroids[0].size();
+        for (const auto &s : segments) {
+            const std::string id(s.speaker_id);
+            const long k = std::strtol(s.speaker_id + 1, nullptr, 10) - 1;
+            std::vector<float> e(dim, 0.0f);
+            if (k >= 0 && static_cast<size_t>(k) < centroids.size()) for (size_t i = 0; i < dim; ++i) e[i] = static_cast<float>(centroids[k][i]);
+            auto it = sums.find(id);
+            if (it == sums.end()) sums.emplace(id, e);
+            else for (size_t i = 0; i < dim; ++i) it->second[i] += e[i];
+            ++counts[id];
+        }
+        for (auto &kv : sums) { const float scale = 1.0f / static_cast<float>(counts[kv.first]); for (float &v : kv.second) v *= scale; }
+        return sums;
+    }
+    Result build(Context &ctx, const std::vector<std::vector<std::vector<float>>> &speakerWeights, const std::vector<double> &chunkOffsets,
+                 const std::vector<std::vector<int>> &hardClusters, const Matrix &centroids) const {
+        Result r;
+        r.segments = buildSegments(ctx, speakerWeights, chunkOffsets, hardClusters, static_cast<int32_t>(centroids.size()));
+        r.speakerDatabase = buildSpeakerDatabase(r.segments, centroids);
+        return r;
+    }
+private:
+    fa_reconstruct_config cfg_;
 };
 
 }  // namespace fluidaudio

@@ -597,6 +597,80 @@ int64_t fa_export_embeddings_json(const fa_export_embedding *items, int64_t n, c
                                   const double *rho128, int32_t rho_dim, const int32_t *assignments, int64_t n_assignments,
                                   char *out, int64_t out_capacity);
 
+/* ------------------------------------------------------------------ speaker segments ------ */
+/* The powerset decode of OfflineSegmentationProcessor (FluidAudio/Diarizer/Offline/Segmentation/OfflineSegmentationProcessor.swift:316-409):
+ * logits float[chunks][frames][classes] -> weights float[chunks][frames][3], 1.0 for each local speaker of powerset[min(argmax, 7)]
+ * (table :15-24: [] [0] [1] [2] [0,1] [0,2] [1,2] [0,1,2]) and 0 otherwise, bit-exact; the argmax is the first strict maximum
+ * seeded at -FLT_MAX (NaN never wins, an all-NaN / all--inf row is class 0).  log_probs float[chunks][frames][classes] (nullable)
+ * = logits - logSumExp(logits) in fp32 (VDSPOperations.swift:142-155; informational, the reference's vvexpf is closed source).
+ * _dev: DEVICE pointers, enqueued on the context's stream (no synchronisation); otherwise HOST pointers. */
+fa_status fa_powerset_decode_dev(fa_ctx *ctx, const float *d_logits, int64_t chunks, int32_t frames, int32_t classes, float *d_weights,
+                                 float *d_log_probs);
+fa_status fa_powerset_decode(fa_ctx *ctx, const float *logits, int64_t chunks, int32_t frames, int32_t classes, float *weights,
+                             float *log_probs);
+/* OfflineDiarizerManager.buildChunkAssignments (FluidAudio/Diarizer/Offline/Core/OfflineDiarizerManager.swift:885-911): hard
+ * int32[chunks][speakers] = -2, then for every embedding i in order hard[chunk_indices[i]][speaker_indices[i]] = labels[i] when the
+ * chunk, the speaker and the label (< cluster_count) are in range; a later embedding overwrites an earlier one.  Pure host function. */
+fa_status fa_offline_chunk_assignments(int64_t n, const int32_t *chunk_indices, const int32_t *speaker_indices, const int32_t *labels,
+                                       int32_t cluster_count, int32_t chunks, int32_t speakers, int32_t *hard);
+/* OfflineReconstruction (FluidAudio/Diarizer/Offline/Utils/OfflineReconstruction.swift:24-237, 359-496).  Defaults =
+ * OfflineDiarizerTypes.swift:46-55, 97-103, 204-214, 232-247. */
+typedef struct {
+    double window_duration;          /* 10.0: start of a chunk without an offset = index * window_duration (:498-507) */
+    double frame_duration;           /* 0 = window_duration / frames (OfflineSegmentationProcessor.swift:286) */
+    double min_duration_on;          /* 0 (segmentation.minDurationOn) */
+    double min_duration_off;         /* 0 (segmentation.minDurationOff) */
+    double min_segment_duration;     /* 1.0 */
+    double min_gap_duration;         /* 0.1 */
+    int32_t exclusive;               /* 1: excludeOverlaps (:359-398) */
+    int32_t zero_vote_enabled;       /* 0: the zero-vote re-embed pass (host side: the caller embeds the runs, see overrides) */
+    double zero_vote_min_duration;   /* 0.4 */
+} fa_reconstruct_config;
+void fa_reconstruct_default_config(fa_reconstruct_config *cfg);
+typedef struct {
+    /* out */
+    int64_t total_frames;            /* global frames (:37-47) */
+    int64_t raw_segments;            /* segments before merge / sanitize */
+    double frame_duration;           /* the frame duration used */
+    int64_t zero_vote_run_count;     /* runs found (when zero_vote_runs is set), also those that did not fit */
+    /* in: optional HOST buffers the call fills (NULL: not wanted) */
+    int64_t *zero_vote_runs;         /* int64[2 * zero_vote_capacity]: [first, end) frames of each zero-vote run of at least
+                                        cfg->zero_vote_min_duration (ZeroVoteReembedder.detectRuns, ZeroVoteReembedder.swift:42-79) */
+    int64_t zero_vote_capacity;
+    int32_t *speaker_counts;         /* int32[speaker_counts_capacity]: speakerCountPerFrame (:145-156), written when it holds total_frames */
+    int64_t speaker_counts_capacity;
+    /* the per-frame decision in fp64 (verification of the summation order), written when frame_capacity >= total_frames; each may be NULL */
+    int64_t frame_capacity;
+    int32_t *frame_clusters;         /* int32[frame_capacity * slots]: each frame's active clusters by rank (overrides applied), -1 past them */
+    double *frame_averages;          /* double[frame_capacity * slots]: their activation averages sum / count (:107-143), 0 past them */
+    double *expected_count_sums;     /* double[frame_capacity]: the fp64 sum of expectedCount over the frame's chunk frames (:90-94) */
+    int32_t frame_slots;             /* out: slots = max(min(max(clusters, 1), speakers), 1) */
+} fa_reconstruct_info;
+/* buildSegments -> mergeSegments -> sanitize on the device (the merge / sanitize pass over the raw segments is host code in the same call).
+ * weights float[chunks][frames][speakers] per-speaker activity (fa_powerset_decode's output, or any finite values: a non-finite one is
+ * INVALID_ARGUMENT, the reference traps); offsets double[n_offsets] chunk start times in seconds (chunks past n_offsets start at
+ * index * window_duration); hard int32[chunks][speakers] cluster per local speaker (fa_offline_chunk_assignments; values outside
+ * [0, max(clusters, 1)) count as none; NULL: none); clusters = centroids.count.  overrides int64[n_overrides][3] = (first frame, end
+ * frame, cluster): those frames' clusters become [cluster], applied in order (the zero-vote re-embed assignments, :249-298).
+ * out: fa_rttm_segment[capacity], speaker_id "S<k+1>"; *count is set even when out is NULL (SUCCESS) or too small (OUTPUT_TOO_SMALL).
+ * Raw segments that close at the same frame are taken in increasing cluster index (the reference uses Dictionary order, which is
+ * hash-seeded); a segment open after the last frame closes at frame total_frames.  Empty input (chunks or frames 0, frame
+ * duration <= 0) -> 0 segments.  weights: HOST pointer; _dev: DEVICE pointer on the context's device, read in stream order.
+ * The other pointers are HOST pointers; the call is synchronous. */
+fa_status fa_offline_reconstruct(fa_ctx *ctx, const fa_reconstruct_config *cfg, const float *weights, int64_t chunks, int32_t frames,
+                                 int32_t speakers, const double *offsets, int64_t n_offsets, const int32_t *hard, int32_t clusters,
+                                 const int64_t *overrides, int64_t n_overrides, fa_rttm_segment *out, int64_t capacity, int64_t *count,
+                                 fa_reconstruct_info *info);
+fa_status fa_offline_reconstruct_dev(fa_ctx *ctx, const fa_reconstruct_config *cfg, const float *d_weights, int64_t chunks, int32_t frames,
+                                     int32_t speakers, const double *offsets, int64_t n_offsets, const int32_t *hard, int32_t clusters,
+                                     const int64_t *overrides, int64_t n_overrides, fa_rttm_segment *out, int64_t capacity,
+                                     int64_t *count, fa_reconstruct_info *info);
+/* mergeSegments (:431-463; same speaker and start - previous end <= max(min_gap_duration, min_duration_off), quality blended by
+ * duration) -> sanitize (:481-496; drop shorter than max(min_segment_duration, min_duration_on), then excludeOverlaps when exclusive)
+ * over raw segments in their raw order.  Pure host function; *count as fa_offline_reconstruct's. */
+fa_status fa_segments_finalize(const fa_reconstruct_config *cfg, const fa_rttm_segment *raw, int64_t n, fa_rttm_segment *out,
+                               int64_t capacity, int64_t *count);
+
 /* ------------------------------------------------------------------ resampling ------ */
 /* AudioConverter.linearResample (FluidAudio/Shared/AudioConverter.swift:388-442): planar float[channels][frames] ->
  * mono mix (weight 1/channels) -> linear interpolation to out_rate.  HOST pointers.  Bit-exact restatement. */
