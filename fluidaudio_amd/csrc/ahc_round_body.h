@@ -136,6 +136,97 @@ __device__ __forceinline__ void block_record(const Ws &w, const int par, const i
     }
 }
 
+// The row of column x against its entry dc for the cluster merged from slots a < b (node nnew), one slot per thread.  e2 bounds the entries of the row OTHER
+// than the nearest neighbour's from below (exact second minimum after the start-up scan, then maintained: an entry that appears lowers it, entries that
+// disappear leave it a bound).  It decides the case that used to make half of all rows stale on chaining data — the nearest neighbour WAS one of the merged
+// slots (every point's nearest neighbour is the growing cluster) and the new entry is larger than the old minimum: if it is still below everything else
+// (dc < e2) the row simply keeps the cluster as its neighbour.  Shared by the merge phase and the speculative merge, so both write the same bits.
+// Returns what changed: bit 0 the row record, bit 1 e2 (flags by value: bool references kept the callers' flags in scratch memory).
+__device__ __forceinline__ int row_update1(RowSt &r, double &e2, const double dc, const int a, const int b, const int nnew) {
+    const bool vld = r.nn >= 0;
+    const bool hit = vld && (r.nn == a || r.nn == b);
+    if (!hit) {
+        if (dc < r.d1 || (vld && dc == r.d1 && a <= r.nn)) {   // new minimum (a stale row: dc below its bound IS its minimum)
+            e2 = r.d1; r.d1 = dc; r.nn = a; r.nnnode = nnew; return 3;
+        } else if (dc < e2) { e2 = dc; return 2; }
+        return 0;
+    } else if (dc < e2) {                                      // unique minimum again (strict: a tie goes to a re-scan)
+        r.d1 = dc; r.nn = a; r.nnnode = nnew; return 1;
+    }
+    r.d1 = e2; r.nn = -1;                                      // minimum lost: every entry is >= min(e2, dc) = e2, a lower bound
+    return 1;
+}
+
+// Lance-Williams centroid value of a column from its entries da, db for the merged slots (weights wa, wb, wab of the merge phase); clamped at 0, which also
+// keeps -0.0 out of the bit-pattern reductions.  Shared by the merge phase, the speculative merge and the ranking of its candidates.
+__device__ __forceinline__ double lw_value(const double wa, const double da, const double wb, const double db, const double wab, const double dab) {
+    double v = wa * da + wb * db - wab * dab;
+    if (!(v > 0.0)) v = 0.0;
+    return v;
+}
+
+// Merged centroid element (FastClusterWrapper.cpp:89-100): explicit rounding steps, so every workgroup that recomputes a centroid gets the bits workgroup 0 stores.
+__device__ __forceinline__ double centroid_elem(const double xa, const double ma, const double xb, const double mb, const double den) {
+    return __ddiv_rn(__dadd_rn(__dmul_rn(xa, ma), __dmul_rn(xb, mb)), den);
+}
+
+// The block records of a speculative round (one slot per thread): the base record and the produced row's partial minimum as block_record writes them, and the
+// same two for the state under the speculated merge (hypothesis records: packed form + partial minimum) — four quantities, one LDS exchange.
+struct WaveOut2 {
+    QOut q[kWaves][4];
+    int cnt[kWaves][2];
+};
+__device__ __forceinline__ void block_record_spec(const Ws &w, const int par, const int blk, const double eps, const double key, const double pkey, const int pnode,
+                                                  const int x, const int nx, const int nnx, const int nnnodex, const double hkey, const double hpkey, const int hpnode,
+                                                  const int hnx, const int hnnx, const int hnnnodex, RecP *const hpart, int4 *const hpack, WaveOut2 *s_out) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const double keys[4] = {key, pkey, hkey, hpkey};
+    double m[4];
+    int L[4];
+    wave_min_multi<4>(keys, m, L);
+    QOut o[4];
+    o[0].v = m[0]; o[0].a = lane_value(x, L[0]); o[0].b = lane_value(nnx, L[0]); o[0].c = lane_value(nx, L[0]); o[0].d = lane_value(nnnodex, L[0]);
+    o[1].v = m[1]; o[1].a = lane_value(x, L[1]); o[1].b = lane_value(pnode, L[1]); o[1].c = 0; o[1].d = 0;
+    o[2].v = m[2]; o[2].a = lane_value(x, L[2]); o[2].b = lane_value(hnnx, L[2]); o[2].c = lane_value(hnx, L[2]); o[2].d = lane_value(hnnnodex, L[2]);
+    o[3].v = m[3]; o[3].a = lane_value(x, L[3]); o[3].b = lane_value(hpnode, L[3]); o[3].c = 0; o[3].d = 0;
+    const int c0 = wave_count(key <= m[0] + 2.0 * eps && key < dinf()), c1 = wave_count(hkey <= m[2] + 2.0 * eps && hkey < dinf());
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s_out->q[wave][q] = o[q];
+        s_out->cnt[wave][0] = c0; s_out->cnt[wave][1] = c1;
+    }
+    lds_barrier();
+    if (tid >= 4) return;
+    QOut best = s_out->q[0][tid];
+    QOut other[kWaves];
+#pragma unroll
+    for (int wv = 1; wv < kWaves; ++wv) other[wv] = s_out->q[wv][tid];
+    const double v0 = best.v;
+#pragma unroll
+    for (int wv = 1; wv < kWaves; ++wv) if (other[wv].v < best.v) best = other[wv];
+    const size_t o1 = static_cast<size_t>(par) * w.nblk + blk;
+    const bool any = best.v < dinf();
+    if (tid == 0 || tid == 2) {
+        const int k = tid >> 1;
+        int cnt = 0;
+        if (v0 <= best.v + 2.0 * eps) cnt += s_out->cnt[0][k];
+#pragma unroll
+        for (int wv = 1; wv < kWaves; ++wv) if (other[wv].v <= best.v + 2.0 * eps) cnt += s_out->cnt[wv][k];
+        const int4 packed = rec_pack(best.v, cnt, any ? best.a - blk * kBlk : 0, any ? best.b : -1, any ? best.c : 0, any ? best.d : 0);
+        if (tid == 0) {
+            RecA ra; ra.v1 = best.v; ra.cnt = cnt; ra.pad = 0;
+            w.recA[o1] = ra;
+            w.recI[o1] = any ? make_int4(best.a, best.b, best.c, best.d) : make_int4(-1, -1, -1, -1);
+            w.recI[2 * static_cast<size_t>(w.nblk) + o1] = packed;
+        } else hpack[o1] = packed;
+    } else {
+        RecP rp; rp.pv = best.v;
+        rp.slot = any ? best.a : -1; rp.node = any ? best.b : -1;
+        if (tid == 1) w.recP[static_cast<size_t>(par) * kPend * w.nblk + blk] = rp;
+        else hpart[o1] = rp;
+    }
+}
+
 template <int CPT>
 __global__ __launch_bounds__(kBlk) void ahc_records(Ws w) {  // records of BOTH parities (blockIdx.y) from the row arrays; one workgroup per block of kBlk * CPT slots.
     // Parity 1 too: a round requests the operands of its presumptive merge from the records BEFORE it looks at the halt flag, and a run that halts in
@@ -284,9 +375,12 @@ struct Dec {
 // wavefront its DPP reductions, the centroid sum, the decision arithmetic: ~830 instructions per wavefront and round whatever it owns — so
 // there a thread owns 4 slots: a quarter of the workgroups, wavefronts and block records per problem, and only the per-slot part of a round
 // (the two matrix entries, the Lance-Williams value, the row bookkeeping) is repeated per slot.
-template <bool N_IN_STATE = false, bool BIG = true, int CPT = 1, int KC = 4 / CPT>
+// SPEC: the speculative round (ahc_ws.h, AhcSpec): one problem, one slot per thread, at most 65 536 slots, AUTO mode, even d <= 256 (the host
+// picks it only then).  Every other instantiation compiles to the one-merge round.
+template <bool N_IN_STATE = false, bool BIG = true, int CPT = 1, int KC = 4 / CPT, bool SPEC = false>
 __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, const int ph /* round index & 3 */, const size_t late_shift = 0) {
     static_assert(CPT == 1 || kPiggy == 0, "piggy-backed re-scans were only ever built for one slot per thread");
+    static_assert(!SPEC || (CPT == 1 && !BIG && !N_IN_STATE && kPend == 1), "the speculative round is built for one problem, one slot per thread, the register path");
     constexpr int kCols = kBlk * CPT;
     // Requests of the round's second memory round trip: behind their conditions (single chain) or unconditional with dropped values (launches over several
     // problems).  A conditional request costs the compiler its count of the in-order memory counter — behind the join it no longer knows how many requests are
@@ -301,6 +395,9 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
     __shared__ double s_sq[kBlk];
     __shared__ double s_val[kWaves];
     __shared__ int s_idx[2 * kWaves];
+    __shared__ Dec s_hdec;        // SPEC: the decision from the hypothesis records
+    __shared__ WaveOut2 s_out2[1];
+    __shared__ int s_zs[2];       // SPEC: the speculated partner (slot, node)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, x0 = (blk * kBlk + tid) * CPT;   // x0: the first of this thread's slots
     const int par = ph & 1, npar = par ^ 1;
@@ -328,12 +425,16 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
     {
         // wave 0 reads the PACKED records (rec_pack, ahc_ws.h: one request per record instead of two — 5.07 -> 4.96 us per round at 43 200 points); a second
         // request per record only where a row wave finishes two rows
-        const void *b0 = wave == 0 ? static_cast<const void *>(w.recI + 2 * static_cast<size_t>(nblk) + ro) : static_cast<const void *>(w.recP + (static_cast<size_t>(par) * kPend + pk0) * nblk);
+        // SPEC: wave 1 reads the packed hypothesis records, wave 2 the hypothesis partial minima of the speculated row (both idle here otherwise)
+        const void *b0 = wave == 0 ? static_cast<const void *>(w.recI + 2 * static_cast<size_t>(nblk) + ro)
+                         : (SPEC && wave == 1) ? static_cast<const void *>(reinterpret_cast<const int4 *>(w.recP + 2 * kPend * static_cast<size_t>(nblk) + 2 * static_cast<size_t>(nblk)) + ro)
+                         : (SPEC && wave == 2) ? static_cast<const void *>(w.recP + 2 * kPend * static_cast<size_t>(nblk) + ro)
+                                               : static_cast<const void *>(w.recP + (static_cast<size_t>(par) * kPend + pk0) * nblk);
         const void *b1 = wave == 0 ? static_cast<const void *>(w.recI + ro) : static_cast<const void *>(w.recP + (static_cast<size_t>(par) * kPend + pk1) * nblk);
 #pragma unroll
         for (int j = 0; j < kC4; ++j) {
             const int i = lane * c + j;
-            qok[j] = c <= kC4 && j < c && i < nblk && (wave == 0 || row_wave);
+            qok[j] = c <= kC4 && j < c && i < nblk && (wave == 0 || row_wave || SPEC);
             const size_t ii = qok[j] ? i : 0;
             q0[j] = rec16(b0, ii);
             if constexpr (kPend > 1) q1[j] = rec16(b1, ii); else q1[j] = q0[j];
@@ -358,6 +459,17 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
     for (int j = 0; j < CPT; ++j) rs[j] = w.row[x0 + j];
     load_f64<CPT>(w.e2 + x0, e2x);
     const int nanflag = w.flags[0];
+    // SPEC: what the previous round speculated, and this column's entry of the speculated row (fixed addresses: part of the first round trip)
+    SpecHot sph{};
+    double msx = 0.0;
+    AhcSpec *const sx = spec_of(w.state);
+    double *const mspec = w.e2 + Np;   // [2][Np] behind e2 (make_layout_core)
+    if constexpr (SPEC) {
+        const int4 *sq = reinterpret_cast<const int4 *>(reinterpret_cast<const char *>(&sx->h[par]) + vz);
+        int4 sraw[2] = {sq[0], sq[1]};
+        __builtin_memcpy(&sph, sraw, sizeof(SpecHot));
+        msx = mspec[static_cast<size_t>(par) * Np + x0];
+    }
     __builtin_amdgcn_sched_barrier(0);
 #ifndef FA_AHC_LATE_KERNARGS
     // Kernel arguments that are first used in the MIDDLE of the dependent chain (N: the step test and the node id of the merged cluster, Np:
@@ -381,6 +493,7 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
     const int perw = (nblk + kWaves - 1) / kWaves;
     // wave 0: the smallest row minimum over all blocks (+ its row, neighbour, node ids) and the rows within 2 eps of it
     auto reduce_minimum = [&](auto cc, const int4 *ra, const int4 *ri, const bool *ok) {
+        Dec &o = s_dec;
         constexpr int C = decltype(cc)::value;
         double va[C], key = dinf();
         int ca[C];
@@ -404,9 +517,9 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
         for (int j = 0; j < C; ++j) cl += (va[j] <= wl && va[j] < dinf()) ? ca[j] : 0;
         const int cnt = wave_count(cl >= 1) + wave_count(cl >= 2) + wave_count(cl >= 3);  // exact up to 3 per lane; only "== 2" matters
         const int r1 = lane_value(ids.x, L[0]), q1_ = lane_value(ids.y, L[0]), nr1 = lane_value(ids.z, L[0]), nq1 = lane_value(ids.w, L[0]);
-        if (lane == 0) { s_dec.v1 = m[0]; s_dec.cnt = cnt; s_dec.r1 = r1; s_dec.q1 = q1_; s_dec.nr1 = nr1; s_dec.nq1 = nq1; }
+        if (lane == 0) { o.v1 = m[0]; o.cnt = cnt; o.r1 = r1; o.q1 = q1_; o.nr1 = nr1; o.nq1 = nq1; }
     };
-    auto reduce_minimum_packed = [&](auto cc, const int4 *rx, const bool *ok) {
+    auto reduce_minimum_packed = [&](auto cc, const int4 *rx, const bool *ok, Dec &o) {
         constexpr int C = decltype(cc)::value;
         double va[C], key = dinf();
         int ca[C], bz = 0, bw = 0, bi = 0;
@@ -433,10 +546,10 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
         int local, q1_, nr1, nq1;
         rec_unpack(uz, uw, local, q1_, nr1, nq1);
         const bool any = m[0] < dinf();
-        if (lane == 0) { s_dec.v1 = m[0]; s_dec.cnt = cnt; s_dec.r1 = any ? ui * kCols + local : -1; s_dec.q1 = any ? q1_ : -1; s_dec.nr1 = any ? nr1 : -1; s_dec.nq1 = any ? nq1 : -1; }
+        if (lane == 0) { o.v1 = m[0]; o.cnt = cnt; o.r1 = any ? ui * kCols + local : -1; o.q1 = any ? q1_ : -1; o.nr1 = any ? nr1 : -1; o.nq1 = any ? nq1 : -1; }
     };
     // waves 2 / 3: block-partial minima of the rows the previous round produced -> their minimum and nearest neighbour
-    auto reduce_rows = [&](auto cc, const int4 *r0, const int4 *r1, const bool *ok) {
+    auto reduce_rows = [&](auto cc, const int4 *r0, const int4 *r1, const bool *ok, Dec &o, const int k0) {
         constexpr int C = decltype(cc)::value;
         double keys[2] = {dinf(), dinf()};
         int ps[2] = {-1, -1}, pn[2] = {-1, -1};
@@ -452,11 +565,13 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
         int L[2];
         wave_min_multi<2>(keys, m, L);
         const int a0 = lane_value(ps[0], L[0]), b0 = lane_value(pn[0], L[0]), a1 = lane_value(ps[1], L[1]), b1 = lane_value(pn[1], L[1]);
-        if (lane == 0) { s_dec.pd[pk0] = m[0]; s_dec.ps[pk0] = a0; s_dec.pn[pk0] = b0; if (phas1) { s_dec.pd[pk1] = m[1]; s_dec.ps[pk1] = a1; s_dec.pn[pk1] = b1; } }
+        if (lane == 0) { o.pd[k0] = m[0]; o.ps[k0] = a0; o.pn[k0] = b0; if (phas1) { o.pd[pk1] = m[1]; o.ps[pk1] = a1; o.pn[pk1] = b1; } }
     };
     if (c <= kC4) {
-        if (wave == 0) reduce_minimum_packed(std::integral_constant<int, kC4>{}, q0, qok);
-        else if (row_wave) reduce_rows(std::integral_constant<int, kC4>{}, q0, q1, qok);
+        if (wave == 0) reduce_minimum_packed(std::integral_constant<int, kC4>{}, q0, qok, s_dec);
+        else if (row_wave) reduce_rows(std::integral_constant<int, kC4>{}, q0, q1, qok, s_dec, pk0);
+        else if (SPEC && wave == 1) reduce_minimum_packed(std::integral_constant<int, kC4>{}, q0, qok, s_hdec);
+        else if (SPEC && wave == 2) reduce_rows(std::integral_constant<int, kC4>{}, q0, q0, qok, s_hdec, 0);
     } else if (BIG && (wave == 0 || row_wave)) {   // more than 65 536 points: 5 .. 12 records per lane, requested together, then the same reductions
         int4 g0[kMaxC], g1[kMaxC];
         bool gok[kMaxC];
@@ -471,7 +586,7 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
             g1[j] = rec16(b1, ii);
         }
         if (wave == 0) reduce_minimum(std::integral_constant<int, kMaxC>{}, g0, g1, gok);
-        else reduce_rows(std::integral_constant<int, kMaxC>{}, g0, g1, gok);
+        else reduce_rows(std::integral_constant<int, kMaxC>{}, g0, g1, gok, s_dec, pk0);
     }
     if (kPiggy > 0 && wave == 1) {   // the smallest stale bound of each QUARTER of the blocks (candidates for the piggy-backed re-scans)
         double keys[kWaves];
@@ -502,7 +617,10 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
     }
     AHC_STAMP(6);
     lds_barrier();
-    const Dec dv = s_dec;  // one batch of LDS reads, everything below is register arithmetic on uniform values (moving it to the scalar
+    const Dec dv = s_dec;
+    Dec dh{};
+    if constexpr (SPEC) dh = s_hdec;
+    // (dv: one batch of LDS reads, everything below is register arithmetic on uniform values (moving it to the scalar
                            // unit with readfirstlane was measured 9 % slower: the chain is latency-bound on either unit)
     AHC_STAMP(7);
     // (a) finish the rows produced by the previous round
@@ -550,10 +668,29 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
             x[2 * r] = in ? q.x : 0.0; x[2 * r + 1] = in ? q.y : 0.0;
         }
     };
-    const bool spec = FA_AHC_SPECULATE && R1 >= 0 && Q1 >= 0;
-    const bool spec_lo = R1 < Q1;
+    // SPEC: the decision of the round after the speculated merge B, from the hypothesis records (B's row hP = sph.a pending, node N + step): the same tests as
+    // plain_merge below.  chain_ok: that decision is a merge of B's row with another — executed in this round if the base records certify B.
+    bool chain_ok = false;
+    const int hP = sph.a, hPn = N + st.step;
+    double hpd = dinf();
+    int hps = -1, hpn = -1, HR1 = -1, HQ1 = -1, HNR1 = -1, HNQ1 = -1;
+    if constexpr (SPEC) {
+        hpd = dh.pd[0]; hps = dh.ps[0]; hpn = dh.pn[0];
+        if (!(hpd < dinf())) { hps = -1; hpn = -1; }
+        double hg1 = dinf();
+        if (dh.v1 < hg1) { hg1 = dh.v1; HR1 = dh.r1; HQ1 = dh.q1; HNR1 = dh.nr1; HNQ1 = dh.nq1; }
+        if (lt2(hpd, hP, hg1, HR1 < 0 ? INT_MAX : HR1)) { hg1 = hpd; HR1 = hP; HQ1 = hps; HNR1 = hPn; HNQ1 = hpn; }
+        if (!(hg1 < dinf())) HR1 = -1;
+        const double hglim = hg1 + 2.0 * st.eps;
+        const int hnwin = (dh.v1 <= hglim ? dh.cnt : 0) + (hpd <= hglim ? 1 : 0);
+        chain_ok = sph.valid && st.mode == FA_AHC_MODE_AUTO && !nanflag && st.step + 1 < N - 1 && HR1 >= 0 && HQ1 >= 0 && hnwin == 2 && (HR1 == hP || HQ1 == hP);
+    }
+    const bool pres_chain = SPEC && chain_ok;   // the presumptive merge: the one after B (almost always certified), else (R1, Q1) as in every round
+    const int pR1 = pres_chain ? HR1 : R1, pQ1 = pres_chain ? HQ1 : Q1, pNR1 = pres_chain ? HNR1 : NR1, pNQ1 = pres_chain ? HNQ1 : NQ1;
+    const bool spec = FA_AHC_SPECULATE && pR1 >= 0 && pQ1 >= 0;
+    const bool spec_lo = pR1 < pQ1;
     // without a pair to speculate on (a re-scan round) the unconditional form requests slot / node 0 and drops the values
-    const int sp_a = !spec ? 0 : (spec_lo ? R1 : Q1), sp_b = !spec ? 0 : (spec_lo ? Q1 : R1), sp_na = !spec ? 0 : (spec_lo ? NR1 : NQ1), sp_nb = !spec ? 0 : (spec_lo ? NQ1 : NR1);
+    const int sp_a = !spec ? 0 : (spec_lo ? pR1 : pQ1), sp_b = !spec ? 0 : (spec_lo ? pQ1 : pR1), sp_na = !spec ? 0 : (spec_lo ? pNR1 : pNQ1), sp_nb = !spec ? 0 : (spec_lo ? pNQ1 : pNR1);
     double sp_ma = 0.0, sp_mb = 0.0, sp_da[CPT], sp_db[CPT], sp_xa[kCk], sp_xb[kCk];
 #pragma unroll
     for (int j = 0; j < kCk; ++j) { sp_xa[j] = 0.0; sp_xb[j] = 0.0; }
@@ -562,7 +699,28 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
     // (the youngest load of the round's first batch is consumed here: the load counter completes in order, so everything older has arrived and
     // nothing in the decision below has to wait on the counter — a wait there would also wait for the requests that follow)
     asm volatile("" :: "v"(nanflag), "v"(e2x[CPT - 1]), "v"(rs[CPT - 1].d1), "v"(nx[CPT - 1]));
-    if (kUncond || spec)
+    // SPEC: the candidates for the partner of the NEXT merge — the block-partial minima of the row P the previous round produced (wave 3: base records, wave 2:
+    // hypothesis records), for a merge of P with w — and their entries d(w, x) (one gather per candidate, with the operands)
+    const int candP = pres_chain ? hP : st.pend_row[0];
+    const bool cand_on = SPEC && spec && st.mode == FA_AHC_MODE_AUTO && candP >= 0 && (sp_a == candP || sp_b == candP);
+    const int cand_wave = pres_chain ? 2 : 3;
+    double cgw[kC4];
+    bool cok[kC4];
+#pragma unroll
+    for (int j = 0; j < kC4; ++j) { cgw[j] = dinf(); cok[j] = false; }
+    if (SPEC && spec && pres_chain) {
+        // B's row is this column's scratch entry and B's size is in the record; its centroid was stored by the previous round
+        const bool hp_a = sp_a == hP;
+        const int ow = hp_a ? sp_b : sp_a, onw = hp_a ? sp_nb : sp_na;
+        const double mw = w.sizes[onw];
+        sp_ma = hp_a ? sph.den : mw; sp_mb = hp_a ? mw : sph.den;
+        cload(w.C + static_cast<size_t>(sp_na) * d, sp_xa); cload(w.C + static_cast<size_t>(sp_nb) * d, sp_xb);
+        __builtin_amdgcn_sched_barrier(0);
+        double ew[CPT];
+        pair_entries<CPT, kEntryBranch>(w.M, Np, ow, onw, x0, nx, st.sym_limit, sp_a, sp_b, ew);
+        const double eh = (nx[0] != kDead && x0 != sp_a && x0 != sp_b) ? msx : 0.0;
+        sp_da[0] = hp_a ? eh : ew[0]; sp_db[0] = hp_a ? ew[0] : eh;
+    } else if (kUncond || spec)
     {
         // sizes and centroids first, the two matrix entries (a cold row each) last: loads complete in order, the centroid arithmetic runs under the entries'
         // latency.  (Entries first measured in round 6: 5.12 against 5.07 us.  Requesting the entries from every thread, round 4: dead columns then read cold
@@ -575,6 +733,20 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
         if (kUncond || st.mode == FA_AHC_MODE_AUTO) {
             pair_entries<CPT, kEntryBranch>(w.M, Np, sp_a, sp_na, x0, nx, st.sym_limit, sp_a, sp_b, sp_da);
             pair_entries<CPT, kEntryBranch>(w.M, Np, sp_b, sp_nb, x0, nx, st.sym_limit, sp_a, sp_b, sp_db);
+        }
+    }
+    if (SPEC && cand_on && wave == cand_wave) {
+        const int ow = sp_a == candP ? sp_b : sp_a, onw = sp_a == candP ? sp_nb : sp_na;
+#pragma unroll
+        for (int j = 0; j < kC4; ++j) {
+            const int cs = q0[j].z, cn = q0[j].w;
+            cok[j] = qok[j] && rec_f64(q0[j]) < dinf() && cs >= 0 && cs != sp_a && cs != sp_b;
+            // Row sp_a is rewritten in THIS launch by the threads that own its columns (other workgroups, at other times): a candidate is never read from
+            // it — its column copy instead, which nobody writes here.  Should that copy be stale the guess gets worse, every workgroup the same: the
+            // ranking must be uniform, not exact (the next round certifies).
+            const bool rc = ow != sp_a && (onw > cn || (onw < st.sym_limit && cn < st.sym_limit));
+            const size_t at = !cok[j] ? static_cast<size_t>(ow) * Np : rc ? static_cast<size_t>(ow) * Np + cs : static_cast<size_t>(cs) * Np + ow;
+            cgw[j] = w.M[at];
         }
     }
     const double glim = g1 + 2.0 * st.eps;
@@ -590,6 +762,7 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
             n.prev_op = OP_NONE;
             for (int k = 0; k < kPend; ++k) n.pend_row[k] = -1;
             *nhot = n;
+            if (SPEC) sx->h[npar].valid = 0;
         }
         return;
     }
@@ -638,13 +811,29 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
         const bool lo = R1 < Q1;
         D.a = lo ? R1 : Q1; D.b = lo ? Q1 : R1; D.na = lo ? NR1 : NQ1; D.nb = lo ? NQ1 : NR1;
     }
+    // SPEC: the base records certify the speculated merge B (exactly the merge the one-merge round would execute) -> B is committed in this round, and the
+    // merge after it is executed from the hypothesis decision (chain_ok) — or, when that is anything else, this round does B alone (`alone`)
+    int step0 = st.step;   // the dendrogram row of the merge executed below
+    bool hit = false, alone = false;
+    if constexpr (SPEC) {
+        hit = sph.valid && st.mode == FA_AHC_MODE_AUTO && plain_merge && D.a == sph.a && D.b == sph.b && D.na == sph.na && D.nb == sph.nb;
+        if (hit) {
+            step0 = st.step + 1;
+            if (chain_ok) {
+                const bool lo = HR1 < HQ1;
+                D.a = lo ? HR1 : HQ1; D.b = lo ? HQ1 : HR1; D.na = lo ? HNR1 : HNQ1; D.nb = lo ? HNQ1 : HNR1;
+            } else {
+                alone = true; D.op = OP_NONE;
+            }
+        }
+    }
     // rows produced this round: [0] the merged row / the forced re-scan, [1..] piggy-backed re-scans of the stale rows
     // with the smallest bounds (one candidate per wave's share of the blocks; a heuristic, any choice is correct)
     int prow[kPend], pnode_[kPend];
 #pragma unroll
     for (int k = 0; k < kPend; ++k) { prow[k] = -1; pnode_[k] = -1; }
     if (D.op == OP_MERGE || D.op == OP_RESCAN) {
-        prow[0] = D.a; pnode_[0] = D.op == OP_MERGE ? N + st.step : D.na;
+        prow[0] = D.a; pnode_[0] = D.op == OP_MERGE ? N + step0 : D.na;
         bool used[kWaves];
 #pragma unroll
         for (int wv = 0; wv < kWaves; ++wv) {
@@ -661,6 +850,7 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
             for (int wv = 0; wv < kWaves; ++wv) if (wv == bw) { used[wv] = true; prow[k] = dv.srow[wv]; pnode_[k] = dv.snode[wv]; }
         }
     }
+    if (SPEC && alone) { prow[0] = sph.a; pnode_[0] = N + st.step; }
     AHC_STAMP(1);
 
     // ---- phase 2 ------------------------------------------------------------------------------------------------
@@ -681,6 +871,7 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
             n.prev_op = OP_NONE;
             for (int k = 0; k < kPend; ++k) n.pend_row[k] = -1;
             *nhot = n;
+            if (SPEC) sx->h[npar].valid = 0;
         }
         if (was_pending) {
 #pragma unroll
@@ -693,6 +884,40 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
     int pslot[kPend], pnd[kPend];
 #pragma unroll
     for (int k = 0; k < kPend; ++k) { pkey[k] = dinf(); pslot[k] = x0; pnd[k] = nx[0]; }
+    if constexpr (SPEC) {
+        if (hit) {   // commit B: what the round of B would have done to this column, from the same values (its entry: the scratch row)
+            const int a = sph.a, b = sph.b, nnew = N + st.step;
+            const bool actB = nx[0] != kDead && x0 != a && x0 != b;
+            if (actB) {
+                w.M[static_cast<size_t>(a) * Np + x0] = msx;
+                const int f = row_update1(rs[0], e2x[0], msx, a, b, nnew);
+                dirty[0] = dirty[0] || (f & 1) != 0; e2_dirty[0] = e2_dirty[0] || (f & 2) != 0;
+            } else if (x0 == a) {
+                nx[0] = nnew; rs[0].d1 = dinf(); rs[0].nn = -1; rs[0].nnnode = -1; e2x[0] = dinf(); dirty[0] = true; e2_dirty[0] = true; in_flight[0] = true;
+                w.sizes[nnew] = sph.den;
+                w.node[x0] = nnew;
+            } else if (x0 == b) {
+                nx[0] = kDead; rs[0].d1 = dinf(); rs[0].nn = -1; rs[0].nnnode = -1; dirty[0] = true;
+                w.node[x0] = kDead;
+            }
+            if (alone) pkey[0] = actB ? msx : dinf();
+            else if (x0 == hP) { rs[0].d1 = hpd; rs[0].nn = hps; rs[0].nnnode = hpn; e2x[0] = hpd; dirty[0] = true; e2_dirty[0] = true; }   // B's row finished
+            if (blk == 0 && tid == 0) {
+                double *z = w.Z + static_cast<size_t>(st.step) * 4;
+                z[0] = sph.na < sph.nb ? sph.na : sph.nb;
+                z[1] = sph.na < sph.nb ? sph.nb : sph.na;
+                z[2] = 0.0;
+                z[3] = sph.den;
+            }
+        }
+    }
+    // SPEC: the merge speculated in this round (D) and the state of this column under it
+    bool spec_next = false;
+    SpecHot shn{};
+    RowSt hrs = rs[0];
+    int hnx = nx[0];
+    bool hin = false;
+    double hpkey = dinf();
 
     if (D.op != OP_MERGE) {
         // a round that does something else drops the speculative operands: consumed here, or their requests stay "pending" for the compiler on this path and
@@ -704,8 +929,8 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
         for (int j = 0; j < CPT; ++j) asm volatile("" :: "v"(sp_da[j]), "v"(sp_db[j]));
     }
     if (D.op == OP_MERGE) {
-        const int a = D.a, b = D.b, na = D.na, nb = D.nb, nnew = N + st.step;
-        const bool sp_hit = spec && a == sp_a && b == sp_b && na == sp_na && nb == sp_nb;   // uniform; false only for the pair an exact window picked
+        const int a = D.a, b = D.b, na = D.na, nb = D.nb, nnew = N + step0;
+        const bool sp_hit = spec && a == sp_a && b == sp_b && na == sp_na && nb == sp_nb && (!pres_chain || hit);   // uniform; false only for the pair an exact window picked
         const double *ca = w.C + static_cast<size_t>(na) * d, *cb = w.C + static_cast<size_t>(nb) * d;
         bool act[CPT], any_act = false, all_act = true;
 #pragma unroll
@@ -755,7 +980,7 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
         for (int j = 0; j < kCk; ++j) {
             const int k = celem(j);
             if (keeps_centroid && k < d) {
-                const double cc = __ddiv_rn(__dadd_rn(__dmul_rn(xa[j], ma), __dmul_rn(xb[j], mb)), den);
+                const double cc = centroid_elem(xa[j], ma, xb[j], mb, den);
                 if (st.mode == FA_AHC_MODE_EXACT) s_cvec[k] = cc;
                 if (blk == 0) w.C[static_cast<size_t>(nnew) * d + k] = cc;
             }
@@ -767,7 +992,7 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
         for (int k = ((d & 1) != 0 && d <= 64 * kCk ? d - 1 : 64 * kCk) + lane; k < d; k += 64) {
             const double ya = ca[k], yb = cb[k];
             if (keeps_centroid) {
-                const double cc = __ddiv_rn(__dadd_rn(__dmul_rn(ya, ma), __dmul_rn(yb, mb)), den);
+                const double cc = centroid_elem(ya, ma, yb, mb, den);
                 if (st.mode == FA_AHC_MODE_EXACT) s_cvec[k] = cc;
                 if (blk == 0) w.C[static_cast<size_t>(nnew) * d + k] = cc;
             }
@@ -777,6 +1002,43 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
         double dab = wave_sum(part);
         if (D.dab >= 0.0) dab = D.dab;
         AHC_STAMP(2);
+        // SPEC: rank the candidates by their Lance-Williams value for the new cluster, hand the best (z*) to every wave, request its row entry, size and centroid
+        int zs = -1, nzs = -1;
+        double dz = 0.0, szs = 0.0, xz[kCk];
+#pragma unroll
+        for (int j = 0; j < kCk; ++j) xz[j] = 0.0;
+        if constexpr (SPEC) {
+            spec_next = cand_on && sp_hit && (hit ? chain_ok : plain_merge) && step0 + 2 < N;
+            if (spec_next) {
+                if (wave == cand_wave) {
+                    const double inv = 1.0 / den, wa = ma * inv, wb = mb * inv, wab = wa * wb;
+                    double best = dinf();
+                    int bs = -1, bn = -1;
+#pragma unroll
+                    for (int j = 0; j < kC4; ++j) {
+                        const double vp = rec_f64(q0[j]);
+                        const double v = lw_value(wa, candP == a ? vp : cgw[j], wb, candP == a ? cgw[j] : vp, wab, dab);
+                        const bool better = cok[j] && v < best;
+                        best = better ? v : best; bs = better ? q0[j].z : bs; bn = better ? q0[j].w : bn;
+                    }
+                    const double keys[1] = {best};
+                    double m[1];
+                    int L[1];
+                    wave_min_multi<1>(keys, m, L);
+                    const int zsl = lane_value(bs, L[0]), znl = lane_value(bn, L[0]);
+                    if (lane == 0) { s_zs[0] = m[0] < dinf() ? zsl : -1; s_zs[1] = znl; }
+                }
+                lds_barrier();
+                zs = s_zs[0]; nzs = s_zs[1];
+                spec_next = zs >= 0;
+                if (spec_next) {
+                    const bool wantD = nx[0] != kDead && x0 != a && x0 != b && x0 != zs;
+                    dz = wantD ? pair_entry(w.M, Np, zs, nzs, x0, nx[0], st.sym_limit) : 0.0;
+                    szs = w.sizes[nzs];
+                    cload(w.C + static_cast<size_t>(nzs) * d, xz);
+                }
+            }
+        }
         double dc[CPT];
 #pragma unroll
         for (int j = 0; j < CPT; ++j) dc[j] = dinf();
@@ -786,12 +1048,8 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
             // 16 u per merge level that eps budgets for 8); three IEEE fp64 divisions were ~40 dependent instructions per round
             const double inv = 1.0 / den, wa = ma * inv, wb = mb * inv, wab = wa * wb;
 #pragma unroll
-            for (int j = 0; j < CPT; ++j) {
-                if (act[j]) {
-                    dc[j] = wa * da[j] + wb * db[j] - wab * dab;
-                    if (!(dc[j] > 0.0)) dc[j] = 0.0;  // also keeps -0.0 out of the bit-pattern reductions
-                }
-            }
+            for (int j = 0; j < CPT; ++j)
+                if (act[j]) dc[j] = lw_value(wa, da[j], wb, db[j], wab, dab);
         } else {
             __syncthreads();
             double sum[CPT];
@@ -818,22 +1076,8 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
             const int x = x0;
             if (act[0]) {
                 w.M[static_cast<size_t>(a) * Np + x] = dc[0];
-                // Row x against its entry for the new cluster.  e2x bounds the entries of the row OTHER than the nearest neighbour's from below
-                // (exact second minimum after the start-up scan, then maintained: an entry that appears lowers it, entries that disappear
-                // leave it a bound).  It decides the case that used to make half of all rows stale on chaining data — the nearest neighbour
-                // WAS one of the merged slots (every point's nearest neighbour is the growing cluster) and the new entry is larger than the
-                // old minimum: if it is still below everything else (dc < e2x) the row simply keeps the cluster as its neighbour.
-                const bool vld = rs[0].nn >= 0;
-                const bool hit = vld && (rs[0].nn == a || rs[0].nn == b);
-                if (!hit) {
-                    if (dc[0] < rs[0].d1 || (vld && dc[0] == rs[0].d1 && a <= rs[0].nn)) {   // new minimum (a stale row: dc below its bound IS its minimum)
-                        e2x[0] = rs[0].d1; rs[0].d1 = dc[0]; rs[0].nn = a; rs[0].nnnode = nnew; dirty[0] = true; e2_dirty[0] = true;
-                    } else if (dc[0] < e2x[0]) { e2x[0] = dc[0]; e2_dirty[0] = true; }
-                } else if (dc[0] < e2x[0]) {                                   // unique minimum again (strict: a tie goes to a re-scan)
-                    rs[0].d1 = dc[0]; rs[0].nn = a; rs[0].nnnode = nnew; dirty[0] = true;
-                } else {                                                        // minimum lost: every entry is >= min(e2x, dc) = e2x, a lower bound
-                    rs[0].d1 = e2x[0]; rs[0].nn = -1; dirty[0] = true;
-                }
+                const int f = row_update1(rs[0], e2x[0], dc[0], a, b, nnew);   // row x against its entry for the new cluster
+                dirty[0] = dirty[0] || (f & 1) != 0; e2_dirty[0] = e2_dirty[0] || (f & 2) != 0;
                 pkey[0] = dc[0];
 #pragma unroll
                 for (int k = 1; k < kPend; ++k)
@@ -889,11 +1133,44 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
             }
         }
         if (blk == 0 && tid == 0) {
-            double *z = w.Z + static_cast<size_t>(st.step) * 4;
+            double *z = w.Z + static_cast<size_t>(step0) * 4;
             z[0] = na < nb ? na : nb;  // LinkageOutput::append (FastClusterWrapper.cpp:150-160)
             z[1] = na < nb ? nb : na;
             z[2] = 0.0;                // exact height filled by ahc_heights after the loop
             z[3] = den;
+        }
+        if constexpr (SPEC) {
+            if (spec_next) {   // the merge D = (this round's cluster at slot a, z*) as ITS round would compute it: centroid, |.|^2, Lance-Williams row, row state
+                const bool ea_lo = a < zs;
+                const int Da = ea_lo ? a : zs, Db = ea_lo ? zs : a, nD = nnew + 1;
+                const double maD = ea_lo ? den : szs, mbD = ea_lo ? szs : den, denD = maD + mbD;
+                double part2 = 0.0;
+#pragma unroll
+                for (int j = 0; j < kCk; ++j) {
+                    const double ce = centroid_elem(xa[j], ma, xb[j], mb, den);   // the bits workgroup 0 stores for the new cluster
+                    const double xda = ea_lo ? ce : xz[j], xdb = ea_lo ? xz[j] : ce;
+                    if (blk == 0 && wave == 0 && celem(j) < d) w.C[static_cast<size_t>(nD) * d + celem(j)] = centroid_elem(xda, maD, xdb, mbD, denD);
+                    const double diff = xda - xdb;
+                    part2 += diff * diff;
+                }
+                const double dabD = wave_sum(part2);
+                const double invD = 1.0 / denD, waD = maD * invD, wbD = mbD * invD, wabD = waD * wbD;
+                const bool actD = nx[0] != kDead && x0 != Da && x0 != Db;
+                hrs = rs[0]; hnx = nx[0]; hin = in_flight[0];
+                double dcD = 0.0;
+                if (actD) {
+                    dcD = lw_value(waD, ea_lo ? dc[0] : dz, wbD, ea_lo ? dz : dc[0], wabD, dabD);
+                    double he2 = e2x[0];
+                    (void)row_update1(hrs, he2, dcD, Da, Db, nD);
+                    hpkey = dcD;
+                } else if (x0 == Da) {
+                    hnx = nD; hrs.d1 = dinf(); hrs.nn = -1; hrs.nnnode = -1; hin = true;
+                } else if (x0 == Db) {
+                    hnx = kDead; hrs.d1 = dinf(); hrs.nn = -1; hrs.nnnode = -1;
+                }
+                mspec[static_cast<size_t>(npar) * Np + x0] = dcD;
+                shn.valid = 1; shn.a = Da; shn.b = Db; shn.na = ea_lo ? nnew : nzs; shn.nb = ea_lo ? nzs : nnew; shn.den = denD;
+            }
         }
     } else if (D.op == OP_RESCAN) {
 #pragma unroll
@@ -968,7 +1245,13 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
         if (j == 0 || keys_all[j] < key) { key = keys_all[j]; bx = x0 + j; bnx = nx[j]; bnn = rs[j].nn; bnnnode = rs[j].nnnode; }
         if (live && rs[j].nn < 0 && rs[j].d1 < skey) skey = rs[j].d1;
     }
-    block_record<CPT>(w, npar, blk, st.eps, key, keys_all, skey, pkey, pslot, pnd, bx, bnx, bnn, bnnnode, s_out);
+    if (SPEC && spec_next) {
+        RecP *const hpart = w.recP + 2 * kPend * static_cast<size_t>(nblk);
+        const double hkey = hnx != kDead && !hin ? hrs.d1 : dinf();
+        block_record_spec(w, npar, blk, st.eps, key, pkey[0], pnd[0], bx, bnx, bnn, bnnnode, hkey, hpkey, nx[0], hnx, hrs.nn, hrs.nnnode, hpart,
+                          reinterpret_cast<int4 *>(hpart + 2 * static_cast<size_t>(nblk)), s_out2);
+    } else
+        block_record<CPT>(w, npar, blk, st.eps, key, keys_all, skey, pkey, pslot, pnd, bx, bnx, bnn, bnnnode, s_out);
     AHC_STAMP(4);
     if (blk == 0 && tid == 0) {  // clear the window counters of the next round (here, in the tail: in front of the decision the store's round
         WinCounters *z = w.cnt + ((ph + 1) & 3);   // trip sat on the critical path of workgroup 0 — the next wait for a load also waits for it)
@@ -976,10 +1259,14 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
     }
     if (blk == 0 && tid == 0) {
         AhcHot n = st;
-        n.prev_op = D.op;
+        n.prev_op = alone ? OP_MERGE : D.op;
         for (int k = 0; k < kPend; ++k) { n.pend_row[k] = prow[k]; n.pend_node[k] = pnode_[k]; if (k > 0 && prow[k] >= 0) bump(&w.state[0].piggy); }
         n.lim = D.lim;
-        if (D.op == OP_MERGE) n.step = st.step + 1;
+        n.step = step0 + (D.op == OP_MERGE ? 1 : 0);
+        if (SPEC) {
+            sx->h[npar] = shn;
+            if (hit) bump(&sx->hits);
+        }
         n.rounds32 = st.rounds32 + 1;
         *nhot = n;
         if (D.op == OP_RESCAN) bump(&w.state[0].rescans);
@@ -1000,7 +1287,8 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
 //                       (constant address space = scalar loads): two dependent memory round trips before the round can start.
 //   ahc_round_args    : up to kArgProblems problems with their workspaces and block ranges IN the kernel arguments: no extra round trip
 //                       (fa_ahc_linkage_batch / fa_offline_cluster_batch with <= 16 recordings).
-template <bool BATCH, bool BIG, int CPT = 1, int KC = 4 / CPT>
+//   ahc_round_t<false, false, 1, KC, true>: the speculative round of one problem (SPEC, ahc_ws.h: AhcSpec).
+template <bool BATCH, bool BIG, int CPT = 1, int KC = 4 / CPT, bool SPEC = false>
 __global__ __launch_bounds__(kBlk) void ahc_round_t(const int ph, const int nblk_, AhcState *const state_, RecA *const recA_, int4 *const recI_, RecP *const recP_,
                                                     const unsigned off_row, const unsigned off_node, const unsigned off_e2, const unsigned off_flags,
                                                     const Ws w_one, const Ws *__restrict__ table, const int2 *__restrict__ blkmap) {
@@ -1028,7 +1316,7 @@ __global__ __launch_bounds__(kBlk) void ahc_round_t(const int ph, const int nblk
         for (unsigned i = 0; i < sizeof(Ws) / 8; ++i) words[i] = src[i];
         __builtin_memcpy(&w_, words, sizeof(Ws));
     }
-    ahc_round_body<false, BIG, CPT, KC>(w_, blk_, ph);
+    ahc_round_body<false, BIG, CPT, KC, SPEC>(w_, blk_, ph);
 }
 
 // A problem of at most 256 points is ONE block: its rounds need no device-wide barrier at all, a workgroup barrier between them (with

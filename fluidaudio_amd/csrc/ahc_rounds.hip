@@ -72,6 +72,7 @@ fa_status prob_setup(fa_ctx *ctx, Prob &p, char *base) {
     else if (p.cpt == 2) hipLaunchKernelGGL(ahc_records<2>, dim3(w.nblk, 2), dim3(kBlk), 0, ctx->stream, w);
     else hipLaunchKernelGGL(ahc_records<1>, dim3(w.nblk, 2), dim3(kBlk), 0, ctx->stream, w);
     FA_HIP_TRY(ctx, hipGetLastError());
+    FA_HIP_TRY(ctx, hipMemsetAsync(spec_of(w.state), 0, sizeof(AhcSpec), ctx->stream));   // no merge speculated yet: the first round takes the one-merge path
     return FA_SUCCESS;
 }
 
@@ -202,6 +203,7 @@ fa_status prob_adopt(fa_ctx *ctx, Prob &p, const int merges, const double eps, c
     hipLaunchKernelGGL(ahc_adopt_rows, dim3(w.Np), dim3(kBlk), 0, ctx->stream, w);
     hipLaunchKernelGGL(ahc_records<1>, dim3(w.nblk, 2), dim3(kBlk), 0, ctx->stream, w);   // needs eps (the state) and the rows
     FA_HIP_TRY(ctx, hipGetLastError());
+    FA_HIP_TRY(ctx, hipMemsetAsync(spec_of(w.state), 0, sizeof(AhcSpec), ctx->stream));   // no hypothesis survives an adoption
     return FA_SUCCESS;
 }
 }  // namespace fa_ahc
@@ -223,8 +225,17 @@ fa_status prob_run_rounds(fa_ctx *ctx, Prob &p) {
         hipLaunchKernelGGL(kernel, dim3(w.nblk), dim3(kBlk), lds, ctx->stream, ph, w.nblk, w.state, w.recA, w.recI, w.recP, o_row, o_node, o_e2, o_flags, w,
                            static_cast<const Ws *>(nullptr), static_cast<const int2 *>(nullptr));
     };
+    // the speculative round (two merges per launch where the next merge was foreseen): one slot per thread, the register path of the first reduction, AUTO, even
+    // d <= 256 (the centroid pairs of one lane hold the whole centroid); FA_AHC_SPEC=0 keeps the one-merge round
+    const bool spec = [&] { const char *e = fa::sw(fa::Sw::AHC_SPEC); return !(e && e[0] == '0' && e[1] == 0); }() && p.cpt == 1 && !big && p.mode == FA_AHC_MODE_AUTO &&
+                      d % 2 == 0 && d <= 256;
     auto dispatch = [&](const int ph, const bool set_lds_only) {
-        if (p.cpt == 4) { if (big) launch_as(ahc_round_t<false, true, 4>, ph, set_lds_only); else launch_as(ahc_round_t<false, false, 4>, ph, set_lds_only); }
+        if (spec) {
+            if (kc == 1) launch_as(ahc_round_t<false, false, 1, 1, true>, ph, set_lds_only);
+            else if (kc == 2) launch_as(ahc_round_t<false, false, 1, 2, true>, ph, set_lds_only);
+            else if (kc == 3) launch_as(ahc_round_t<false, false, 1, 3, true>, ph, set_lds_only);
+            else launch_as(ahc_round_t<false, false, 1, 4, true>, ph, set_lds_only);
+        } else if (p.cpt == 4) { if (big) launch_as(ahc_round_t<false, true, 4>, ph, set_lds_only); else launch_as(ahc_round_t<false, false, 4>, ph, set_lds_only); }
         else if (p.cpt == 2) { if (big) launch_as(ahc_round_t<false, true, 2>, ph, set_lds_only); else launch_as(ahc_round_t<false, false, 2>, ph, set_lds_only); }
         else if (big) launch_as(ahc_round_t<false, true, 1>, ph, set_lds_only);
         else if (kc == 1) launch_as(ahc_round_t<false, false, 1, 1>, ph, set_lds_only);
@@ -248,12 +259,12 @@ fa_status prob_run_rounds(fa_ctx *ctx, Prob &p) {
         }
     } else {
         CachedGraph *cg = static_cast<CachedGraph *>(ctx->ahc_graph);
-        if (!cg || cg->base != ctx->ahc_ws || cg->N != N || cg->d != d || cg->cpt != p.cpt || !cg->rg.ok) {
+        if (!cg || cg->base != ctx->ahc_ws || cg->N != N || cg->d != d || cg->cpt != p.cpt || cg->spec != spec || !cg->rg.ok) {
             delete cg;
             cg = new CachedGraph();
             ctx->ahc_graph = cg;
             ctx->ahc_graph_free = cached_graph_free;
-            cg->base = ctx->ahc_ws; cg->N = N; cg->d = d; cg->cpt = p.cpt;
+            cg->base = ctx->ahc_ws; cg->N = N; cg->d = d; cg->cpt = p.cpt; cg->spec = spec;
             cg->rg.capture(ctx, launch, rounds_for(N));
         }
         rgp = &cg->rg;
@@ -271,6 +282,16 @@ fa_status prob_run_rounds(fa_ctx *ctx, Prob &p) {
         FA_HIP_TRY(ctx, hipMemcpyAsync(&p.h, w.state, sizeof(p.h), hipMemcpyDeviceToHost, ctx->stream));
         FA_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         FA_TRY(prob_after_replay(ctx, p));
+    }
+    p.spec_hits = 0;
+    if (fa::sw_on(fa::Sw::AHC_DEBUG) || fa_debug_hooks_enabled()) {   // the commit counter: only for the debug line and the test hook (one more copy)
+        if (spec) {
+            long long hits = 0;
+            FA_HIP_TRY(ctx, hipMemcpyAsync(&hits, &spec_of(w.state)->hits, sizeof(hits), hipMemcpyDeviceToHost, ctx->stream));
+            FA_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            p.spec_hits = hits;
+        }
+        ctx->ahc_spec_hits = p.spec_hits;
     }
     return prob_finish(ctx, p);
 }
@@ -351,8 +372,8 @@ fa_status fa::ahc_run_device(fa_ctx *ctx, const double *d_data, size_t N, size_t
     }
 #endif
     if (fa::sw(fa::Sw::AHC_DEBUG))
-        fprintf(stderr, "ahc: N %zu rounds %lld merges %d forced re-scans %lld piggy-backed re-scans %lld windows %lld fallback %lld (kPiggy %d)\n", N, p.h.rounds,
-                p.h.step, p.h.rescans, p.h.piggy, p.h.windows, p.fallback, kPiggy);
+        fprintf(stderr, "ahc: N %zu rounds %lld merges %d speculated merges committed %lld forced re-scans %lld piggy-backed re-scans %lld windows %lld fallback %lld (kPiggy %d)\n",
+                N, p.h.rounds, p.h.step, p.spec_hits, p.h.rescans, p.h.piggy, p.h.windows, p.fallback, kPiggy);
     if (stats) {
         float t01 = 0, t12 = 0;
         (void)hipEventElapsedTime(&t01, ev[0], ev[1]);

@@ -103,10 +103,21 @@ __device__ __forceinline__ void rec_unpack(const unsigned z, const unsigned wv, 
     nq1 = q1 >= 0 ? static_cast<int>((wv >> 17) | (((z >> 29) & 3u) << 15)) : -1;
 }
 
+// Speculative rounds (FA_AHC_SPEC, one problem, one slot per thread, AUTO): a round that merges A = (P, w) — P the row the previous round produced — also
+// evaluates the merge B = (A', z*) that most likely follows (z*: the best of P's block-partial minima, re-ranked by their Lance-Williams value for A') and
+// leaves B's row in a scratch row (Mspec), B's centroid in C[its node id], and the block records the round of B would write (hypothesis records).  The next
+// round commits B when its base records certify exactly that merge, and then decides and executes the merge after B from the hypothesis records: two merges
+// in one launch.  The record of what was speculated lives behind state[2] (make_layout_core), by round parity like the state; `hits` counts commits.
+struct __attribute__((aligned(16))) SpecHot { int32_t valid, a, b, na, nb, pad; double den; };   // B: slots (a < b), node ids, size of the merged cluster
+struct __attribute__((aligned(16))) AhcSpec { SpecHot h[2]; long long hits, pad; };
+static_assert(sizeof(SpecHot) == 32 && sizeof(AhcSpec) == 80, "the speculation record is read in 16-byte pieces");
+
 struct __attribute__((aligned(16))) RowSt {  // per slot, owned by thread (slot & 255) of workgroup (slot >> 8)
     double d1;               // minimum over all other live slots (lower bound while nn < 0)
     int nn, nnnode;          // nearest neighbour slot (lowest on ties; -1: merged away) and its node id
 };
+
+__device__ __host__ inline AhcSpec *spec_of(AhcState *state) { return reinterpret_cast<AhcSpec *>(state + 2); }
 
 struct Ws {   // what a round touches first comes first: with kernel-argument preloading (Makefile: -amdgpu-kernarg-preload-count) the leading
               // 16 dwords arrive in SGPRs with the wavefront instead of through a scalar load at its start
@@ -250,16 +261,16 @@ inline Layout make_layout_core(size_t N, size_t Np, size_t d, size_t nblk) {
     Layout L{};
     size_t o = 0;
     auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 255) & ~static_cast<size_t>(255); return at; };
-    L.state = take(sizeof(AhcState) * 2);
+    L.state = take(sizeof(AhcState) * 2 + sizeof(AhcSpec));   // AhcSpec right behind state[2] (spec_of)
     L.cnt = take(sizeof(WinCounters) * 4);
     L.flags = take(sizeof(int32_t) * 4);
     L.prof = take(sizeof(unsigned long long) * 16);
     L.reca = take(sizeof(RecA) * 2 * nblk);
     L.reci = take(sizeof(int4) * 4 * nblk);   // [2][nblk] recI, then [2][nblk] the packed records (rec_pack)
     L.recs = take(sizeof(RecS) * 2 * nblk);
-    L.recp = take(sizeof(RecP) * 2 * kPend * nblk);
+    L.recp = take(sizeof(RecP) * 2 * kPend * nblk + (sizeof(RecP) + sizeof(int4)) * 2 * nblk);   // then the hypothesis records: [2][nblk] partial minima of B', [2][nblk] packed
     L.row = take(sizeof(RowSt) * Np);
-    L.e2 = take(sizeof(double) * Np);
+    L.e2 = take(sizeof(double) * 3 * Np);   // [Np] e2, then [2][Np] the scratch row of the speculative merge (Mspec)
     L.node = take(sizeof(int32_t) * Np);
     L.sizes = take(sizeof(double) * 2 * N);
     L.z = take(sizeof(double) * 4 * (N > 1 ? N - 1 : 1));
@@ -294,6 +305,7 @@ struct Prob {   // one linkage problem: its workspace, its copy of the device st
     fa_status st = FA_SUCCESS;
     bool active = true;
     bool z_on_host = false;  // d_Z is the caller's host buffer
+    long long spec_hits = 0; // speculated merges committed by the last prob_run_rounds (read back only for the debug line / fa_debug_ahc_spec_hits)
     bool needs_ro = false;   // an exact tie at the minimum (or a window overflowing with near-ties): to be recomputed in reference order
 };
 
@@ -369,6 +381,7 @@ struct CachedGraph {   // the round launches of one problem shape, kept in the c
     const void *base = nullptr;
     size_t N = 0, d = 0;
     int cpt = 1;
+    bool spec = false;            // the speculative round (FA_AHC_SPEC)
     int grid_y = 0, kernel = 0;   // uniform batches: problems in the grid and which build of the round serves them
 };
 void cached_graph_free(void *p);

@@ -242,6 +242,13 @@ fa_status fa_debug_ahc_adopted(const fa_ctx *ctx, int64_t *row, int32_t *kind, d
     return FA_SUCCESS;
 }
 
+fa_status fa_debug_ahc_spec_hits(const fa_ctx *ctx, int64_t *hits) {
+    if (!ctx || !hits) return FA_INVALID_ARGUMENT;
+    if (!debug_hooks()) return FA_RUNTIME_ERROR;
+    *hits = ctx->ahc_spec_hits;
+    return FA_SUCCESS;
+}
+
 fa_status fa_ctx_create(int device, void *stream, fa_ctx **out) {
     if (!out) return FA_INVALID_ARGUMENT;
     *out = nullptr;

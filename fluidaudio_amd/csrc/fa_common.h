@@ -71,6 +71,9 @@ struct fa_ctx {
         std::vector<int32_t> node, nn, nnnode;
         std::vector<double> d1, e2;
     } ahc_adopted;
+    // test hook (fa_debug_ahc_spec_hits): speculated merges the filter-based rounds committed in their last run on this context (-1: none recorded);
+    // recorded while debug hooks or FA_AHC_DEBUG are on
+    int64_t ahc_spec_hits = -1;
 };
 
 namespace fa {
@@ -131,6 +134,7 @@ bool fault_hit(int site);
     ROUTE(AHC_RO_NO_MATRIX, "FA_AHC_RO_NO_MATRIX") ROUTE(AHC_RO_NO_HANDOVER, "FA_AHC_RO_NO_HANDOVER") ROUTE(AHC_UNI_CPT, "FA_AHC_UNI_CPT") ROUTE(AHC_UNI_GROUPS, "FA_AHC_UNI_GROUPS")    \
     ROUTE(AHC_RO_HANDOVER_AT, "FA_AHC_RO_HANDOVER_AT") ROUTE(AHC_RO_REPLAY_PAIRS, "FA_AHC_RO_REPLAY_PAIRS")                           \
     ROUTE(AHC_UNI_WAVES, "FA_AHC_UNI_WAVES") ROUTE(AHC_IN_FLIGHT, "FA_AHC_IN_FLIGHT") ROUTE(AHC_DEBUG, "FA_AHC_DEBUG")                \
+    ROUTE(AHC_SPEC, "FA_AHC_SPEC")                                                                                                   \
     ROUTE(MEL_GENERIC, "FA_MEL_GENERIC") ROUTE(MEL_SLICE_MB, "FA_MEL_SLICE_MB") ROUTE(VBX_NO_TILED, "FA_VBX_NO_TILED")                \
     ROUTE(RESAMPLE_SIMPLE, "FA_RESAMPLE_SIMPLE") ROUTE(RESAMPLE_NO_DECIM, "FA_RESAMPLE_NO_DECIM")                                     \
     ROUTE(RESAMPLE_NO_DECIM_TILES, "FA_RESAMPLE_NO_DECIM_TILES") ROUTE(RESAMPLE_NO_ROWS, "FA_RESAMPLE_NO_ROWS")                       \

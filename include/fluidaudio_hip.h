@@ -93,6 +93,7 @@ const char *fa_version(void);
  *                                            to 4)); a positive multiple of 4, anything else fails a call that runs in reference order with
  *                                            INVALID_ARGUMENT.  4: a hand-over lands within 4 rows of any chosen row
  *   FA_AHC_DEBUG                             one line of statistics per linkage call on stderr
+ *   FA_AHC_SPEC=0                            the one-merge round instead of the speculative one (two merges per launch where the next was foreseen)
  *   FA_MEL_GENERIC, FA_MEL_SLICE_MB=n        the generic mel kernel; slice size of host-pointer batches
  *   FA_VBX_NO_TILED                          the untiled VBx iteration
  *   FA_RESAMPLE_SIMPLE, _NO_DECIM, _NO_DECIM_TILES, _NO_ROWS, _NO_WIDE, FA_RESAMPLE_WIDE=rows:waves (16:8, 16:10, 32:8, 32:10)   polyphase kernel family
@@ -109,6 +110,10 @@ int32_t fa_debug_hooks_enabled(void);
  * entry other than column nn).  RUNTIME_ERROR without FLUIDAUDIO_HIP_DEBUG_HOOKS=1. */
 fa_status fa_debug_ahc_adopted(const fa_ctx *ctx, int64_t *row, int32_t *kind, double *eps, size_t *slots, size_t capacity, int32_t *node, double *d1,
                                int32_t *nn, int32_t *nnnode, double *e2);
+/* Test hook: how many speculated merges the filter-based rounds committed in their last run on this context (the speculative round, FA_AHC_SPEC: a
+ * launch that merges a pair also evaluates the merge most likely to follow; the next launch commits it when its records certify exactly that merge).
+ * 0 when the run used the one-merge round, -1 when nothing was recorded.  RUNTIME_ERROR without FLUIDAUDIO_HIP_DEBUG_HOOKS=1. */
+fa_status fa_debug_ahc_spec_hits(const fa_ctx *ctx, int64_t *hits);
 /* Test hook: the next `count` passes through `site` fail the way the real failure would (count 0 disarms).  Process-wide; one relaxed
  * atomic load on the paths that carry a site.  Inert unless the process was started with FLUIDAUDIO_HIP_DEBUG_HOOKS=1.  Used by the
  * fault-injection tests of the degrade contracts:
