@@ -8,11 +8,12 @@ from .ahc import AHCClustering, check_dendrogram, cut, fastcluster_compute_centr
 from .beam import ARPAError, ARPALanguageModel, CtcVocabulary, ctc_beam_search, ctc_beam_search_ids_batch  # noqa: F401
 from .ctc import (LogitsArgmax, ctc_greedy_decode, ctc_greedy_ids_batch, ctc_greedy_rows, ctc_greedy_ids_dev, ctc_log_probs_dev,  # noqa: F401
                   decode_ctc_token_ids)
+from .embedding import EmbeddingConfig, EmbeddingPlan, plan_embeddings, span_inputs, weight_resample  # noqa: F401
 from .formats import AudioWAV, RTTMParser, RTTMParserError, TimedSpeakerSegment, export_embeddings_json  # noqa: F401
 from .kmeans import KMeansClustering, SeededRNG, SpeakerCountConstraints  # noqa: F401
 from .mel import AudioMelSpectrogram, LuxTtsMelExtractor, MelPlan, UnifiedMelExtractor  # noqa: F401
 from .pipeline import (ClusteringResult, OfflineClusteringConfig, cluster_embeddings, cluster_embeddings_batch, cluster_embeddings_stagewise, diarize_segments,  # noqa: F401
-                       select_training_embeddings)
+                       extract_embeddings, select_training_embeddings, span_embedder)
 from .pool import Pool, device_count  # noqa: F401
 from .reconstruct import (OfflineReconstruction, ReconstructionConfig, SegmentationOutput, chunk_assignments, finalize_segments,  # noqa: F401
                           powerset_decode)

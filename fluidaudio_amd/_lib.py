@@ -53,6 +53,8 @@ EXPORTED_SYMBOLS = [
     "fa_mel_batch_sharded", "fa_ctc_greedy_batch_sharded", "fa_ahc_linkage_many",
     "fa_powerset_decode_dev", "fa_powerset_decode", "fa_offline_chunk_assignments", "fa_reconstruct_default_config",
     "fa_offline_reconstruct", "fa_offline_reconstruct_dev", "fa_segments_finalize",
+    "fa_embedding_default_config", "fa_embedding_plan", "fa_embedding_plan_dev", "fa_embedding_windows_dev", "fa_embedding_span_inputs",
+    "fa_embedding_span_inputs_dev", "fa_weight_resample", "fa_weight_resample_dev",
 ]
 
 
@@ -107,6 +109,21 @@ class ReconstructInfo(C.Structure):
                 ("zero_vote_run_count", C.c_int64), ("zero_vote_runs", C.c_void_p), ("zero_vote_capacity", C.c_int64),
                 ("speaker_counts", C.c_void_p), ("speaker_counts_capacity", C.c_int64), ("frame_capacity", C.c_int64),
                 ("frame_clusters", C.c_void_p), ("frame_averages", C.c_void_p), ("expected_count_sums", C.c_void_p), ("frame_slots", C.c_int32)]
+
+
+class EmbeddingConfig(C.Structure):
+    _fields_ = [("window_duration", C.c_double), ("sample_rate", C.c_int32), ("samples_per_window", C.c_int32), ("overlap_threshold", C.c_float),
+                ("exclude_overlap", C.c_int32), ("min_segment_duration", C.c_double), ("batch_size", C.c_int32), ("skip_enabled", C.c_int32),
+                ("skip_threshold", C.c_float), ("weight_frames", C.c_int32), ("frame_duration", C.c_double)]
+
+
+class EmbeddingInfo(C.Structure):
+    _fields_ = [("planned_chunks", C.c_int64), ("batches", C.c_int64), ("jobs", C.c_int64), ("runs", C.c_int64), ("evaluated_masks", C.c_int64),
+                ("empty_masks", C.c_int64), ("fallback_masks", C.c_int64), ("skipped_embeddings", C.c_int64), ("frame_duration", C.c_double),
+                ("min_frames", C.c_int32), ("samples_per_window", C.c_int32), ("batch_size", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 def build(force: bool = False) -> str:
@@ -306,6 +323,15 @@ def lib() -> C.CDLL:
                                          C.POINTER(i64), C.POINTER(ReconstructInfo)]
     L.fa_offline_reconstruct_dev.argtypes = L.fa_offline_reconstruct.argtypes
     L.fa_segments_finalize.argtypes = [C.POINTER(ReconstructConfig), vp, i64, vp, i64, C.POINTER(i64)]
+    L.fa_embedding_default_config.argtypes = [C.POINTER(EmbeddingConfig)]
+    L.fa_embedding_default_config.restype = None
+    L.fa_embedding_plan.argtypes = [vp, C.POINTER(EmbeddingConfig), vp, i64, i32, i32, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(EmbeddingInfo)]
+    L.fa_embedding_plan_dev.argtypes = L.fa_embedding_plan.argtypes
+    L.fa_embedding_windows_dev.argtypes = [vp, vp, i64, vp, i64, i32, vp]
+    L.fa_embedding_span_inputs.argtypes = [vp, C.POINTER(EmbeddingConfig), vp, i64, vp, i64, vp, vp, vp]
+    L.fa_embedding_span_inputs_dev.argtypes = L.fa_embedding_span_inputs.argtypes
+    L.fa_weight_resample.argtypes = [vp, vp, i64, i32, i32, vp]
+    L.fa_weight_resample_dev.argtypes = L.fa_weight_resample.argtypes
     _lib = L
     return L
 

@@ -31,11 +31,13 @@
 #include <string>
 #include <vector>
 
+#include "block_scan.h"
 #include "fa_common.h"
 
 namespace {
 
-constexpr int kThreads = 256;
+using fa::scan::block_exclusive;
+constexpr int kThreads = fa::scan::kThreads;
 constexpr int kTileG = 64;        // global frames per workgroup of the frame kernel (16 per wavefront)
 constexpr int kListCap = 1024;    // chunks of a tile listed in LDS (irregular offsets); more: every wavefront scans all chunks
 constexpr int kScanPer = 8;       // items per thread of the run compaction
@@ -317,22 +319,6 @@ __device__ inline int run_start(const int32_t *word, const int32_t *sel, int sma
     return g == 0 || active_slot(word, sel, smax, g - 1, sel[e]) < 0;
 }
 
-// exclusive prefix over the workgroup (kThreads); *total = the sum
-__device__ inline int block_exclusive(int v, int *total) {
-    __shared__ int wsum[kThreads / 64];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const int y = __shfl_up(x, off); if (lane >= off) x += y; }
-    if (lane == 63) wsum[wid] = x;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int w = 0; w < kThreads / 64; ++w) { if (w < wid) base += wsum[w]; tot += wsum[w]; }
-    __syncthreads();
-    *total = tot;
-    return base + x - v;
-}
-
 __global__ __launch_bounds__(kThreads) void run_count(const int32_t *__restrict__ word, const int32_t *__restrict__ sel, int smax, int64_t items,
                                                       int32_t *__restrict__ bsum) {
     const int64_t e0 = (static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x) * kScanPer;
@@ -341,20 +327,6 @@ __global__ __launch_bounds__(kThreads) void run_count(const int32_t *__restrict_
     int tot;
     (void)block_exclusive(n, &tot);
     if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-
-// exclusive scan of the nb block totals in place, one workgroup; total -> *total
-__global__ __launch_bounds__(kThreads) void scan_totals(int32_t *__restrict__ bsum, int64_t nb, int32_t *__restrict__ total) {
-    int carry = 0;
-    for (int64_t b0 = 0; b0 < nb; b0 += kThreads) {
-        const int64_t b = b0 + threadIdx.x;
-        const int v = b < nb ? bsum[b] : 0;
-        int tot;
-        const int ex = block_exclusive(v, &tot);
-        if (b < nb) bsum[b] = carry + ex;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) *total = carry;
 }
 
 __global__ __launch_bounds__(kThreads) void run_write(const int32_t *__restrict__ word, const int32_t *__restrict__ sel, int smax, int64_t items,
@@ -551,7 +523,7 @@ fa_status reconstruct(fa_ctx *ctx, const fa_reconstruct_config *cfg, const float
     if (Kc <= 64) hipLaunchKernelGGL(recon_frames<1>, dim3(fgrid), dim3(kThreads), 0, st, fa_args);
     else hipLaunchKernelGGL(recon_frames<4>, dim3(fgrid), dim3(kThreads), 0, st, fa_args);
     hipLaunchKernelGGL(run_count, dim3(static_cast<unsigned>(nb)), dim3(kThreads), 0, st, b_word.as<int32_t>(), b_sel.as<int32_t>(), smax, items, b_bsum.as<int32_t>());
-    hipLaunchKernelGGL(scan_totals, dim3(1), dim3(kThreads), 0, st, b_bsum.as<int32_t>(), nb, b_flags.as<int32_t>() + 1);
+    hipLaunchKernelGGL(fa::scan::scan_totals<>, dim3(1), dim3(kThreads), 0, st, b_bsum.as<int32_t>(), nb, b_flags.as<int32_t>() + 1);
     hipLaunchKernelGGL(run_write, dim3(static_cast<unsigned>(nb)), dim3(kThreads), 0, st, b_word.as<int32_t>(), b_sel.as<int32_t>(), smax, items,
                        b_bsum.as<int32_t>(), b_starts.as<int64_t>());
     FA_HIP_TRY(ctx, hipGetLastError());

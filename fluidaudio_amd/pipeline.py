@@ -15,6 +15,7 @@ assignment is skipped when the count was forced.  Segmentation, embedding extrac
 reference (out of scope)."""
 from __future__ import annotations
 
+import dataclasses
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -295,3 +296,70 @@ def diarize_segments(embedding256, rho128, chunk_indices, speaker_indices, phi, 
     rec = OfflineReconstruction(reconstruction, ctx=ctx)
     segs = rec.build_segments(segmentation, hard, res.centroids, span_embedder)
     return DiarizationSegments(segs, rec.build_speaker_database(segs, res.centroids), res, hard, dict(rec.last_info))
+
+
+@dataclass
+class ExtractedEmbeddings:
+    """extractEmbeddings' [TimedEmbedding] as arrays, in the reference's order: what diarize_segments takes (embedding256 [n, 256] fp32,
+    rho128 [n, 128] fp64, chunk_indices, speaker_indices) plus the metadata records (embedding.RECORD_DTYPE) and the plan behind them."""
+    embedding256: np.ndarray
+    rho128: np.ndarray
+    chunk_indices: np.ndarray
+    speaker_indices: np.ndarray
+    records: np.ndarray
+    plan: object
+
+
+def extract_embeddings(segmentation, audio, embedder, plda, config=None, ctx: L.Context | None = None) -> ExtractedEmbeddings:
+    """OfflineEmbeddingExtractor.extractEmbeddings (OfflineEmbeddingExtractor.swift:177-711) with the networks supplied by the caller:
+    ``embedder(windows [Bw, S], weights [Br, W], window_of_run [Br]) -> [Br, 256]`` is called once per fbank batch with that batch's
+    audio windows, the resampled masks of its model runs and, per run, the index of its window in ``windows`` (all torch CUDA tensors);
+    ``plda(emb [n, 256]) -> rho [n, 128]`` (fp64).  ``segmentation``: a ``reconstruct.SegmentationOutput`` (speaker weights on the host
+    are moved to ctx's device first); ``audio``: the recording, fp32.  ``config``: an ``embedding.EmbeddingConfig``.  Jobs skipped by maskSimilarity carry their cached
+    run's embedding."""
+    import torch
+    from .embedding import EmbeddingConfig, plan_embeddings
+    ctx = ctx or L.default_context()
+    cfg = config or EmbeddingConfig()
+    dev = torch.device("cuda", ctx.device)
+    a = audio if hasattr(audio, "data_ptr") else torch.from_numpy(np.ascontiguousarray(audio, np.float32))
+    a = a.to(dev, torch.float32).contiguous()
+    w = segmentation.speaker_weights
+    if not (hasattr(w, "is_cuda") and w.is_cuda):                       # the device entry: run_weights stay on the device for the embedder
+        w = torch.as_tensor(np.ascontiguousarray(w, np.float32) if not hasattr(w, "data_ptr") else w).to(dev, torch.float32)
+        segmentation = dataclasses.replace(segmentation, speaker_weights=w)
+    plan = plan_embeddings(segmentation, a.numel(), cfg, ctx=ctx)
+    runs = int(plan.info["runs"])
+    run_emb = []
+    for b in range(plan.batches):
+        r = plan.batch_runs(b)
+        if len(r) == 0:
+            continue
+        wins = plan.windows(b, a)
+        wor = torch.as_tensor(plan.window_of_run[r.start:r.stop] - plan.batch_windows(b).start, dtype=torch.int64, device=dev)
+        e = embedder(wins, plan.run_weights[r.start:r.stop], wor)
+        run_emb.append(torch.as_tensor(e).detach().float().cpu().numpy())
+    emb_runs = np.concatenate(run_emb, axis=0) if run_emb else np.zeros((runs, 256), np.float32)
+    emb = np.ascontiguousarray(emb_runs[plan.run_of_job], np.float32) if plan.run_of_job.size else np.zeros((0, emb_runs.shape[1]), np.float32)
+    rho = np.asarray(torch.as_tensor(plda(emb)).detach().double().cpu().numpy(), np.float64) if emb.shape[0] else np.zeros((0, 128))
+    return ExtractedEmbeddings(emb, rho, plan.chunk_indices, plan.speaker_indices, plan.records, plan)
+
+
+def span_embedder(audio, embedder, config=None, ctx: L.Context | None = None):
+    """A ``span_embedder(start_s, end_s) -> embedding or None`` for ``OfflineReconstruction.build_segments`` (the zero-vote re-embed pass):
+    embedSpan (OfflineEmbeddingExtractor.swift:243-297) through ``embedding.span_inputs`` and the same ``embedder`` as extract_embeddings
+    (one window, one run); None for a span without samples."""
+    import torch
+    from .embedding import EmbeddingConfig, span_inputs
+    ctx = ctx or L.default_context()
+    cfg = config or EmbeddingConfig()
+    a = audio if hasattr(audio, "data_ptr") else torch.from_numpy(np.ascontiguousarray(audio, np.float32))
+    a = a.to(torch.device("cuda", ctx.device), torch.float32).contiguous()
+
+    def embed(start_s, end_s):
+        win, wts, ok = span_inputs(a, [(start_s, end_s)], cfg, ctx=ctx)
+        if not bool(ok[0]):
+            return None
+        e = embedder(win, wts, torch.zeros(1, dtype=torch.int64, device=a.device))
+        return torch.as_tensor(e).detach().float().cpu().numpy()[0]
+    return embed

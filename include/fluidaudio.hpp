@@ -595,4 +595,62 @@ private:
     fa_reconstruct_config cfg_;
 };
 
+// ------------------------------------------------------------------------------------------------------------------ embedding inputs
+// OfflineEmbeddingExtractor.extractEmbeddings up to the networks (Sources/FluidAudio/Diarizer/Offline/Extraction/OfflineEmbeddingExtractor.swift:
+// 177-711) over fa_embedding_plan: speakerWeights [chunks][frames][speakers] (powerset decode output) -> which (chunk, speaker) pairs get an
+// embedding (records: the TimedEmbedding metadata), the model run each one carries (runOfJob), the fbank window of each run (windowOfRun,
+// windowStart) and the resampled masks the embedding model takes (runWeights [runs][weightFrames]).  The networks are the caller's.
+class OfflineEmbeddingPlanner {
+public:
+    struct Plan {
+        std::vector<fa_export_embedding> records;
+        std::vector<int32_t> runOfJob, windowOfRun, windowChunk;
+        std::vector<int64_t> windowStart;
+        std::vector<std::vector<float>> runWeights, frameWeights;   // frameWeights: the chosen masks before resampling (when asked for)
+        fa_embedding_info info{};
+    };
+    explicit OfflineEmbeddingPlanner(fa_embedding_config config = defaultConfig()) : cfg_(config) {}
+    static fa_embedding_config defaultConfig() { fa_embedding_config c; fa_embedding_default_config(&c); return c; }
+    Plan plan(Context &ctx, const std::vector<std::vector<std::vector<float>>> &speakerWeights, const std::vector<double> &chunkOffsets,
+              int64_t totalSamples, double frameDuration = 0.0, bool frameWeights = false) const {
+        const int64_t C = static_cast<int64_t>(speakerWeights.size());
+        const int32_t F = C ? static_cast<int32_t>(speakerWeights[0].size()) : 0;
+        const int32_t S = F ? static_cast<int32_t>(speakerWeights[0][0].size()) : 0;
+        std::vector<float> w;
+        w.reserve(static_cast<size_t>(C * F * S));
+        for (const auto &chunk : speakerWeights) {
+            if (static_cast<int32_t>(chunk.size()) != F) throw Error(FA_INVALID_ARGUMENT, "OfflineEmbeddingPlanner: ragged frames");
+            for (const auto &frame : chunk) {
+                if (static_cast<int32_t>(frame.size()) != S) throw Error(FA_INVALID_ARGUMENT, "OfflineEmbeddingPlanner: ragged speakers");
+                w.insert(w.end(), frame.begin(), frame.end());
+            }
+        }
+        fa_embedding_config cfg = cfg_;
+        cfg.frame_duration = frameDuration;
+        const size_t cap = static_cast<size_t>(std::max<int64_t>(C * S, 1)), W = static_cast<size_t>(std::max(cfg.weight_frames, 1));
+        Plan p;
+        p.records.resize(cap);
+        p.runOfJob.resize(cap);
+        p.windowOfRun.resize(cap);
+        p.windowStart.resize(static_cast<size_t>(std::max<int64_t>(C, 1)));
+        p.windowChunk.resize(p.windowStart.size());
+        std::vector<float> rows(cap * W), masks(frameWeights ? cap * static_cast<size_t>(std::max(F, 1)) : 0);
+        ctx.check(fa_embedding_plan(ctx.handle(), &cfg, w.data(), C, F, S, chunkOffsets.data(), static_cast<int64_t>(chunkOffsets.size()), totalSamples,
+                                    p.records.data(), p.runOfJob.data(), p.windowOfRun.data(), p.windowStart.data(), p.windowChunk.data(), rows.data(),
+                                    frameWeights ? masks.data() : nullptr, &p.info),
+                  "fa_embedding_plan");
+        const size_t jobs = static_cast<size_t>(p.info.jobs), runs = static_cast<size_t>(p.info.runs), nw = static_cast<size_t>(p.info.planned_chunks);
+        p.records.resize(jobs);
+        p.runOfJob.resize(jobs);
+        p.windowOfRun.resize(runs);
+        p.windowStart.resize(nw);
+        p.windowChunk.resize(nw);
+        for (size_t r = 0; r < runs; ++r) p.runWeights.emplace_back(rows.begin() + r * W, rows.begin() + (r + 1) * W);
+        if (frameWeights) for (size_t j = 0; j < jobs; ++j) p.frameWeights.emplace_back(masks.begin() + j * F, masks.begin() + (j + 1) * F);
+        return p;
+    }
+private:
+    fa_embedding_config cfg_;
+};
+
 }  // namespace fluidaudio

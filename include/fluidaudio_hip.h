@@ -676,6 +676,81 @@ fa_status fa_offline_reconstruct_dev(fa_ctx *ctx, const fa_reconstruct_config *c
 fa_status fa_segments_finalize(const fa_reconstruct_config *cfg, const fa_rttm_segment *raw, int64_t n, fa_rttm_segment *out,
                                int64_t capacity, int64_t *count);
 
+/* ------------------------------------------------------------------ embedding inputs ------ */
+/* OfflineEmbeddingExtractor.extractEmbeddings (FluidAudio/Diarizer/Offline/Extraction/OfflineEmbeddingExtractor.swift:177-711) up to the
+ * networks: which (chunk, local speaker) pairs get an embedding, each one's mask resampled to the embedding model's weight length
+ * (WeightInterpolation.swift:19-116), the fbank windows, and the TimedEmbedding metadata.  The networks (fbank, embedding, PLDA) are the
+ * caller's.  Defaults = OfflineDiarizerTypes.swift:46-55, 82-105, 297-303, 348-353. */
+typedef struct {
+    double window_duration;          /* 10.0: offset of a chunk without a finite offset = index * window_duration (:197-202, :658-661) */
+    int32_t sample_rate;             /* 16000 */
+    int32_t samples_per_window;      /* 0 = Int(sample_rate * window_duration) */
+    float overlap_threshold;         /* 1e-3: a speaker is active in a frame above this (:303) */
+    int32_t exclude_overlap;         /* 1: the clean mask zeroes frames with more than one active speaker */
+    double min_segment_duration;     /* 1.0: minFrames = max(1, ceil(min_segment_duration / frame_duration)) */
+    int32_t batch_size;              /* 32: fbank batches of clamp(batch_size, 1, 32) planned chunks (:162) */
+    int32_t skip_enabled;            /* 0: EmbeddingSkipStrategy.none; 1: maskSimilarity(skip_threshold) */
+    float skip_threshold;            /* 0.95 */
+    int32_t weight_frames;           /* 589: the embedding model's weight length */
+    double frame_duration;           /* 0 = window_duration / frames */
+} fa_embedding_config;
+void fa_embedding_default_config(fa_embedding_config *cfg);
+typedef struct {
+    int64_t planned_chunks;          /* chunks whose window holds audio: the fbank windows */
+    int64_t batches;                 /* fbank batches */
+    int64_t jobs;                    /* valid masks = embeddings (records) */
+    int64_t runs;                    /* embedding-model runs (jobs - skipped) */
+    int64_t evaluated_masks;         /* the reference's counters (:713-735) */
+    int64_t empty_masks;
+    int64_t fallback_masks;          /* base mask used because the clean one was shorter than minFrames (also counted when then empty) */
+    int64_t skipped_embeddings;
+    double frame_duration;           /* the frame duration used */
+    int32_t min_frames;
+    int32_t samples_per_window;
+    int32_t batch_size;              /* the clamped batch size */
+} fa_embedding_info;
+/* weights float[chunks][frames][speakers] (fa_powerset_decode's output or soft weights); offsets double[n_offsets] chunk starts in seconds;
+ * total_samples = the audio's length.  A chunk is planned when start = clamp(round-half-away(offset * rate), 0, total) < min(start +
+ * samples_per_window, total).  Per planned chunk and speaker (in this order): baseSum <= 0, cleanSum < Float(frames) * 0.2 and a zero
+ * sum of the resampled mask make the mask empty; cleanSum >= Float(minFrames) picks the clean mask, otherwise the base one.  Every sum and
+ * dot product is sequential in frame order in fp32 (exact, hence the reference's bits, for 0/1 weights; pinned to the restatement for soft
+ * weights).  Departure: a non-finite weight in a planned chunk is INVALID_ARGUMENT (the reference would feed NaN to the model).
+ * Outputs, capacity chunks * speakers rows each, in the reference's order (chunk-major, speaker-minor):
+ *   records       HOST fa_export_embedding[jobs]: chunk, speaker, first / last active frame, start / end time (fp64, no FMA)
+ *   run_of_job    HOST int32[jobs]: the model run whose embedding the job carries (its own, or a cached one under maskSimilarity)
+ *   window_of_run HOST int32[runs]: the planned window (index into window_start) each run's fbank input comes from
+ *   window_start  HOST int64[planned_chunks] (nullable): first sample of each planned window; window_chunk HOST int32[...] (nullable): its chunk
+ *   run_weights   float[runs][weight_frames]: the model's weights input; mask_rows (nullable) float[jobs][frames]: the chosen masks
+ *                 before resampling (TimedEmbedding.frameWeights)
+ * _dev: weights, run_weights and mask_rows are DEVICE pointers on the context's device, read / written in stream order; otherwise HOST
+ * pointers.  Both calls are synchronous for the counts in info. */
+fa_status fa_embedding_plan(fa_ctx *ctx, const fa_embedding_config *cfg, const float *weights, int64_t chunks, int32_t frames, int32_t speakers,
+                            const double *offsets, int64_t n_offsets, int64_t total_samples, fa_export_embedding *records, int32_t *run_of_job,
+                            int32_t *window_of_run, int64_t *window_start, int32_t *window_chunk, float *run_weights, float *mask_rows,
+                            fa_embedding_info *info);
+fa_status fa_embedding_plan_dev(fa_ctx *ctx, const fa_embedding_config *cfg, const float *d_weights, int64_t chunks, int32_t frames,
+                                int32_t speakers, const double *offsets, int64_t n_offsets, int64_t total_samples, fa_export_embedding *records,
+                                int32_t *run_of_job, int32_t *window_of_run, int64_t *window_start, int32_t *window_chunk, float *d_run_weights,
+                                float *d_mask_rows, fa_embedding_info *info);
+/* The fbank windows of `count` planned windows (a range of window_start, HOST int64[count]): d_out float[count][samples_per_window] =
+ * audio[start : min(start + samples_per_window, total_samples)] followed by zeros (:807-832, AudioSampleSource.swift:23-39).  d_audio,
+ * d_out: DEVICE pointers.  Synchronous (the host starts are staged in the call). */
+fa_status fa_embedding_windows_dev(fa_ctx *ctx, const float *d_audio, int64_t total_samples, const int64_t *window_start, int64_t count,
+                                   int32_t samples_per_window, float *d_out);
+/* embedSpan's inputs (:243-297) for n spans double[n][2] (start, end seconds, HOST): startSample = max(0, round(start * rate)), endSample
+ * = min(total, round(end * rate)), len = min(endSample - startSample, samples_per_window); windows float[n][samples_per_window] = the span's
+ * samples then zeros, weights float[n][weight_frames] = 1 for the first max(1, min(W, round(len / samples_per_window * W))) frames.
+ * statuses HOST fa_status[n]: INVALID_ARGUMENT for an empty or non-finite span (its rows are zeros).  _dev: audio, windows, weights are
+ * DEVICE pointers; otherwise HOST pointers.  Synchronous. */
+fa_status fa_embedding_span_inputs(fa_ctx *ctx, const fa_embedding_config *cfg, const float *audio, int64_t total_samples, const double *spans,
+                                   int64_t n, float *windows, float *weights, fa_status *statuses);
+fa_status fa_embedding_span_inputs_dev(fa_ctx *ctx, const fa_embedding_config *cfg, const float *d_audio, int64_t total_samples,
+                                       const double *spans, int64_t n, float *d_windows, float *d_weights, fa_status *statuses);
+/* WeightInterpolation.resample2D (:19-116): rows float[rows][in_frames] -> float[rows][out_frames], bit-exact (identity when the lengths
+ * agree; nothing is written when a length is 0).  _dev: DEVICE pointers, enqueued on the context's stream; otherwise HOST pointers. */
+fa_status fa_weight_resample(fa_ctx *ctx, const float *in, int64_t rows, int32_t in_frames, int32_t out_frames, float *out);
+fa_status fa_weight_resample_dev(fa_ctx *ctx, const float *d_in, int64_t rows, int32_t in_frames, int32_t out_frames, float *d_out);
+
 /* ------------------------------------------------------------------ resampling ------ */
 /* AudioConverter.linearResample (FluidAudio/Shared/AudioConverter.swift:388-442): planar float[channels][frames] ->
  * mono mix (weight 1/channels) -> linear interpolation to out_rate.  HOST pointers.  Bit-exact restatement. */
