@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the hot path on N MI355X GPUs of one node.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
 
 BASELINE.json metric: "audio hours/sec featurized+clustered per node; AHC wall-clock @ 50k x 256 embeds".
@@ -11,17 +11,23 @@ features, resident in HBM): AHC (threshold 0.6) -> VBx -> gamma-weighted centroi
 library call (fa_offline_cluster).  `value` = audio hours featurized + clustered per second over all ranks (weak scaling: every
 rank owns its own recording; the merge chain of one recording does not shard — DESIGN.md §4).  The session of rank 0 is the one
 whose CPU-side results are committed (tests/golden/e2e_8h.json: AHC on the REFERENCE's own linkage build, the rest from the C
-restatements); `e2e_equals_reference_digest` says the timed calls reproduced them.
+restatements); with --full, `e2e_equals_reference_digest` says the timed calls reproduced them.
+
+A plain run does what its headline figure needs and nothing more: it sets up, warms up, times the K steps, writes --dump-outputs,
+prints the headline's own leg line (e2e_8h) and, LAST, the result line the driver parses.  --full then runs everything else: the
+headline's digest checks and mel share, the CPU baselines and the other legs below (the --skip-* options leave legs out of it).
 
 Output (rank 0): one `{"leg": name, "result": {...}}` line per leg as soon as the leg is done, everything again in bench_legs.json,
-one `{"summary": {...}}` line, and LAST the result line the driver parses — the contract's keys, scalars only, < 4 KB — with
+with --full one `{"summary": {...}}` line, and LAST the result line — the contract's keys, scalars only, < 4 KB — with
   roofline      — the dominant kernel of the step (ahc_round_t, one launch per merge): algorithmic bytes per launch / average
                   launch period measured with HIP events around the merge phase, against 8 TB/s; traffic from the committed PMC pass
-  cpu_baseline  — the same path on this box's host cores: the reference's linkage build (oracle/_ref) + the C restatements, 1 thread
+  cpu_baseline  — --full: the same path on the host's own cores: the reference's linkage build (oracle/_ref) + the C restatements,
+                  1 thread; null in a plain run
+The figures of `config` that come from other legs (ahc_50k_seconds, mel_realtime_factor, ...) are null in a plain run.
 --dump-outputs DIR: after the timed steps, rank 0 writes what the last one returned (a seeded sample of the mel chunks, the mel lengths,
 the assignments, the centroids) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
-Legs:
-  e2e_8h        — the timed region itself (stages, digest checks, start-up TFLOP/s)
+Legs (all but e2e_8h with --full only):
+  e2e_8h        — the timed region itself (stages, start-up TFLOP/s; --full: digest checks, mel share)
   mel           — BASELINE configs[1]: 1024 x 15 s chunks per GPU, its own HBM roofline (HIP events per launch)
   mel_single_10s— configs[0] shape: one 10 s utterance through the host-pointer entry, p50 / p99 latency
   ctc           — configs[3]: greedy CTC on 10 000 x [1500, 1024] matrices (sharded over the ranks at N > 1), ids verified in-bench
@@ -693,13 +699,14 @@ def measured_traffic_of(pattern, files):
     return None, {"file": None, "note": "no PMC summary for the present kernel sources (sha256 %s...)" % now[:12]}
 
 
-def e2e_session_for(rank, hours):
+def e2e_session_for(rank, hours, digests):
+    """The recording of a rank; with `digests`, rank 0 also gets the committed CPU-side results of the 8 h session (gold, aux) when they apply."""
     sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
     from e2e_inputs import e2e_session, input_digest
     s = e2e_session(hours, 12, seed=5 + rank)
     gold = aux = None
     gp = os.path.join(ROOT, "tests", "golden", "e2e_8h.json")
-    if rank == 0 and hours == 8.0 and os.path.exists(gp):
+    if digests and rank == 0 and hours == 8.0 and os.path.exists(gp):
         with open(gp) as f:
             gold = json.load(f)
         if gold["input_sha256"] != input_digest(s):
@@ -835,11 +842,12 @@ def dump_outputs(dump_dir, torch, d_out, d_len, result):
         np.save(os.path.join(dump_dir, f"{name}.npy"), a)
 
 
-def headline_leg(fa, ctx, torch, dist, rank, world, steps, warmup, hours=8.0, dump_dir=None):
+def headline_leg(fa, ctx, torch, dist, rank, world, steps, warmup, hours=8.0, dump_dir=None, full=False):
     """The timed region of the bench: K x (mel over the recording's chunks + fa_offline_cluster on its embeddings), inputs resident.
-    dump_dir: rank 0 writes what the last timed step computed there (dump_outputs)."""
+    dump_dir: rank 0 writes what the last timed step computed there (dump_outputs).  full: afterwards, the mel share of a step is timed
+    on its own and the last step is checked against the committed digests (a clustering call of its own); a plain run does neither."""
     from e2e_inputs import sha256 as sha
-    s, gold, aux = e2e_session_for(rank, hours)
+    s, gold, aux = e2e_session_for(rank, hours, digests=full)
     n_chunks15 = int(hours * 3600 / 15)
     d_pcm = synth_pcm(torch, n_chunks15, 99 + rank)
     mel = fa.AudioMelSpectrogram(ctx=ctx)
@@ -885,11 +893,13 @@ def headline_leg(fa, ctx, torch, dist, rank, world, steps, warmup, hours=8.0, du
         elapsed = float(tt)
     if dump_dir is not None and rank == 0:
         dump_outputs(dump_dir, torch, d_out, d_len, results[-1])
-    # mel share of a step, timed on its own (not part of the timed region above)
-    t0 = time.perf_counter()
-    plan.execute(d_pcm, d_out, d_len, order=False)
-    ctx.synchronize()
-    t_mel = time.perf_counter() - t0
+    t_mel = None
+    if full:
+        # mel share of a step, timed on its own (not part of the timed region above)
+        t0 = time.perf_counter()
+        plan.execute(d_pcm, d_out, d_len, order=False)
+        ctx.synchronize()
+        t_mel = time.perf_counter() - t0
     assert int(d_len[0]) == 1501 and bool(torch.isfinite(d_out[n_chunks15 // 2]).all())
     # ---- verification of what was timed
     lab = [np.asarray(r.assignments, np.int32) for r in results]
@@ -1221,13 +1231,13 @@ def result_line_of(full):
         out["cpu_baseline"] = {k: _num(cpu.get(k)) for k in ("value", "unit", "cores", "kind", "sample", "mel_s", "cluster_s") if k in cpu} if "error" not in cpu \
             else {"error": _num(cpu["error"])}
     else:
-        out["cpu_baseline"] = None            # N > 1 (rank 0 of a multi-rank run does not time the CPU side) or --skip-cpu
+        out["cpu_baseline"] = None            # a plain run (no --full), N > 1 (rank 0 of a multi-rank run does not time the CPU side) or --skip-cpu
     out["legs_file"] = "bench_legs.json"
     return out
 
 
-def finish(full, rank):
-    """Rank 0: bench_legs.json (everything), the summary line, the result line (last)."""
+def finish(full, rank, all_legs):
+    """Rank 0: bench_legs.json (everything), the summary line (all_legs: a --full run), the result line (last)."""
     if rank != 0:
         return
     for dest in (os.path.join(ROOT, "bench_legs.json"), os.path.join(ROOT, "gpurun_out", "bench_legs.json")):
@@ -1237,7 +1247,8 @@ def finish(full, rank):
                     json.dump(_strict_tree(full), f, allow_nan=False, default=str)
             except OSError as e:
                 print(f"bench.py: could not write {dest}: {e}", file=sys.stderr)
-    print(json.dumps({"summary": summary_of(full)}, allow_nan=False), flush=True)
+    if all_legs:
+        print(json.dumps({"summary": summary_of(full)}, allow_nan=False), flush=True)
     text = json.dumps(result_line_of(full), allow_nan=False)
     assert len(text) < RESULT_LINE_MAX_BYTES, len(text)
     print(text, flush=True)
@@ -1264,117 +1275,10 @@ def ranks_seen(torch, dist, device):
     return int(one.item())
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10, help="timed steps; one step = one 8 h recording featurized + clustered (~0.3 s)")
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--hours", type=float, default=8.0, help="length of the recording of a step (BASELINE configs[4]: 8)")
-    ap.add_argument("--mel-steps", type=int, default=200, help="launches of the configs[1] mel leg")
-    ap.add_argument("--mel-warmup", type=int, default=20)
-    ap.add_argument("--clock-warm-s", type=float, default=0.3,
-                    help="mel leg: seconds of the same launches before its warm-up steps: the device leaves idle clocks only after ~30 ms "
-                         "of sustained load (launch time falls from 0.95 to 0.68 ms over the first ~40 launches, scripts/mel_variance.py)")
-    ap.add_argument("--chunks", type=int, default=CHUNKS_PER_GPU, help="mel leg: 15 s chunks per GPU per launch (BASELINE config: 1024)")
-    ap.add_argument("--skip-mel", action="store_true")
-    ap.add_argument("--skip-ahc", action="store_true")
-    ap.add_argument("--skip-ctc", action="store_true")
-    ap.add_argument("--skip-cpu", action="store_true")
-    ap.add_argument("--cpu-full", action="store_true", help="time the CPU side on the full --hours session instead of the bounded 1 h sample (8 h: ~20 minutes on one core)")
-    ap.add_argument("--skip-e2e", action="store_true", help="skip the 16 x 1 h leg (the headline itself cannot be skipped)")
-    ap.add_argument("--skip-beam", action="store_true")
-    ap.add_argument("--skip-resample", action="store_true")
-    ap.add_argument("--in-flight", action="store_true", help="also run round 3's four-chains-in-flight leg (queue-dependent; superseded by e2e_8h_batch)")
-    ap.add_argument("--vbx-sharded", action="store_true", help="run the sharded-VBx leg at N = 1 too (it always runs at N > 1)")
-    ap.add_argument("--only-mel", action="store_true", help="profiling helper: the configs[1] mel leg alone, printed as a reduced line")
-    ap.add_argument("--ctc-matrices", type=int, default=10000)
-    ap.add_argument("--launch-check", action="store_true", help="start the ranks, form the process group, all-reduce a one per rank, print what was seen; no device work")
-    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy")
-    args = ap.parse_args()
-
-    if args.gpus < 1:
-        ap.error("--gpus must be >= 1")
-    if args.steps < 1 or args.warmup < 0:
-        ap.error("--steps must be >= 1 and --warmup >= 0")
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        sys.exit(launch_ranks(args.gpus))                          # `python bench.py --gpus N` starts its own N ranks
-    import torch
-
-    rank = int(os.environ.get("RANK", "0"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    if world != args.gpus:
-        # one rank per GPU is the contract: a launcher that started a different number of ranks than --gpus says is a mistake, not a warning
-        if rank == 0:
-            print(f"bench.py: --gpus {args.gpus} but the launcher started WORLD_SIZE {world} rank(s)", file=sys.stderr)
-        sys.exit(2)
-    backend = os.environ.get("FA_BENCH_BACKEND", "nccl")          # "gloo": a rehearsal of the N > 1 control flow on a box with fewer GPUs than ranks
-    dist = None
-    if world > 1:
-        import torch.distributed as dist
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        if args.launch_check:                                      # control flow only (runs without a GPU): rendezvous + one all-reduce
-            dist.init_process_group("gloo" if not torch.cuda.is_available() else backend, rank=rank, world_size=world)
-            seen = ranks_seen(torch, dist, torch.device("cuda", local_rank % torch.cuda.device_count()) if torch.cuda.is_available() and backend == "nccl" else None)
-            if rank == 0:
-                print(json.dumps({"launch_check": True, "n_gpus": seen, "world_size_env": world, "backend": dist.get_backend()}))
-            dist.barrier()
-            dist.destroy_process_group()
-            return
-        have = torch.cuda.device_count()
-        if backend == "nccl" and have < world:
-            if rank == 0:
-                print(f"bench.py: --gpus {world} needs {world} visible GPUs, this box has {have} (FA_BENCH_BACKEND=gloo rehearses the control flow "
-                      "with several ranks per GPU)", file=sys.stderr)
-            sys.exit(2)
-        if backend != "nccl":
-            local_rank %= max(have, 1)
-        torch.cuda.set_device(local_rank)
-        if backend == "nccl":
-            dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank))
-        else:
-            dist.init_process_group(backend, rank=rank, world_size=world)
-        seen = ranks_seen(torch, dist, torch.device("cuda", local_rank) if backend == "nccl" else None)
-        if seen != world:
-            raise RuntimeError(f"the process group saw {seen} ranks, WORLD_SIZE says {world}")
-    else:
-        if args.launch_check:
-            print(json.dumps({"launch_check": True, "n_gpus": 1, "world_size_env": 1, "backend": None}))
-            return
-        torch.cuda.set_device(local_rank)
-    import fluidaudio_amd as fa
-    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
-
-    ctx = fa.default_context(local_rank)
+def full_legs(args, line, fa, ctx, torch, dist, rank, world):
+    """--full: every leg after the headline (the CPU baselines, the other BASELINE configs, kernels and serving shapes, each with its own
+    roofline and in-bench check), added to `line` one by one.  Ranks other than 0 take part in the legs with a collective only."""
     solo = world == 1
-    if args.only_mel:
-        m = mel_leg(fa, ctx, torch, dist, rank, world, args.chunks, args.mel_steps, args.mel_warmup, args.clock_warm_s, measure_aligned=False)
-        if rank == 0:
-            print(json.dumps({"metric": "mel leg only (profiling helper)", "mel": m}))
-        if dist is not None:
-            dist.barrier()
-            dist.destroy_process_group()
-        return
-
-    # ---------------- the timed region: K steps of configs[4]
-    h = headline_leg(fa, ctx, torch, dist, rank, world, args.steps, args.warmup, args.hours, args.dump_outputs)
-    elapsed = h.pop("elapsed")
-    value = world * args.hours * args.steps / elapsed
-    roof = h.pop("roofline")
-    line = LegRecord(rank)
-    line.update({
-        "metric": "audio hours/sec featurized+clustered per node; AHC wall-clock @ 50k x 256 embeds (ahc_50k.seconds)",
-        "value": value, "unit": "audio_hours/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic",
-        # strings of the result line stay <= 120 characters (the driver cuts at 128); the long form of the workload is DESIGN.md section 5
-        "config": {"workload": f"configs[4]: per GPU one {args.hours:g} h 16 kHz recording -> mel -> {int(args.hours * 5400)} embeds -> AHC+VBx+assignment, HBM-resident",
-                   "hours_per_step_per_gpu": args.hours, "embeddings_per_recording": h["embeddings"], "realtime_factor": value * 3600.0,
-                   "parallelism": f"dp{world}"},
-        "e2e_equals_reference_digest": h["e2e_equals_reference_digest"],
-        "roofline": roof,
-    })
-    line["e2e_8h"] = h
     torch.cuda.empty_cache()
     if solo and not args.skip_cpu and rank == 0:
         try:
@@ -1404,9 +1308,6 @@ def main():
         line["vbx_sharded"] = r
         torch.cuda.empty_cache()
     if rank != 0:
-        if dist is not None:
-            dist.barrier()
-            dist.destroy_process_group()
         return
     if solo and not args.skip_mel:
         try:
@@ -1484,7 +1385,127 @@ def main():
             line["beam_search"] = beam_leg(fa, ctx, torch)
         except Exception as e:  # noqa: BLE001
             line["beam_search"] = {"error": repr(e)}
-    finish(line, rank)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps; one step = one 8 h recording featurized + clustered (~0.3 s)")
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--hours", type=float, default=8.0, help="length of the recording of a step (BASELINE configs[4]: 8)")
+    ap.add_argument("--mel-steps", type=int, default=200, help="launches of the configs[1] mel leg")
+    ap.add_argument("--mel-warmup", type=int, default=20)
+    ap.add_argument("--clock-warm-s", type=float, default=0.3,
+                    help="mel leg: seconds of the same launches before its warm-up steps: the device leaves idle clocks only after ~30 ms "
+                         "of sustained load (launch time falls from 0.95 to 0.68 ms over the first ~40 launches, scripts/mel_variance.py)")
+    ap.add_argument("--chunks", type=int, default=CHUNKS_PER_GPU, help="mel leg: 15 s chunks per GPU per launch (BASELINE config: 1024)")
+    ap.add_argument("--skip-mel", action="store_true")
+    ap.add_argument("--skip-ahc", action="store_true")
+    ap.add_argument("--skip-ctc", action="store_true")
+    ap.add_argument("--skip-cpu", action="store_true")
+    ap.add_argument("--cpu-full", action="store_true", help="time the CPU side on the full --hours session instead of the bounded 1 h sample (8 h: ~20 minutes on one core)")
+    ap.add_argument("--skip-e2e", action="store_true", help="skip the 16 x 1 h leg (the headline itself cannot be skipped)")
+    ap.add_argument("--skip-beam", action="store_true")
+    ap.add_argument("--skip-resample", action="store_true")
+    ap.add_argument("--in-flight", action="store_true", help="also run round 3's four-chains-in-flight leg (queue-dependent; superseded by e2e_8h_batch)")
+    ap.add_argument("--vbx-sharded", action="store_true", help="run the sharded-VBx leg at N = 1 too (it always runs at N > 1)")
+    ap.add_argument("--only-mel", action="store_true", help="profiling helper: the configs[1] mel leg alone, printed as a reduced line")
+    ap.add_argument("--ctc-matrices", type=int, default=10000)
+    ap.add_argument("--launch-check", action="store_true", help="start the ranks, form the process group, all-reduce a one per rank, print what was seen; no device work")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run what it does not need: its digest checks and mel share, the CPU baselines and every other leg "
+                         "(the --skip-* options leave legs out of it, --cpu-full / --in-flight / --vbx-sharded add to it)")
+    args = ap.parse_args()
+
+    if args.gpus < 1:
+        ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    extras = [f"--{k.replace('_', '-')}" for k in ("cpu_full", "in_flight", "vbx_sharded") if getattr(args, k)]
+    if extras and not args.full:
+        ap.error(f"{' '.join(extras)} adds to the legs of --full: give --full as well")
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        sys.exit(launch_ranks(args.gpus))                          # `python bench.py --gpus N` starts its own N ranks
+    import torch
+
+    rank = int(os.environ.get("RANK", "0"))
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world != args.gpus:
+        # one rank per GPU is the contract: a launcher that started a different number of ranks than --gpus says is a mistake, not a warning
+        if rank == 0:
+            print(f"bench.py: --gpus {args.gpus} but the launcher started WORLD_SIZE {world} rank(s)", file=sys.stderr)
+        sys.exit(2)
+    backend = os.environ.get("FA_BENCH_BACKEND", "nccl")          # "gloo": a rehearsal of the N > 1 control flow on a box with fewer GPUs than ranks
+    dist = None
+    if world > 1:
+        import torch.distributed as dist
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        if args.launch_check:                                      # control flow only (runs without a GPU): rendezvous + one all-reduce
+            dist.init_process_group("gloo" if not torch.cuda.is_available() else backend, rank=rank, world_size=world)
+            seen = ranks_seen(torch, dist, torch.device("cuda", local_rank % torch.cuda.device_count()) if torch.cuda.is_available() and backend == "nccl" else None)
+            if rank == 0:
+                print(json.dumps({"launch_check": True, "n_gpus": seen, "world_size_env": world, "backend": dist.get_backend()}))
+            dist.barrier()
+            dist.destroy_process_group()
+            return
+        have = torch.cuda.device_count()
+        if backend == "nccl" and have < world:
+            if rank == 0:
+                print(f"bench.py: --gpus {world} needs {world} visible GPUs, this box has {have} (FA_BENCH_BACKEND=gloo rehearses the control flow "
+                      "with several ranks per GPU)", file=sys.stderr)
+            sys.exit(2)
+        if backend != "nccl":
+            local_rank %= max(have, 1)
+        torch.cuda.set_device(local_rank)
+        if backend == "nccl":
+            dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank))
+        else:
+            dist.init_process_group(backend, rank=rank, world_size=world)
+        seen = ranks_seen(torch, dist, torch.device("cuda", local_rank) if backend == "nccl" else None)
+        if seen != world:
+            raise RuntimeError(f"the process group saw {seen} ranks, WORLD_SIZE says {world}")
+    else:
+        if args.launch_check:
+            print(json.dumps({"launch_check": True, "n_gpus": 1, "world_size_env": 1, "backend": None}))
+            return
+        torch.cuda.set_device(local_rank)
+    import fluidaudio_amd as fa
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+
+    ctx = fa.default_context(local_rank)
+    if args.only_mel:
+        m = mel_leg(fa, ctx, torch, dist, rank, world, args.chunks, args.mel_steps, args.mel_warmup, args.clock_warm_s, measure_aligned=False)
+        if rank == 0:
+            print(json.dumps({"metric": "mel leg only (profiling helper)", "mel": m}))
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---------------- the timed region: K steps of configs[4]
+    h = headline_leg(fa, ctx, torch, dist, rank, world, args.steps, args.warmup, args.hours, args.dump_outputs, full=args.full)
+    elapsed = h.pop("elapsed")
+    value = world * args.hours * args.steps / elapsed
+    roof = h.pop("roofline")
+    line = LegRecord(rank)
+    line.update({
+        "metric": "audio hours/sec featurized+clustered per node; AHC wall-clock @ 50k x 256 embeds (ahc_50k.seconds)",
+        "value": value, "unit": "audio_hours/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        # strings of the result line stay <= 120 characters (the driver cuts at 128); the long form of the workload is DESIGN.md section 5
+        "config": {"workload": f"configs[4]: per GPU one {args.hours:g} h 16 kHz recording -> mel -> {int(args.hours * 5400)} embeds -> AHC+VBx+assignment, HBM-resident",
+                   "hours_per_step_per_gpu": args.hours, "embeddings_per_recording": h["embeddings"], "realtime_factor": value * 3600.0,
+                   "parallelism": f"dp{world}"},
+        "e2e_equals_reference_digest": h["e2e_equals_reference_digest"],
+        "roofline": roof,
+    })
+    line["e2e_8h"] = h
+    if args.full:
+        full_legs(args, line, fa, ctx, torch, dist, rank, world)
+    finish(line, rank, args.full)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
