@@ -136,6 +136,16 @@ def lib() -> C.CDLL:
         L.fa_oracle_resample_linear_frames.restype = C.c_long
         L.fa_oracle_resample_linear.argtypes = [_f32p, C.c_int, C.c_long, C.c_double, C.c_double, _f32p]
         L.fa_oracle_resample_linear.restype = C.c_long
+        _i64p = np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS")
+        L.fa_oracle_lm_create.argtypes = [C.c_long, C.c_char_p, _i64p, _f32p, _f32p, C.c_long, C.c_char_p, _i64p, C.c_char_p, _i64p, _f32p]
+        L.fa_oracle_lm_create.restype = C.c_void_p
+        L.fa_oracle_lm_destroy.argtypes = [C.c_void_p]
+        L.fa_oracle_lm_destroy.restype = None
+        L.fa_oracle_lm_score.argtypes = [C.c_void_p, C.c_char_p, C.c_long, C.c_char_p, C.c_long]
+        L.fa_oracle_lm_score.restype = C.c_float
+        L.fa_oracle_ctc_beam_search.argtypes = [_f32p, C.c_long, C.c_long, C.c_long, C.c_char_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                C.c_float, C.c_float, C.c_int, C.c_int, _i32p, C.POINTER(C.c_float)]
+        L.fa_oracle_ctc_beam_search.restype = C.c_long
     return _lib
 
 
@@ -640,7 +650,7 @@ def rttm_parse(text: str, strict: bool = True):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# CTC prefix beam search with ARPA language model (pure Python restatement; small cases only)
+# CTC prefix beam search with ARPA language model (pure Python restatement, small cases; ctc_beam_search_c is its compiled twin)
 WORD_BOUNDARY = "▁"          # ASRConstants.sentencePieceWordBoundary
 
 
@@ -786,6 +796,83 @@ def ctc_beam_search(log_probs, vocabulary: dict, lm=None, beam_width=100, lm_wei
         if best is None or t > best_total:
             best, best_total = b, t
     return list(best["prefix"]), float(best_total)
+
+
+def _byte_table(strings):
+    """UTF-8 bytes of the strings back to back and their offsets (len + 1)"""
+    raw = [w.encode("utf-8") for w in strings]
+    off = np.zeros(len(raw) + 1, np.int64)
+    off[1:] = np.cumsum([len(b) for b in raw], dtype=np.int64)
+    return b"".join(raw), off
+
+
+class CLanguageModel:
+    """An ARPALanguageModel's unigrams and bigrams handed to the C restatement (fa_oracle_lm: sorted tables, bsearch over bytes).
+    A snapshot: entries added to the Python model later are not seen.  Usable as a context manager."""
+
+    def __init__(self, lm: ARPALanguageModel):
+        uw = list(lm.unigrams)
+        ub, uo = _byte_table(uw)
+        up = np.array([lm.unigrams[w][0] for w in uw], np.float32)
+        ubo = np.array([lm.unigrams[w][1] for w in uw], np.float32)
+        pairs = [(c, w, e[0]) for c, d in lm.bigrams.items() for w, e in d.items()]
+        cb, co = _byte_table([c for c, _, _ in pairs])
+        wb, wo = _byte_table([w for _, w, _ in pairs])
+        bp = np.array([p for _, _, p in pairs], np.float32)
+        self.handle = lib().fa_oracle_lm_create(len(uw), ub, uo, up, ubo, len(pairs), cb, co, wb, wo, bp)
+        if not self.handle:
+            raise MemoryError("fa_oracle_lm_create")
+
+    def score(self, word: str, prev) -> np.float32:
+        w = word.encode("utf-8")
+        p = None if prev is None else prev.encode("utf-8")
+        return np.float32(lib().fa_oracle_lm_score(self.handle, w, len(w), p, -1 if p is None else len(p)))
+
+    def close(self):
+        h, self.handle = getattr(self, "handle", None), None
+        if h:
+            lib().fa_oracle_lm_destroy(h)
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def ctc_beam_search_c(log_probs, vocabulary: dict, lm=None, beam_width=100, lm_weight=0.3, word_bonus=0.0, blank_id=1024,
+                      token_candidates=40, valid_frames=None):
+    """ctc_beam_search restated in C (fa_oracle_ctc_beam_search): same arguments, rules and result, at the cost of a
+    compiled walk.  `lm` is an ARPALanguageModel (converted for this call) or a CLanguageModel (reused); valid_frames:
+    only the first valid_frames rows are decoded (clamped to [0, T], like the device's per-utterance counts)."""
+    lp = np.ascontiguousarray(log_probs, np.float32)
+    if lp.size == 0:
+        return [], None
+    T, V = lp.shape
+    if valid_frames is not None:
+        T = min(max(int(valid_frames), 0), T)
+    if T == 0:
+        return [], None
+    pieces = off = None
+    clm = owned = None
+    if lm is not None:
+        pieces, off = _byte_table(vocabulary.get(v, "") for v in range(V))
+        clm = lm if isinstance(lm, CLanguageModel) else CLanguageModel(lm)
+        owned = clm if clm is not lm else None
+    out = np.zeros(T, np.int32)
+    total = C.c_float()
+    try:
+        n = lib().fa_oracle_ctc_beam_search(lp, T, V, V, pieces, None if off is None else off.ctypes.data, None if clm is None else clm.handle,
+                                            int(beam_width), float(np.float32(lm_weight)), float(np.float32(word_bonus)), int(blank_id),
+                                            int(token_candidates), out, C.byref(total))
+    finally:
+        if owned is not None:
+            owned.close()
+    if n < 0:
+        raise (MemoryError if n == -1 else ValueError)(f"fa_oracle_ctc_beam_search -> {n}")
+    return out[:n].tolist(), float(np.float32(total.value))
 
 
 def decode_ctc_token_ids(ids, vocabulary: dict) -> str:                             # CtcDecoder.swift:289-294

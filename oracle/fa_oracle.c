@@ -1170,3 +1170,286 @@ void fa_oracle_speaker_constraints(long num_embeddings, int has_num, long num, i
     out[0] = rmin == rmax ? rmin : (has_num ? num : -1);
     out[1] = rmin; out[2] = rmax;
 }
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * CTC prefix beam search with a word-level ARPA model (CtcDecoder.swift:118-241, ARPALanguageModel.swift:98-103): the
+ * compiled twin of oracle.ctc_beam_search, written from it and from the Swift.  Prefixes are interned trie nodes
+ * (parent node, token) found by a full key compare; the model is two sorted tables searched with bsearch over bytes.
+ * ------------------------------------------------------------------------------------------------------------------- */
+typedef struct { const char *s; long n; } ob_str;
+
+static int ob_str_cmp(ob_str a, ob_str b) {           /* byte order, a proper prefix first */
+    const long n = a.n < b.n ? a.n : b.n;
+    const int c = n > 0 ? memcmp(a.s, b.s, (size_t)n) : 0;
+    return c ? c : (a.n > b.n) - (a.n < b.n);
+}
+
+typedef struct { ob_str w; float logp, backoff; } ob_uni;
+typedef struct { ob_str c, w; float logp; } ob_bi;
+
+struct fa_oracle_lm {
+    char *bytes;
+    ob_uni *uni; long n_uni;
+    ob_bi *bi; long n_bi;
+};
+
+static int ob_uni_cmp(const void *x, const void *y) { return ob_str_cmp(((const ob_uni *)x)->w, ((const ob_uni *)y)->w); }
+static int ob_bi_cmp(const void *x, const void *y) {
+    const ob_bi *a = (const ob_bi *)x, *b = (const ob_bi *)y;
+    const int c = ob_str_cmp(a->c, b->c);
+    return c ? c : ob_str_cmp(a->w, b->w);
+}
+
+fa_oracle_lm *fa_oracle_lm_create(long n_uni, const char *uni_bytes, const int64_t *uni_off, const float *uni_logp,
+                                  const float *uni_backoff, long n_bi, const char *ctx_bytes, const int64_t *ctx_off,
+                                  const char *word_bytes, const int64_t *word_off, const float *bi_logp) {
+    if (n_uni < 0 || n_bi < 0) return NULL;
+    const long nu = n_uni > 0 ? (long)uni_off[n_uni] : 0, nc = n_bi > 0 ? (long)ctx_off[n_bi] : 0, nw = n_bi > 0 ? (long)word_off[n_bi] : 0;
+    fa_oracle_lm *lm = calloc(1, sizeof *lm);
+    if (!lm) return NULL;
+    lm->bytes = malloc((size_t)(nu + nc + nw + 1));
+    lm->uni = malloc(sizeof(ob_uni) * (size_t)(n_uni + 1));
+    lm->bi = malloc(sizeof(ob_bi) * (size_t)(n_bi + 1));
+    if (!lm->bytes || !lm->uni || !lm->bi) { fa_oracle_lm_destroy(lm); return NULL; }
+    char *U = lm->bytes, *Cb = U + nu, *Wb = Cb + nc;
+    if (nu) memcpy(U, uni_bytes, (size_t)nu);
+    if (nc) memcpy(Cb, ctx_bytes, (size_t)nc);
+    if (nw) memcpy(Wb, word_bytes, (size_t)nw);
+    for (long i = 0; i < n_uni; ++i)
+        lm->uni[i] = (ob_uni){{U + uni_off[i], (long)(uni_off[i + 1] - uni_off[i])}, uni_logp[i], uni_backoff[i]};
+    for (long i = 0; i < n_bi; ++i)
+        lm->bi[i] = (ob_bi){{Cb + ctx_off[i], (long)(ctx_off[i + 1] - ctx_off[i])}, {Wb + word_off[i], (long)(word_off[i + 1] - word_off[i])}, bi_logp[i]};
+    lm->n_uni = n_uni; lm->n_bi = n_bi;
+    qsort(lm->uni, (size_t)n_uni, sizeof(ob_uni), ob_uni_cmp);
+    qsort(lm->bi, (size_t)n_bi, sizeof(ob_bi), ob_bi_cmp);
+    return lm;
+}
+
+void fa_oracle_lm_destroy(fa_oracle_lm *lm) {
+    if (!lm) return;
+    free(lm->bytes); free(lm->uni); free(lm->bi); free(lm);
+}
+
+static float ob_lm_score(const fa_oracle_lm *lm, ob_str word, const ob_str *prev) {   /* :98-103; prev NULL = nil */
+    if (prev) {
+        const ob_bi key = {*prev, word, 0.0f};
+        const ob_bi *b = bsearch(&key, lm->bi, (size_t)lm->n_bi, sizeof(ob_bi), ob_bi_cmp);
+        if (b) return b->logp;
+    }
+    float backoff = 0.0f;
+    if (prev) {
+        const ob_uni key = {*prev, 0.0f, 0.0f};
+        const ob_uni *u = bsearch(&key, lm->uni, (size_t)lm->n_uni, sizeof(ob_uni), ob_uni_cmp);
+        if (u) backoff = u->backoff;
+    }
+    const ob_uni key = {word, 0.0f, 0.0f};
+    const ob_uni *u = bsearch(&key, lm->uni, (size_t)lm->n_uni, sizeof(ob_uni), ob_uni_cmp);
+    return backoff + (u ? u->logp : (float)-23.026);                                   /* unkLogProb (:33) */
+}
+
+float fa_oracle_lm_score(const fa_oracle_lm *lm, const char *word, long word_len, const char *prev, long prev_len) {
+    const ob_str w = {word, word_len}, p = {prev, prev_len};
+    return ob_lm_score(lm, w, prev_len >= 0 ? &p : NULL);
+}
+
+static float ob_log_add_exp(float a, float b) {       /* CtcDecoder.swift:279-284, in double, rounded once; no shortcut */
+    if (a == -INFINITY) return b;
+    if (b == -INFINITY) return a;
+    const float m = b > a ? b : a;
+    return (float)((double)m + log(exp((double)(a - m)) + exp((double)(b - m))));
+}
+
+typedef struct { float lp; int32_t v; } ob_top;
+typedef struct { float total; int32_t i; } ob_rank;
+
+static int ob_top_cmp(const void *x, const void *y) {     /* log-prob descending (NaN last), index ascending */
+    const ob_top *a = (const ob_top *)x, *b = (const ob_top *)y;
+    const int na = isnan(a->lp), nb = isnan(b->lp);
+    if (na != nb) return na - nb;
+    if (!na && a->lp != b->lp) return a->lp > b->lp ? -1 : 1;
+    return (a->v > b->v) - (a->v < b->v);
+}
+
+static int ob_rank_cmp(const void *x, const void *y) {    /* total descending (NaN last), earlier candidate first: a stable sort */
+    const ob_rank *a = (const ob_rank *)x, *b = (const ob_rank *)y;
+    const int na = isnan(a->total), nb = isnan(b->total);
+    if (na != nb) return na - nb;
+    if (!na && a->total != b->total) return a->total > b->total ? -1 : 1;
+    return (a->i > b->i) - (a->i < b->i);
+}
+
+/* the trie: node 0 = the empty prefix; node n > 0 = prefix(parent[n]) + [token[n]], found through an open-addressing table */
+typedef struct { int32_t *parent, *token, *slot; long n, cap, mask; } ob_trie;
+
+static long ob_trie_slot(const ob_trie *t, int32_t parent, int32_t token) {   /* slot holding (parent, token), or the empty one where it goes */
+    uint64_t h = ((uint64_t)(uint32_t)parent << 32 | (uint32_t)token) * 0x9e3779b97f4a7c15ull;
+    for (long s = (long)(h >> 32) & t->mask;; s = (s + 1) & t->mask) {
+        const int32_t n = t->slot[s];
+        if (n < 0 || (t->parent[n] == parent && t->token[n] == token)) return s;
+    }
+}
+
+typedef struct {                      /* a hypothesis; its running word and previous word live in the frame's byte pool */
+    int32_t node; float pb, pnb, lm;
+    long word, word_len, prev, prev_len;   /* prev_len < 0: prevWord == nil */
+    float wdelta;                     /* lmWeight * score(word, prev) + wordBonus: what completing the word adds (0 for an empty word) */
+} ob_beam;
+
+typedef struct { int32_t node, src, tok; float pb, pnb, lm; } ob_cand;   /* node -1: a prefix that is no trie node yet; tok -1: beam src itself */
+
+typedef struct { char *p; long len, cap; } ob_pool;
+
+static long ob_pool_put(ob_pool *pl, const char *a, long na, const char *b, long nb) {   /* appends a + b, returns its offset (-1: no memory) */
+    if (pl->len + na + nb + 1 > pl->cap) {
+        long cap = pl->cap ? pl->cap : 4096;
+        while (pl->len + na + nb + 1 > cap) cap *= 2;
+        char *q = realloc(pl->p, (size_t)cap);
+        if (!q) return -1;
+        pl->p = q; pl->cap = cap;
+    }
+    const long at = pl->len;
+    if (na) memcpy(pl->p + at, a, (size_t)na);
+    if (nb) memcpy(pl->p + at + na, b, (size_t)nb);
+    pl->len += na + nb;
+    return at;
+}
+
+long fa_oracle_ctc_beam_search(const float *log_probs, long frames, long vocab, long row_stride, const char *piece_bytes,
+                               const int64_t *piece_off, const fa_oracle_lm *lm, int beam_width, float lm_weight,
+                               float word_bonus, int blank_id, int token_candidates, int32_t *out_ids, float *out_total) {
+    static const char kBoundary[] = "\xe2\x96\x81";                               /* U+2581 (ASRConstants.sentencePieceWordBoundary) */
+    *out_total = NAN;
+    if (frames < 0 || vocab < 0 || beam_width < 1 || token_candidates < 0 || (lm && !piece_off) || row_stride < vocab) return -2;
+    if (frames == 0 || vocab == 0) return 0;                                        /* guards (:129-131) */
+    const long W = beam_width, max_nodes = 1 + frames * W, max_cands = W * ((long)token_candidates + 1);
+    long status = -1;
+    ob_trie tr = {0};
+    long cap = 16;
+    while (cap < 2 * max_nodes) cap *= 2;
+    tr.cap = cap; tr.mask = cap - 1;
+    tr.parent = malloc(sizeof(int32_t) * (size_t)max_nodes); tr.token = malloc(sizeof(int32_t) * (size_t)max_nodes);
+    tr.slot = malloc(sizeof(int32_t) * (size_t)cap);
+    int32_t *seen = malloc(sizeof(int32_t) * (size_t)max_nodes), *cand_of = malloc(sizeof(int32_t) * (size_t)max_nodes);
+    ob_top *top = malloc(sizeof(ob_top) * (size_t)vocab);
+    ob_cand *cand = malloc(sizeof(ob_cand) * (size_t)max_cands);
+    ob_rank *rank = malloc(sizeof(ob_rank) * (size_t)max_cands);
+    ob_beam *beams = malloc(sizeof(ob_beam) * (size_t)W), *next = malloc(sizeof(ob_beam) * (size_t)W);
+    ob_pool pool[2] = {{0}, {0}};
+    if (!tr.parent || !tr.token || !tr.slot || !seen || !cand_of || !top || !cand || !rank || !beams || !next) goto done;
+    memset(tr.slot, 0xff, sizeof(int32_t) * (size_t)cap);
+    memset(seen, 0xff, sizeof(int32_t) * (size_t)max_nodes);
+    tr.parent[0] = -1; tr.token[0] = -1; tr.n = 1;
+    const float NEG = -INFINITY;
+    long nb = 1;
+    int cur = 0;
+    beams[0] = (ob_beam){0, 0.0f, NEG, 0.0f, 0, 0, 0, -1, 0.0f};
+    for (long t = 0; t < frames; ++t) {
+        const float *frame = log_probs + t * row_stride;
+        const float blank_lp = blank_id >= 0 && blank_id < vocab ? frame[blank_id] : NEG;
+        long ntop = 0;
+        for (long v = 0; v < vocab; ++v)
+            if (v != blank_id) top[ntop++] = (ob_top){frame[v], (int32_t)v};
+        qsort(top, (size_t)ntop, sizeof(ob_top), ob_top_cmp);
+        if (ntop > token_candidates) ntop = token_candidates;
+        long nc = 0;
+        /* merge (:149-158): the prefix's first candidate keeps its place and its word state */
+#define OB_MERGE(NODE, SRC, TOK, PB, PNB, LM) do {                                                        \
+            const int32_t n_ = (NODE);                                                                    \
+            if (n_ >= 0 && seen[n_] == (int32_t)t) {                                                      \
+                ob_cand *e_ = &cand[cand_of[n_]];                                                         \
+                e_->pb = ob_log_add_exp(e_->pb, (PB)); e_->pnb = ob_log_add_exp(e_->pnb, (PNB));          \
+            } else {                                                                                      \
+                if (n_ >= 0) { seen[n_] = (int32_t)t; cand_of[n_] = (int32_t)nc; }                        \
+                cand[nc++] = (ob_cand){n_, (SRC), (TOK), (PB), (PNB), (LM)};                              \
+            }                                                                                             \
+        } while (0)
+        for (long i = 0; i < nb; ++i) {
+            const ob_beam *b = &beams[i];
+            const float prev_total = ob_log_add_exp(b->pb, b->pnb);                      /* totalAcoustic */
+            const int32_t last = tr.token[b->node];                                        /* -1 for the empty prefix */
+            OB_MERGE(b->node, (int32_t)i, -1, prev_total + blank_lp, NEG, b->lm);         /* blank extension (:166-170) */
+            for (long r = 0; r < ntop; ++r) {
+                const int32_t v = top[r].v;
+                const float tlp = top[r].lp;
+                float delta = 0.0f;                                                       /* :180-197 */
+                if (lm) {
+                    const long po = (long)piece_off[v], pn = (long)(piece_off[v + 1] - piece_off[v]);
+                    if (pn >= 3 && memcmp(piece_bytes + po, kBoundary, 3) == 0 && b->word_len > 0) delta = b->wdelta;
+                }
+                const float ext_lm = b->lm + delta;
+                const long s = ob_trie_slot(&tr, b->node, v);
+                const int32_t ext = tr.slot[s];                                           /* -1: no node yet, so no other candidate is this prefix */
+                if (last == v) {                                                          /* :199-213 */
+                    OB_MERGE(b->node, (int32_t)i, -1, NEG, b->pnb + tlp, b->lm);
+                    OB_MERGE(ext, (int32_t)i, v, NEG, b->pb + tlp, ext_lm);
+                } else {
+                    OB_MERGE(ext, (int32_t)i, v, NEG, prev_total + tlp, ext_lm);          /* :215-223 */
+                }
+            }
+        }
+#undef OB_MERGE
+        for (long c = 0; c < nc; ++c) rank[c] = (ob_rank){ob_log_add_exp(cand[c].pb, cand[c].pnb) + cand[c].lm, (int32_t)c};
+        qsort(rank, (size_t)nc, sizeof(ob_rank), ob_rank_cmp);                           /* prune (:227-232) */
+        const long keep = nc < W ? nc : W;
+        ob_pool *pl = &pool[cur ^ 1], *old = &pool[cur];
+        pl->len = 0;
+        for (long k = 0; k < keep; ++k) {
+            const ob_cand *c = &cand[rank[k].i];
+            const ob_beam *src = &beams[c->src];
+            ob_beam *nw = &next[k];
+            int32_t node = c->node;
+            if (node < 0) {                                                               /* a new prefix: intern (parent, token) */
+                const long s = ob_trie_slot(&tr, src->node, c->tok);
+                node = (int32_t)tr.n++;
+                tr.parent[node] = src->node; tr.token[node] = c->tok; tr.slot[s] = node;
+            }
+            *nw = (ob_beam){node, c->pb, c->pnb, c->lm, 0, 0, 0, -1, 0.0f};
+            const char *sw = old->p ? old->p + src->word : "", *sp = old->p ? old->p + src->prev : "";
+            long wo = 0, wn = 0, po = 0, pn = -1;
+            if (c->tok < 0 || !lm) {                                                      /* the beam itself / no word tracking */
+                wo = ob_pool_put(pl, sw, src->word_len, "", 0); wn = src->word_len;
+                pn = src->prev_len;
+                po = pn >= 0 ? ob_pool_put(pl, sp, pn, "", 0) : 0;
+            } else {
+                const char *piece = piece_bytes + piece_off[c->tok];
+                const long plen = (long)(piece_off[c->tok + 1] - piece_off[c->tok]);
+                if (plen >= 3 && memcmp(piece, kBoundary, 3) == 0) {                      /* the word so far is complete (:183-194) */
+                    if (src->word_len > 0) { pn = src->word_len; po = ob_pool_put(pl, sw, pn, "", 0); }
+                    else { pn = src->prev_len; po = pn >= 0 ? ob_pool_put(pl, sp, pn, "", 0) : 0; }
+                    wn = plen - 3; wo = ob_pool_put(pl, piece + 3, wn, "", 0);
+                } else {                                                                  /* wordPieces.append(piece) (:195-197) */
+                    pn = src->prev_len; po = pn >= 0 ? ob_pool_put(pl, sp, pn, "", 0) : 0;
+                    wn = src->word_len + plen; wo = ob_pool_put(pl, sw, src->word_len, piece, plen);
+                }
+            }
+            if (wo < 0 || po < 0) goto done;
+            nw->word = wo; nw->word_len = wn; nw->prev = po; nw->prev_len = pn;
+            if (lm && wn > 0) {
+                const ob_str w = {pl->p + wo, wn}, p = {pl->p + po, pn};
+                nw->wdelta = lm_weight * ob_lm_score(lm, w, pn >= 0 ? &p : NULL) + word_bonus;
+            }
+        }
+        ob_beam *sw = beams; beams = next; next = sw;
+        nb = keep;
+        cur ^= 1;
+    }
+    /* finalize (:235-243): the trailing partial word is scored, the first maximum wins */
+    long best = -1;
+    float best_total = 0.0f;
+    for (long i = 0; i < nb; ++i) {
+        const ob_beam *b = &beams[i];
+        const float tot = ob_log_add_exp(b->pb, b->pnb);
+        const float total = lm && b->word_len > 0 ? tot + (b->lm + b->wdelta) : tot + b->lm;
+        if (best < 0 || total > best_total) { best = i; best_total = total; }
+    }
+    long len = 0;
+    for (int32_t n = beams[best].node; n > 0; n = tr.parent[n]) ++len;
+    long pos = len;
+    for (int32_t n = beams[best].node; n > 0; n = tr.parent[n]) out_ids[--pos] = tr.token[n];
+    *out_total = best_total;
+    status = len;
+done:
+    free(tr.parent); free(tr.token); free(tr.slot); free(seen); free(cand_of); free(top); free(cand); free(rank);
+    free(beams); free(next); free(pool[0].p); free(pool[1].p);
+    return status;
+}

@@ -186,6 +186,31 @@ int fa_oracle_kmeans_ninit(const double *emb, long n, long d, long num_clusters,
                            int32_t *labels, double *centroids, long *out_k, long *best_run, double *inertias);
 void fa_oracle_speaker_constraints(long num_embeddings, int has_num, long num, int has_min, long mn, int has_max, long mx, long out[3]);
 
+/* ---- CTC prefix beam search + word-level ARPA model (ASR/Parakeet/SlidingWindow/CTC/CtcDecoder.swift:118-241,
+ *      .../CTC/ARPALanguageModel.swift:98-103) -------------------------------------------------------------------- */
+
+/* The model's unigrams and bigrams as byte strings (UTF-8, no terminator needed): string i of a table is
+ * bytes[off[i] .. off[i + 1]).  Kept as arrays sorted by byte order and searched with bsearch; a word is equal to
+ * another only when all its bytes are.  Returns NULL on allocation failure. */
+typedef struct fa_oracle_lm fa_oracle_lm;
+fa_oracle_lm *fa_oracle_lm_create(long n_uni, const char *uni_bytes, const int64_t *uni_off, const float *uni_logp,
+                                  const float *uni_backoff, long n_bi, const char *ctx_bytes, const int64_t *ctx_off,
+                                  const char *word_bytes, const int64_t *word_off, const float *bi_logp);
+void fa_oracle_lm_destroy(fa_oracle_lm *lm);
+/* ARPALanguageModel.score(word:prev:); prev_len < 0 encodes prev == nil. */
+float fa_oracle_lm_score(const fa_oracle_lm *lm, const char *word, long word_len, const char *prev, long prev_len);
+
+/* ctcBeamSearch on frames x vocab log-probabilities (row t at log_probs + t * row_stride), the tie rules of
+ * oracle.ctc_beam_search: top tokens by (log-prob descending, index ascending); candidates in beam order, each beam's
+ * blank / repeat part first, then its extensions in top-token order; a merged hypothesis keeps the earlier position;
+ * pruning is a stable sort by total; the first maximum wins at the end.  logAddExp is the full evaluation in double,
+ * rounded once.  pieces: vocab + 1 offsets into piece_bytes (an empty piece = an id without one); NULL when lm is NULL.
+ * out_ids holds frames ids.  Returns the number of ids of the best prefix (*out_total its score), 0 with
+ * *out_total = NaN when there is no frame or no token, -1 on allocation failure, -2 on bad arguments. */
+long fa_oracle_ctc_beam_search(const float *log_probs, long frames, long vocab, long row_stride, const char *piece_bytes,
+                               const int64_t *piece_off, const fa_oracle_lm *lm, int beam_width, float lm_weight,
+                               float word_bonus, int blank_id, int token_candidates, int32_t *out_ids, float *out_total);
+
 #ifdef __cplusplus
 }
 #endif

@@ -296,9 +296,10 @@ def test_device_matches_restatement(fa, gpu_ctx, oracle_mod, T, V, W_, K, peaky,
 
 
 @pytest.mark.gpu
-def test_limits_and_argument_errors(fa, gpu_ctx):
-    """Largest supported beam / candidate counts on a TDT-sized vocabulary: structural sanity (no oracle at this size), the
-    greedy path is among the hypotheses so the beam score can only be better, and out-of-range parameters are refused."""
+def test_limits_and_argument_errors(fa, gpu_ctx, oracle_mod):
+    """Largest supported beam / candidate counts on a TDT-sized vocabulary: structural sanity, the greedy path is among the
+    hypotheses so the beam score can only be better, the compiled restatement's ids and score (tests/test_gpu_beam_scale.py goes
+    further), and out-of-range parameters are refused."""
     rng = np.random.default_rng(3)
     T, V, blank = 120, 8193, 8192
     x = random_case(rng, T, V, 4.0)
@@ -306,6 +307,8 @@ def test_limits_and_argument_errors(fa, gpu_ctx):
     assert len(ids[0]) <= T and all(0 <= t < V and t != blank for t in ids[0]) and np.isfinite(scores[0])
     greedy_path = float(x.max(axis=1).sum())                      # log-prob of the best single alignment
     assert scores[0] >= greedy_path - 1e-3                        # the prefix total sums over alignments incl. that one
+    want, total = oracle_mod.ctc_beam_search_c(x, {}, None, 128, 0.0, 0.0, blank, 64)
+    assert ids[0] == want and scores[0] == pytest.approx(total, rel=2e-6, abs=2e-5)
     ids1, _ = fa.ctc_beam_search_ids_batch(x[None], None, None, 1, 0.0, 0.0, blank, 1, ctx=gpu_ctx)   # beam 1, one candidate
     assert len(ids1[0]) <= T
     for bw, k in ((0, 40), (129, 40), (100, 65), (100, -1)):
