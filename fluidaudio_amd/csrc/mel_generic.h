@@ -13,35 +13,10 @@
 // Throughput is not the point here (the batched NeMo configuration takes the tuned kernels); every sample is still read
 // from HBM only ~win/hop times through L2 and every output written once.
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
+#include "mel_launch.h"   // GenArgs, kWaves, kThreads
 
 namespace fa {
 namespace melgen {
-
-constexpr int kWaves = 4;
-constexpr int kThreads = 64 * kWaves;
-
-struct GenArgs {
-    const float *pcm;
-    const int64_t *offsets;      // B + 1
-    const int32_t *frames;       // B: frames T(b) the caller gets (expectedFrameCount override applied)
-    const int32_t *stft_frames;  // B: frames the signal itself yields (tail_replicate: frames beyond repeat the last of these)
-    const float *last;           // B or nullptr
-    float *out;
-    int32_t *lengths;            // B or nullptr
-    const float *window;         // [win]
-    const float2 *tw;            // [n_fft/2 + 1]  exp(-2 pi i k / n_fft)
-    const int32_t *mel_lo;       // [n_mels] first bin of the row's support
-    const int32_t *mel_cnt;      // [n_mels] bins in the support
-    const int32_t *mel_start;    // [n_mels] offset of the row's weights in mel_w
-    const float *mel_w;
-    int64_t utt_stride;
-    int32_t batch, frame_stride, n_mels, n_fft, log2_m, win, off, hop, pad;
-    float preemph, log_floor;
-    int32_t floor_clamped, reflect, magnitude, tail_replicate, frame_major;
-};
 
 // pre-emphasised sample i of the utterance (AudioMelSpectrogram.swift:211,:219-225); outside [0, len): 0, or the reflected
 // sample (LuxTtsMelExtractor.swift:60-66: left audio[min(-i, n-1)], right audio[max(2n-2-i, 0)])

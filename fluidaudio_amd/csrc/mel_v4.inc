@@ -20,22 +20,11 @@
 // stride is 4 x odd dwords); ds_read2_b32 4.5 clocks per 8 bytes against 2.6 for ds_read_b64.  The compiler merges neighbouring 8-byte
 // reads into ds_read2_b64, so every table / transpose / power read below is a VOLATILE 8- or 16-byte load (never merged), the
 // transpose rows hold 18 pairs (144 bytes: 16-byte aligned rows, lane stride 36 dwords) and the twiddle tables are laid out by
-// lane ([lane][k], 16-byte reads) instead of by k.
-constexpr int kV4EStride = 18;                                 // frame pairs per transpose row
-constexpr int kV4RegionFloats = 2 * 16 * kV4EStride;           // 576 floats = 288 frame pairs of 8 bytes per group
-constexpr int kV4AreaFloats = kRegions * kV4RegionFloats;      // 9216 floats; the staged tile needs 5472
-constexpr int kV4HalfSamples = kStageVec * kThreads * 2;   // 3072: every thread stages all of its 6 float4 groups (the tile needs 2736
-                                                           // even / odd samples; staging the rest too keeps the loop free of exec masking
-                                                           // and of loads the wait-count pass would have to treat as pending afterwards)
-constexpr int kV4WeightFloats = ((kFastSlots + 1) / 2) * 2 * kGroup;   // slot pairs: entry (pair, lane) = (w[2 pair][lane], w[2 pair + 1][lane]), one 8-byte read
-constexpr int kV4T1Stride = 36, kV4T2Stride = 20;              // floats per lane row: 16 / 8 pairs + padding to 4 x odd dwords
-constexpr int kV4T1Floats = kGroup * kV4T1Stride, kV4T2Floats = kGroup * kV4T2Stride;
+// lane ([lane][k], 16-byte reads) instead of by k.  The sizes of this carve-up (kV4*) are in mel_launch.h: the host sizes the launch from them.
 typedef float v4f __attribute__((ext_vector_type(4)));
 // (explicit LDS address space: address-space inference leaves volatile accesses alone, they would become flat loads)
 __device__ __forceinline__ fa::melpk::f2 lds_ld8(const fa::melpk::f2 *p) { return *(__attribute__((address_space(3))) const volatile fa::melpk::f2 *)p; }
 __device__ __forceinline__ v4f lds_ld16(const float *p) { return *(__attribute__((address_space(3))) const volatile v4f *)p; }
-constexpr size_t kV4LdsBytes = sizeof(float) * (kV4AreaFloats + kV4WeightFloats + fa::melpk::kWindowTableFloats + kV4T1Floats + kV4T2Floats + 4);   // + 2 tile-queue slots
-static_assert(2 * kV4HalfSamples <= kV4AreaFloats, "staged tile must fit the shared area");
 
 // Both frames (f, f + 2) of a 16-lane group from the de-interleaved staged samples: v.re[n1] = (E[16 n1], E[16 n1 + 160]),
 // v.im[n1] likewise from the odd samples; e = the lane's pointer into E (frame start / 2 + lane), o the same into O.
