@@ -21,6 +21,8 @@ from .post import (ConstrainedClusterAssignment, HungarianAssignment, assign_emb
                    compute_centroids)
 from .resample import linear_resample, poly_taps, resample_poly  # noqa: F401
 from .sharding import gather_ragged_int32, shard_offsets, shard_range  # noqa: F401
+from .sortformer import (DiarizerSegment, DiarizerTimeline, DiarizerTimelineConfig, OfflineSortformerConfig, OfflineSortformerDiarizer,  # noqa: F401
+                         offline_windows, pack_windows, stitch, stitcher_alignment, timeline_segments)
 from .tdt import (TdtConfig, TdtDurationMapping, TdtFrameNavigation, decode_logits as tdt_decode_logits,  # noqa: F401
                   decode_tables as tdt_decode_tables)
 from .vbx import VBxClustering, VBxOutput  # noqa: F401

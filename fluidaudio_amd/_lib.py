@@ -55,6 +55,8 @@ EXPORTED_SYMBOLS = [
     "fa_offline_reconstruct", "fa_offline_reconstruct_dev", "fa_segments_finalize",
     "fa_embedding_default_config", "fa_embedding_plan", "fa_embedding_plan_dev", "fa_embedding_windows_dev", "fa_embedding_span_inputs",
     "fa_embedding_span_inputs_dev", "fa_weight_resample", "fa_weight_resample_dev",
+    "fa_sortformer_offline_default_config", "fa_sortformer_offline_windows", "fa_sortformer_pack_windows_dev", "fa_sortformer_stitch_dev",
+    "fa_sortformer_stitcher_alignment", "fa_timeline_default_config", "fa_timeline_segments_dev", "fa_timeline_segments",
 ]
 
 
@@ -124,6 +126,27 @@ class EmbeddingInfo(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SortformerOfflineConfig(C.Structure):
+    _fields_ = [("window_output_frames", C.c_int32), ("subsampling", C.c_int32), ("speakers", C.c_int32), ("n_mels", C.c_int32),
+                ("overlap_output_frames", C.c_int32)]
+
+
+class SortformerWindow(C.Structure):
+    _fields_ = [("recording", C.c_int32), ("valid_mel", C.c_int32), ("valid_out", C.c_int32), ("first", C.c_int32),
+                ("mel_start", C.c_int64), ("g_start", C.c_int64)]
+
+
+class TimelineConfig(C.Structure):
+    _fields_ = [("onset_threshold", C.c_float), ("offset_threshold", C.c_float), ("onset_pad_frames", C.c_int32),
+                ("offset_pad_frames", C.c_int32), ("min_frames_on", C.c_int32), ("min_frames_off", C.c_int32),
+                ("frame_duration", C.c_float), ("speakers", C.c_int32), ("activity_type", C.c_int32)]
+
+
+class DiarizerSegmentRecord(C.Structure):
+    _fields_ = [("recording", C.c_int32), ("speaker", C.c_int32), ("start_frame", C.c_int64), ("end_frame", C.c_int64),
+                ("activity", C.c_float), ("finalized", C.c_int32)]
 
 
 def build(force: bool = False) -> str:
@@ -332,6 +355,16 @@ def lib() -> C.CDLL:
     L.fa_embedding_span_inputs_dev.argtypes = L.fa_embedding_span_inputs.argtypes
     L.fa_weight_resample.argtypes = [vp, vp, i64, i32, i32, vp]
     L.fa_weight_resample_dev.argtypes = L.fa_weight_resample.argtypes
+    L.fa_sortformer_offline_default_config.argtypes = [C.POINTER(SortformerOfflineConfig)]
+    L.fa_sortformer_offline_default_config.restype = None
+    L.fa_sortformer_offline_windows.argtypes = [C.POINTER(SortformerOfflineConfig), vp, i32, vp, i64, C.POINTER(i64), vp, vp]
+    L.fa_sortformer_pack_windows_dev.argtypes = [vp, C.POINTER(SortformerOfflineConfig), vp, i32, i64, i64, vp, i32, i64, vp, vp]
+    L.fa_sortformer_stitch_dev.argtypes = [vp, C.POINTER(SortformerOfflineConfig), vp, vp, i32, i64, vp, vp]
+    L.fa_sortformer_stitcher_alignment.argtypes = [vp, vp, i64, i32, vp]
+    L.fa_timeline_default_config.argtypes = [C.POINTER(TimelineConfig)]
+    L.fa_timeline_default_config.restype = None
+    L.fa_timeline_segments_dev.argtypes = [vp, C.POINTER(TimelineConfig), vp, vp, vp, vp, i32, i32, vp, i64, C.POINTER(i64), vp]
+    L.fa_timeline_segments.argtypes = L.fa_timeline_segments_dev.argtypes
     _lib = L
     return L
 

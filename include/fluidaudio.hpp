@@ -653,4 +653,126 @@ private:
     fa_embedding_config cfg_;
 };
 
+// ------------------------------------------------------------------------------------------------------------------ offline Sortformer, timeline
+// OfflineSortformerConfig (Sources/FluidAudio/Diarizer/Sortformer/Offline/OfflineSortformerDiarizer.swift:14-58) with the window geometry of
+// processComplete (:303-363) over fa_sortformer_offline_windows.
+struct OfflineSortformerConfig {
+    int windowOutputFrames = 384, subsamplingFactor = 8, numSpeakers = 4, melFeatures = 128, sampleRate = 16000, melStride = 160, overlapOutputFrames = 100;
+    int windowMelFrames() const { return windowOutputFrames * subsamplingFactor; }
+    float frameDurationSeconds() const { return static_cast<float>(subsamplingFactor) * static_cast<float>(melStride) / static_cast<float>(sampleRate); }
+    fa_sortformer_offline_config c() const { return fa_sortformer_offline_config{windowOutputFrames, subsamplingFactor, numSpeakers, melFeatures, overlapOutputFrames}; }
+    struct Windows { std::vector<fa_sortformer_window> windows; std::vector<int64_t> totalOut, windowRange; };
+    Windows windows(const std::vector<int64_t> &numMelFrames) const {
+        const fa_sortformer_offline_config cfg = c();
+        const int32_t B = static_cast<int32_t>(numMelFrames.size());
+        Windows w;
+        w.totalOut.resize(numMelFrames.size());
+        w.windowRange.resize(numMelFrames.size() + 1);
+        int64_t n = 0;
+        fa_status st = fa_sortformer_offline_windows(&cfg, numMelFrames.data(), B, nullptr, 0, &n, w.totalOut.data(), w.windowRange.data());
+        if (st != FA_SUCCESS) throw Error(st, "fa_sortformer_offline_windows");
+        w.windows.resize(static_cast<size_t>(n));
+        st = fa_sortformer_offline_windows(&cfg, numMelFrames.data(), B, w.windows.data(), n, &n, nullptr, nullptr);
+        if (st != FA_SUCCESS) throw Error(st, "fa_sortformer_offline_windows");
+        return w;
+    }
+};
+
+// SortformerSpeakerStitcher.alignment (Sortformer/Offline/SortformerSpeakerStitcher.swift:27-77): mapping[windowSpeaker] == globalSpeaker
+struct SortformerSpeakerStitcher {
+    static std::vector<int> alignment(const std::vector<float> &global, const std::vector<float> &window, int frames, int numSpeakers) {
+        std::vector<int> identity(static_cast<size_t>(std::max(numSpeakers, 0)));
+        for (int i = 0; i < numSpeakers; ++i) identity[i] = i;
+        const int64_t need = static_cast<int64_t>(frames) * numSpeakers;
+        if (!(frames > 0 && numSpeakers > 0 && static_cast<int64_t>(global.size()) >= need && static_cast<int64_t>(window.size()) >= need)) return identity;
+        std::vector<int32_t> m(static_cast<size_t>(numSpeakers));
+        const fa_status st = fa_sortformer_stitcher_alignment(global.data(), window.data(), frames, numSpeakers, m.data());
+        if (st != FA_SUCCESS) throw Error(st, "fa_sortformer_stitcher_alignment");
+        return std::vector<int>(m.begin(), m.end());
+    }
+};
+
+// DiarizerTimelineConfig (Sources/FluidAudio/Diarizer/DiarizerTimeline.swift:9-164); fromSeconds is the second initialiser's
+// Int(round(x / frameDuration)) in fp32 (std::round: half away from zero)
+struct DiarizerTimelineConfig {
+    int numSpeakers = 1;
+    float frameDurationSeconds = 0.08f, onsetThreshold = 0.5f, offsetThreshold = 0.5f;
+    int onsetPadFrames = 0, offsetPadFrames = 0, minFramesOn = 0, minFramesOff = 0;
+    static DiarizerTimelineConfig sortformerDefault() { DiarizerTimelineConfig c; c.numSpeakers = 4; return c; }
+    static DiarizerTimelineConfig fromSeconds(int numSpeakers, float frameDurationSeconds, float onsetThreshold, float offsetThreshold, float onsetPadSeconds,
+                                              float offsetPadSeconds, float minDurationOn, float minDurationOff) {
+        DiarizerTimelineConfig c;
+        c.numSpeakers = numSpeakers;
+        c.frameDurationSeconds = frameDurationSeconds;
+        c.onsetThreshold = onsetThreshold;
+        c.offsetThreshold = offsetThreshold;
+        c.onsetPadFrames = static_cast<int>(std::round(onsetPadSeconds / frameDurationSeconds));
+        c.offsetPadFrames = static_cast<int>(std::round(offsetPadSeconds / frameDurationSeconds));
+        c.minFramesOn = static_cast<int>(std::round(minDurationOn / frameDurationSeconds));
+        c.minFramesOff = static_cast<int>(std::round(minDurationOff / frameDurationSeconds));
+        return c;
+    }
+    fa_timeline_config c() const {
+        fa_timeline_config t;
+        fa_timeline_default_config(&t);
+        t.onset_threshold = onsetThreshold;
+        t.offset_threshold = offsetThreshold;
+        t.onset_pad_frames = onsetPadFrames;
+        t.offset_pad_frames = offsetPadFrames;
+        t.min_frames_on = minFramesOn;
+        t.min_frames_off = minFramesOff;
+        t.frame_duration = frameDurationSeconds;
+        t.speakers = numSpeakers;
+        return t;
+    }
+};
+
+struct DiarizerSegment {   // DiarizerSegment (:492-560)
+    int speakerIndex = 0;
+    int64_t startFrame = 0, endFrame = 0;
+    bool isFinalized = true;
+    float frameDurationSeconds = 0.08f, activity = 0.0f;
+    int64_t length() const { return endFrame - startFrame; }
+    float startTime() const { return static_cast<float>(startFrame) * frameDurationSeconds; }
+    float endTime() const { return static_cast<float>(endFrame) * frameDurationSeconds; }
+    float duration() const { return static_cast<float>(endFrame - startFrame) * frameDurationSeconds; }
+};
+
+// DiarizerTimeline.rebuild(finalizedPredictions:tentativePredictions:keepingSpeakers:false,isComplete:) (:945-1003) over fa_timeline_segments:
+// flat [frames * numSpeakers] predictions of one recording -> its speakers' segments, by speaker, the finalized list before the tentative one.
+class DiarizerTimeline {
+public:
+    explicit DiarizerTimeline(DiarizerTimelineConfig config = DiarizerTimelineConfig::sortformerDefault()) : cfg_(config) {}
+    std::vector<DiarizerSegment> rebuild(Context &ctx, const std::vector<float> &finalizedPredictions, const std::vector<float> &tentativePredictions = {},
+                                         bool isComplete = true) const {
+        const size_t S = static_cast<size_t>(std::max(cfg_.numSpeakers, 1));
+        if (finalizedPredictions.size() % S != 0 || tentativePredictions.size() % S != 0) throw Error(FA_INVALID_ARGUMENT, "DiarizerTimeline: misaligned predictions");
+        const fa_timeline_config cfg = cfg_.c();
+        const int64_t nf = static_cast<int64_t>(finalizedPredictions.size() / S), nt = static_cast<int64_t>(tentativePredictions.size() / S);
+        int64_t n = 0;
+        const auto call = [&](fa_diarizer_segment *out, int64_t cap) {
+            return fa_timeline_segments(ctx.handle(), &cfg, finalizedPredictions.data(), &nf, tentativePredictions.data(), &nt, 1, isComplete ? 1 : 0, out, cap, &n,
+                                        nullptr);
+        };
+        ctx.check(call(nullptr, 0), "fa_timeline_segments");
+        std::vector<fa_diarizer_segment> recs(static_cast<size_t>(n));
+        if (n > 0) ctx.check(call(recs.data(), n), "fa_timeline_segments");
+        std::vector<DiarizerSegment> out;
+        out.reserve(recs.size());
+        for (const auto &r : recs) {
+            DiarizerSegment s;
+            s.speakerIndex = r.speaker;
+            s.startFrame = r.start_frame;
+            s.endFrame = r.end_frame;
+            s.isFinalized = (r.finalized & 1) != 0;
+            s.frameDurationSeconds = cfg_.frameDurationSeconds;
+            s.activity = r.activity;
+            out.push_back(s);
+        }
+        return out;
+    }
+private:
+    DiarizerTimelineConfig cfg_;
+};
+
 }  // namespace fluidaudio

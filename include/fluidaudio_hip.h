@@ -751,6 +751,95 @@ fa_status fa_embedding_span_inputs_dev(fa_ctx *ctx, const fa_embedding_config *c
 fa_status fa_weight_resample(fa_ctx *ctx, const float *in, int64_t rows, int32_t in_frames, int32_t out_frames, float *out);
 fa_status fa_weight_resample_dev(fa_ctx *ctx, const float *d_in, int64_t rows, int32_t in_frames, int32_t out_frames, float *d_out);
 
+/* ------------------------------------------------------------------ offline Sortformer ------ */
+/* OfflineSortformerDiarizer.processComplete (FluidAudio/Diarizer/Sortformer/Offline/OfflineSortformerDiarizer.swift:279-375) around its
+ * network: window geometry, the model's inputs, and the stitching of the windows' speaker columns into one global timeline
+ * (SortformerSpeakerStitcher.swift:27-77).  The network is the caller's; it runs between pack and stitch.  Defaults = :14-43. */
+typedef struct {
+    int32_t window_output_frames;    /* 384 */
+    int32_t subsampling;             /* 8 mel frames per output frame */
+    int32_t speakers;                /* 4 */
+    int32_t n_mels;                  /* 128 */
+    int32_t overlap_output_frames;   /* 100; used as max(0, min(overlap, window - 1)) (:303) */
+} fa_sortformer_offline_config;
+void fa_sortformer_offline_default_config(fa_sortformer_offline_config *cfg);
+typedef struct {
+    int32_t recording;               /* index into the batch */
+    int32_t valid_mel;               /* mel frames of the window that hold data (the model's mel_length) */
+    int32_t valid_out;               /* min(window, ceil(valid_mel / subsampling)) */
+    int32_t first;                   /* 1 for a recording's first window */
+    int64_t mel_start;               /* first mel frame */
+    int64_t g_start;                 /* first output frame on the recording's timeline: mel_start / subsampling */
+} fa_sortformer_window;
+/* The loop of :303-363 for `batch` recordings of n_mel_frames[b] mel frames: windows start every (window - overlap) * subsampling mel
+ * frames while the start lies inside the recording, and the first window shorter than window * subsampling is the last (a recording
+ * whose last full window ends exactly at its tail gets one more, short, window inside it).  total_out[batch] (nullable) =
+ * ceil(n_mel_frames / subsampling); window_range[batch + 1] (nullable) = the first window of each recording, then the count.
+ * windows[capacity] in recording order; *count is set even when windows is NULL (SUCCESS) or too small (OUTPUT_TOO_SMALL).
+ * Pure host function. */
+fa_status fa_sortformer_offline_windows(const fa_sortformer_offline_config *cfg, const int64_t *n_mel_frames, int32_t batch,
+                                        fa_sortformer_window *windows, int64_t capacity, int64_t *count, int64_t *total_out,
+                                        int64_t *window_range);
+/* The model's inputs (:98-119) for every window of the batch: d_out float[windows][n_mels][window * subsampling] with the tail past
+ * valid_mel zero-filled, d_mel_length int32[windows].  d_mel is the batch's mel on the device in either layout the mel plan writes:
+ * FA_MEL_LAYOUT_MEL_MAJOR recording b at d_mel + b * rec_stride as [n_mels][frame_stride], FA_MEL_LAYOUT_FRAME_MAJOR as
+ * [frames][n_mels] (frame_stride unused).  `windows` must be the count fa_sortformer_offline_windows gives for the same lengths.
+ * n_mel_frames: HOST pointer; the call returns when the kernel has finished (the staged window table lives for the call). */
+fa_status fa_sortformer_pack_windows_dev(fa_ctx *ctx, const fa_sortformer_offline_config *cfg, const float *d_mel, int32_t layout,
+                                         int64_t rec_stride, int64_t frame_stride, const int64_t *n_mel_frames, int32_t batch,
+                                         int64_t windows, float *d_out, int32_t *d_mel_length);
+/* :321-358 for every recording: d_preds float[windows][window][speakers] (the model's output, in window order) -> d_global
+ * float[sum total_out][speakers], the recordings' timelines one after the other, and d_mapping int32[windows][speakers],
+ * mapping[window column] = global column.  Bit for bit the reference's arithmetic: each correlation is a sequential fp32 chain in frame
+ * order (multiply, then add; terms whose global value equals 0 skipped), the bijections are tried in the reference's enumeration order,
+ * the strictly greatest score wins and the first enumerated wins ties, NaN never wins.  1 to 4 speakers (INVALID_ARGUMENT above).
+ * With 2 * overlap <= window (the default geometry) the windows' correlations and the merge run in parallel; any other geometry runs
+ * window by window in one workgroup per recording, which gives the same bits and is slow.  Synchronous like the pack. */
+fa_status fa_sortformer_stitch_dev(fa_ctx *ctx, const fa_sortformer_offline_config *cfg, const float *d_preds, const int64_t *n_mel_frames,
+                                   int32_t batch, int64_t windows, float *d_global, int32_t *d_mapping);
+/* SortformerSpeakerStitcher.alignment on HOST arrays float[frames][speakers]: mapping int32[speakers]; identity when frames <= 0. */
+fa_status fa_sortformer_stitcher_alignment(const float *global, const float *window, int64_t frames, int32_t speakers, int32_t *mapping);
+
+/* ------------------------------------------------------------------ diarizer timeline ------ */
+/* DiarizerTimeline (FluidAudio/Diarizer/DiarizerTimeline.swift), the segment detection shared by Sortformer (offline and streaming)
+ * and LS-EEND.  DiarizerTimelineConfig (:9-164); the seconds initialiser's Int(round(x / frameDuration)) lives in the wrappers. */
+enum { FA_ACTIVITY_SIGMOIDS = 0, FA_ACTIVITY_LOGITS = 1 };
+typedef struct {
+    float onset_threshold;           /* 0.5: silent -> speaking when activity > onset */
+    float offset_threshold;          /* 0.5: speaking stays speaking while activity >= offset */
+    int32_t onset_pad_frames;        /* 0 */
+    int32_t offset_pad_frames;       /* 0 */
+    int32_t min_frames_on;           /* 0 */
+    int32_t min_frames_off;          /* 0 */
+    float frame_duration;            /* 0.08 s; segment times are Float(frame) * frame_duration in the wrappers */
+    int32_t speakers;                /* 4; any value >= 1 */
+    int32_t activity_type;           /* FA_ACTIVITY_SIGMOIDS.  FA_ACTIVITY_LOGITS is INVALID_ARGUMENT: it goes through the platform's log,
+                                        and no caller in the reference selects it */
+} fa_timeline_config;
+void fa_timeline_default_config(fa_timeline_config *cfg);   /* DiarizerTimelineConfig.sortformerDefault */
+typedef struct {
+    int32_t recording, speaker;
+    int64_t start_frame, end_frame;  /* a start before frame 0 (onset padding) is kept, as the reference keeps it */
+    float activity;                  /* activitySum / Float(activeFrameCount), 0 for no frames */
+    int32_t finalized;               /* bit 0: DiarizerSegment.isFinalized; bit 1: held in the speaker's finalized list after the call
+                                        (3 finalized, 2 tentative moved there by finalize() when is_complete, 0 tentative) */
+} fa_diarizer_segment;
+/* rebuild(finalizedPredictions:tentativePredictions:keepingSpeakers:false,isComplete:) (:945-1003, 1169-1336) for `batch` recordings:
+ * finalized float[sum finalized_frames][speakers] and tentative float[sum tentative_frames][speakers], the recordings one after the
+ * other (tentative and tentative_frames may be NULL: none).  The records come ordered by recording, then speaker, then as the speaker's
+ * lists hold them after the call (the finalized list, then the tentative one).  Every activity sum is the reference's sequential fp32
+ * chain.  Not covered: addChunk's state across calls, maxStoredFrames, speaker names and snapshots.
+ * segs HOST fa_diarizer_segment[capacity]; *count is set even when segs is NULL (SUCCESS) or too small (OUTPUT_TOO_SMALL, the first
+ * `capacity` records are written); recording_counts HOST int64[batch] (nullable).  _dev: the predictions are DEVICE pointers read in
+ * stream order; otherwise HOST pointers.  Synchronous: one host synchronisation for the raw run count, one for the segment counts,
+ * then the copy of the records. */
+fa_status fa_timeline_segments_dev(fa_ctx *ctx, const fa_timeline_config *cfg, const float *d_finalized, const int64_t *finalized_frames,
+                                   const float *d_tentative, const int64_t *tentative_frames, int32_t batch, int32_t is_complete,
+                                   fa_diarizer_segment *segs, int64_t capacity, int64_t *count, int64_t *recording_counts);
+fa_status fa_timeline_segments(fa_ctx *ctx, const fa_timeline_config *cfg, const float *finalized, const int64_t *finalized_frames,
+                               const float *tentative, const int64_t *tentative_frames, int32_t batch, int32_t is_complete,
+                               fa_diarizer_segment *segs, int64_t capacity, int64_t *count, int64_t *recording_counts);
+
 /* ------------------------------------------------------------------ resampling ------ */
 /* AudioConverter.linearResample (FluidAudio/Shared/AudioConverter.swift:388-442): planar float[channels][frames] ->
  * mono mix (weight 1/channels) -> linear interpolation to out_rate.  HOST pointers.  Bit-exact restatement. */
