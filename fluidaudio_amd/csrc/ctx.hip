@@ -285,8 +285,7 @@ void fa_ctx_destroy(fa_ctx *ctx) {
     if (ctx->scratch) (void)hipFree(ctx->scratch);
     { std::lock_guard<std::mutex> lock(ctx->buf_mutex); fa::buf_cache_flush(ctx); }
     if (ctx->ahc_ws) (void)hipFree(ctx->ahc_ws);
-    if (ctx->poly_taps) (void)hipFree(ctx->poly_taps);
-    if (ctx->poly_rows && ctx->poly_rows_free) ctx->poly_rows_free(ctx->poly_rows);
+    if (ctx->resample_plan && ctx->resample_plan_free) ctx->resample_plan_free(ctx->resample_plan);
     if (ctx->ahc_graph && ctx->ahc_graph_free) ctx->ahc_graph_free(ctx->ahc_graph);
     if (ctx->ahc_uni_graph && ctx->ahc_graph_free) ctx->ahc_graph_free(ctx->ahc_uni_graph);
     if (ctx->mel_cache && ctx->mel_cache_free) ctx->mel_cache_free(ctx->mel_cache);

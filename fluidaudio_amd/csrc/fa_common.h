@@ -43,12 +43,9 @@ struct fa_ctx {
     // mel: plans of small host-pointer calls (tables + geometry on the device) are kept (mel_host.hip) — a streaming caller repeats one shape
     void *mel_cache = nullptr;
     void (*mel_cache_free)(void *) = nullptr;
-    // polyphase resampler taps of the last (up, down) pair, device resident (resample.hip)
-    void *poly_taps = nullptr;
-    size_t poly_taps_bytes = 0;
-    int32_t poly_up = 0, poly_down = 0, poly_half = 0;
-    void *poly_rows = nullptr;                 // per-phase tables of the same pair for poly_rows_kernel (owned by resample.hip)
-    void (*poly_rows_free)(void *) = nullptr;
+    // polyphase resampler: the plan of the last (up, down) pair — taps and row tables on the device, the kernel families that serve it (resample_host.hip)
+    void *resample_plan = nullptr;
+    void (*resample_plan_free)(void *) = nullptr;
     // Device buffers of the clustering stage (inputs, VBx state, centroids, scores: ~30 per recording) are kept by the context that allocated
     // them and handed out again (fa::DevBuf::alloc(ctx, bytes), ctx.hip): a context is ONE stream, so reuse is ordered by the stream, and neither
     // the hipMalloc nor the hipFree — which waits for EVERY stream of the device, i.e. for the other recordings' kernels — is paid per call.

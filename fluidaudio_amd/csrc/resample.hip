@@ -1,27 +1,21 @@
-// resample.hip — sample-rate conversion to the 16 kHz mono fp32 the featurizer consumes (gfx950).
+// resample.hip — the kernels of the sample-rate converter (gfx950) and, behind resample_launch.h, one launcher per kernel family.  The taps, the
+// tables, the per-context plan, the choice of kernel for a call and the C ABI are in resample_host.hip; the geometry both sides (and the CPU
+// emulation of the tests) compute with is in resample_geom.h.
 //
-// (1) fa_resample_linear replaces AudioConverter.linearResample
-//     (reference: Sources/FluidAudio/Shared/AudioConverter.swift:388-442): mix N planar channels down to mono with
-//     weight 1/N (:399-408), then linear interpolation at sourceIndex = i * (inRate / outRate) in double precision
-//     (:419-434).  This is the only resampling arithmetic that exists in the reference tree; it is pinned by
-//     AudioConverterTests.swift:546-761 and reproduced bit-for-bit (fp32 mix and blend with one rounding per operation).
-// (2) fa_resample_poly is an EXTENSION with its own specification (PARITY UNPINNED): the reference's default path hands
-//     the job to Apple's closed-source AVAudioConverter (AudioConverter.swift:299-370), whose arithmetic cannot be
-//     restated.  The kernel is a rational-ratio polyphase FIR (Kaiser beta = 5 windowed sinc, half length
-//     10 * max(up, down), unit DC gain, the output alignment of scipy.signal.resample_poly) so that an independent
-//     second opinion exists on the CPU.  One thread per output sample walks the ~2*10*max(up,down)/up taps of its
-//     phase; consecutive threads read consecutive input samples and taps `up` apart.
-#include <algorithm>
-#include <cmath>
-#include <type_traits>
+// fa_resample_poly is an EXTENSION with its own specification (PARITY UNPINNED): the reference's default path hands the job to Apple's
+// closed-source AVAudioConverter (AudioConverter.swift:299-370), whose arithmetic cannot be restated.  It is a rational-ratio polyphase FIR
+// (Kaiser beta = 5 windowed sinc, half length 10 * max(up, down), unit DC gain, the output alignment of scipy.signal.resample_poly) so that an
+// independent second opinion exists on the CPU.  Every kernel adds the terms of an output in ascending input order with fused multiply-adds: all
+// of them give the bits of poly_kernel, the one the tests pin the others to.
+//   poly_kernel               one thread per output straight from global memory: any pair, any range of outputs — the edges of every other kernel
+//   poly_lds_kernel           taps and a tile's input span in LDS: any pair whose filter fits
+//   poly_decim_tile_kernel    integer decimation (up = 1), whole tiles through two LDS buffers; poly_decim_kernel: the same from registers (the remainder)
+//   poly_interp_kernel        small interpolation factors (up = 2 .. 4) from registers
+//   poly_rows_kernel          many-phase pairs (44.1 kHz and its kin): one 64-row tile per workgroup; poly_rows_wide*_kernel: persistent, two LDS buffers
 #include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+#include <type_traits>
 
-#include "fa_common.h"
-#include "resample_geom.h"
+#include "resample_launch.h"
 
 namespace {
 
@@ -30,26 +24,8 @@ using fa::kRowsThreads;
 using fa::kRowsWaves;
 using fa::kRowsOffLane;
 constexpr int kThreads = 256;
-
-__global__ void mixdown_kernel(const float *__restrict__ planar, float *__restrict__ mono, int channels, int64_t frames) {
-    const int64_t f = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (f >= frames) return;
-    float sum = 0.0f;
-    for (int c = 0; c < channels; ++c) sum = __fadd_rn(sum, planar[static_cast<int64_t>(c) * frames + f]);  // :403-407
-    mono[f] = __fmul_rn(sum, 1.0f / static_cast<float>(channels));
-}
-
-__global__ void linear_kernel(const float *__restrict__ mono, float *__restrict__ out, int64_t frames, int64_t out_frames, double ratio) {
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i >= out_frames) return;
-    const double src = static_cast<double>(i) * ratio;       // :424
-    const int64_t idx = static_cast<int64_t>(src);            // Int(sourceIndex): truncation
-    const float frac = static_cast<float>(src - static_cast<double>(idx));
-    float v = 0.0f;
-    if (idx < frames - 1) v = __fadd_rn(__fmul_rn(mono[idx], __fsub_rn(1.0f, frac)), __fmul_rn(mono[idx + 1], frac));  // :428-430
-    else if (idx < frames) v = mono[idx];                     // :431-432
-    out[i] = v;
-}
+typedef const float __attribute__((address_space(4))) *c_f32;   // through the scalar cache
+typedef float f4v __attribute__((ext_vector_type(4)));
 
 __global__ void poly_kernel(const float *__restrict__ x, const float *__restrict__ h, float *__restrict__ y, int64_t n_in, int64_t n_out,
                             int64_t h_len, int up, int down, int64_t pre_remove, int64_t m_lo, int64_t m_hi) {
@@ -130,7 +106,7 @@ __device__ __forceinline__ void static_for(F &&f) {
     if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for<I + 1, N>(f); }
 }
 
-constexpr int kDecimR = 8;
+constexpr int kDecimR = fa::kDecimRegOutputs;
 template <int DOWN>
 __global__ __launch_bounds__(kThreads) void poly_decim_kernel(const float *__restrict__ x, const float *__restrict__ h, float *__restrict__ y, int64_t m_begin,
                                                               int64_t groups) {
@@ -146,7 +122,6 @@ __global__ __launch_bounds__(kThreads) void poly_decim_kernel(const float *__res
     float xin[4 * NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v) { const float4 q = src[v]; xin[4 * v] = q.x; xin[4 * v + 1] = q.y; xin[4 * v + 2] = q.z; xin[4 * v + 3] = q.w; }
-    typedef const float __attribute__((address_space(4))) *c_f32;
     const c_f32 taps = (c_f32)h;
     constexpr int NQ = (NT + 15) / 16;
     float tq[NQ];                                   // DOWN >= 4: the taps in vector registers, 16 per register, for the DPP form of the multiply-add
@@ -168,7 +143,7 @@ __global__ __launch_bounds__(kThreads) void poly_decim_kernel(const float *__res
 #pragma unroll
             for (int j = 0; j < R; ++j) {
                 const int ti = NT - 1 + j * DOWN - i;
-                if (ti >= 0 && ti < NT) asm("v_fmac_f32 %0, %1, %2" : "+v"(acc[j]) : "s"(taps[ti]), "v"(xin[i]));   // <= 64 taps: they all fit the scalar registers
+                if (ti >= 0 && ti < NT) fmac_scalar(acc[j], taps[ti], xin[i]);   // <= 64 taps: they all fit the scalar registers
             }
     } else {
         // 85 / 106 / 127 taps: through DPP from six to eight registers (round 4 left down = 4, 5 to the compiler's packed pairs + register moves and had no
@@ -180,9 +155,7 @@ __global__ __launch_bounds__(kThreads) void poly_decim_kernel(const float *__res
             });
         });
     }
-    float4 *dst = reinterpret_cast<float4 *>(y + m0);   // m0 = 10 (mod 4) + multiple of 8: 8-byte aligned only -> two-float stores
-    (void)dst;
-    if (!mine) return;
+    if (!mine) return;                              // m0 = 10 (mod 4) + multiple of 8: 8-byte aligned only -> two-float stores
 #pragma unroll
     for (int j = 0; j < R; j += 2) *reinterpret_cast<float2 *>(y + m0 + j) = make_float2(acc[j], acc[j + 1]);
 }
@@ -199,14 +172,13 @@ struct __attribute__((packed, aligned(4))) f4u { float x, y, z, w; };
 template <int UP, int DOWN, int NT>
 __global__ __launch_bounds__(kThreads) void poly_interp_kernel(const float *__restrict__ x, const float *__restrict__ h, float *__restrict__ y, const int64_t m_begin,
                                                                const int64_t q_begin, const int64_t groups) {
-    constexpr int R = 4, NO = R * UP, KB = (NT - 1) / UP, NIN = ((NO - 1) * DOWN) / UP + KB + 1, NV = (NIN + 3) / 4;
+    constexpr int R = fa::kInterpR, NO = R * UP, KB = (NT - 1) / UP, NIN = ((NO - 1) * DOWN) / UP + KB + 1, NV = (NIN + 3) / 4;
     const int64_t g = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
     if (g >= groups) return;
     const f4u *src = reinterpret_cast<const f4u *>(x + (q_begin - KB + g * (R * DOWN)));
     float xin[4 * NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v) { const f4u q = src[v]; xin[4 * v] = q.x; xin[4 * v + 1] = q.y; xin[4 * v + 2] = q.z; xin[4 * v + 3] = q.w; }
-    typedef const float __attribute__((address_space(4))) *c_f32;
     const c_f32 taps = (c_f32)h;
     float acc[NO];
 #pragma unroll
@@ -221,20 +193,6 @@ __global__ __launch_bounds__(kThreads) void poly_interp_kernel(const float *__re
     f4u *dst = reinterpret_cast<f4u *>(y + m_begin + g * NO);
 #pragma unroll
     for (int v = 0; v < NO / 4; ++v) { f4u o; o.x = acc[4 * v]; o.y = acc[4 * v + 1]; o.z = acc[4 * v + 2]; o.w = acc[4 * v + 3]; dst[v] = o; }
-}
-
-// launches poly_interp_kernel on the outputs whose inputs all exist; returns the covered range [m_lo, m_hi) (empty when the pair has no instance)
-template <int UP, int DOWN, int NT>
-void poly_interp_launch(fa_ctx *ctx, const float *d_x, const float *d_h, float *d_y, int64_t frames, int64_t n_out, int64_t pre_remove, int64_t &m_lo, int64_t &m_hi) {
-    constexpr int R = 4, NO = R * UP, KB = (NT - 1) / UP, NIN = ((NO - 1) * DOWN) / UP + KB + 1, NV = (NIN + 3) / 4;
-    int64_t m_begin = 0, q_begin = 0, groups = 0;
-    fa::interp_geometry(UP, DOWN, NT, R, frames, n_out, pre_remove, m_begin, q_begin, groups);   // resample_geom.h
-    (void)KB; (void)NIN; (void)NV; (void)NO;
-    m_lo = m_hi = 0;
-    if (groups <= 0) return;
-    hipLaunchKernelGGL((poly_interp_kernel<UP, DOWN, NT>), dim3(static_cast<unsigned>((groups + kThreads - 1) / kThreads)), dim3(kThreads), 0, ctx->stream, d_x, d_h, d_y, m_begin,
-                       q_begin, groups);
-    m_lo = m_begin; m_hi = m_begin + groups * NO;
 }
 
 // ------------------------------------------------------------------------------ non-integer ratios (44.1 / 22.05 / 11.025 kHz -> 16 kHz)
@@ -255,7 +213,7 @@ void poly_interp_launch(fa_ctx *ctx, const float *d_x, const float *d_h, float *
 //     transaction per output sample, 128 G transactions per second).
 // Summation order per output: ascending input index over the k range of poly_kernel, zero taps in front and behind -> identical bits on finite input.
 // The tile geometry (first output, first input, per-phase window offsets and counts) is computed once per rate pair on the host
-// (PolyRows below); outputs whose windows touch the ends of the signal go to poly_kernel.
+// (fa::rows_geometry, kept with the plan of resample_host.hip); outputs whose windows touch the ends of the signal go to poly_kernel.
 // (PolyRowsGeom, kRowsThreads / kRowsWaves / kRowsOffLane and the host-side geometry: resample_geom.h — shared with the CPU emulation of the tests)
 // one phase: `trow` = its table row (one value per lane), rowp = this lane's LDS row (shifted by the group's first staged offset).
 // The table row holds the phase's taps SHIFTED by the misalignment of its window (zeros in front and behind), so the window is read from the
@@ -272,19 +230,7 @@ void poly_interp_launch(fa_ctx *ctx, const float *d_x, const float *d_h, float *
 // more on either side than its true FIR window; poly_kernel, the edges and the register-tiled kernels skip taps instead.  Documented, tested.)
 template <int NTW>
 __device__ __forceinline__ void rows_dot(float &acc, const float *tq, const float *xr) {   // acc += sum over the window positions i < NTW of tap i * xr[i], ascending i
-#define FA_ROWS_Q(Q)                                                                                                  \
-    if constexpr (16 * Q < NTW) {                                                                                     \
-        if constexpr (16 * Q + 0 < NTW) fmac_bcast<0>(acc, tq[Q], xr[16 * Q + 0]);   if constexpr (16 * Q + 1 < NTW) fmac_bcast<1>(acc, tq[Q], xr[16 * Q + 1]);   \
-        if constexpr (16 * Q + 2 < NTW) fmac_bcast<2>(acc, tq[Q], xr[16 * Q + 2]);   if constexpr (16 * Q + 3 < NTW) fmac_bcast<3>(acc, tq[Q], xr[16 * Q + 3]);   \
-        if constexpr (16 * Q + 4 < NTW) fmac_bcast<4>(acc, tq[Q], xr[16 * Q + 4]);   if constexpr (16 * Q + 5 < NTW) fmac_bcast<5>(acc, tq[Q], xr[16 * Q + 5]);   \
-        if constexpr (16 * Q + 6 < NTW) fmac_bcast<6>(acc, tq[Q], xr[16 * Q + 6]);   if constexpr (16 * Q + 7 < NTW) fmac_bcast<7>(acc, tq[Q], xr[16 * Q + 7]);   \
-        if constexpr (16 * Q + 8 < NTW) fmac_bcast<8>(acc, tq[Q], xr[16 * Q + 8]);   if constexpr (16 * Q + 9 < NTW) fmac_bcast<9>(acc, tq[Q], xr[16 * Q + 9]);   \
-        if constexpr (16 * Q + 10 < NTW) fmac_bcast<10>(acc, tq[Q], xr[16 * Q + 10]); if constexpr (16 * Q + 11 < NTW) fmac_bcast<11>(acc, tq[Q], xr[16 * Q + 11]); \
-        if constexpr (16 * Q + 12 < NTW) fmac_bcast<12>(acc, tq[Q], xr[16 * Q + 12]); if constexpr (16 * Q + 13 < NTW) fmac_bcast<13>(acc, tq[Q], xr[16 * Q + 13]); \
-        if constexpr (16 * Q + 14 < NTW) fmac_bcast<14>(acc, tq[Q], xr[16 * Q + 14]); if constexpr (16 * Q + 15 < NTW) fmac_bcast<15>(acc, tq[Q], xr[16 * Q + 15]); \
-    }
-    FA_ROWS_Q(0) FA_ROWS_Q(1) FA_ROWS_Q(2) FA_ROWS_Q(3)
-#undef FA_ROWS_Q
+    static_for<0, NTW>([&](auto ic) { constexpr int i = decltype(ic)::value; fmac_bcast<i % 16>(acc, tq[i / 16], xr[i]); });
 }
 
 #ifndef FA_ROWS_ATTR
@@ -415,13 +361,30 @@ __global__ __launch_bounds__(kRowsThreads) FA_ROWS_ATTR void poly_rows_kernel(co
 // Same tables, same order of additions: the bits of poly_rows_kernel.
 // ROWS = rows of a tile: 32 (one workgroup per CU, two buffers of 64 KB, lanes = 2 phase quads x 32 rows) or 16 (two workgroups per CU, buffers of 32 KB,
 // lanes = 4 phase quads x 16 rows — one quad per DPP row); a UNIT is the 4 x 64 / ROWS phases one wavefront-instruction covers.
-// floats per LDS row, at most: two buffers of 32 x 512 floats = 128 KB (one workgroup per CU), of 16 x 512 = 64 KB or of 32 x 288 = 72 KB (two per CU);
-// 16 x 576 for windows of 32 reads: 88.2 -> 16 kHz stages 564 floats per row
-constexpr int wide_row_floats(int rows, int waves, int nv) { return rows == 32 ? (waves == 10 ? (nv == 32 ? 576 : 288) : 512) : (nv == 32 ? 576 : 512); }
+// The five forms, each described ONCE — the kernels, their LDS buffers, wide_instance and launch_rows_wide are all derived from this list:
+//   X(kernel, rows per tile, wavefronts, windows it serves (0: of up to 16 reads, 1: of 32 reads, 2: both), floats per LDS row at most for the short /
+//     the long windows, wavefronts per SIMD of the launch bounds, workgroups per CU, phase groups at most)
+// Two buffers of 32 x 512 floats = 128 KB (one workgroup per CU), of 16 x 512 = 64 KB or of 32 x 288 = 72 KB (two per CU); rows of 576 floats for windows
+// of 32 reads (88.2 -> 16 kHz stages 564 floats per row).  wide32: 2 wavefronts per SIMD, 256 registers; wide16: 4 per SIMD, 128 registers; wide16w10: two
+// workgroups of ten wavefronts, 96 registers; wide32w10l: ONE workgroup of ten wavefronts per CU, 170 registers; wide32w10: 32-row tiles of one phase
+// GROUP (rows of <= 288 floats): groups of 80 k phases = 10 k units (44.1 / 22.05 / 11.025 kHz)
+#define FA_WIDE_FORMS(X)                                            \
+    X(poly_rows_wide32_kernel,     32,  8, 2, 512, 512, 2, 1, 1)    \
+    X(poly_rows_wide16_kernel,     16,  8, 2, 512, 576, 4, 2, 1)    \
+    X(poly_rows_wide16w10_kernel,  16, 10, 2, 512, 576, 5, 2, 1)    \
+    X(poly_rows_wide32w10l_kernel, 32, 10, 1, 576, 576, 3, 1, 8)    \
+    X(poly_rows_wide32w10_kernel,  32, 10, 0, 288, 288, 5, 2, 8)
+struct WideForm { int row_floats, per_cu, max_groups; };
+constexpr WideForm wide_form(int rows, int waves, int nv) {
+#define FA_WIDE_IS(NAME, R_, W_, WIN, FS, FL, MINW, PCU, G) if (rows == R_ && waves == W_ && (WIN == 2 || WIN == (nv == 32))) return {nv == 32 ? FL : FS, PCU, G};
+    FA_WIDE_FORMS(FA_WIDE_IS)
+#undef FA_WIDE_IS
+    return {0, 0, 0};
+}
 template <int ROWS, int WAVES, int NV, int SHARE, int CH>
 __device__ __forceinline__ void poly_rows_wide_body(const float *__restrict__ x, const float *__restrict__ tt, float *__restrict__ y, const PolyRowsGeom g_,
                                                     const int2 *__restrict__ gtab, const int tiles_, const int64_t m_end_, const int64_t k_lim_, const int vec_ok_, const int rot) {
-    constexpr int kWideBuf = ROWS * wide_row_floats(ROWS, WAVES, NV), PU = 4 * 64 / ROWS;     // floats per LDS buffer; phases per unit
+    constexpr int kWideBuf = ROWS * wide_form(ROWS, WAVES, NV).row_floats, PU = 4 * 64 / ROWS;     // floats per LDS buffer; phases per unit
     __shared__ float buf_a[kWideBuf];
     __shared__ float buf_b[kWideBuf];
     constexpr int NTW = 4 * NV, NQ = (NTW + 15) / 16, NW = 4 / SHARE;
@@ -506,7 +469,6 @@ __device__ __forceinline__ void poly_rows_wide_body(const float *__restrict__ x,
     }
     float st_acc[CH][4];
     int st_tile = -1;
-    typedef float f4v __attribute__((ext_vector_type(4)));
     constexpr int AHEAD = (WAVES == 10 && NV != 32) ? 1 : (ROWS == 32 ? 3 : 2), RING = AHEAD + 1;    // pieces read ahead (two workgroups per CU: 4 - 5 wavefronts per SIMD cover each other, and 128 / 96 registers are all there is; the long-window ten-wavefront instance is ONE workgroup per CU with 170 registers: three ahead, 0.530 -> 0.512 ms at 88.2 kHz)
     f4v xq[RING][4] = {};                                   // the ring of window quarters (see the arithmetic below)
     auto flush = [&]() {
@@ -599,17 +561,13 @@ __device__ __forceinline__ void poly_rows_wide_body(const float *__restrict__ x,
 }
 
 // (separate kernels, not one with launch bounds that depend on ROWS / WAVES: hipcc emits no host stub for a kernel template whose bounds are value-dependent)
-#define FA_WIDE_KERNEL(NAME, ROWS_, WAVES_, MINW)                                                                                                     \
+#define FA_WIDE_KERNEL(NAME, ROWS_, WAVES_, WIN, FS, FL, MINW, PCU, G)                                                                                \
     template <int NV, int SHARE, int CH>                                                                                                              \
     __global__ __launch_bounds__(64 * WAVES_, MINW) void NAME(const float *__restrict__ x, const float *__restrict__ tt, float *__restrict__ y, const PolyRowsGeom g, \
                                                               const int2 *__restrict__ gtab, const int tiles, const int64_t m_end, const int64_t k_lim, const int vec_ok, const int rot) { \
         poly_rows_wide_body<ROWS_, WAVES_, NV, SHARE, CH>(x, tt, y, g, gtab, tiles, m_end, k_lim, vec_ok, rot);                                             \
     }
-FA_WIDE_KERNEL(poly_rows_wide32_kernel, 32, 8, 2)        // one workgroup per CU: 2 wavefronts per SIMD, 256 registers
-FA_WIDE_KERNEL(poly_rows_wide16_kernel, 16, 8, 4)        // two per CU: 4 per SIMD, 128 registers
-FA_WIDE_KERNEL(poly_rows_wide16w10_kernel, 16, 10, 5)    // two of ten wavefronts: 5 per SIMD, 96 registers
-FA_WIDE_KERNEL(poly_rows_wide32w10l_kernel, 32, 10, 3)   // windows of 32 reads (88.2 kHz: rows of 564 floats, two buffers of 72 KB): ONE workgroup of ten wavefronts per CU, 170 registers
-FA_WIDE_KERNEL(poly_rows_wide32w10_kernel, 32, 10, 5)    // the same with 32-row tiles of one phase GROUP (rows of <= 288 floats): groups of 80 k phases = 10 k units (44.1 / 22.05 / 11.025 kHz)
+FA_WIDE_FORMS(FA_WIDE_KERNEL)
 #undef FA_WIDE_KERNEL
 
 // ------------------------------------------------------------------------------ integer decimation through LDS tiles (32 / 48 / 64 / 80 / 96 kHz -> 16 kHz)
@@ -636,7 +594,6 @@ __global__ __launch_bounds__(kThreads) void poly_decim_tile_kernel(const float *
     int64_t m_begin = m_begin_, k_lim = k_lim_;
     int tiles = tiles_, grid = static_cast<int>(gridDim.x);
     asm volatile("" : "+s"(m_begin), "+s"(k_lim), "+s"(tiles), "+s"(grid));      // (no kernel argument re-loaded inside the loop: see poly_rows_wide_body)
-    typedef const float __attribute__((address_space(4))) *c_f32;
     auto stage = [&](const int tile, float *buf) {
         const int64_t k0 = (m_begin + static_cast<int64_t>(tile) * TO - 10) * DOWN;      // first input of the tile (a multiple of 4: m_begin = 10 mod 4)
         const float *src = x + k0;
@@ -681,7 +638,6 @@ __global__ __launch_bounds__(kThreads) void poly_decim_tile_kernel(const float *
         float acc[R];
 #pragma unroll
         for (int j = 0; j < R; ++j) acc[j] = 0.0f;
-        typedef float f4v __attribute__((ext_vector_type(4)));
         f4v q[2][4] = {};
         auto load = [&](auto bc) {
             constexpr int b = decltype(bc)::value;
@@ -725,415 +681,140 @@ __global__ __launch_bounds__(kThreads) void poly_decim_tile_kernel(const float *
     flush();
 }
 
-// host side of poly_rows_kernel: the tables of one rate pair, resident on the device with the context
-struct PolyRows {
-    bool wide = false;              // served by poly_rows_wide_kernel (32-row tiles, every phase in one item, two LDS buffers)
-    int ch = 0, wide_rows = 0, wide_waves = 0;   // its units per wavefront; rows per tile (32: units of 8 phases, 16: of 16); wavefronts per workgroup
-    PolyRowsGeom g{};
-    int nv = 0;                     // 16-byte reads per phase window
-    size_t lds = 0;
-    void *d_tables = nullptr;       // [gtab int2 x groups, padded to 256 B][table rows: 64 floats per phase]
-    size_t tt_offset = 0;
-    int up = 0, down = 0;
-    ~PolyRows() { if (d_tables) (void)hipFree(d_tables); }
+// ------------------------------------------------------------------------------ launchers (resample_launch.h)
+// Each family lists its template instances ONCE: pick<Inst<...>, ...>(f, key...) calls f(Inst<...>{}) for the instance whose arguments equal the
+// runtime key and says whether there was one — the launcher passes its launch, the "is there an instance" query an empty function.
+template <int... VS>
+struct Inst {
+    static constexpr int v[] = {VS...};
+    template <class... K> static bool is(const K... key) { return ((static_cast<int64_t>(key) == VS) && ...); }
 };
-void poly_rows_free(void *p) { delete static_cast<PolyRows *>(p); }
-bool wide_instance(int rows, int waves, int nv, int share, int ch);
+template <class... IS, class F, class... K>
+bool pick(F &&f, const K... key) { return ((IS::is(key...) ? (f(IS{}), true) : false) || ...); }
 
-// Geometry + tables (resample_geom.h); false when the pair does not suit the kernel (then poly_lds_kernel serves it).
-bool poly_rows_build(PolyRows &R, const std::vector<float> &h, int up, int down, int64_t pre_remove, std::vector<int> &gtab, std::vector<float> &tt) {
-    // the persistent kernel with two buffers (FA_RESAMPLE_NO_WIDE=1: the one-tile-per-workgroup kernel): one phase group — an unbounded LDS budget keeps
-    // rows_geometry from splitting —, rows of at most 512 floats, and one of the instantiated (window, sharing, units per wavefront) combinations
-    R.wide = false;
-    if (!fa::sw_on(fa::Sw::RESAMPLE_NO_WIDE)) {
-        // candidates, in order: {rows, wavefronts, LDS budget of rows_geometry (per 64 rows: it decides the phase groups)}.  FA_RESAMPLE_WIDE = "rows:waves" picks
-        // one.  Measured per audio hour (profiles/r05_resample_wide_steps.json): 16-row tiles, 8 wavefronts, two workgroups per CU — 44.1 kHz 233 - 250 us,
-        // 22.05 kHz 128, 11.025 kHz 116; 32-row tiles with one workgroup per CU 243 - 262 / 152 / (no instance); 32-row tiles of one phase GROUP (80 k phases:
-        // rows of <= 288 floats, two workgroups of ten wavefronts, no LDS bank conflicts, every wavefront the same number of units) 245 - 257 / 152 / 159.
-        // The 16-row form wins or ties in spite of its 2-way LDS bank conflicts (two phase quads with different window offsets share a ds_read_b128 lane group)
-        struct Cand { int rows, waves; size_t budget; };
-        const size_t group_budget = size_t{64} * 288 * 4;      // (rows_geometry budgets 64 rows)
-        // (round 6: windows of 32 reads — 88.2 kHz, 80 phases — first try 32-row tiles with ten wavefronts: 10 units of 8 phases, one per wavefront; with 16-row
-        // tiles the 5 units of 16 phases leave three of eight wavefronts without work, and those still issue their share of the LDS reads)
-        std::vector<Cand> cands = {{32, 10, size_t{1} << 30}, {16, 8, size_t{1} << 30}, {32, 10, group_budget}, {32, 8, size_t{1} << 30}};
-        if (const char *e = fa::sw(fa::Sw::RESAMPLE_WIDE)) {
-            int r_ = 0, w_ = 0;
-            // only the instantiated forms: any other pair would reach the geometry arithmetic below (rows 0: a division by zero)
-            if (sscanf(e, "%d:%d", &r_, &w_) == 2 && (r_ == 16 || r_ == 32) && (w_ == 8 || w_ == 10))
-                cands = r_ == 32 && w_ == 10 ? std::vector<Cand>{{32, 10, size_t{1} << 30}, {32, 10, group_budget}} : std::vector<Cand>{{r_, w_, size_t{1} << 30}};
-        }
-        for (const Cand &c : cands) {
-            PolyRowsGeom g2{};
-            int nv2 = 0;
-            std::vector<int> gtab2;
-            std::vector<float> tt2;
-            if (!fa::rows_geometry(g2, nv2, h, up, down, pre_remove, gtab2, tt2, c.budget)) continue;
-            if (c.rows == 32 && c.waves == 10 && c.budget > group_budget && nv2 != 32) continue;   // the ungrouped ten-wavefront form exists for the long windows only
-            if (g2.sld > wide_row_floats(c.rows, c.waves, nv2) || g2.groups > 8) continue;
-            if (!(c.rows == 32 && c.waves == 10) && g2.groups != 1) continue;
-            const int pu = 4 * 64 / c.rows, units = (g2.ppg + pu - 1) / pu, ch = (units + c.waves - 1) / c.waves;
-            if (c.waves == 10 && units % 10 != 0) continue;              // (ten wavefronts only where they divide the units)
-            if (!wide_instance(c.rows, c.waves, nv2, g2.share, ch)) continue;
-            R.g = g2; R.nv = nv2; R.ch = ch; R.wide_rows = c.rows; R.wide_waves = c.waves; gtab.swap(gtab2); tt.swap(tt2);
-            R.wide = true;
-            R.lds = 0; R.up = up; R.down = down;     // (static LDS)
-            return true;
-        }
-    }
-    if (!fa::rows_geometry(R.g, R.nv, h, up, down, pre_remove, gtab, tt)) return false;   // the automatic LDS budget (resample_geom.h)
-    if (R.g.sld > 64 * 5 && R.g.share != 1 && !fa::rows_geometry(R.g, R.nv, h, up, down, pre_remove, gtab, tt, 0, 1)) return false;   // the long-row build is instantiated for share = 1 only
-    R.lds = static_cast<size_t>(R.g.sld) * 64 * sizeof(float); R.up = up; R.down = down;
-    return true;
+template <class F> bool decim_tiles_pick(const int down, F &&f) { return pick<Inst<2>, Inst<3>, Inst<4>, Inst<5>, Inst<6>, Inst<12>>(f, down); }   // 192 kHz: tiles only
+template <class F> bool decim_pick(const int down, F &&f) { return pick<Inst<2>, Inst<3>, Inst<4>, Inst<5>, Inst<6>>(f, down); }   // 96 kHz: 127 taps in eight registers, 169 inputs
+template <class F> bool interp_pick(const int up, const int down, const int64_t nt, F &&f) {   // {up, down, taps}: 8 / 24 / 12 / 4 / 5.33 / 10.67 kHz -> 16 kHz
+    return pick<Inst<2, 1, 42>, Inst<2, 3, 64>, Inst<4, 3, 83>, Inst<4, 1, 82>, Inst<3, 1, 62>, Inst<3, 2, 63>>(f, up, down, nt);
 }
-
-template <int NV, int IT, int SHARE, int HALVES = 1>
-void poly_rows_launch_it(fa_ctx *ctx, const PolyRows &R, const float *d_x, float *d_y, int64_t tiles, int64_t m_end) {
-    const int2 *gtab = static_cast<const int2 *>(R.d_tables);
-    const float *tt = reinterpret_cast<const float *>(static_cast<const char *>(R.d_tables) + R.tt_offset);
-    const int vec_ok = R.up % 4 == 0 && (reinterpret_cast<uintptr_t>(d_y) & 15) == 0 ? 1 : 0;   // m_begin and the chunk starts are multiples of 4
-    if (R.lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(poly_rows_kernel<NV, IT, SHARE, HALVES>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(R.lds));
-    const int64_t tiles8 = (tiles + 7) / 8 * 8;   // whole rounds of the 8 XCDs: the index -> (tile, group) map of the kernel
-    hipLaunchKernelGGL((poly_rows_kernel<NV, IT, SHARE, HALVES>), dim3(static_cast<unsigned>(tiles8 * R.g.groups)), dim3(kRowsThreads), R.lds, ctx->stream, d_x, tt, gtab, d_y, R.g, tiles, m_end, vec_ok);
-}
-// the instantiated combinations of the wide kernels: {rows per tile, wavefronts, 16-byte reads per window, phases per window, units per wavefront}
+template <class F> bool rows_pick(const int nv, F &&f) { return pick<Inst<4>, Inst<6>, Inst<8>, Inst<10>, Inst<12>, Inst<14>, Inst<16>, Inst<32>>(f, nv); }
+// {rows per tile, wavefronts, 16-byte reads per window, phases per window, units per wavefront}
 //   44.1 -> 16 kHz: windows {16, 2}, 10 units of 16 phases or 20 of 8; 22.05 -> 16 kHz {10, 4}, 20 or 40 units; 11.025 -> 16 kHz {8, 4}, 40 units; 37.8 -> 16 kHz {16, 4}, 5 units;
 //   88.2 -> 16 kHz {32, 1} (two windows' worth of reads per phase), 5 units; other pairs: poly_rows_kernel
-#define FA_WIDE_INSTANCES(X) X(32, 8, 16, 2, 3) X(32, 8, 10, 4, 5) X(16, 8, 16, 2, 2) X(16, 8, 10, 4, 3) X(16, 8, 8, 4, 5) X(16, 8, 16, 4, 1) X(16, 8, 32, 1, 1) X(16, 10, 16, 2, 1) X(16, 10, 10, 4, 2) X(16, 10, 8, 4, 4) \
-    X(32, 10, 16, 2, 1) X(32, 10, 10, 4, 2) X(32, 10, 8, 4, 4) X(32, 10, 16, 4, 1) X(32, 10, 32, 1, 1)
-bool wide_instance(int rows, int waves, int nv, int share, int ch) {
-#define FA_WIDE_IS(R_, W_, V, S, C) if (rows == R_ && waves == W_ && nv == V && share == S && ch == C) return true;
-    FA_WIDE_INSTANCES(FA_WIDE_IS)
-#undef FA_WIDE_IS
-    return false;
+template <class F> bool wide_pick(const int rows, const int waves, const int nv, const int share, const int ch, F &&f) {
+    return pick<Inst<32, 8, 16, 2, 3>, Inst<32, 8, 10, 4, 5>, Inst<16, 8, 16, 2, 2>, Inst<16, 8, 10, 4, 3>, Inst<16, 8, 8, 4, 5>, Inst<16, 8, 16, 4, 1>, Inst<16, 8, 32, 1, 1>,
+                Inst<16, 10, 16, 2, 1>, Inst<16, 10, 10, 4, 2>, Inst<16, 10, 8, 4, 4>, Inst<32, 10, 16, 2, 1>, Inst<32, 10, 10, 4, 2>, Inst<32, 10, 8, 4, 4>, Inst<32, 10, 16, 4, 1>,
+                Inst<32, 10, 32, 1, 1>>(f, rows, waves, nv, share, ch);
 }
-void poly_rows_wide_launch(fa_ctx *ctx, const PolyRows &R, const float *d_x, float *d_y, int64_t tiles, int64_t m_end, int64_t frames) {
-    const int2 *gtab = static_cast<const int2 *>(R.d_tables);
-    const float *tt = reinterpret_cast<const float *>(static_cast<const char *>(R.d_tables) + R.tt_offset);
-    const int vec_ok = R.up % 4 == 0 && (reinterpret_cast<uintptr_t>(d_y) & 15) == 0 ? 1 : 0;
-    // the resident workgroups: one (128 KB of LDS) or two (64 / 72 KB) per CU, in whole sets of 8 x groups (kernel: workgroup -> XCD, group, tile chain)
-    const int per_cu = R.wide_rows == 32 && (R.wide_waves == 8 || R.nv == 32) ? 1 : 2, set = 8 * R.g.groups;
-    int64_t sets = 256 * per_cu / set;
-    sets = std::max<int64_t>(1, std::min<int64_t>(sets, (tiles + 7) / 8));
-    const unsigned grid = static_cast<unsigned>(sets * set);
-    int rot = 0;                                                     // (sld / 4)^-1 mod 16 (sld / 4 is odd)
-    for (int c = 1; c < 16; c += 2) if ((c * (R.g.sld / 4)) % 16 == 1) rot = c;
-    const int n_tiles = static_cast<int>(tiles);
-    const int64_t k_lim = frames - 4;
-#define FA_WIDE_GO(R_, W_, V, S, C)                                                                                                                 \
-    if (R.wide_rows == R_ && R.wide_waves == W_ && R.nv == V && R.g.share == S && R.ch == C) {                                                     \
-        if constexpr (R_ == 32 && W_ == 8) hipLaunchKernelGGL((poly_rows_wide32_kernel<V, S, C>), dim3(grid), dim3(64 * W_), 0, ctx->stream, d_x, tt, d_y, R.g, gtab, n_tiles, m_end, k_lim, vec_ok, rot);   \
-        else if constexpr (R_ == 32 && V == 32) hipLaunchKernelGGL((poly_rows_wide32w10l_kernel<V, S, C>), dim3(grid), dim3(64 * W_), 0, ctx->stream, d_x, tt, d_y, R.g, gtab, n_tiles, m_end, k_lim, vec_ok, rot); \
-        else if constexpr (R_ == 32) hipLaunchKernelGGL((poly_rows_wide32w10_kernel<V, S, C>), dim3(grid), dim3(64 * W_), 0, ctx->stream, d_x, tt, d_y, R.g, gtab, n_tiles, m_end, k_lim, vec_ok, rot); \
-        else if constexpr (W_ == 8) hipLaunchKernelGGL((poly_rows_wide16_kernel<V, S, C>), dim3(grid), dim3(64 * W_), 0, ctx->stream, d_x, tt, d_y, R.g, gtab, n_tiles, m_end, k_lim, vec_ok, rot); \
-        else hipLaunchKernelGGL((poly_rows_wide16w10_kernel<V, S, C>), dim3(grid), dim3(64 * W_), 0, ctx->stream, d_x, tt, d_y, R.g, gtab, n_tiles, m_end, k_lim, vec_ok, rot); \
-        return;                                                                                                                                    \
-    }
-    FA_WIDE_INSTANCES(FA_WIDE_GO)
-#undef FA_WIDE_GO
-}
-template <int NV>
-void poly_rows_launch(fa_ctx *ctx, const PolyRows &R, const float *d_x, float *d_y, int64_t tiles, int64_t m_end, int64_t frames) {
-    if constexpr (NV == 32) {                                                               // phases of 65 .. 128 taps (88.2 -> 16 kHz): two windows of 16 reads per phase
-        if (R.g.sld > 64 * 5) poly_rows_launch_it<16, 10, 1, 2>(ctx, R, d_x, d_y, tiles, m_end);
-        else poly_rows_launch_it<16, 5, 1, 2>(ctx, R, d_x, d_y, tiles, m_end);
-    } else
-    if (R.g.sld > 64 * 5) poly_rows_launch_it<NV, 10, 1>(ctx, R, d_x, d_y, tiles, m_end);   // few phases with long windows: one group per tile (built with share = 1)
-    else if (R.g.share == 4) poly_rows_launch_it<NV, 5, 4>(ctx, R, d_x, d_y, tiles, m_end);  // rows of a group within 74 KB (the common case)
-    else if (R.g.share == 2) poly_rows_launch_it<NV, 5, 2>(ctx, R, d_x, d_y, tiles, m_end);
-    else poly_rows_launch_it<NV, 5, 1>(ctx, R, d_x, d_y, tiles, m_end);
-}
+const auto no_op = [](auto) {};
+int64_t lds_span(const int up, const int down, const int64_t n_taps) { return (static_cast<int64_t>(kPolyTile) * down + up - 1) / up + (n_taps + up - 1) / up + 4; }
+unsigned blocks(const int64_t threads) { return static_cast<unsigned>((threads + kThreads - 1) / kThreads); }
 
-double bessel_i0(double x) {  // power series, converges fast for the beta used here
-    double sum = 1.0, term = 1.0;
-    const double q = x * x / 4.0;
-    for (int k = 1; k < 200; ++k) { term *= q / (static_cast<double>(k) * k); sum += term; if (term < 1e-18 * sum) break; }
-    return sum;
+struct RowsArgs { const int2 *gtab; const float *tt; int vec_ok; };   // the two tables, and whether the outputs can go out as 16-byte pieces
+RowsArgs rows_args(const fa::resample::Job &j, const fa::resample::RowsTables &t) {
+    return {static_cast<const int2 *>(t.d_tables), reinterpret_cast<const float *>(static_cast<const char *>(t.d_tables) + t.tt_offset),
+            t.g.up % 4 == 0 && (reinterpret_cast<uintptr_t>(j.y) & 15) == 0 ? 1 : 0};   // m_begin and the chunk starts are multiples of 4
 }
-
-int64_t gcd64(int64_t a, int64_t b) { while (b) { const int64_t t = a % b; a = b; b = t; } return a; }
+template <int NV, int IT, int SHARE, int HALVES = 1>
+void rows_go(const fa::resample::Job &j, const fa::resample::RowsTables &t, const int64_t tiles, const int64_t m_end) {
+    const RowsArgs a = rows_args(j, t);
+    const size_t lds = static_cast<size_t>(t.g.sld) * 64 * sizeof(float);
+    if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(poly_rows_kernel<NV, IT, SHARE, HALVES>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+    const int64_t tiles8 = (tiles + 7) / 8 * 8;   // whole rounds of the 8 XCDs: the index -> (tile, group) map of the kernel
+    hipLaunchKernelGGL((poly_rows_kernel<NV, IT, SHARE, HALVES>), dim3(static_cast<unsigned>(tiles8 * t.g.groups)), dim3(kRowsThreads), lds, j.stream, j.x, a.tt, a.gtab, j.y, t.g, tiles, m_end, a.vec_ok);
+}
 
 }  // namespace
 
-extern "C" {
+namespace fa {
+namespace resample {
 
-int64_t fa_resample_linear_frames(int64_t frames, double in_rate, double out_rate) {
-    if (frames < 0 || !(in_rate > 0) || !(out_rate > 0)) return 0;
-    if (in_rate == out_rate) return frames;  // :414-416
-    return static_cast<int64_t>(static_cast<double>(frames) / (in_rate / out_rate));  // :420
+void launch_edges(const Job &j, const int64_t m_lo, const int64_t m_hi) {
+    if (m_hi <= m_lo) return;
+    hipLaunchKernelGGL(poly_kernel, dim3(blocks(m_hi - m_lo)), dim3(kThreads), 0, j.stream, j.x, j.h, j.y, j.frames, j.n_out, j.n_taps, j.up, j.down, j.pre_remove, m_lo, m_hi);
 }
 
-fa_status fa_resample_linear(fa_ctx *ctx, const float *planar, int32_t channels, int64_t frames, double in_rate, double out_rate,
-                             float *out, int64_t out_capacity, int64_t *out_frames) {
-    if (!ctx || !out_frames) return FA_INVALID_ARGUMENT;
-    *out_frames = 0;
-    if (channels < 1 || frames < 0 || !(in_rate > 0) || !(out_rate > 0)) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "resample: bad arguments");
-    const int64_t n_out = fa_resample_linear_frames(frames, in_rate, out_rate);
-    if (n_out > out_capacity) return fa::set_error(ctx, FA_OUTPUT_TOO_SMALL, "resample: output buffer too small");
-    *out_frames = n_out;
-    if (frames == 0 || n_out == 0) return FA_SUCCESS;
-    if (!planar || !out) return FA_INVALID_ARGUMENT;
-    fa::DeviceGuard guard(ctx->device);
-    fa::DevBuf d_in, d_mono, d_out;
-    hipError_t e;
-    do {
-        if ((e = d_in.alloc(sizeof(float) * frames * channels)) != hipSuccess) break;
-        if ((e = d_mono.alloc(sizeof(float) * frames)) != hipSuccess) break;
-        if ((e = d_out.alloc(sizeof(float) * n_out)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(d_in.p, planar, sizeof(float) * frames * channels, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) break;
-        hipLaunchKernelGGL(mixdown_kernel, dim3(static_cast<unsigned>((frames + kThreads - 1) / kThreads)), dim3(kThreads), 0, ctx->stream,
-                           d_in.as<float>(), d_mono.as<float>(), channels, frames);
-        const float *src = d_mono.as<float>();
-        if (in_rate != out_rate) {
-            hipLaunchKernelGGL(linear_kernel, dim3(static_cast<unsigned>((n_out + kThreads - 1) / kThreads)), dim3(kThreads), 0, ctx->stream,
-                               d_mono.as<float>(), d_out.as<float>(), frames, n_out, in_rate / out_rate);
-            src = d_out.as<float>();
-        }
-        if ((e = hipGetLastError()) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(out, src, sizeof(float) * n_out, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) break;
-        e = hipStreamSynchronize(ctx->stream);
-    } while (0);
-    return fa::hip_status(ctx, e, "fa_resample_linear");
+size_t lds_need(const int up, const int down, const int64_t n_taps) {
+    return sizeof(float) * (static_cast<size_t>((n_taps + 3) & ~static_cast<int64_t>(3)) + static_cast<size_t>(lds_span(up, down, n_taps)));
+}
+void launch_lds(const Job &j, const size_t lds) {
+    if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(poly_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+    const int64_t tiles = (j.n_out + kPolyTile - 1) / kPolyTile;
+    const int per_cu = lds > 80 * 1024 ? 1 : (lds > 53 * 1024 ? 2 : 3);
+    const int grid = static_cast<int>(tiles < 256 * per_cu ? tiles : 256 * per_cu);
+    hipLaunchKernelGGL(poly_lds_kernel, dim3(grid), dim3(kThreads), lds, j.stream, j.x, j.h, j.y, j.frames, j.n_out, static_cast<int>(j.n_taps), j.up, j.down, j.pre_remove, static_cast<int>(lds_span(j.up, j.down, j.n_taps)));
 }
 
-int64_t fa_resample_poly_frames(int64_t frames, int32_t up, int32_t down) {
-    if (frames < 0 || up < 1 || down < 1) return 0;
-    const int64_t g = gcd64(up, down);
-    const int64_t u = up / g, dn = down / g;
-    return (frames * u + dn - 1) / dn;  // ceil(n * up / down)
+bool decim_tiles_instance(const int down) { return decim_tiles_pick(down, no_op); }
+void launch_decim_tiles(const int down, const Job &j, const int64_t m_begin, const int64_t m_end) {
+    decim_tiles_pick(down, [&](auto inst) {
+        constexpr int DN = decltype(inst)::v[0];
+        typedef DecimTile<DN> D;
+        const int64_t tiles = (m_end - m_begin) / D::TO;
+        if (tiles <= 0) return;
+        const int per_cu = std::max(1, std::min(4, static_cast<int>(160 * 1024 / (2 * sizeof(float) * D::BUF))));
+        const unsigned grid = static_cast<unsigned>(std::min<int64_t>(tiles, 256 * per_cu));
+        hipLaunchKernelGGL(poly_decim_tile_kernel<DN>, dim3(grid), dim3(kThreads), 0, j.stream, j.x, j.h, j.y, m_begin, static_cast<int>(tiles), j.frames - 4);
+    });
 }
 
-fa_status fa_resample_poly_taps(int32_t up, int32_t down, float *taps, int64_t capacity, int64_t *n_taps, int64_t *pre_remove) {
-    if (up < 1 || down < 1 || !n_taps || !pre_remove) return FA_INVALID_ARGUMENT;
-    const int64_t g = gcd64(up, down);
-    const int64_t u = up / g, dn = down / g, mx = u > dn ? u : dn;
-    const int64_t half = 10 * mx, len = 2 * half + 1;
-    const int64_t pre_pad = dn - half % dn;
-    *n_taps = len + pre_pad;
-    *pre_remove = (half + pre_pad) / dn;
-    if (!taps) return FA_SUCCESS;
-    if (capacity < *n_taps) return FA_OUTPUT_TOO_SMALL;
-    try {
-        // firwin(len, 1/mx, window=('kaiser', 5.0)) * up : windowed sinc, cut-off 1/mx of Nyquist, unit DC gain
-        std::vector<double> h(len);
-        const double fc = 1.0 / static_cast<double>(mx), alpha = 0.5 * (len - 1), beta = 5.0, i0b = bessel_i0(beta);
-        double sum = 0.0;
-        for (int64_t n = 0; n < len; ++n) {
-            const double m = static_cast<double>(n) - alpha;
-            const double a = M_PI * fc * m;
-            const double sinc = m == 0.0 ? 1.0 : sin(a) / a;
-            const double r = 2.0 * n / static_cast<double>(len - 1) - 1.0;
-            const double w = bessel_i0(beta * sqrt(1.0 - r * r > 0 ? 1.0 - r * r : 0.0)) / i0b;
-            h[n] = fc * sinc * w;
-            sum += h[n];
-        }
-        for (int64_t n = 0; n < pre_pad; ++n) taps[n] = 0.0f;
-        for (int64_t n = 0; n < len; ++n) taps[pre_pad + n] = static_cast<float>(h[n] / sum * static_cast<double>(u));
-        return FA_SUCCESS;
-    } catch (const std::bad_alloc &) {
-        return FA_ALLOCATION_FAILURE;
-    }
+bool decim_instance(const int down) { return decim_pick(down, no_op); }
+void launch_decim(const int down, const Job &j, const int64_t m_begin, const int64_t m_end) {
+    const int64_t groups = (m_end - m_begin) / kDecimR;
+    if (groups <= 0) return;
+    decim_pick(down, [&](auto inst) {
+        hipLaunchKernelGGL(poly_decim_kernel<decltype(inst)::v[0]>, dim3(blocks(groups)), dim3(kThreads), 0, j.stream, j.x, j.h, j.y, m_begin, groups);
+    });
 }
 
-// Device-resident form: d_x (frames samples) -> d_y (fa_resample_poly_frames samples), enqueued on the context's stream.
-fa_status fa_resample_poly_dev(fa_ctx *ctx, const float *d_x, int64_t frames, int32_t up, int32_t down, float *d_y, int64_t out_capacity, int64_t *out_frames) {
-    if (!ctx || !out_frames) return FA_INVALID_ARGUMENT;
-    *out_frames = 0;
-    if (frames < 0 || up < 1 || down < 1) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "resample_poly: bad arguments");
-    const int64_t g = gcd64(up, down);
-    const int u = static_cast<int>(up / g), dn = static_cast<int>(down / g);
-    const int64_t n_out = fa_resample_poly_frames(frames, up, down);
-    if (n_out > out_capacity) return fa::set_error(ctx, FA_OUTPUT_TOO_SMALL, "resample_poly: output buffer too small");
-    *out_frames = n_out;
-    if (frames == 0) return FA_SUCCESS;
-    if (!d_x || !d_y) return FA_INVALID_ARGUMENT;
-    try {
-        int64_t n_taps = 0, pre_remove = 0;
-        FA_TRY(fa_resample_poly_taps(u, dn, nullptr, 0, &n_taps, &pre_remove));
-        fa::DeviceGuard guard(ctx->device);
-        // The Kaiser taps of a rate pair are computed and uploaded ONCE per context (a context-owned buffer, not the shared scratch):
-        // a repeated call with the same (up, down) enqueues its kernel and returns without touching the host or synchronising.
-        if (ctx->poly_up != u || ctx->poly_down != dn || !ctx->poly_taps) {
-            std::vector<float> taps(n_taps);
-            FA_TRY(fa_resample_poly_taps(u, dn, taps.data(), n_taps, &n_taps, &pre_remove));
-            FA_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // an earlier call may still read the previous pair's taps
-            if (ctx->poly_taps_bytes < sizeof(float) * n_taps) {
-                if (ctx->poly_taps) { (void)hipFree(ctx->poly_taps); ctx->poly_taps = nullptr; ctx->poly_taps_bytes = 0; }
-                FA_HIP_TRY(ctx, hipMalloc(&ctx->poly_taps, sizeof(float) * n_taps));
-                ctx->poly_taps_bytes = sizeof(float) * n_taps;
-            }
-            ctx->poly_up = 0;
-            FA_HIP_TRY(ctx, hipMemcpyAsync(ctx->poly_taps, taps.data(), sizeof(float) * n_taps, hipMemcpyHostToDevice, ctx->stream));
-            FA_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // taps is a host temporary (first call of a rate pair only)
-            ctx->poly_up = u; ctx->poly_down = dn;
-            // per-phase tables of the pair for poly_rows_kernel (non-integer ratios), built and uploaded with the taps
-            if (ctx->poly_rows && ctx->poly_rows_free) { ctx->poly_rows_free(ctx->poly_rows); ctx->poly_rows = nullptr; }
-            {
-                PolyRows *R = new PolyRows();
-                std::vector<int> gtab;
-                std::vector<float> tt;
-                bool ok = poly_rows_build(*R, taps, u, dn, pre_remove, gtab, tt);
-                if (ok) {
-                    const size_t b0 = (sizeof(int) * gtab.size() + 255) & ~static_cast<size_t>(255), b1 = sizeof(float) * tt.size();
-                    R->tt_offset = b0;
-                    ok = hipMalloc(&R->d_tables, b0 + b1) == hipSuccess &&
-                         hipMemcpyAsync(R->d_tables, gtab.data(), sizeof(int) * gtab.size(), hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
-                         hipMemcpyAsync(static_cast<char *>(R->d_tables) + b0, tt.data(), b1, hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
-                         hipStreamSynchronize(ctx->stream) == hipSuccess;
-                    if (!ok) (void)hipGetLastError();
-                }
-                if (ok) { ctx->poly_rows = R; ctx->poly_rows_free = poly_rows_free; }
-                else delete R;                                            // the LDS-staged kernel serves the pair
-            }
-        }
-        float *d_h = static_cast<float *>(ctx->poly_taps);
-        // the kernel-choice switches of the tests, read ONCE per call, here (the forms fixed with a context's tables — FA_RESAMPLE_WIDE, _NO_WIDE —
-        // are read when the tables are built)
-        struct { bool simple, no_decim, no_decim_tiles, no_rows; } const sw = {
-            fa::sw_on(fa::Sw::RESAMPLE_SIMPLE), fa::sw_on(fa::Sw::RESAMPLE_NO_DECIM), fa::sw_on(fa::Sw::RESAMPLE_NO_DECIM_TILES),
-            fa::sw_on(fa::Sw::RESAMPLE_NO_ROWS)};
-        const bool simple = sw.simple;
-        auto edges = [&](const int64_t m_lo, const int64_t m_hi) {   // outputs [m_lo, m_hi) by the one-thread-per-output kernel (clamps at the signal's ends)
-            if (m_hi <= m_lo) return;
-            hipLaunchKernelGGL(poly_kernel, dim3(static_cast<unsigned>((m_hi - m_lo + kThreads - 1) / kThreads)), dim3(kThreads), 0, ctx->stream, d_x, d_h, d_y, frames, n_out,
-                               n_taps, u, dn, pre_remove, m_lo, m_hi);
-        };
-        // integer decimation: register-tiled kernel on the outputs whose inputs all exist, poly_kernel on the two edges
-        bool decim = false;
-        if (!simple && u == 1 && ((dn >= 2 && dn <= 6) || dn == 12) && !sw.no_decim &&
-            (reinterpret_cast<uintptr_t>(d_x) & 15) == 0 && (reinterpret_cast<uintptr_t>(d_y) & 7) == 0 && n_taps == 21 * dn + 1 && pre_remove == 11) {
-            const int64_t m_begin = 10;                                                  // inputs start at (m - 10) dn >= 0; 10 = 10 (mod 4)
-            const int64_t m_last = (frames - 1) / dn - 11;                               // (m + 11) dn <= frames - 1
-            const int64_t avail = m_last >= m_begin ? std::min(m_last + 1, n_out) - m_begin : 0;   // outputs whose inputs all exist
-            int64_t m_done = m_begin;                                                    // outputs [m_begin, m_done) are served by the tiled kernel
-            if (!sw.no_decim_tiles) {
-                // whole tiles of 256 R outputs through LDS (poly_decim_tile_kernel); what is left goes to the register-tiled kernel and the edges
-                auto go = [&](auto dc) {
-                    constexpr int DN = decltype(dc)::value;
-                    typedef DecimTile<DN> D;
-                    int64_t tiles = std::min<int64_t>(avail / D::TO, (int64_t{1} << 30) / D::TO);
-                    // the 16-byte piece that holds a tile's last input may run up to 3 samples past it: a last tile whose piece would leave the signal is not a
-                    // tile (its piece would be clamped and land shifted in LDS) — its outputs go to the register-tiled kernel and the edges (the same
-                    // guard as the register-tiled kernel's below, mirrored in tests/cpu/resample_geom_emul.cpp)
-                    while (tiles > 0 && ((m_begin + tiles * D::TO - 1) + 11) * DN + 3 > frames - 1) --tiles;
-                    if (tiles <= 0) return;
-                    const int per_cu = std::max(1, std::min(4, static_cast<int>(160 * 1024 / (2 * sizeof(float) * D::BUF))));
-                    const unsigned grid = static_cast<unsigned>(std::min<int64_t>(tiles, 256 * per_cu));
-                    hipLaunchKernelGGL(poly_decim_tile_kernel<DN>, dim3(grid), dim3(kThreads), 0, ctx->stream, d_x, d_h, d_y, m_begin, static_cast<int>(tiles), frames - 4);
-                    m_done = m_begin + tiles * D::TO;
-                };
-                switch (dn) {
-                    case 2: go(std::integral_constant<int, 2>{}); break;
-                    case 3: go(std::integral_constant<int, 3>{}); break;
-                    case 4: go(std::integral_constant<int, 4>{}); break;
-                    case 5: go(std::integral_constant<int, 5>{}); break;
-                    case 6: go(std::integral_constant<int, 6>{}); break;
-                    default: go(std::integral_constant<int, 12>{}); break;          // 192 kHz: tiles only (no register-tiled instance: what is left goes to the edges' kernel)
-                }
-            }
-            const int64_t m_rest = m_done;                                               // m_done - 10 is a multiple of 4 (tiles of 256 R outputs)
-            const int64_t groups = dn <= 6 ? (avail - (m_rest - m_begin)) / kDecimR : 0;
-            // the 16-byte loads of the last group may run up to 3 samples past its last input: keep them inside the signal
-            int64_t gr = groups;
-            while (gr > 0 && ((m_rest + gr * kDecimR - 1) + 11) * dn + 3 > frames - 1) --gr;
-            if (gr > 0) {
-                const unsigned grid = static_cast<unsigned>((gr + kThreads - 1) / kThreads);
-                switch (dn) {
-                    case 2: hipLaunchKernelGGL(poly_decim_kernel<2>, dim3(grid), dim3(kThreads), 0, ctx->stream, d_x, d_h, d_y, m_rest, gr); break;
-                    case 3: hipLaunchKernelGGL(poly_decim_kernel<3>, dim3(grid), dim3(kThreads), 0, ctx->stream, d_x, d_h, d_y, m_rest, gr); break;
-                    case 4: hipLaunchKernelGGL(poly_decim_kernel<4>, dim3(grid), dim3(kThreads), 0, ctx->stream, d_x, d_h, d_y, m_rest, gr); break;
-                    case 5: hipLaunchKernelGGL(poly_decim_kernel<5>, dim3(grid), dim3(kThreads), 0, ctx->stream, d_x, d_h, d_y, m_rest, gr); break;
-                    default: hipLaunchKernelGGL(poly_decim_kernel<6>, dim3(grid), dim3(kThreads), 0, ctx->stream, d_x, d_h, d_y, m_rest, gr); break;   // 96 kHz: 127 taps in eight registers, 169 inputs
-                }
-            }
-            if (gr > 0 || m_done > m_begin) {
-                edges(0, m_begin);
-                edges(m_rest + gr * kDecimR, n_out);
-                decim = true;
-            }
-        }
-        // small interpolation factors: register-tiled kernel on the outputs whose inputs all exist, poly_kernel on the two ends
-        if (!decim && !simple && u >= 2 && u <= 4) {
-            int64_t lo = 0, hi = 0;
-            if (u == 2 && dn == 1 && n_taps == 42) poly_interp_launch<2, 1, 42>(ctx, d_x, d_h, d_y, frames, n_out, pre_remove, lo, hi);
-            else if (u == 2 && dn == 3 && n_taps == 64) poly_interp_launch<2, 3, 64>(ctx, d_x, d_h, d_y, frames, n_out, pre_remove, lo, hi);
-            else if (u == 4 && dn == 3 && n_taps == 83) poly_interp_launch<4, 3, 83>(ctx, d_x, d_h, d_y, frames, n_out, pre_remove, lo, hi);
-            else if (u == 4 && dn == 1 && n_taps == 82) poly_interp_launch<4, 1, 82>(ctx, d_x, d_h, d_y, frames, n_out, pre_remove, lo, hi);
-            else if (u == 3 && dn == 1 && n_taps == 62) poly_interp_launch<3, 1, 62>(ctx, d_x, d_h, d_y, frames, n_out, pre_remove, lo, hi);
-            else if (u == 3 && dn == 2 && n_taps == 63) poly_interp_launch<3, 2, 63>(ctx, d_x, d_h, d_y, frames, n_out, pre_remove, lo, hi);
-            if (hi > lo) {
-                edges(0, lo);
-                edges(hi, n_out);
-                decim = true;   // served: the kernels below have nothing left to do
-            }
-        }
-        // non-integer ratios: row-tiled kernel on the tiles whose staged inputs all exist, poly_kernel on the two ends
-        bool rows = false;
-        if (!decim && !simple && ctx->poly_rows && !sw.no_rows) {
-            const PolyRows &R = *static_cast<const PolyRows *>(ctx->poly_rows);
-            const PolyRowsGeom &G = R.g;
-            const int tile_rows = R.wide ? R.wide_rows : 64;
-            int64_t tiles = fa::rows_tiles(G, frames, n_out, tile_rows);       // tiles whose staged inputs all exist (resample_geom.h)
-            const int64_t per_tile = static_cast<int64_t>(tile_rows) * G.up;
-            if (tiles > 0 && (tiles + 8) * G.groups < (1LL << 31)) {
-                const int64_t m_stop = std::min(n_out, G.m_begin + tiles * per_tile);
-                if (R.wide) poly_rows_wide_launch(ctx, R, d_x, d_y, tiles, m_stop, frames);
-                else switch (R.nv) {
-#define FA_ROWS_CASE(V) case V: poly_rows_launch<V>(ctx, R, d_x, d_y, tiles, m_stop, frames); break;
-                    FA_ROWS_CASE(4) FA_ROWS_CASE(6) FA_ROWS_CASE(8) FA_ROWS_CASE(10) FA_ROWS_CASE(12) FA_ROWS_CASE(14) FA_ROWS_CASE(16) FA_ROWS_CASE(32)
-#undef FA_ROWS_CASE
-                    default: tiles = 0; break;
-                }
-                if (tiles > 0) {
-                    edges(0, G.m_begin);
-                    edges(m_stop, n_out);
-                    rows = true;
-                }
-            }
-        }
-        const int64_t span = (static_cast<int64_t>(kPolyTile) * dn + u - 1) / u + (n_taps + u - 1) / u + 4;
-        const size_t lds = sizeof(float) * (static_cast<size_t>((n_taps + 3) & ~static_cast<int64_t>(3)) + static_cast<size_t>(span));
-        if (decim || rows) {
-        } else if (lds <= 150 * 1024 && !simple) {
-            if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(poly_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-            const int64_t tiles = (n_out + kPolyTile - 1) / kPolyTile;
-            const int per_cu = lds > 80 * 1024 ? 1 : (lds > 53 * 1024 ? 2 : 3);
-            const int grid = static_cast<int>(tiles < 256 * per_cu ? tiles : 256 * per_cu);
-            hipLaunchKernelGGL(poly_lds_kernel, dim3(grid), dim3(kThreads), lds, ctx->stream, d_x, d_h, d_y, frames, n_out, static_cast<int>(n_taps), u, dn, pre_remove,
-                               static_cast<int>(span));
-        } else {   // very long filters (extreme rate ratios): one thread per output straight from global memory
-            edges(0, n_out);
-        }
-        FA_HIP_TRY(ctx, hipGetLastError());
-        return FA_SUCCESS;
-    } catch (const std::bad_alloc &) {
-        return FA_ALLOCATION_FAILURE;
-    } catch (...) {
-        return FA_UNKNOWN_ERROR;
-    }
+bool interp_instance(const int up, const int down, const int64_t n_taps) { return interp_pick(up, down, n_taps, no_op); }
+void launch_interp(const Job &j, const int64_t m_begin, const int64_t q_begin, const int64_t groups) {
+    if (groups <= 0) return;
+    interp_pick(j.up, j.down, j.n_taps, [&](auto inst) {
+        typedef decltype(inst) I;
+        hipLaunchKernelGGL((poly_interp_kernel<I::v[0], I::v[1], I::v[2]>), dim3(blocks(groups)), dim3(kThreads), 0, j.stream, j.x, j.h, j.y, m_begin, q_begin, groups);
+    });
 }
 
-fa_status fa_resample_poly(fa_ctx *ctx, const float *x, int64_t frames, int32_t up, int32_t down, float *out, int64_t out_capacity,
-                           int64_t *out_frames) {
-    if (!ctx || !out_frames) return FA_INVALID_ARGUMENT;
-    *out_frames = 0;
-    if (frames < 0 || up < 1 || down < 1) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "resample_poly: bad arguments");
-    const int64_t n_out = fa_resample_poly_frames(frames, up, down);
-    if (n_out > out_capacity) return fa::set_error(ctx, FA_OUTPUT_TOO_SMALL, "resample_poly: output buffer too small");
-    *out_frames = n_out;
-    if (frames == 0) return FA_SUCCESS;
-    if (!x || !out) return FA_INVALID_ARGUMENT;
-    fa::DeviceGuard guard(ctx->device);
-    fa::DevBuf d_x, d_y;
-    if (d_x.alloc(sizeof(float) * frames) != hipSuccess || d_y.alloc(sizeof(float) * n_out) != hipSuccess) {
-        (void)hipGetLastError();
-        return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "resample_poly: device allocation failed");
-    }
-    FA_HIP_TRY(ctx, hipMemcpyAsync(d_x.p, x, sizeof(float) * frames, hipMemcpyHostToDevice, ctx->stream));
-    int64_t got = 0;
-    FA_TRY(fa_resample_poly_dev(ctx, d_x.as<float>(), frames, up, down, d_y.as<float>(), n_out, &got));
-    FA_HIP_TRY(ctx, hipMemcpyAsync(out, d_y.p, sizeof(float) * n_out, hipMemcpyDeviceToHost, ctx->stream));
-    FA_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return FA_SUCCESS;
+bool rows_instance(const int nv) { return rows_pick(nv, no_op); }
+void launch_rows(const Job &j, const RowsTables &t, const int64_t tiles, const int64_t m_end) {
+    rows_pick(t.nv, [&](auto inst) {
+        constexpr int NV = decltype(inst)::v[0];
+        const bool long_rows = t.g.sld > 64 * 5;                           // few phases with long windows: one group per tile (built with share = 1)
+        if constexpr (NV == 32) {                                          // phases of 65 .. 128 taps (88.2 -> 16 kHz): two windows of 16 reads per phase
+            if (long_rows) rows_go<16, 10, 1, 2>(j, t, tiles, m_end);
+            else rows_go<16, 5, 1, 2>(j, t, tiles, m_end);
+        } else if (long_rows) rows_go<NV, 10, 1>(j, t, tiles, m_end);
+        else if (t.g.share == 4) rows_go<NV, 5, 4>(j, t, tiles, m_end);      // rows of a group within 74 KB (the common case)
+        else if (t.g.share == 2) rows_go<NV, 5, 2>(j, t, tiles, m_end);
+        else rows_go<NV, 5, 1>(j, t, tiles, m_end);
+    });
 }
 
-}  // extern "C"
+bool wide_instance(const int rows, const int waves, const int nv, const int share, const int ch, const int sld, const int groups) {
+    const WideForm f = wide_form(rows, waves, nv);
+    return sld <= f.row_floats && groups <= f.max_groups && wide_pick(rows, waves, nv, share, ch, no_op);
+}
+void launch_rows_wide(const Job &j, const RowsTables &t, const int64_t tiles, const int64_t m_end) {
+    const RowsArgs a = rows_args(j, t);
+    // the resident workgroups: one (128 KB of LDS) or two (64 / 72 KB) per CU, in whole sets of 8 x groups (kernel: workgroup -> XCD, group, tile chain)
+    const int set = 8 * t.g.groups;
+    int64_t sets = 256 * wide_form(t.wide_rows, t.wide_waves, t.nv).per_cu / set;
+    sets = std::max<int64_t>(1, std::min<int64_t>(sets, (tiles + 7) / 8));
+    const unsigned grid = static_cast<unsigned>(sets * set);
+    int rot = 0;                                                     // (sld / 4)^-1 mod 16 (sld / 4 is odd)
+    for (int c = 1; c < 16; c += 2) if ((c * (t.g.sld / 4)) % 16 == 1) rot = c;
+    const int n_tiles = static_cast<int>(tiles);
+    const int64_t k_lim = j.frames - 4;                              // the last 16-byte piece inside the signal
+    wide_pick(t.wide_rows, t.wide_waves, t.nv, t.g.share, t.ch, [&](auto inst) {
+        typedef decltype(inst) I;
+        constexpr int R = I::v[0], W = I::v[1], V = I::v[2], S = I::v[3], C = I::v[4];
+#define FA_WIDE_GO(NAME, R_, W_, WIN, FS, FL, MINW, PCU, G) \
+        if constexpr (R == R_ && W == W_ && (WIN == 2 || WIN == (V == 32))) hipLaunchKernelGGL((NAME<V, S, C>), dim3(grid), dim3(64 * W), 0, j.stream, j.x, a.tt, j.y, t.g, a.gtab, n_tiles, m_end, k_lim, a.vec_ok, rot);
+        FA_WIDE_FORMS(FA_WIDE_GO)
+#undef FA_WIDE_GO
+    });
+}
+
+}  // namespace resample
+}  // namespace fa

@@ -1,5 +1,6 @@
-// resample_geom.h — host-side geometry of the polyphase kernels of resample.hip, in plain C++ so that the CPU tests can run it
-// (tests/cpu/resample_geom_emul.cpp emulates the kernels' indexing with it and checks every staged / read / written index).
+// resample_geom.h — host-side geometry of the polyphase kernels of resample.hip, in plain C++ so that the CPU tests can run it: the host code
+// (resample_host.hip), the kernels and tests/cpu/resample_geom_emul.cpp — which emulates the kernels' indexing and checks every staged / read /
+// written index — all take it from here.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -50,7 +51,7 @@ inline bool rows_geometry(PolyRowsGeom &g, int &nv_out, const std::vector<float>
         off[ph] = static_cast<int>(k_lo - k_begin);
         if (cnt[ph] < 1) return false;
     }
-    static const int sizes[] = {4, 6, 8, 10, 12, 14, 16};               // instantiated window sizes (poly_rows_launch); a larger one only reads a little further into the row
+    static const int sizes[] = {4, 6, 8, 10, 12, 14, 16};               // instantiated window sizes (launch_rows of resample.hip); a larger one only reads a little further into the row
     // the reach of a shared window: phases q .. q + share - 1 (q a multiple of `share`; groups start at multiples of 4) measured from off[q] & ~3
     auto reach_of = [&](const int share) {
         int reach = 0;
@@ -128,6 +129,7 @@ inline int64_t rows_tiles(const PolyRowsGeom &G, int64_t frames, int64_t n_out, 
 }
 
 // poly_interp_kernel<UP, DOWN, NT> with R outputs-per-phase-cycle groups per thread: first output, first phase cycle, number of threads' groups
+constexpr int kInterpR = 4;                                                  // the kernel's R
 inline void interp_geometry(int up, int down, int nt, int r, int64_t frames, int64_t n_out, int64_t pre_remove, int64_t &m_begin, int64_t &q_begin, int64_t &groups) {
     const int no = r * up, kb = (nt - 1) / up, nin = ((no - 1) * down) / up + kb + 1, nv = (nin + 3) / 4;
     // first output: (m + pre_remove) = j UP with j DOWN >= KB (the first input of the thread exists)
@@ -143,14 +145,36 @@ inline void interp_geometry(int up, int down, int nt, int r, int64_t frames, int
 
 // poly_decim_tile_kernel<DOWN>: the constants of a tile (resample.hip explains the kernel)
 constexpr int kDecimThreads = 256;
+constexpr int kDecimRegOutputs = 8;                                          // outputs per thread of poly_decim_kernel
+constexpr int decim_tile_r(int down) { return down == 2 ? 6 : down == 3 ? 4 : down == 4 ? 3 : down == 5 ? 4 : down == 6 ? 2 : 1; }   // R DOWN = 12, 12, 12, 20, 12 floats between two threads' windows; DOWN = 12 (192 kHz): R = 1
 template <int DOWN>
 struct DecimTile {
-    static constexpr int R = DOWN == 2 ? 6 : DOWN == 3 ? 4 : DOWN == 4 ? 3 : DOWN == 5 ? 4 : DOWN == 6 ? 2 : 1;     // R DOWN = 12, 12, 12, 20, 12 floats between two threads' windows; DOWN = 12 (192 kHz): R = 1
+    static constexpr int R = decim_tile_r(DOWN);
     static constexpr int NT = 21 * DOWN + 1, RS = R * DOWN, NIN = NT + (R - 1) * DOWN, NB = (NIN + 15) / 16;
     static constexpr int TO = kDecimThreads * R;                                  // outputs of a tile
     static constexpr int SPAN = TO * DOWN + NT - 1, PIECES = (SPAN + 3) / 4;   // its inputs, in floats and in 16-byte pieces
     static constexpr int BUF_A = (PIECES + 63) / 64 * 64 * 4, BUF_B = (kDecimThreads - 1) * RS + 16 * NB;
     static constexpr int BUF = BUF_A > BUF_B ? BUF_A : BUF_B;                // floats per buffer: whole requests, and the last thread's last (partly unused) quarter
 };
+
+// Integer decimation (up = 1; half = 10 down, pre_remove = 11: output m reads the inputs (m - 10) down .. (m + 11) down): the outputs whose inputs all
+// exist, split into [m_begin, m_tiles) for whole tiles of poly_decim_tile_kernel (none unless `tiles`) and [m_tiles, m_regs) for whole threads of
+// poly_decim_kernel (kDecimRegOutputs outputs each); the one-thread-per-output kernel takes the two edges.
+struct DecimSplit { int64_t m_begin, m_tiles, m_regs; };
+inline DecimSplit decim_split(int down, int64_t frames, int64_t n_out, bool tiles) {
+    const int64_t m_begin = 10;                                                  // inputs start at (m - 10) down >= 0; 10 = 2 (mod 4): see the kernels' alignment
+    const int64_t m_last = (frames - 1) / down - 11;                             // (m + 11) down <= frames - 1
+    const int64_t m_avail = std::max(m_begin, std::min(m_last + 1, n_out));       // [m_begin, m_avail): outputs whose inputs all exist
+    // whole units of `step` outputs from m0 on.  The 16-byte piece that holds a unit's last input may reach 3 samples past it: a last unit whose piece would
+    // leave the signal is not taken (a tile's piece would be clamped and land shifted in LDS; a thread's load would read outside the buffer)
+    auto whole = [&](const int64_t m0, const int64_t step, const int64_t most) {
+        int64_t n = std::min((m_avail - m0) / step, most);
+        while (n > 0 && ((m0 + n * step - 1) + 11) * down + 3 > frames - 1) --n;
+        return m0 + n * step;
+    };
+    const int64_t to = static_cast<int64_t>(kDecimThreads) * decim_tile_r(down);
+    const int64_t m_tiles = tiles ? whole(m_begin, to, (int64_t{1} << 30) / to) : m_begin;   // (the kernel counts tiles in an int)
+    return {m_begin, m_tiles, whole(m_tiles, kDecimRegOutputs, INT64_MAX)};
+}
 
 }  // namespace fa

@@ -1,5 +1,5 @@
 // CPU emulation of the indexing of poly_rows_kernel / poly_interp_kernel (fluidaudio_amd/csrc/resample.hip) on the host-side geometry the
-// library computes (csrc/resample_geom.h): every staged, read and written index is range-checked, every output of the covered range is
+// library computes (csrc/resample_geom.h, which resample_host.hip routes and builds tables with): every staged, read and written index is range-checked, every output of the covered range is
 // written exactly once, and the values are compared by the caller with a plain one-output-at-a-time evaluation (poly_simple below =
 // poly_kernel of resample.hip).  Test infrastructure: built by tests/test_resample_geom_emul.py with g++, no GPU.
 #include <cmath>
@@ -11,16 +11,14 @@
 #include "../../fluidaudio_amd/csrc/resample_geom.h"
 
 
-// poly_decim_tile_kernel<DOWN> on whole tiles of the outputs [10, ...) whose inputs all exist (the host's split in fa_resample_poly_dev): every staged index
+// poly_decim_tile_kernel<DOWN> on whole tiles of the outputs [10, ...) whose inputs all exist (fa::decim_split of resample_geom.h): every staged index
 // inside the signal or clamped (-2 if a READ position was clamped or lies outside), every window read inside the buffer (-3); every output of the tiles written
 // once (-4 / -5); a tile's first input 16-byte aligned (-6).  Values = the ascending-input fused multiply-adds of the kernel.
 template <int DOWN>
 static int decim_tiles_emulate_t(const float *x, int64_t n_in, const float *h, int64_t n_out, float *y, int64_t *m_lo, int64_t *m_hi) {
     typedef fa::DecimTile<DOWN> D;
-    const int64_t m_begin = 10, m_last = (n_in - 1) / DOWN - 11;
-    const int64_t avail = m_last >= m_begin ? std::min(m_last + 1, n_out) - m_begin : 0;
-    int64_t tiles = avail / D::TO;
-    while (tiles > 0 && ((m_begin + tiles * D::TO - 1) + 11) * DOWN + 3 > n_in - 1) --tiles;   // the host's guard: the last tile's last 16-byte piece stays inside the signal
+    const fa::DecimSplit split = fa::decim_split(DOWN, n_in, n_out, true);   // the library's own split (fa_resample_poly_dev routes a call with it)
+    const int64_t m_begin = split.m_begin, tiles = (split.m_tiles - m_begin) / D::TO;
     *m_lo = *m_hi = m_begin;
     if (tiles <= 0) return 0;
     static_assert(D::RS % 4 == 0 && (D::RS / 4) % 2 == 1, "a thread's window starts 4 x odd floats behind its neighbour's: conflict-free 16-byte LDS reads");
@@ -157,7 +155,7 @@ int rows_emulate(const float *x, int64_t n_in, const float *h, int64_t h_len, in
 
 // poly_interp_kernel<up, down, nt>, R = 4
 int interp_emulate(const float *x, int64_t n_in, const float *h, int nt, int up, int down, int64_t pre_remove, int64_t n_out, float *y, int64_t *m_lo, int64_t *m_hi) {
-    const int R = 4, NO = R * up, KB = (nt - 1) / up, NIN = ((NO - 1) * down) / up + KB + 1, NV = (NIN + 3) / 4;
+    const int R = fa::kInterpR, NO = R * up, KB = (nt - 1) / up, NIN = ((NO - 1) * down) / up + KB + 1, NV = (NIN + 3) / 4;
     int64_t m_begin = 0, q_begin = 0, groups = 0;
     fa::interp_geometry(up, down, nt, R, n_in, n_out, pre_remove, m_begin, q_begin, groups);
     *m_lo = *m_hi = 0;

@@ -1,4 +1,4 @@
-"""Build-time ISA check of the hand-written DPP multiply-adds.  resample.hip emits `v_fmac_f32_dpp ... row_newbcast` as inline assembly;
+"""Build-time ISA check of the hand-written DPP multiply-adds.  resample.hip (the resampler's kernels; its host code is in resample_host.hip) emits `v_fmac_f32_dpp ... row_newbcast` as inline assembly;
 LLVM's hazard recogniser does not look inside inline assembly, and gfx9 needs 2 wait states between a VALU write of a VGPR and a DPP read of it
 (5 after a VALU write of EXEC).  Today the tap registers come straight from loads; a compiler upgrade that copies one through a v_mov right in front
 of the multiply-add would silently read stale data.  This test compiles the file to assembly and checks every such instruction."""

@@ -70,7 +70,7 @@ def test_rows_kernel_indexing_on_the_library_geometry(fa, emul, up, down, n, sha
                                           (3, 2, 63, 10667), (4, 3, 83, 64), (3, 2, 63, 40)])
 def test_interp_kernel_indexing_on_the_library_geometry(fa, emul, up, down, nt, n):
     taps, pre = fa.poly_taps(up, down)
-    assert taps.size == nt                                                       # the instantiated tap counts of resample.hip
+    assert taps.size == nt                                                       # the instantiated tap counts of resample.hip (launch_interp)
     x = signal_of(n, n + 1)
     n_out = fa.lib().fa_resample_poly_frames(n, up, down)
     y = np.full(n_out, np.nan, np.float32)
@@ -89,7 +89,7 @@ def test_interp_kernel_indexing_on_the_library_geometry(fa, emul, up, down, nt, 
                                     # a last tile whose last input sits 1 .. 3 samples before the end of the signal (n = (TO t + 20) down + {1, 2, 3})
                                     (3, 3133), (3, 3134), (3, 3135), (2, 3113), (2, 3114), (2, 3115), (3, 6205), (4, 3155), (5, 5221), (6, 3193), (12, 3314)])
 def test_decim_tile_kernel_indexing(fa, emul, down, n):
-    """Round 5: integer decimation through LDS tiles (poly_decim_tile_kernel): the tiles the host launches, every staged piece inside the signal or clamped and
+    """Round 5: integer decimation through LDS tiles (poly_decim_tile_kernel): the tiles of the library's own split (fa::decim_split, which the emulation calls), every staged piece inside the signal or clamped and
     never read where clamped, every window inside the buffer, every output of the tiles written once; values = the one-output-at-a-time evaluation bit for bit."""
     taps, pre = fa.poly_taps(1, down)
     assert taps.size == 21 * down + 1 and pre == 11
