@@ -8,6 +8,7 @@ from .ahc import AHCClustering, check_dendrogram, cut, fastcluster_compute_centr
 from .beam import ARPAError, ARPALanguageModel, CtcVocabulary, ctc_beam_search, ctc_beam_search_ids_batch  # noqa: F401
 from .ctc import (LogitsArgmax, ctc_greedy_decode, ctc_greedy_ids_batch, ctc_greedy_rows, ctc_greedy_ids_dev, ctc_log_probs_dev,  # noqa: F401
                   decode_ctc_token_ids)
+from .der import DERResult, DERSpeakerSegment, compute_der, compute_der_batch, segments_from_timed, segments_from_timeline  # noqa: F401
 from .embedding import EmbeddingConfig, EmbeddingPlan, plan_embeddings, span_inputs, weight_resample  # noqa: F401
 from .formats import AudioWAV, RTTMParser, RTTMParserError, TimedSpeakerSegment, export_embeddings_json  # noqa: F401
 from .kmeans import KMeansClustering, SeededRNG, SpeakerCountConstraints  # noqa: F401

@@ -57,6 +57,7 @@ EXPORTED_SYMBOLS = [
     "fa_embedding_span_inputs_dev", "fa_weight_resample", "fa_weight_resample_dev",
     "fa_sortformer_offline_default_config", "fa_sortformer_offline_windows", "fa_sortformer_pack_windows_dev", "fa_sortformer_stitch_dev",
     "fa_sortformer_stitcher_alignment", "fa_timeline_default_config", "fa_timeline_segments_dev", "fa_timeline_segments",
+    "fa_der_default_config", "fa_der_score_batch",
 ]
 
 
@@ -147,6 +148,19 @@ class TimelineConfig(C.Structure):
 class DiarizerSegmentRecord(C.Structure):
     _fields_ = [("recording", C.c_int32), ("speaker", C.c_int32), ("start_frame", C.c_int64), ("end_frame", C.c_int64),
                 ("activity", C.c_float), ("finalized", C.c_int32)]
+
+
+class DerSegment(C.Structure):
+    _fields_ = [("label", C.c_int32), ("reserved", C.c_int32), ("start", C.c_double), ("end", C.c_double)]
+
+
+class DerConfig(C.Structure):
+    _fields_ = [("frame_step", C.c_double), ("collar", C.c_double)]
+
+
+class DerCounts(C.Structure):
+    _fields_ = [("frames", C.c_int64), ("miss", C.c_int64), ("false_alarm", C.c_int64), ("confusion", C.c_int64), ("ref", C.c_int64),
+                ("ref_labels", C.c_int32), ("hyp_labels", C.c_int32)]
 
 
 def build(force: bool = False) -> str:
@@ -365,6 +379,9 @@ def lib() -> C.CDLL:
     L.fa_timeline_default_config.restype = None
     L.fa_timeline_segments_dev.argtypes = [vp, C.POINTER(TimelineConfig), vp, vp, vp, vp, i32, i32, vp, i64, C.POINTER(i64), vp]
     L.fa_timeline_segments.argtypes = L.fa_timeline_segments_dev.argtypes
+    L.fa_der_default_config.argtypes = [C.POINTER(DerConfig)]
+    L.fa_der_default_config.restype = None
+    L.fa_der_score_batch.argtypes = [vp, C.POINTER(DerConfig), vp, vp, vp, vp, i32, vp, vp, vp, vp, i64]
     _lib = L
     return L
 

@@ -775,4 +775,64 @@ private:
     DiarizerTimelineConfig cfg_;
 };
 
+// ------------------------------------------------------------------------------------------------------------------ diarization error rate
+// DERSpeakerSegment, DERResult and DiarizationDER.compute (Sources/FluidAudio/Diarizer/DiarizationDER.swift:26-175) over fa_der_score_batch.
+// The labels are numbered here by first appearance (:61-80) and the seconds and the rate are formed here with the reference's expressions
+// (:160-164); the counts come from the device.  A side holds at most FA_DER_MAX_LABELS speakers (INVALID_ARGUMENT beyond, as for the
+// arguments the reference traps on: frameStep <= 0, collar < 0, a non-finite time).
+struct DERSpeakerSegment {
+    std::string speaker;
+    double start = 0.0, end = 0.0;
+};
+
+struct DERResult {
+    double der = 0.0, confusion = 0.0, falseAlarm = 0.0, miss = 0.0, totalRefSpeech = 0.0;
+    std::map<std::string, std::string> mapping;   // hyp label -> ref label; hyp labels without a partner are left out
+    fa_der_counts counts{};                       // the integers behind the seconds
+    std::vector<std::string> refLabels, hypLabels;
+    std::vector<int32_t> indexMapping;            // hyp index -> ref index or -1
+    std::vector<int64_t> overlap;                 // [hypLabels][refLabels] frames both are active in, before the collar
+};
+
+struct DiarizationDER {
+    static DERResult compute(Context &ctx, const std::vector<DERSpeakerSegment> &ref, const std::vector<DERSpeakerSegment> &hyp, double frameStep = 0.01,
+                             double collar = 0.0) {
+        return compute(ctx.handle(), ref, hyp, frameStep, collar);
+    }
+    // on a raw handle: argument errors are answered before the handle is looked at
+    static DERResult compute(fa_ctx *ctx, const std::vector<DERSpeakerSegment> &ref, const std::vector<DERSpeakerSegment> &hyp, double frameStep = 0.01,
+                             double collar = 0.0) {
+        DERResult out;
+        const auto number = [](const std::vector<DERSpeakerSegment> &segs, std::vector<std::string> &labels) {
+            std::map<std::string, int32_t> idx;
+            std::vector<fa_der_segment> packed;
+            packed.reserve(segs.size());
+            for (const auto &s : segs) {
+                const auto it = idx.emplace(s.speaker, static_cast<int32_t>(labels.size()));
+                if (it.second) labels.push_back(s.speaker);
+                packed.push_back(fa_der_segment{it.first->second, 0, s.start, s.end});
+            }
+            return packed;
+        };
+        const std::vector<fa_der_segment> r = number(ref, out.refLabels), h = number(hyp, out.hypLabels);
+        if (out.refLabels.size() > FA_DER_MAX_LABELS || out.hypLabels.size() > FA_DER_MAX_LABELS) throw Error(FA_INVALID_ARGUMENT, "DiarizationDER: more than 64 labels on a side");
+        const int64_t refRange[2] = {0, static_cast<int64_t>(r.size())}, hypRange[2] = {0, static_cast<int64_t>(h.size())};
+        const int64_t mapRange[2] = {0, static_cast<int64_t>(out.hypLabels.size())};
+        out.indexMapping.assign(out.hypLabels.size(), -1);
+        out.overlap.assign(out.hypLabels.size() * out.refLabels.size(), 0);
+        const fa_der_config cfg{frameStep, collar};
+        const fa_status st = fa_der_score_batch(ctx, &cfg, r.data(), refRange, h.data(), hypRange, 1, &out.counts, out.indexMapping.data(), mapRange,
+                                                out.overlap.data(), static_cast<int64_t>(out.overlap.size()));
+        if (st != FA_SUCCESS) throw Error(st, "fa_der_score_batch", ctx ? fa_ctx_last_error(ctx) : nullptr);
+        out.miss = static_cast<double>(out.counts.miss) * frameStep;
+        out.falseAlarm = static_cast<double>(out.counts.false_alarm) * frameStep;
+        out.confusion = static_cast<double>(out.counts.confusion) * frameStep;
+        out.totalRefSpeech = static_cast<double>(out.counts.ref) * frameStep;
+        out.der = out.totalRefSpeech > 0 ? (out.miss + out.falseAlarm + out.confusion) / out.totalRefSpeech : 0.0;
+        for (size_t i = 0; i < out.indexMapping.size(); ++i)
+            if (out.indexMapping[i] >= 0) out.mapping[out.hypLabels[i]] = out.refLabels[static_cast<size_t>(out.indexMapping[i])];
+        return out;
+    }
+};
+
 }  // namespace fluidaudio

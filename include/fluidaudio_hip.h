@@ -840,6 +840,43 @@ fa_status fa_timeline_segments(fa_ctx *ctx, const fa_timeline_config *cfg, const
                                const float *tentative, const int64_t *tentative_frames, int32_t batch, int32_t is_complete,
                                fa_diarizer_segment *segs, int64_t capacity, int64_t *count, int64_t *recording_counts);
 
+/* ------------------------------------------------------------------ diarization error rate ------ */
+/* DiarizationDER.compute (FluidAudio/Diarizer/DiarizationDER.swift:52-231) with the integer Kuhn-Munkres it calls
+ * (Diarizer/HungarianAssignment.swift:8-61), for `batch` (reference, hypothesis) pairs in one call: the frame-wise score the
+ * reference's Sortformer and LS-EEND benchmarks print.  Every quantity is an integer count; the wrappers form the seconds and the
+ * rate with the reference's expressions (:160-164).
+ * A segment's label is its speaker's index BY FIRST APPEARANCE on its side of its recording (the wrappers number the strings); a
+ * side holds at most FA_DER_MAX_LABELS labels (AMI has 5 speakers, VoxConverse at most 21).  A segment with end <= start is never
+ * rasterised, but its label and its end count (:67-80).  Negative starts clip to frame 0. */
+enum { FA_DER_MAX_LABELS = 64 };
+typedef struct {
+    int32_t label;                   /* 0 ... FA_DER_MAX_LABELS - 1 */
+    int32_t reserved;
+    double start, end;               /* seconds; finite */
+} fa_der_segment;
+typedef struct {
+    double frame_step;               /* 0.01 s: the analysis grid; > 0 and finite */
+    double collar;                   /* 0: the full width dropped around every reference boundary; >= 0 and finite */
+} fa_der_config;
+void fa_der_default_config(fa_der_config *cfg);
+typedef struct {
+    int64_t frames;                  /* Int(ceil(maxEnd / frameStep)) + 1; 0 for a pair without any label */
+    int64_t miss, false_alarm, confusion, ref;   /* frames; seconds are Double(count) * frameStep */
+    int32_t ref_labels, hyp_labels;  /* R, H */
+} fa_der_counts;
+/* HOST pointers.  ref_segs / hyp_segs hold the recordings' segments one after the other: recording b's are
+ * [ref_range[b], ref_range[b + 1]) and [hyp_range[b], hyp_range[b + 1]).  counts HOST [batch].  mapping HOST int32: recording b's
+ * hypothesis label h maps to reference label mapping[mapping_range[b] + h], or to -1 (no partner, or no overlap with it); the
+ * range must hold hyp_labels entries (OUTPUT_TOO_SMALL otherwise) and what it holds beyond them is set to -1.  overlap (nullable)
+ * HOST int64[overlap_capacity]: the [hyp_labels][ref_labels] tables of overlapping frames, counted before the collar, recording
+ * after recording (OUTPUT_TOO_SMALL when they do not fit).
+ * INVALID_ARGUMENT — decided before any device work — for a non-finite time, a label outside 0 ... 63, frame_step <= 0 or
+ * non-finite, collar < 0 or non-finite; INDEX_OVERFLOW for a recording of 2^31 frames or more.  Everything between the upload of
+ * the segments and the download of the counts stays on the device; one host synchronisation. */
+fa_status fa_der_score_batch(fa_ctx *ctx, const fa_der_config *cfg, const fa_der_segment *ref_segs, const int64_t *ref_range,
+                             const fa_der_segment *hyp_segs, const int64_t *hyp_range, int32_t batch, fa_der_counts *counts,
+                             int32_t *mapping, const int64_t *mapping_range, int64_t *overlap, int64_t overlap_capacity);
+
 /* ------------------------------------------------------------------ resampling ------ */
 /* AudioConverter.linearResample (FluidAudio/Shared/AudioConverter.swift:388-442): planar float[channels][frames] ->
  * mono mix (weight 1/channels) -> linear interpolation to out_rate.  HOST pointers.  Bit-exact restatement. */
