@@ -1,6 +1,6 @@
 """Host-side mirror of ``ctcBeamSearch`` and ``ARPALanguageModel`` (reference:
 Sources/FluidAudio/ASR/Parakeet/SlidingWindow/CTC/CtcDecoder.swift:72-241, .../CTC/ARPALanguageModel.swift:16-147) over the
-HIP C ABI (csrc/beam.hip): one workgroup per utterance, the language model's hash tables resident in HBM."""
+HIP C ABI (host side and C ABI: csrc/beam_host.hip; kernels: csrc/beam.hip): one workgroup per utterance, the language model's hash tables resident in HBM."""
 from __future__ import annotations
 
 import ctypes as C

@@ -20,82 +20,37 @@
 // Order-dependent details of the reference (it iterates Swift dictionaries) are resolved as in the CPU restatement
 // (oracle.ctc_beam_search): candidates are ordered beam-major / token-minor, a merged hypothesis takes the earlier position,
 // ties keep that order.  logAddExp is evaluated in double and rounded to float (within 1 ulp of the reference's Float libm).
-#include <algorithm>
-#include <cfloat>
+//
+// This file holds the kernels, their device-only helpers and one launcher per kernel family.  The host side — the ARPA reader, the builder of
+// the hash tables, the vocabulary, the launch plan and the C ABI — is beam_host.hip; what both share (records, operands, the scoring functions
+// that fa_arpa_score and the walk have in common) is beam_launch.h.
 #include <cmath>
-#include <cstdlib>
-#include <string>
-#include <unordered_map>
-#include <vector>
 
-#include "fa_common.h"
-#include "text_util.h"
+#include "beam_launch.h"
 
 namespace {
 
+using namespace fa::beam;
 constexpr int kThreads = 256;
-constexpr int kMaxBeam = 128;
-constexpr int kMaxTop = 64;
 constexpr int kMapSlots = 256;
-constexpr uint64_t kHashBase = 0x100000001b3ull;   // odd: multiplication by it is a bijection mod 2^64
-constexpr float kUnkLogProb = -23.026f;            // ARPALanguageModel.unkLogProb (:33)
-
-struct UniEntry { uint64_t h; int32_t len; float logp, backoff; int32_t used; };
-struct BiEntry { uint64_t hp, hw; int32_t lp, lw; float logp; int32_t used; };
-struct TokInfo { uint64_t mult, add; int32_t len, boundary; };   // stripped piece: h' = h * mult + add, len' = len + this len
-
-struct LmView {
-    const UniEntry *uni; const BiEntry *bi;
-    uint32_t uni_mask, bi_mask;   // capacity - 1
-};
-
-__host__ __device__ inline uint64_t mix64(uint64_t x) { x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33; return x; }
-
-__host__ __device__ inline bool uni_find(const LmView &lm, uint64_t h, int32_t len, float &logp, float &backoff) {
-    if (!lm.uni) return false;
-    for (uint32_t s = static_cast<uint32_t>(mix64(h + static_cast<uint64_t>(len))) & lm.uni_mask;; s = (s + 1) & lm.uni_mask) {
-        const UniEntry e = lm.uni[s];
-        if (!e.used) return false;
-        if (e.h == h && e.len == len) { logp = e.logp; backoff = e.backoff; return true; }
-    }
-}
-
-__host__ __device__ inline bool bi_find(const LmView &lm, uint64_t hp, int32_t lp, uint64_t hw, int32_t lw, float &logp) {
-    if (!lm.bi) return false;
-    for (uint32_t s = static_cast<uint32_t>(mix64(mix64(hp + static_cast<uint64_t>(lp)) ^ (hw + static_cast<uint64_t>(lw) * 0x9e3779b97f4a7c15ull))) & lm.bi_mask;;
-         s = (s + 1) & lm.bi_mask) {
-        const BiEntry e = lm.bi[s];
-        if (!e.used) return false;
-        if (e.hp == hp && e.hw == hw && e.lp == lp && e.lw == lw) { logp = e.logp; return true; }
-    }
-}
-
-// ARPALanguageModel.score (:98-103); plen < 0 encodes prev == nil
-__host__ __device__ inline float lm_score(const LmView &lm, uint64_t hw, int32_t lw, uint64_t hp, int32_t plen) {
-    float logp, bo;
-    if (plen >= 0 && bi_find(lm, hp, plen, hw, lw, logp)) return logp;
-    float backoff = 0.0f;
-    if (plen >= 0 && uni_find(lm, hp, plen, logp, bo)) backoff = bo;
-    const float uni = uni_find(lm, hw, lw, logp, bo) ? logp : kUnkLogProb;
-    return backoff + uni;
-}
 
 // The same score on the device with the three first probes (bigram, context unigram, word unigram) requested together: they are dependent
-// HBM / L2 round trips on the serial frame walk, and the bigram usually misses.  Collisions continue with the sequential probes above.
+// HBM / L2 round trips on the serial frame walk, and the bigram usually misses.  Collisions continue with the sequential probes of lm_score.
 __device__ inline float lm_score_dev(const LmView &lm, uint64_t hw, int32_t lw, uint64_t hp, int32_t plen) {
     if (!lm.uni) return lm_score(lm, hw, lw, hp, plen);
-    const uint32_t sw = static_cast<uint32_t>(mix64(hw + static_cast<uint64_t>(lw))) & lm.uni_mask;
+    const uint32_t sw = uni_slot(hw, lw, lm.uni_mask);
     const UniEntry ew = lm.uni[sw];
     if (plen < 0) {
         if (!ew.used) return kUnkLogProb;                       // backoff 0 + unknown word
         if (ew.h == hw && ew.len == lw) return 0.0f + ew.logp;
         return lm_score(lm, hw, lw, hp, plen);
     }
-    const uint32_t sp = static_cast<uint32_t>(mix64(hp + static_cast<uint64_t>(plen))) & lm.uni_mask;
+    const uint32_t sp = uni_slot(hp, plen, lm.uni_mask);
     const UniEntry ep = lm.uni[sp];
     bool bi_known = !lm.bi, bi_hit = false;
     float bi_logp = 0.0f;
     if (lm.bi) {
+        // bi_slot(hp, plen, hw, lw, lm.bi_mask), written out: through the helper the same arithmetic is scheduled differently in ctc_beam_kernel
         const uint32_t sb = static_cast<uint32_t>(mix64(mix64(hp + static_cast<uint64_t>(plen)) ^ (hw + static_cast<uint64_t>(lw) * 0x9e3779b97f4a7c15ull))) & lm.bi_mask;
         const BiEntry eb = lm.bi[sb];
         if (!eb.used) bi_known = true;
@@ -107,11 +62,6 @@ __device__ inline float lm_score_dev(const LmView &lm, uint64_t hw, int32_t lw, 
     const float backoff = ep.used ? ep.backoff : 0.0f;
     const float uni = ew.used ? ew.logp : kUnkLogProb;
     return backoff + uni;
-}
-
-inline void hash_bytes(const char *s, size_t n, uint64_t &h, uint64_t &mult) {
-    h = 0; mult = 1;
-    for (size_t i = 0; i < n; ++i) { h = h * kHashBase + static_cast<unsigned char>(s[i]); mult *= kHashBase; }
 }
 
 // monotone float -> uint map (larger float, larger uint); NaN sorts below everything
@@ -133,22 +83,10 @@ __device__ __forceinline__ float log_add_exp(float a, float b) {   // CtcDecoder
     return static_cast<float>(static_cast<double>(m) + log(sum));
 }
 
-struct TopEntry { int32_t tok; float lp; };   // tok: token id, bit 31 = the piece starts a word (TokInfo::boundary)
-
 struct Beams {   // structure of arrays in LDS
     int32_t node[kMaxBeam], parent[kMaxBeam], last[kMaxBeam], wlen[kMaxBeam], plen[kMaxBeam];
     float pb[kMaxBeam], pnb[kMaxBeam], tot[kMaxBeam], lm[kMaxBeam], wscore[kMaxBeam];   // tot = logAddExp(pb, pnb) = totalAcoustic (:83), carried along
     uint64_t wh[kMaxBeam], ph[kMaxBeam];
-};
-
-struct BeamArgs {
-    const float *logp; const int32_t *valid; const TokInfo *tok; LmView lm;
-    unsigned long long *arena;   // [B][arena_stride] trie = hash table of (parent node << 32 | token), node id = slot; -1 = empty prefix
-    int32_t *tokens, *lens; float *scores;
-    int64_t row_stride, matrix_stride, arena_stride;
-    int32_t frames, vocab, blank, beam_width, top_k, use_lm, first;
-    float lm_weight, word_bonus;
-    const TopEntry *top;   // the pre-pass' table (ctc_topk_kernel): [workgroup][frame][top_k + 1]
 };
 
 struct Shared {
@@ -212,13 +150,6 @@ __device__ __forceinline__ int wave_incl_scan(int v) {
 // search over the bits of u, from the first bit in which the row's keys differ, keeps T with count(u < T) < K; it stops as soon as a tested
 // bound H has K <= count(u < H) <= 64 — those keys are gathered and ranked, the first K kept — or when all 32 bits are fixed: then T is the
 // K-th smallest key and ties at T enter in index order.  No barrier, no LDS atomics: DPP reductions, ballots and one 512-byte LDS slab per wave.
-
-struct TopArgs {
-    const float *logp; const int32_t *valid; const TokInfo *tok;
-    TopEntry *top;                             // [utterance of the launch][frame][top_k + 1]: the K best tokens, then (lp) the blank's log-probability
-    int64_t row_stride, matrix_stride, rows;
-    int32_t frames, vocab, blank, top_k, first, use_lm;
-};
 
 __device__ __forceinline__ int wave_sum(int v) {   // total over the wavefront, in every lane's scalar copy
     return __builtin_amdgcn_readlane(wave_incl_scan(v), 63);
@@ -638,264 +569,40 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(const BeamArgs a) {
     }
 }
 
-inline uint32_t pow2_at_least(size_t n) { uint32_t c = 16; while (c < n) c <<= 1; return c; }
-
-bool parse_float_full(const std::string &s, float &out) { return fa_text::parse_float(s, out); }   // Swift's Float(String)
-
 }  // namespace
 
-struct fa_arpa_lm {
-    fa_ctx *ctx = nullptr;
-    std::vector<UniEntry> uni;
-    std::vector<BiEntry> bi;
-    int64_t n_uni = 0, n_bi_ctx = 0, n_bi = 0;
-    void *d_uni = nullptr, *d_bi = nullptr;
-    int dev_id = -1;   // device holding d_uni / d_bi
-    LmView host_view() const { return LmView{uni.empty() ? nullptr : uni.data(), bi.empty() ? nullptr : bi.data(), static_cast<uint32_t>(uni.size() - 1), static_cast<uint32_t>(bi.size() - 1)}; }
-    LmView dev_view() const { return LmView{static_cast<const UniEntry *>(d_uni), static_cast<const BiEntry *>(d_bi), static_cast<uint32_t>(uni.size() - 1), static_cast<uint32_t>(bi.size() - 1)}; }
-};
+namespace fa {
+namespace beam {
 
-struct fa_ctc_vocab {
-    fa_ctx *ctx = nullptr;
-    int32_t vocab_size = 0;
-    void *d_tok = nullptr;
-};
+// ---- the pre-pass: ctc_topk_kernel<kTopRegs> holds a row of up to 64 * kTopRegs tokens in registers, ctc_topk_kernel<0> reads longer rows again
+int top_regs(const int vocab) { return vocab <= 64 * kTopRegs ? kTopRegs : 0; }
 
-extern "C" {
-
-fa_status fa_arpa_parse(fa_ctx *ctx, const char *text, int64_t len, fa_arpa_lm **out) {
-    if (!out || (!text && len > 0) || len < 0) return FA_INVALID_ARGUMENT;   // ctx may be NULL: parsing and scoring are host code
-    *out = nullptr;
-    try {
-        const float log10_to_nat = static_cast<float>(std::log(10.0));           // ARPALanguageModel.log10ToNat (:30)
-        struct U { std::string w; float p, b; };
-        struct B2 { std::string c, w; float p; };
-        std::unordered_map<std::string, size_t> uidx;
-        std::unordered_map<std::string, size_t> bidx;
-        std::vector<U> us;
-        std::vector<B2> bs;
-        std::unordered_map<std::string, int> contexts;
-        std::string section;
-        for (int64_t pos = 0; pos <= len;) {
-            int64_t e = pos;
-            while (e < len && text[e] != '\n') ++e;                                              // the reader cuts at the byte \n only (:126)
-            const char *la = text + pos, *lb = text + e;
-            pos = e + 1;
-            fa_text::trim(la, lb, fa_text::ws_or_nl_len);                                        // trimmingCharacters(in: .whitespacesAndNewlines) (:131)
-            const std::string line(la, lb);
-            if (line.empty() || line.rfind("\\data\\", 0) == 0) continue;                       // :54
-            if (line == "\\end\\") break;                                                       // :55
-            if (line[0] == '\\') { section = line; continue; }                                  // :56-59
-            if (line.rfind("ngram ", 0) == 0) continue;                                         // :61
-            std::vector<std::string> parts;
-            for (size_t i = 0;;) { const size_t j = line.find('\t', i); parts.emplace_back(line.substr(i, j == std::string::npos ? j : j - i)); if (j == std::string::npos) break; i = j + 1; }
-            float l10;
-            if (!parse_float_full(parts[0], l10)) continue;                                     // malformed line skipped (:64-67)
-            const float prob = l10 * log10_to_nat;
-            auto backoff = [&](size_t i) { float v; return parts.size() > i ? (parse_float_full(parts[i], v) ? v : 0.0f) * log10_to_nat : 0.0f; };
-            if (section == "\\1-grams:" && parts.size() >= 2) {
-                const float bo = backoff(2);
-                auto it = uidx.find(parts[1]);
-                if (it == uidx.end()) { uidx[parts[1]] = us.size(); us.push_back({parts[1], prob, bo}); } else { us[it->second].p = prob; us[it->second].b = bo; }
-            } else if (section == "\\2-grams:" && parts.size() >= 3) {
-                const std::string key = parts[1] + '\t' + parts[2];
-                auto it = bidx.find(key);
-                if (it == bidx.end()) { bidx[key] = bs.size(); bs.push_back({parts[1], parts[2], prob}); } else bs[it->second].p = prob;
-                contexts[parts[1]] = 1;
-            }
-        }
-        fa_arpa_lm *lm = new fa_arpa_lm();
-        lm->ctx = ctx; lm->n_uni = static_cast<int64_t>(us.size()); lm->n_bi = static_cast<int64_t>(bs.size()); lm->n_bi_ctx = static_cast<int64_t>(contexts.size());
-        lm->uni.assign(pow2_at_least(2 * us.size() + 1), UniEntry{0, 0, 0.f, 0.f, 0});
-        lm->bi.assign(pow2_at_least(2 * bs.size() + 1), BiEntry{0, 0, 0, 0, 0.f, 0});
-        const uint32_t um = static_cast<uint32_t>(lm->uni.size() - 1), bm = static_cast<uint32_t>(lm->bi.size() - 1);
-        for (const U &x : us) {
-            uint64_t h, m; hash_bytes(x.w.data(), x.w.size(), h, m);
-            const int32_t l = static_cast<int32_t>(x.w.size());
-            uint32_t s = static_cast<uint32_t>(mix64(h + static_cast<uint64_t>(l))) & um;
-            while (lm->uni[s].used) s = (s + 1) & um;
-            lm->uni[s] = UniEntry{h, l, x.p, x.b, 1};
-        }
-        for (const B2 &x : bs) {
-            uint64_t hp, hw, m; hash_bytes(x.c.data(), x.c.size(), hp, m); hash_bytes(x.w.data(), x.w.size(), hw, m);
-            const int32_t lp = static_cast<int32_t>(x.c.size()), lw = static_cast<int32_t>(x.w.size());
-            uint32_t s = static_cast<uint32_t>(mix64(mix64(hp + static_cast<uint64_t>(lp)) ^ (hw + static_cast<uint64_t>(lw) * 0x9e3779b97f4a7c15ull))) & bm;
-            while (lm->bi[s].used) s = (s + 1) & bm;
-            lm->bi[s] = BiEntry{hp, hw, lp, lw, x.p, 1};
-        }
-        *out = lm;
-        return FA_SUCCESS;
-    } catch (const std::bad_alloc &) {
-        return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "arpa: host allocation failed");
-    } catch (...) {
-        return fa::set_error(ctx, FA_UNKNOWN_ERROR, "arpa: unexpected failure");
-    }
+void launch_top(hipStream_t stream, const TopArgs &a) {
+    const unsigned blocks = static_cast<unsigned>((a.rows + kThreads / 64 - 1) / (kThreads / 64));   // one wavefront per row
+    if (top_regs(a.vocab)) hipLaunchKernelGGL(ctc_topk_kernel<kTopRegs>, dim3(blocks), dim3(kThreads), 0, stream, a);
+    else hipLaunchKernelGGL(ctc_topk_kernel<0>, dim3(blocks), dim3(kThreads), 0, stream, a);
 }
 
-void fa_arpa_destroy(fa_arpa_lm *lm) {
-    if (!lm) return;
-    if (lm->d_uni || lm->d_bi) { fa::DeviceGuard guard(lm->dev_id); (void)hipFree(lm->d_uni); (void)hipFree(lm->d_bi); }
-    delete lm;
+// ---- the walk: the instances of ctc_beam_kernel<MAXE>, smallest first; an instance serves up to 2 * MAXE top tokens (two threads per beam)
+#define FA_BEAM_WALKS(X) X(8) X(20) X(32)
+#define FA_BEAM_COVERS(MAXE) || 2 * MAXE >= kMaxTop
+static_assert(false FA_BEAM_WALKS(FA_BEAM_COVERS), "an instance for every supported number of top tokens");
+#undef FA_BEAM_COVERS
+
+int walk_keys(const int ntop) {
+#define FA_BEAM_SERVES(MAXE) if (ntop <= 2 * MAXE) return MAXE;
+    FA_BEAM_WALKS(FA_BEAM_SERVES)
+#undef FA_BEAM_SERVES
+    return 0;   // more than kMaxTop top tokens: the host entries refuse that
 }
 
-int64_t fa_arpa_unigram_count(const fa_arpa_lm *lm) { return lm ? lm->n_uni : 0; }
-int64_t fa_arpa_bigram_context_count(const fa_arpa_lm *lm) { return lm ? lm->n_bi_ctx : 0; }
-
-fa_status fa_arpa_score(const fa_arpa_lm *lm, const char *word, const char *prev, float *out) {
-    if (!lm || !word || !out) return FA_INVALID_ARGUMENT;
-    uint64_t hw, hp = 0, m;
-    hash_bytes(word, strlen(word), hw, m);
-    if (prev) hash_bytes(prev, strlen(prev), hp, m);
-    *out = lm_score(lm->host_view(), hw, static_cast<int32_t>(strlen(word)), hp, prev ? static_cast<int32_t>(strlen(prev)) : -1);
-    return FA_SUCCESS;
+void launch_walk(hipStream_t stream, const BeamArgs &a, const int utterances, const int ntop) {
+    const int keys = walk_keys(ntop);
+#define FA_BEAM_LAUNCH(MAXE) if (keys == MAXE) hipLaunchKernelGGL(ctc_beam_kernel<MAXE>, dim3(utterances), dim3(kThreads), 0, stream, a);
+    FA_BEAM_WALKS(FA_BEAM_LAUNCH)
+#undef FA_BEAM_LAUNCH
 }
+#undef FA_BEAM_WALKS
 
-fa_status fa_ctc_vocab_create(fa_ctx *ctx, const int32_t *ids, const char *const *pieces, int32_t n, int32_t vocab_size, fa_ctc_vocab **out) {
-    if (!ctx || !out || n < 0 || vocab_size < 1 || (n > 0 && (!ids || !pieces))) return FA_INVALID_ARGUMENT;
-    *out = nullptr;
-    std::vector<TokInfo> tok(vocab_size, TokInfo{1, 0, 0, 0});                        // missing id: vocabulary[v] ?? "" (:181)
-    static const char kBoundary[] = "\xe2\x96\x81";                                   // U+2581, ASRConstants.sentencePieceWordBoundary
-    for (int32_t i = 0; i < n; ++i) {
-        if (ids[i] < 0 || ids[i] >= vocab_size || !pieces[i]) continue;
-        const char *p = pieces[i];
-        size_t len = strlen(p);
-        TokInfo t{1, 0, 0, 0};
-        if (len >= 3 && memcmp(p, kBoundary, 3) == 0) { t.boundary = 1; p += 3; len -= 3; }   // hasPrefix + dropFirst (:184,:192)
-        hash_bytes(p, len, t.add, t.mult);
-        t.len = static_cast<int32_t>(len);
-        tok[ids[i]] = t;
-    }
-    fa::DeviceGuard guard(ctx->device);
-    fa_ctc_vocab *v = new (std::nothrow) fa_ctc_vocab();
-    if (!v) return FA_ALLOCATION_FAILURE;
-    v->ctx = ctx; v->vocab_size = vocab_size;
-    hipError_t e = hipMalloc(&v->d_tok, sizeof(TokInfo) * vocab_size);
-    if (e == hipSuccess) e = hipMemcpy(v->d_tok, tok.data(), sizeof(TokInfo) * vocab_size, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(v->d_tok); delete v; return fa::hip_status(ctx, e, "ctc vocab upload"); }
-    *out = v;
-    return FA_SUCCESS;
-}
-
-void fa_ctc_vocab_destroy(fa_ctc_vocab *v) {
-    if (!v) return;
-    if (v->d_tok) { fa::DeviceGuard guard(v->ctx->device); (void)hipFree(v->d_tok); }
-    delete v;
-}
-
-fa_status fa_ctc_beam_search_batch_dev(fa_ctx *ctx, const float *d_log_probs, int32_t batch, int32_t frames, int32_t vocab, int64_t row_stride,
-                                       int64_t matrix_stride, const int32_t *d_valid_frames, const fa_ctc_vocab *vocabulary, fa_arpa_lm *lm,
-                                       int32_t beam_width, float lm_weight, float word_bonus, int32_t blank_id, int32_t token_candidates,
-                                       int32_t *d_tokens, int32_t *d_lens, float *d_scores) {
-    if (!ctx) return FA_INVALID_ARGUMENT;
-    if (batch == 0) return FA_SUCCESS;
-    if (batch < 0 || frames < 0 || vocab < 1 || !d_tokens || !d_lens || (frames > 0 && !d_log_probs))
-        return fa::set_error(ctx, FA_INVALID_ARGUMENT, "beam search: bad arguments");
-    if (beam_width < 1 || beam_width > kMaxBeam || token_candidates < 0 || token_candidates > kMaxTop)
-        return fa::set_error(ctx, FA_INVALID_ARGUMENT, "beam search: beam width 1..%d, token candidates 0..%d", kMaxBeam, kMaxTop);
-    if (lm && (!vocabulary || vocabulary->vocab_size < vocab)) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "beam search: the language model needs a vocabulary covering all tokens");
-    if (row_stride < vocab) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "beam search: row stride < vocab");
-    fa::DeviceGuard guard(ctx->device);
-    if (lm && (!lm->d_uni || lm->dev_id != ctx->device)) {   // first use on this device: upload the tables (all or nothing)
-        if (lm->d_uni || lm->d_bi) {   // tables of another device: release them there
-            fa::DeviceGuard other(lm->dev_id);
-            (void)hipDeviceSynchronize();
-            (void)hipFree(lm->d_uni); (void)hipFree(lm->d_bi);
-            lm->d_uni = nullptr; lm->d_bi = nullptr;
-        }
-        void *du = nullptr, *db = nullptr;
-        hipError_t e = hipMalloc(&du, sizeof(UniEntry) * lm->uni.size());
-        if (e == hipSuccess) e = hipMalloc(&db, sizeof(BiEntry) * lm->bi.size());
-        if (e == hipSuccess) e = hipMemcpy(du, lm->uni.data(), sizeof(UniEntry) * lm->uni.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(db, lm->bi.data(), sizeof(BiEntry) * lm->bi.size(), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(du); (void)hipFree(db); return fa::hip_status(ctx, e, "arpa table upload"); }
-        lm->d_uni = du; lm->d_bi = db;
-        lm->ctx = ctx; lm->dev_id = ctx->device;
-    }
-    BeamArgs a{};
-    a.logp = d_log_probs; a.valid = d_valid_frames; a.tok = vocabulary ? static_cast<const TokInfo *>(vocabulary->d_tok) : nullptr;
-    if (lm) a.lm = lm->dev_view();
-    a.tokens = d_tokens; a.lens = d_lens; a.scores = d_scores;
-    a.row_stride = row_stride; a.matrix_stride = matrix_stride;
-    a.frames = frames; a.vocab = vocab; a.blank = blank_id; a.beam_width = beam_width; a.top_k = token_candidates;
-    a.use_lm = lm != nullptr; a.lm_weight = lm_weight; a.word_bonus = word_bonus;
-    a.arena_stride = pow2_at_least(static_cast<size_t>(2) * frames * beam_width + 2);
-    // trie tables: one per utterance in flight, at most ~2 GiB at a time
-    const int64_t per = a.arena_stride * static_cast<int64_t>(sizeof(unsigned long long));
-    const int chunk = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(batch, (int64_t(2) << 30) / std::max<int64_t>(per, 1))));
-    fa::DevBuf d_arena;
-    FA_HIP_TRY(ctx, d_arena.alloc(ctx, static_cast<size_t>(per) * chunk));   // the context's buffer cache: a second call pays no hipMalloc
-    a.arena = d_arena.as<unsigned long long>();
-    // the pre-pass' table of one launch: K (token, log-prob) pairs + the blank's log-prob per frame
-    fa::DevBuf d_top;
-    const size_t rows_max = static_cast<size_t>(chunk) * std::max(frames, 1);
-    FA_HIP_TRY(ctx, d_top.alloc(ctx, sizeof(TopEntry) * rows_max * (token_candidates + 1)));
-    a.top = d_top.as<TopEntry>();
-    TopArgs ta{};
-    ta.logp = d_log_probs; ta.valid = d_valid_frames; ta.tok = a.tok; ta.top = d_top.as<TopEntry>();
-    ta.row_stride = row_stride; ta.matrix_stride = matrix_stride; ta.frames = frames; ta.vocab = vocab; ta.blank = blank_id;
-    ta.top_k = token_candidates; ta.use_lm = a.use_lm;
-    if (ctx->timing) FA_HIP_TRY(ctx, hipEventRecord(ctx->tim_ev[0], ctx->stream));   // device work of the call: behind the allocations
-    for (int first = 0; first < batch; first += chunk) {
-        const int now = std::min(chunk, batch - first);
-        a.first = first;
-        FA_HIP_TRY(ctx, hipMemsetAsync(d_arena.p, 0xff, static_cast<size_t>(per) * now, ctx->stream));
-        if (frames > 0) {
-            ta.first = first; ta.rows = static_cast<int64_t>(now) * frames;
-            const unsigned blocks = static_cast<unsigned>((ta.rows + kThreads / 64 - 1) / (kThreads / 64));
-            if (vocab <= 64 * kTopRegs) hipLaunchKernelGGL(ctc_topk_kernel<kTopRegs>, dim3(blocks), dim3(kThreads), 0, ctx->stream, ta);
-            else hipLaunchKernelGGL(ctc_topk_kernel<0>, dim3(blocks), dim3(kThreads), 0, ctx->stream, ta);
-            FA_HIP_TRY(ctx, hipGetLastError());
-        }
-        const int ntop = std::min(token_candidates, vocab - (blank_id >= 0 && blank_id < vocab ? 1 : 0));   // extension keys per thread = ceil(ntop / 2)
-        if (ntop <= 16) hipLaunchKernelGGL(ctc_beam_kernel<8>, dim3(now), dim3(kThreads), 0, ctx->stream, a);
-        else if (ntop <= 40) hipLaunchKernelGGL(ctc_beam_kernel<20>, dim3(now), dim3(kThreads), 0, ctx->stream, a);
-        else hipLaunchKernelGGL(ctc_beam_kernel<32>, dim3(now), dim3(kThreads), 0, ctx->stream, a);
-        FA_HIP_TRY(ctx, hipGetLastError());
-    }
-    if (ctx->timing) FA_HIP_TRY(ctx, hipEventRecord(ctx->tim_ev[1], ctx->stream));
-    FA_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // the arena and the tables go back to the context's cache on return
-    if (ctx->timing) { float ms = -1.0f; FA_HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->tim_ev[0], ctx->tim_ev[1])); ctx->last_device_ms = ms; }
-    return FA_SUCCESS;
-}
-
-// What a call of these shapes launches (bench.py prints it next to its timing): out = { trie slots per utterance (arena_stride), utterances
-// per launch (the ~2 GiB arena cap), launches, extension keys per thread of the ctc_beam_kernel<MAXE> instance (8 / 20 / 32) }.
-fa_status fa_ctc_beam_plan(int32_t batch, int32_t frames, int32_t vocab, int32_t beam_width, int32_t blank_id, int32_t token_candidates, int64_t out[4]) {
-    if (!out || batch < 0 || frames < 0 || vocab < 1 || beam_width < 1 || beam_width > kMaxBeam || token_candidates < 0 || token_candidates > kMaxTop) return FA_INVALID_ARGUMENT;
-    const int64_t stride = static_cast<int64_t>(pow2_at_least(static_cast<size_t>(2) * frames * beam_width + 2));
-    const int64_t per = stride * static_cast<int64_t>(sizeof(unsigned long long));
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(batch, (int64_t(2) << 30) / std::max<int64_t>(per, 1)));
-    const int ntop = std::min(token_candidates, vocab - (blank_id >= 0 && blank_id < vocab ? 1 : 0));
-    out[0] = stride; out[1] = chunk; out[2] = batch > 0 ? (batch + chunk - 1) / chunk : 0; out[3] = ntop <= 16 ? 8 : (ntop <= 40 ? 20 : 32);
-    return FA_SUCCESS;
-}
-
-fa_status fa_ctc_beam_search_batch(fa_ctx *ctx, const float *log_probs, int32_t batch, int32_t frames, int32_t vocab, const int32_t *valid_frames,
-                                   const fa_ctc_vocab *vocabulary, fa_arpa_lm *lm, int32_t beam_width, float lm_weight, float word_bonus,
-                                   int32_t blank_id, int32_t token_candidates, int32_t *tokens, int32_t *lens, float *scores) {
-    if (!ctx) return FA_INVALID_ARGUMENT;
-    if (batch == 0) return FA_SUCCESS;
-    if (batch < 0 || frames < 0 || vocab < 1 || !tokens || !lens || (frames > 0 && !log_probs)) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "beam search: bad arguments");
-    fa::DeviceGuard guard(ctx->device);
-    const size_t n = static_cast<size_t>(batch) * frames * vocab;
-    fa::DevBuf d_lp, d_valid, d_tok, d_len, d_sc;
-    FA_HIP_TRY(ctx, d_lp.alloc(sizeof(float) * n));
-    FA_HIP_TRY(ctx, d_tok.alloc(sizeof(int32_t) * static_cast<size_t>(batch) * std::max(frames, 1)));
-    FA_HIP_TRY(ctx, d_len.alloc(sizeof(int32_t) * batch));
-    FA_HIP_TRY(ctx, d_sc.alloc(sizeof(float) * batch));
-    if (n) FA_HIP_TRY(ctx, hipMemcpyAsync(d_lp.p, log_probs, sizeof(float) * n, hipMemcpyHostToDevice, ctx->stream));
-    if (valid_frames) {
-        FA_HIP_TRY(ctx, d_valid.alloc(sizeof(int32_t) * batch));
-        FA_HIP_TRY(ctx, hipMemcpyAsync(d_valid.p, valid_frames, sizeof(int32_t) * batch, hipMemcpyHostToDevice, ctx->stream));
-    }
-    FA_TRY(fa_ctc_beam_search_batch_dev(ctx, d_lp.as<float>(), batch, frames, vocab, vocab, static_cast<int64_t>(frames) * vocab,
-                                        valid_frames ? d_valid.as<int32_t>() : nullptr, vocabulary, lm, beam_width, lm_weight, word_bonus, blank_id,
-                                        token_candidates, d_tok.as<int32_t>(), d_len.as<int32_t>(), d_sc.as<float>()));
-    if (frames > 0) FA_HIP_TRY(ctx, hipMemcpyAsync(tokens, d_tok.p, sizeof(int32_t) * static_cast<size_t>(batch) * frames, hipMemcpyDeviceToHost, ctx->stream));
-    FA_HIP_TRY(ctx, hipMemcpyAsync(lens, d_len.p, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, ctx->stream));
-    if (scores) FA_HIP_TRY(ctx, hipMemcpyAsync(scores, d_sc.p, sizeof(float) * batch, hipMemcpyDeviceToHost, ctx->stream));
-    FA_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return FA_SUCCESS;
-}
-
-}  // extern "C"
+}  // namespace beam
+}  // namespace fa

@@ -1,7 +1,7 @@
 // asan_text.cpp — the host-only text entries of the C ABI (RTTM reader / writer, ARPA reader + scoring, WAV reader, embedding JSON) under
 // AddressSanitizer + UndefinedBehaviorSanitizer: generated and mutated inputs in exact-size heap buffers (no terminator, no slack), so
 // that a read past the end of the caller's buffer is a report instead of luck.  Built and run by scripts/asan_text_fuzz.sh from the host
-// side of formats.hip / beam.hip (hipcc --cuda-host-only); no GPU, no kernel launch.  Test infrastructure, not part of the product.
+// side of formats.hip / beam_host.hip / beam.hip (hipcc --cuda-host-only); no GPU, no kernel launch.  Test infrastructure, not part of the product.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>

@@ -173,6 +173,36 @@ def test_reference_arpa_fixture_parses_identically(fa, oracle_mod):
     assert lib.score("diabetes", "doctor") == pytest.approx((-0.2 - 2.2) * LOG10, rel=1e-6)      # backoff of "doctor" + unigram
 
 
+PLAN_ROWS = [   # (batch, frames, vocab, beam, blank, K) -> [stride, per launch, launches, keys]
+    ((512, 1500, 1025, 100, 1024, 40), [524288, 512, 1, 20]),   # 300 002 nodes -> 2^19 slots = 4 MiB; 2 GiB / 4 MiB = 512; ntop 40
+    ((258, 2049, 6, 128, 5, 3), [1048576, 256, 2, 8]),          # 524 546 -> 2^20 slots = 8 MiB; 256 per launch: 256 + 2 (test_gpu_beam_scale.py)
+    ((0, 10, 8, 4, 7, 2), [128, 1, 0, 8]),                      # an empty batch: never fewer than 1 per launch, no launch; 82 -> 128 slots
+    ((1, 0, 8, 4, 7, 2), [16, 1, 1, 8]),                        # no frames: the smallest table
+    ((1, 4, 17, 4, 16, 17), [64, 1, 1, 8]),                     # ntop 16 | 17: the blank in range leaves 16 tokens
+    ((1, 4, 17, 4, -1, 17), [64, 1, 1, 20]),                    # no blank in the vocabulary: all 17
+    ((1, 4, 64, 4, 63, 40), [64, 1, 1, 20]),                    # ntop 40 | 41
+    ((1, 4, 64, 4, 63, 41), [64, 1, 1, 32]),
+    ((1, 4, 10, 4, 9, 64), [64, 1, 1, 8]),                      # K beyond what the vocabulary offers: ntop 9
+]
+
+
+def test_beam_plan_is_the_documented_one(fa):
+    """fa_ctc_beam_plan (host only) against include/fluidaudio_hip.h worked by hand: a prefix trie of the smallest power of two (>= 16) of slots
+    holding 2 * frames * beam_width + 2 nodes, 8 bytes each; as many utterances per launch as fit 2 GiB, at least 1; ceil(batch / that) launches;
+    and ceil(ntop / 2) extension keys per thread rounded up to an instance (8 / 20 / 32), ntop = min(K, tokens other than the blank)."""
+    import ctypes as C
+    plan = (C.c_int64 * 4)()
+    for args, want in PLAN_ROWS:
+        assert fa.lib().fa_ctc_beam_plan(*args, plan) == 0 and list(plan) == want, (args, list(plan), want)
+    good = (4, 10, 8, 4, 7, 2)                                    # batch, frames, vocab, beam width, blank, K
+    assert fa.lib().fa_ctc_beam_plan(*good, plan) == 0
+    for pos, bad in ((3, 0), (3, 129), (5, -1), (5, 65), (2, 0), (0, -1), (1, -1)):
+        args = list(good)
+        args[pos] = bad
+        assert fa.lib().fa_ctc_beam_plan(*args, plan) == 1, args  # FA_INVALID_ARGUMENT
+    assert fa.lib().fa_ctc_beam_plan(*good, None) == 1
+
+
 def random_case(rng, T, V, peaky):
     x = rng.standard_normal((T, V)).astype(np.float32) * peaky
     x = x - np.log(np.exp(x.astype(np.float64)).sum(1, keepdims=True)).astype(np.float32)
@@ -293,6 +323,21 @@ def test_device_matches_restatement(fa, gpu_ctx, oracle_mod, T, V, W_, K, peaky,
         assert ids[b] == want, (b, ids[b], want)
         if total is not None:
             assert scores[b] == pytest.approx(total, rel=2e-6, abs=2e-5)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("K,blank", [(16, 79), (17, 79), (40, 79), (41, 79), (17, -1)])
+def test_walk_instance_boundaries(fa, gpu_ctx, oracle_mod, K, blank):
+    """The walk has three instances, for up to 16 / 40 / 64 top tokens per frame.  With 80 tokens ntop = K: one search on each side of both
+    boundaries, and K = 17 once more without a blank in the vocabulary (the other branch of ntop's expression)."""
+    rng = np.random.default_rng(1617)
+    B, T, V = 3, 24, 80
+    batch = np.stack([random_case(rng, T, V, 2.0) for _ in range(B)])
+    ids, scores = fa.ctc_beam_search_ids_batch(batch, None, None, 16, 0.0, 0.0, blank, K, ctx=gpu_ctx)
+    for b in range(B):
+        want, total = oracle_mod.ctc_beam_search(batch[b], {}, None, 16, 0.0, 0.0, blank, K)
+        assert ids[b] == want, (b, ids[b], want)
+        assert scores[b] == pytest.approx(total, rel=2e-6, abs=2e-5)
 
 
 @pytest.mark.gpu

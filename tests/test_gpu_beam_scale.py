@@ -1,4 +1,4 @@
-"""CTC prefix beam search on the device (csrc/beam.hip) against the compiled restatement (oracle.ctc_beam_search_c) at the shapes the
+"""CTC prefix beam search on the device (kernels: csrc/beam.hip, host side: csrc/beam_host.hip) against the compiled restatement (oracle.ctc_beam_search_c) at the shapes the
 kernel exists for and at its limits: the benchmark's shape with a 4 000-word / 32 000-bigram model, beam 128 x 64 candidates on an 8 193-token
 vocabulary, a ragged batch, a batch split over two launches, the strided device entry over poisoned padding, and multi-byte pieces.
 Per utterance: token ids identical, scores within the tolerance of test_beam.py.  Every case with a model shows that the model acts: most

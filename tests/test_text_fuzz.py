@@ -139,7 +139,7 @@ def test_line_and_field_separators_of_the_reference(fa, oracle_mod):
 
 
 def test_text_entries_under_address_and_ub_sanitizers(tmp_path):
-    """scripts/asan_text_fuzz.sh: the host side of formats.hip / beam.hip built with -fsanitize=address,undefined and driven by
+    """scripts/asan_text_fuzz.sh: the host side of formats.hip / beam_host.hip / beam.hip built with -fsanitize=address,undefined and driven by
     tests/cabi/asan_text.cpp (300 000 generated RTTM / ARPA / WAV inputs in exact-size heap buffers + the JSON writer): a read past a
     caller's buffer, a leak or undefined behaviour in the C++ readers is a failure here.  Skipped where the sanitizer build is impossible."""
     import os
