@@ -22,10 +22,10 @@ from .post import (ConstrainedClusterAssignment, HungarianAssignment, assign_emb
                    compute_centroids)
 from .resample import linear_resample, poly_taps, resample_poly  # noqa: F401
 from .sharding import gather_ragged_int32, shard_offsets, shard_range  # noqa: F401
-from .sortformer import (DiarizerSegment, DiarizerTimeline, DiarizerTimelineConfig, OfflineSortformerConfig, OfflineSortformerDiarizer,  # noqa: F401
-                         offline_windows, pack_windows, stitch, stitcher_alignment, timeline_segments)
+from .sortformer import OfflineSortformerConfig, OfflineSortformerDiarizer, offline_windows, pack_windows, stitch, stitcher_alignment  # noqa: F401
 from .tdt import (TdtConfig, TdtDurationMapping, TdtFrameNavigation, decode_logits as tdt_decode_logits,  # noqa: F401
                   decode_tables as tdt_decode_tables)
+from .timeline import DiarizerSegment, DiarizerTimeline, DiarizerTimelineConfig, timeline_segments  # noqa: F401
 from .vbx import VBxClustering, VBxOutput  # noqa: F401
 
 __version__ = "0.1.0"

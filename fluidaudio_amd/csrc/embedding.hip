@@ -36,6 +36,7 @@
 
 namespace {
 
+using fa::grid_for;
 using fa::scan::block_exclusive;
 constexpr int kThreads = fa::scan::kThreads;
 constexpr int kScanPer = 8;             // items per thread of a compaction
@@ -46,8 +47,6 @@ constexpr int kValid = 1, kFallback = 2, kEmpty = 4;
 struct ItemRec {   // one (planned window, local speaker)
     int32_t flags, first, last, pad;
 };
-
-unsigned grid_for(int64_t n, int per_block) { return static_cast<unsigned>((n + per_block - 1) / per_block); }
 
 // WeightInterpolation.InterpolationCoefficients (:19-52) for output index i
 struct Coef { int l, r; float wl, wr; };

@@ -118,6 +118,9 @@ inline fa_status no_throw(fa_ctx *ctx, const char *what, F &&f) noexcept {
         if (fa_s_ != FA_SUCCESS) return fa_s_;  \
     } while (0)
 
+// workgroups of per_block items that cover n items
+inline unsigned grid_for(int64_t n, int per_block) { return static_cast<unsigned>((n + per_block - 1) / per_block); }
+
 // Test hook (fa_debug_inject_fault, ctx.hip): true for the next `count` passes through `site`.  One relaxed atomic load when nothing is armed.
 bool fault_hit(int site);
 

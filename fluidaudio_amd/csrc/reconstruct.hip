@@ -36,6 +36,7 @@
 
 namespace {
 
+using fa::grid_for;
 using fa::scan::block_exclusive;
 constexpr int kThreads = fa::scan::kThreads;
 constexpr int kTileG = 64;        // global frames per workgroup of the frame kernel (16 per wavefront)
@@ -361,8 +362,6 @@ __global__ __launch_bounds__(kThreads) void run_walk(const int64_t *__restrict__
         out[i] = RawRun{g0, g, k, g - g0, s};
     }
 }
-
-unsigned grid_for(int64_t n, int per_block) { return static_cast<unsigned>((n + per_block - 1) / per_block); }
 
 // ---------------------------------------------------------------- host passes
 

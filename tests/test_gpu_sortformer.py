@@ -1,4 +1,4 @@
-"""csrc/sortformer.hip on the device against tests/sortformer_restatement.py, bit for bit: np.array_equal on the fp32 arrays viewed as
+"""csrc/sortformer.hip, csrc/sortformer_host.hip and csrc/timeline.hip on the device against tests/sortformer_restatement.py, bit for bit: np.array_equal on the fp32 arrays viewed as
 uint32 and on every integer field.  There are no tolerances here."""
 import ctypes as C
 import os
@@ -192,6 +192,46 @@ def test_stitch_general_geometry(fa, gpu_ctx):
     small = R.OfflineConfig(10, 2, 3, 8, 7)                       # 2 * 7 > 10
     lengths = [20 * 3 * 2 + 9, 41]
     run_stitch(fa, gpu_ctx, small, lengths, [synthetic_preds(rng, small, n)[0] for n in lengths])
+
+
+@pytest.mark.parametrize("overlap", [5, 6])
+def test_stitch_route_boundary(fa, gpu_ctx, overlap):
+    """window 10: 2 * 5 = 10 is the last geometry of the parallel route (stitch_corr, stitch_chain, stitch_merge), 2 * 6 > 10 the first of
+    the serial one (stitch_serial).  Recordings of many windows, of a short tail window, and of exactly one window's mel frames."""
+    rng = np.random.default_rng(50 + overlap)
+    cfg = R.OfflineConfig(10, 2, 4, 8, overlap)
+    lengths = [207, 41, 20]
+    run_stitch(fa, gpu_ctx, cfg, lengths, [synthetic_preds(rng, cfg, n)[0] for n in lengths])
+
+
+@pytest.mark.parametrize("overlap", [64, 65])
+def test_stitch_overlap_staging_boundary(fa, gpu_ctx, overlap):
+    """stitch_corr stages 64 overlap frames per pass through LDS: 64 frames are one full pass, 65 a second pass of one frame (2 * 65 = 130:
+    still the parallel route).  A NaN sits in the last overlap frame on either side — with 65 frames the one frame of the second pass:
+    window 1's own frame overlap - 1, and window 2's last frame, which window 3 correlates against."""
+    rng = np.random.default_rng(60 + overlap)
+    cfg = R.OfflineConfig(130, 1, 4, 8, overlap)
+    lengths = [370, 131, 130]
+    preds = [synthetic_preds(rng, cfg, n)[0] for n in lengths]
+    assert preds[0].shape[0] >= 4
+    preds[0][1, overlap - 1, 2] = np.nan
+    preds[0][2, 129, 1] = np.nan
+    run_stitch(fa, gpu_ctx, cfg, lengths, preds)
+
+
+def test_stitch_statuses(fa, gpu_ctx):
+    import torch
+    cfg = fa.OfflineSortformerConfig().c_config()
+    n = np.array([5000], np.int64)                                # 2 windows, 625 frames of the global timeline
+    d_preds = torch.zeros((2, 384, 4), device="cuda")
+    d_global = torch.zeros((625, 4), device="cuda")
+    d_map = torch.zeros((2, 4), dtype=torch.int32, device="cuda")
+    f = fa.lib().fa_sortformer_stitch_dev
+    args = (gpu_ctx.handle, C.byref(cfg), d_preds.data_ptr(), n.ctypes.data, 1)
+    assert f(*args, 3, d_global.data_ptr(), d_map.data_ptr()) == fa.INVALID_ARGUMENT                                  # 2 windows, not 3
+    assert gpu_ctx.last_error().startswith("sortformer stitch:")
+    assert f(*args, 2, None, d_map.data_ptr()) == fa.INVALID_ARGUMENT
+    assert f(*args, 2, d_global.data_ptr(), d_map.data_ptr()) == fa.SUCCESS
 
 
 # ---------------------------------------------------------------- timeline
