@@ -9,6 +9,7 @@ from .beam import ARPAError, ARPALanguageModel, CtcVocabulary, ctc_beam_search, 
 from .ctc import (LogitsArgmax, ctc_greedy_decode, ctc_greedy_ids_batch, ctc_greedy_rows, ctc_greedy_ids_dev, ctc_log_probs_dev,  # noqa: F401
                   decode_ctc_token_ids)
 from .der import DERResult, DERSpeakerSegment, compute_der, compute_der_batch, segments_from_timed, segments_from_timeline  # noqa: F401
+from .kws import KWS_DETECTION_DTYPE, KWS_WINDOW_DTYPE, adjusted_threshold, score_windows, spot_keywords_batch  # noqa: F401
 from .embedding import EmbeddingConfig, EmbeddingPlan, plan_embeddings, span_inputs, weight_resample  # noqa: F401
 from .formats import AudioWAV, RTTMParser, RTTMParserError, TimedSpeakerSegment, export_embeddings_json  # noqa: F401
 from .kmeans import KMeansClustering, SeededRNG, SpeakerCountConstraints  # noqa: F401

@@ -138,7 +138,8 @@ bool fault_hit(int site);
     ROUTE(MEL_GENERIC, "FA_MEL_GENERIC") ROUTE(MEL_SLICE_MB, "FA_MEL_SLICE_MB") ROUTE(VBX_NO_TILED, "FA_VBX_NO_TILED")                \
     ROUTE(RESAMPLE_SIMPLE, "FA_RESAMPLE_SIMPLE") ROUTE(RESAMPLE_NO_DECIM, "FA_RESAMPLE_NO_DECIM")                                     \
     ROUTE(RESAMPLE_NO_DECIM_TILES, "FA_RESAMPLE_NO_DECIM_TILES") ROUTE(RESAMPLE_NO_ROWS, "FA_RESAMPLE_NO_ROWS")                       \
-    ROUTE(RESAMPLE_NO_WIDE, "FA_RESAMPLE_NO_WIDE") ROUTE(RESAMPLE_WIDE, "FA_RESAMPLE_WIDE")
+    ROUTE(RESAMPLE_NO_WIDE, "FA_RESAMPLE_NO_WIDE") ROUTE(RESAMPLE_WIDE, "FA_RESAMPLE_WIDE")                                            \
+    ROUTE(KWS_ARENA, "FA_KWS_ARENA")
 enum class Sw : int {
 #define FA_SW_ENUM(id, name) id,
     FA_SWITCHES(FA_SW_ENUM)

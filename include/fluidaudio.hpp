@@ -835,4 +835,105 @@ struct DiarizationDER {
     }
 };
 
+// ------------------------------------------------------------------------------------------------------------------ CTC word spotting
+// CtcKeywordSpotter.spotKeywordsFromLogProbs (…/WordSpotting/CtcKeywordSpotter.swift:191-254) and the two scans of CtcDPAlgorithm it and
+// the rescorer call (CtcDPAlgorithm.swift:250-392), over fa_ctc_kws_spot_batch / fa_ctc_kws_score_windows.  A term carries its token ids
+// (the tokenizer is not part of this library); the caller leaves out terms shorter than minTermLength.  The threshold rule (:217-222) and
+// startTime = frame x frameDuration (:232-233) are applied here; the DP runs on the device.
+struct CtcKeywordSpotter {
+    static constexpr int32_t wildcardTokenId = FA_KWS_WILDCARD;   // ContextBiasingConstants
+    static constexpr int32_t defaultBlankId = 1024;
+    static constexpr float defaultMinSpotterScore = -15.0f;
+    struct Term {
+        std::string text;
+        std::vector<int32_t> tokenIds;
+    };
+    struct KeywordDetection {
+        size_t term = 0;   // index into the vocabulary's terms
+        float score = 0.0f;
+        int32_t totalFrames = 0, startFrame = 0, endFrame = 0;
+        double startTime = 0.0, endTime = 0.0;
+    };
+    struct Spot {
+        float score;
+        int32_t startFrame, endFrame;
+    };
+    using LogProbs = std::vector<std::vector<float>>;   // [T][V], every frame of one length
+
+    static std::vector<KeywordDetection> spotKeywordsFromLogProbs(fa_ctx *ctx, const LogProbs &logProbs, double frameDuration, const std::vector<Term> &terms,
+                                                                  std::optional<float> minScore = std::nullopt, int32_t blankId = defaultBlankId) {
+        std::vector<KeywordDetection> out;
+        const int32_t T = static_cast<int32_t>(logProbs.size());
+        if (T == 0) return out;   // :198-200
+        std::vector<std::vector<int32_t>> ids;
+        std::vector<float> thresholds;
+        for (const Term &t : terms) {
+            ids.push_back(t.tokenIds);
+            thresholds.push_back(fa_kws_adjusted_threshold(minScore ? 1 : 0, minScore.value_or(0.0f), static_cast<int32_t>(t.tokenIds.size())));
+        }
+        for (const fa_kws_detection &d : spot(ctx, logProbs, ids, thresholds, true, blankId))
+            out.push_back(KeywordDetection{static_cast<size_t>(d.keyword), d.score, T, d.start_frame, d.end_frame, static_cast<double>(d.start_frame) * frameDuration,
+                                           static_cast<double>(d.end_frame) * frameDuration});
+        return out;
+    }
+    static std::vector<Spot> ctcWordSpotMultiple(fa_ctx *ctx, const LogProbs &logProbs, const std::vector<int32_t> &keywordTokens,
+                                                 float minScore = defaultMinSpotterScore, bool mergeOverlap = true, int32_t blankId = defaultBlankId) {
+        std::vector<Spot> out;
+        for (const fa_kws_detection &d : spot(ctx, logProbs, {keywordTokens}, {minScore}, mergeOverlap, blankId)) out.push_back(Spot{d.score, d.start_frame, d.end_frame});
+        return out;
+    }
+    static Spot ctcWordSpotConstrained(fa_ctx *ctx, const LogProbs &logProbs, const std::vector<int32_t> &keywordTokens, int32_t searchStartFrame,
+                                       int32_t searchEndFrame, int32_t blankId = defaultBlankId) {
+        int32_t T = 0, V = 0;
+        const std::vector<float> flat = flatten(logProbs, T, V);
+        const int64_t off[2] = {0, static_cast<int64_t>(keywordTokens.size())};
+        const fa_kws_window w{0, 0, searchStartFrame, searchEndFrame};
+        fa_kws_detection d{};
+        const fa_status st = fa_ctc_kws_score_windows(ctx, flat.data(), 1, T, V, V, static_cast<int64_t>(T) * V, nullptr, keywordTokens.data(), off, 1, &w, 1, blankId, &d);
+        if (st != FA_SUCCESS) throw Error(st, "fa_ctc_kws_score_windows", ctx ? fa_ctx_last_error(ctx) : nullptr);
+        return Spot{d.score, d.start_frame, d.end_frame};
+    }
+    static std::vector<KeywordDetection> spotKeywordsFromLogProbs(Context &ctx, const LogProbs &logProbs, double frameDuration, const std::vector<Term> &terms,
+                                                                  std::optional<float> minScore = std::nullopt, int32_t blankId = defaultBlankId) {
+        return spotKeywordsFromLogProbs(ctx.handle(), logProbs, frameDuration, terms, minScore, blankId);
+    }
+
+private:
+    static std::vector<float> flatten(const LogProbs &lp, int32_t &T, int32_t &V) {
+        T = static_cast<int32_t>(lp.size());
+        V = T > 0 ? static_cast<int32_t>(lp[0].size()) : 1;
+        std::vector<float> flat;
+        flat.reserve(static_cast<size_t>(T) * static_cast<size_t>(V));
+        for (const auto &row : lp) {
+            if (static_cast<int32_t>(row.size()) != V) throw Error(FA_INVALID_ARGUMENT, "CtcKeywordSpotter: frames of different lengths");
+            flat.insert(flat.end(), row.begin(), row.end());
+        }
+        if (V < 1) V = 1;
+        return flat;
+    }
+    static std::vector<fa_kws_detection> spot(fa_ctx *ctx, const LogProbs &logProbs, const std::vector<std::vector<int32_t>> &keywords, const std::vector<float> &thresholds,
+                                              bool mergeOverlap, int32_t blankId) {
+        int32_t T = 0, V = 0;
+        const std::vector<float> flat = flatten(logProbs, T, V);
+        std::vector<int32_t> tokens;
+        std::vector<int64_t> off{0};
+        for (const auto &k : keywords) {
+            tokens.insert(tokens.end(), k.begin(), k.end());
+            off.push_back(static_cast<int64_t>(tokens.size()));
+        }
+        std::vector<fa_kws_detection> dets(64);
+        int64_t count = 0;
+        for (int attempt = 0; attempt < 2; ++attempt) {   // the second call has room for the count the first one reported
+            const fa_status st = fa_ctc_kws_spot_batch(ctx, flat.data(), 1, T, V, V, static_cast<int64_t>(T) * V, nullptr, tokens.data(), off.data(),
+                                                       static_cast<int32_t>(keywords.size()), thresholds.data(), blankId, mergeOverlap ? 1 : 0, dets.data(),
+                                                       static_cast<int64_t>(dets.size()), &count, nullptr);
+            if (st == FA_OUTPUT_TOO_SMALL && attempt == 0) { dets.resize(static_cast<size_t>(count)); continue; }
+            if (st != FA_SUCCESS) throw Error(st, "fa_ctc_kws_spot_batch", ctx ? fa_ctx_last_error(ctx) : nullptr);
+            break;
+        }
+        dets.resize(static_cast<size_t>(count));
+        return dets;
+    }
+};
+
 }  // namespace fluidaudio

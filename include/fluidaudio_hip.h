@@ -97,6 +97,8 @@ const char *fa_version(void);
  *   FA_MEL_GENERIC, FA_MEL_SLICE_MB=n        the generic mel kernel; slice size of host-pointer batches
  *   FA_VBX_NO_TILED                          the untiled VBx iteration
  *   FA_RESAMPLE_SIMPLE, _NO_DECIM, _NO_DECIM_TILES, _NO_ROWS, _NO_WIDE, FA_RESAMPLE_WIDE=rows:waves (16:8, 16:10, 32:8, 32:10)   polyphase kernel family
+ *   FA_KWS_ARENA=records                     the candidate arena of a word-spotting call (never less than one job can need): a small one forces the
+ *                                            passes that walk overflowed jobs again
  * fa_debug_set_switch(name, value): value NULL = unset.  Changes what the NEXT calls see (process-wide; not for use while calls are in flight
  * on other threads).  RUNTIME_ERROR without FLUIDAUDIO_HIP_DEBUG_HOOKS=1, INVALID_ARGUMENT for an unknown name. */
 fa_status fa_debug_set_switch(const char *name, const char *value);
@@ -264,6 +266,48 @@ fa_status fa_ctc_greedy_rows(fa_ctx *ctx, const float *values, const int64_t *ro
 fa_status fa_ctc_log_softmax_batch_dev(fa_ctx *ctx, const void *d_logits, int32_t dtype, int32_t batch, int32_t frames,
                                        int32_t vocab, int64_t row_stride, int64_t matrix_stride, float temperature,
                                        float blank_bias, int32_t blank_id, float *d_log_probs);
+
+/* CTC word spotting (CTC-WS, arXiv:2406.07096) over such log-probabilities, batched over utterances: CtcDPAlgorithm.fillDPTable,
+ * ctcWordSpotMultiple, ctcWordSpotConstrained and nonWildcardCount (…/WordSpotting/CtcDPAlgorithm.swift:121-392) and the per-term loop
+ * of CtcKeywordSpotter.spotKeywordsFromLogProbs (…/WordSpotting/CtcKeywordSpotter.swift:191-254).  Scores and frames are the
+ * reference's bit for bit.  Not covered: the tokenizer, minTermLength (a text property: leave such terms out), NaN log-probabilities.
+ * A keyword is a run of token ids; FA_KWS_WILDCARD matches any frame at no cost, any other id outside [0, vocab) can never match
+ * (it emits -FLT_MAX), a blank id outside [0, vocab) emits 0.  A keyword of more than FA_KWS_MAX_TOKENS tokens is INVALID_ARGUMENT. */
+typedef struct { int32_t utterance, keyword; float score; int32_t start_frame, end_frame; } fa_kws_detection;
+typedef struct { int32_t utterance, keyword, start_frame, end_frame; } fa_kws_window;
+enum { FA_KWS_WILDCARD = -1, FA_KWS_MAX_TOKENS = 127 };
+/* The threshold of a term (CtcKeywordSpotter.swift:217-222): base - Float(max(0, token_count - 3)) * 1.0, or -15.0 without a base. */
+float fa_kws_adjusted_threshold(int32_t has_base, float base, int32_t token_count);
+/* ctcWordSpotMultiple for every (utterance, keyword) pair.  The log-probs are addressed like the logits of fa_ctc_greedy_batch_dev
+ * (a DEVICE pointer read in stream order for _dev, a HOST pointer otherwise); everything else is HOST memory.  valid_frames
+ * int32[batch] (nullable: all frames).  Keyword k is keyword_tokens[keyword_offsets[k] .. keyword_offsets[k + 1]); an empty one
+ * contributes nothing.  min_scores float[keywords] are the thresholds as ctcWordSpotMultiple takes them (NULL: -15 for all).
+ * The records come ordered by utterance, then keyword, then as the reference's array holds them (by start frame after the merge).
+ * dets HOST [capacity]; *count is set even when dets is NULL (SUCCESS) or too small (OUTPUT_TOO_SMALL, the first `capacity` records
+ * are written); utterance_counts HOST int64[batch] (nullable).  Argument errors are answered before any device work.
+ * Synchronous.  Device scratch is O(pairs + capacity) records; only candidate records come back over PCIe. */
+fa_status fa_ctc_kws_spot_batch_dev(fa_ctx *ctx, const float *d_log_probs, int32_t batch, int32_t frames, int32_t vocab,
+                                    int64_t row_stride, int64_t matrix_stride, const int32_t *valid_frames,
+                                    const int32_t *keyword_tokens, const int64_t *keyword_offsets, int32_t keywords,
+                                    const float *min_scores, int32_t blank_id, int32_t merge_overlap, fa_kws_detection *dets,
+                                    int64_t capacity, int64_t *count, int64_t *utterance_counts);
+fa_status fa_ctc_kws_spot_batch(fa_ctx *ctx, const float *log_probs, int32_t batch, int32_t frames, int32_t vocab,
+                                int64_t row_stride, int64_t matrix_stride, const int32_t *valid_frames,
+                                const int32_t *keyword_tokens, const int64_t *keyword_offsets, int32_t keywords,
+                                const float *min_scores, int32_t blank_id, int32_t merge_overlap, fa_kws_detection *dets,
+                                int64_t capacity, int64_t *count, int64_t *utterance_counts);
+/* ctcWordSpotConstrained for n_windows (utterance, keyword, [start_frame, end_frame)) windows: out[w] answers windows[w], frames in
+ * the utterance's coordinates; (-inf, clampedStart, clampedStart) for an empty keyword, an empty window or one shorter than the
+ * keyword.  A window's utterance or keyword outside the batch is INVALID_ARGUMENT.  _dev: the log-probs are a DEVICE pointer; otherwise a
+ * HOST pointer.  One host synchronisation behind the uploads. */
+fa_status fa_ctc_kws_score_windows_dev(fa_ctx *ctx, const float *d_log_probs, int32_t batch, int32_t frames, int32_t vocab,
+                                       int64_t row_stride, int64_t matrix_stride, const int32_t *valid_frames,
+                                       const int32_t *keyword_tokens, const int64_t *keyword_offsets, int32_t keywords,
+                                       const fa_kws_window *windows, int64_t n_windows, int32_t blank_id, fa_kws_detection *out);
+fa_status fa_ctc_kws_score_windows(fa_ctx *ctx, const float *log_probs, int32_t batch, int32_t frames, int32_t vocab,
+                                   int64_t row_stride, int64_t matrix_stride, const int32_t *valid_frames,
+                                   const int32_t *keyword_tokens, const int64_t *keyword_offsets, int32_t keywords,
+                                   const fa_kws_window *windows, int64_t n_windows, int32_t blank_id, fa_kws_detection *out);
 
 /* ------------------------------------------------------------------ TDT ------------- */
 /* Control flow of TdtDecoderV3.decodeWithTimings (FluidAudio/ASR/Parakeet/SlidingWindow/TDT/Decoder/TdtDecoderV3.swift:103-607)
