@@ -28,5 +28,7 @@ from .tdt import (TdtConfig, TdtDurationMapping, TdtFrameNavigation, decode_logi
                   decode_tables as tdt_decode_tables)
 from .timeline import DiarizerSegment, DiarizerTimeline, DiarizerTimelineConfig, timeline_segments  # noqa: F401
 from .vbx import VBxClustering, VBxOutput  # noqa: F401
+from .wer import (EDIT_COUNTS_DTYPE, CorpusErrorRate, WERAndCER, WERMetrics, edit_distance_batch, edit_distance_batch_dev, levenshtein_distance,  # noqa: F401
+                  wer_and_cer_batch, wer_metrics_batch)
 
 __version__ = "0.1.0"

@@ -58,6 +58,7 @@ EXPORTED_SYMBOLS = [
     "fa_sortformer_offline_default_config", "fa_sortformer_offline_windows", "fa_sortformer_pack_windows_dev", "fa_sortformer_stitch_dev",
     "fa_sortformer_stitcher_alignment", "fa_timeline_default_config", "fa_timeline_segments_dev", "fa_timeline_segments",
     "fa_der_default_config", "fa_der_score_batch",
+    "fa_edit_distance_batch", "fa_edit_distance_batch_dev",
     "fa_kws_adjusted_threshold", "fa_ctc_kws_spot_batch_dev", "fa_ctc_kws_spot_batch", "fa_ctc_kws_score_windows_dev", "fa_ctc_kws_score_windows",
 ]
 
@@ -162,6 +163,11 @@ class DerConfig(C.Structure):
 class DerCounts(C.Structure):
     _fields_ = [("frames", C.c_int64), ("miss", C.c_int64), ("false_alarm", C.c_int64), ("confusion", C.c_int64), ("ref", C.c_int64),
                 ("ref_labels", C.c_int32), ("hyp_labels", C.c_int32)]
+
+
+class EditCounts(C.Structure):
+    _fields_ = [("total", C.c_int32), ("insertions", C.c_int32), ("deletions", C.c_int32), ("substitutions", C.c_int32),
+                ("hyp_len", C.c_int32), ("ref_len", C.c_int32)]
 
 
 class KwsDetection(C.Structure):
@@ -391,6 +397,8 @@ def lib() -> C.CDLL:
     L.fa_der_default_config.argtypes = [C.POINTER(DerConfig)]
     L.fa_der_default_config.restype = None
     L.fa_der_score_batch.argtypes = [vp, C.POINTER(DerConfig), vp, vp, vp, vp, i32, vp, vp, vp, vp, i64]
+    L.fa_edit_distance_batch.argtypes = [vp, vp, vp, vp, vp, i64, vp]
+    L.fa_edit_distance_batch_dev.argtypes = L.fa_edit_distance_batch.argtypes
     L.fa_kws_adjusted_threshold.argtypes = [i32, f32, i32]
     L.fa_kws_adjusted_threshold.restype = f32
     L.fa_ctc_kws_spot_batch_dev.argtypes = [vp, vp, i32, i32, i32, i64, i64, vp, vp, vp, i32, vp, i32, i32, vp, i64, C.POINTER(i64), vp]

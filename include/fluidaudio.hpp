@@ -835,6 +835,66 @@ struct DiarizationDER {
     }
 };
 
+// ------------------------------------------------------------------------------------------------------------------ word / character error rate
+// WERCalculator.editDistance and the metrics formed from it (Sources/FluidAudioCLI/Utils/WERCalculator.swift:7-56, 178-239) and
+// StringUtils.levenshteinDistance (Sources/FluidAudio/Shared/StringUtils.swift:12-40) over fa_edit_distance_batch.  The tokens are numbered
+// here by first appearance and compared as integers on the device; the rates are formed here with the reference's expressions (:19, :40,
+// :45).  TextNormalizer, the split at whitespace and grapheme segmentation are the caller's: the tokens arrive normalised.
+struct WERCalculator {
+    using Tokens = std::vector<std::string>;
+    struct EditDistanceResult {   // :171-176
+        int total = 0, insertions = 0, deletions = 0, substitutions = 0;
+    };
+    struct WERMetrics {           // the tuple of calculateWERMetrics (:10)
+        double wer = 0.0;
+        int insertions = 0, deletions = 0, substitutions = 0, totalWords = 0;
+    };
+    // the batch form: every (hypothesis, reference) pair in one device call, answers in input order
+    static std::vector<EditDistanceResult> editDistance(fa_ctx *ctx, const std::vector<std::pair<Tokens, Tokens>> &pairs) {
+        std::map<std::string, int32_t> idx;
+        std::vector<int32_t> hyp, ref;
+        std::vector<int64_t> hypRange{0}, refRange{0};
+        const auto number = [&idx](const Tokens &t, std::vector<int32_t> &ids, std::vector<int64_t> &range) {
+            for (const std::string &s : t) ids.push_back(idx.emplace(s, static_cast<int32_t>(idx.size())).first->second);
+            range.push_back(static_cast<int64_t>(ids.size()));
+        };
+        for (const auto &p : pairs) {
+            number(p.first, hyp, hypRange);
+            number(p.second, ref, refRange);
+        }
+        std::vector<EditDistanceResult> out;
+        for (const fa_edit_counts &c : run(ctx, hyp, hypRange, ref, refRange)) out.push_back(EditDistanceResult{c.total, c.insertions, c.deletions, c.substitutions});
+        return out;
+    }
+    static EditDistanceResult editDistance(fa_ctx *ctx, const Tokens &hyp, const Tokens &ref) { return editDistance(ctx, {{hyp, ref}})[0]; }
+    static EditDistanceResult editDistance(Context &ctx, const Tokens &hyp, const Tokens &ref) { return editDistance(ctx.handle(), hyp, ref); }
+    // calculateWERMetrics (:7-22) behind the normalizer and the split
+    static WERMetrics calculateWERMetrics(fa_ctx *ctx, const Tokens &hypWords, const Tokens &refWords) {
+        const EditDistanceResult d = editDistance(ctx, hypWords, refWords);
+        const double wer = refWords.empty() ? 0.0 : static_cast<double>(d.total) / static_cast<double>(refWords.size());
+        return WERMetrics{wer, d.insertions, d.deletions, d.substitutions, static_cast<int>(refWords.size())};
+    }
+    static std::vector<fa_edit_counts> run(fa_ctx *ctx, const std::vector<int32_t> &hyp, const std::vector<int64_t> &hypRange, const std::vector<int32_t> &ref,
+                                           const std::vector<int64_t> &refRange) {
+        const int64_t n = static_cast<int64_t>(hypRange.size()) - 1;
+        std::vector<fa_edit_counts> out(static_cast<size_t>(n > 0 ? n : 0));
+        if (n <= 0) return out;
+        static const int32_t none = 0;   // a side without symbols still gets an array
+        const fa_status st = fa_edit_distance_batch(ctx, hyp.empty() ? &none : hyp.data(), hypRange.data(), ref.empty() ? &none : ref.data(), refRange.data(), n, out.data());
+        if (st != FA_SUCCESS) throw Error(st, "fa_edit_distance_batch", ctx ? fa_ctx_last_error(ctx) : nullptr);
+        return out;
+    }
+};
+
+struct StringUtils {
+    // levenshteinDistance<T: Equatable>(_ a: [T], _ b: [T]) for T = Int (:12-36)
+    static int levenshteinDistance(fa_ctx *ctx, const std::vector<int> &a, const std::vector<int> &b) {
+        const std::vector<int32_t> x(a.begin(), a.end()), y(b.begin(), b.end());
+        return WERCalculator::run(ctx, x, {0, static_cast<int64_t>(x.size())}, y, {0, static_cast<int64_t>(y.size())})[0].total;
+    }
+    static int levenshteinDistance(Context &ctx, const std::vector<int> &a, const std::vector<int> &b) { return levenshteinDistance(ctx.handle(), a, b); }
+};
+
 // ------------------------------------------------------------------------------------------------------------------ CTC word spotting
 // CtcKeywordSpotter.spotKeywordsFromLogProbs (…/WordSpotting/CtcKeywordSpotter.swift:191-254) and the two scans of CtcDPAlgorithm it and
 // the rescorer call (CtcDPAlgorithm.swift:250-392), over fa_ctc_kws_spot_batch / fa_ctc_kws_score_windows.  A term carries its token ids

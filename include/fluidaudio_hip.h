@@ -126,7 +126,7 @@ fa_status fa_debug_ahc_spec_hits(const fa_ctx *ctx, int64_t *hits);
  *   FA_FAULT_AHC            the linkage of fa_offline_cluster fails -> singletons (AHCClustering.swift:52-55) */
 enum { FA_FAULT_VBX = 0, FA_FAULT_THREAD_START = 1, FA_FAULT_DEVBUF_MALLOC = 2, FA_FAULT_WS_MALLOC = 3, FA_FAULT_AHC = 4, FA_FAULT_SITES = 5 };
 void fa_debug_inject_fault(int32_t site, int32_t count);
-/* Measurement support.  fa_ctx_set_timing(1): entries that support it (fa_ctc_beam_search_batch_dev) bracket the DEVICE work of a call —
+/* Measurement support.  fa_ctx_set_timing(1): entries that support it (fa_ctc_beam_search_batch_dev, fa_edit_distance_batch(_dev)) bracket the DEVICE work of a call —
  * behind its allocations — with two events on the context's stream; fa_ctx_last_device_ms returns that time (< 0: none recorded), so a
  * caller can tell kernel time from host-side allocation time.  fa_debug_sclk_mhz: the shader clock right now (one wavefront counts
  * s_memtime cycles over spin_us microseconds of the constant 100 MHz s_memrealtime counter). */
@@ -920,6 +920,29 @@ typedef struct {
 fa_status fa_der_score_batch(fa_ctx *ctx, const fa_der_config *cfg, const fa_der_segment *ref_segs, const int64_t *ref_range,
                              const fa_der_segment *hyp_segs, const int64_t *hyp_range, int32_t batch, fa_der_counts *counts,
                              int32_t *mapping, const int64_t *mapping_range, int64_t *overlap, int64_t overlap_capacity);
+
+/* ------------------------------------------------------------------ word / character error rate ------ */
+/* WERCalculator.editDistance (FluidAudioCLI/Utils/WERCalculator.swift:178-239) for n_pairs (hypothesis, reference) pairs of symbol
+ * sequences in one call: the Levenshtein distance and the insertion / deletion / substitution counts of the reference's traceback
+ * (a match first, then a substitution, a deletion, an insertion).  The total is StringUtils.levenshteinDistance
+ * (FluidAudio/Shared/StringUtils.swift:12-40) and the CLI's levenshteinDistance.  Integers only: a symbol is any int32 (the wrappers
+ * number words and characters by first appearance) and is compared for equality.  The wrappers form the rates with the reference's
+ * expressions (Double(total) / Double(ref_len), 0 for an empty reference). */
+typedef struct {
+    int32_t total;                   /* the edit distance = insertions + deletions + substitutions */
+    int32_t insertions, deletions, substitutions;
+    int32_t hyp_len, ref_len;        /* m, n */
+} fa_edit_counts;
+/* hyp / ref hold the pairs' sequences one after the other: pair k's are hyp[hyp_range[k] ... hyp_range[k + 1]) and
+ * ref[ref_range[k] ... ref_range[k + 1]).  The ranges (n_pairs + 1 entries each) and out [n_pairs] are HOST memory; hyp and ref are
+ * HOST pointers, for _dev DEVICE pointers on the context's device read in stream order.  The results come in input order.
+ * INVALID_ARGUMENT for a null or descending range, a negative range start or n_pairs < 0, INDEX_OVERFLOW for a side longer than
+ * INT32_MAX or 2^31 - 1 pairs or more — decided from the ranges alone, before any device work.  n_pairs == 0: SUCCESS, nothing is
+ * written.  Pairs with an empty side are answered on the host; one host synchronisation per call. */
+fa_status fa_edit_distance_batch(fa_ctx *ctx, const int32_t *hyp, const int64_t *hyp_range, const int32_t *ref, const int64_t *ref_range,
+                                 int64_t n_pairs, fa_edit_counts *out);
+fa_status fa_edit_distance_batch_dev(fa_ctx *ctx, const int32_t *d_hyp, const int64_t *hyp_range, const int32_t *d_ref, const int64_t *ref_range,
+                                     int64_t n_pairs, fa_edit_counts *out);
 
 /* ------------------------------------------------------------------ resampling ------ */
 /* AudioConverter.linearResample (FluidAudio/Shared/AudioConverter.swift:388-442): planar float[channels][frames] ->
