@@ -1,6 +1,7 @@
-// block_scan.h — the scan behind the block-scan compactions of reconstruct.hip (segment run starts) and embedding.hip (jobs, model runs):
-// a per-block count kernel writes one total per workgroup, scan_totals turns them into exclusive offsets in one workgroup, and a write
-// kernel places each kept item at its block's offset plus block_exclusive of its thread.
+// block_scan.h — the scan behind the block-scan compactions of the kernel units reconstruct.hip (segment run starts, issued by its
+// launch_frames) and embedding.hip (jobs, model runs, issued by its launch_select); their host units never see it.  A per-block count
+// kernel writes one total per workgroup, scan_totals turns them into exclusive offsets in one workgroup, and a write kernel places each
+// kept item at its block's offset plus block_exclusive of its thread.
 #pragma once
 #include <hip/hip_runtime.h>
 

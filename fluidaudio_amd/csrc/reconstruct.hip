@@ -1,4 +1,6 @@
-// reconstruct.hip — from segmentation logits and per-chunk cluster labels to speaker segments, on the device.
+// reconstruct.hip — from segmentation logits and per-chunk cluster labels to speaker segments: the kernels and one launcher per stage.
+// The frame plan's staging, the host passes over the raw runs and the C ABI are reconstruct_host.hip; the host arithmetic is
+// reconstruct_geom.h; what the two units share is reconstruct_launch.h.
 //
 //   * powerset decode (reference: Sources/FluidAudio/Diarizer/Offline/Segmentation/OfflineSegmentationProcessor.swift:316-409):
 //     per chunk frame the first strict maximum of the class logits (seeded at -Float.greatestFiniteMagnitude, so NaN never wins and
@@ -13,7 +15,7 @@
 //     maximal run of frames in which a cluster is active is one raw segment, start g0*fd, end g1*fd when closed at frame g1 and
 //     g_last*fd + fd when still open at the last frame, quality = Float(clamp(scoreSum / frames, 0, 1)) with scoreSum the
 //     sequential fp64 sum of the run's per-frame averages (:400-429).
-//   * mergeSegments / sanitize / excludeOverlaps (:359-398, :431-496) as host code over the compact raw list (one D2H).
+//   * mergeSegments / sanitize / excludeOverlaps (:359-398, :431-496) as host code over the compact raw list (one D2H): reconstruct_host.hip.
 //
 // Where the reference is not deterministic: raw segments that close at the same frame, and those flushed after the last frame,
 // are appended in Swift Dictionary order (hash-seeded), and that order decides merges between speakers whose segments start at the
@@ -26,37 +28,17 @@
 // chunks.  Both visit chunks in increasing index and, per chunk, the frames whose exact forward map is g.
 #include <algorithm>
 #include <climits>
-#include <cmath>
-#include <cstring>
-#include <string>
-#include <vector>
 
 #include "block_scan.h"
-#include "fa_common.h"
+#include "reconstruct_launch.h"
 
 namespace {
 
+using namespace fa::reconstruct;
 using fa::grid_for;
 using fa::scan::block_exclusive;
 constexpr int kThreads = fa::scan::kThreads;
-constexpr int kTileG = 64;        // global frames per workgroup of the frame kernel (16 per wavefront)
-constexpr int kListCap = 1024;    // chunks of a tile listed in LDS (irregular offsets); more: every wavefront scans all chunks
 constexpr int kScanPer = 8;       // items per thread of the run compaction
-constexpr int kSelBits = 15;      // per-frame word: [0, 15) clusters active, [15, 30) speakerCountPerFrame, bit 30 zero-vote
-constexpr int kSelMask = (1 << kSelBits) - 1;
-constexpr int kZeroVote = 1 << 30;
-
-// powerset (OfflineSegmentationProcessor.swift:15-24): [] [0] [1] [2] [0,1] [0,2] [1,2] [0,1,2] as speaker bit masks, one nibble per class
-__host__ __device__ inline unsigned powerset_mask(int cls) { return (0x76534210u >> (4 * cls)) & 0xFu; }
-
-// chunk frame -> global frame (:69-77): frameStart = offset + Double(f) * fd (two roundings), rounded half away from zero, clamped
-__host__ __device__ inline int global_frame(double offset, int f, double fd, int T) {
-    const double fs = offset + static_cast<double>(f) * fd;   // this file is built with -ffp-contract=off: no FMA
-    const double r = round(fs / fd);
-    if (!(r > 0.0)) return 0;
-    if (r >= static_cast<double>(T)) return T - 1;
-    return static_cast<int>(r);
-}
 
 // ---------------------------------------------------------------- powerset decode
 
@@ -114,23 +96,6 @@ __global__ __launch_bounds__(kThreads) void powerset_decode_rows(const float *__
 }
 
 // ---------------------------------------------------------------- per-frame accumulation and decision
-
-struct FrameArgs {
-    const float *w;          // [C][F][S] speaker weights
-    const double *start;     // [C] chunk start times
-    const int32_t *first_g;  // [C] global frame of chunk frame 0 / F-1
-    const int32_t *last_g;
-    const int32_t *hard;     // [C][S] cluster of each local speaker, -1 = none (host-mapped from anything outside [0, K))
-    const int32_t *ovr;      // [T] zero-vote override cluster or -1; nullptr: none
-    int32_t *word;           // [T] kSelBits fields (see above)
-    int32_t *sel;            // [T][smax] active clusters, by rank
-    double *avg;             // [T][smax] their activation averages
-    int32_t *bad;            // set when a weight is not finite
-    double *esum_out;        // [T] the fp64 expected-count sum of each frame, or nullptr (fa_reconstruct_info.expected_count_sums)
-    int64_t C;
-    int32_t F, S, K, T, smax, maxc, sorted;
-    double fd;
-};
 
 // first index in [0, n) with a[i] >= v (a non-decreasing)
 __device__ inline int64_t lower_bound_i32(const int32_t *a, int64_t n, int v) {
@@ -340,11 +305,6 @@ __global__ __launch_bounds__(kThreads) void run_write(const int32_t *__restrict_
     for (int i = 0; i < kScanPer; ++i) if (flags & (1 << i)) starts[pos++] = e0 + i;
 }
 
-struct RawRun {
-    int32_t g0, g1, k, frames;   // frames [g0, g1) of cluster k
-    double score;                // sequential fp64 sum of the per-frame averages (:207-213)
-};
-
 // one lane per run: walk forward while the cluster stays active
 __global__ __launch_bounds__(kThreads) void run_walk(const int64_t *__restrict__ starts, const int32_t *__restrict__ total, const int32_t *__restrict__ word,
                                                      const int32_t *__restrict__ sel, const double *__restrict__ avg, int smax, int T, RawRun *__restrict__ out) {
@@ -363,339 +323,42 @@ __global__ __launch_bounds__(kThreads) void run_walk(const int64_t *__restrict__
     }
 }
 
-// ---------------------------------------------------------------- host passes
-
-bool same_speaker(const fa_rttm_segment &a, const fa_rttm_segment &b) { return strncmp(a.speaker_id, b.speaker_id, sizeof(a.speaker_id)) == 0; }
-
-// blendedQuality (:465-479)
-float blended_quality(const fa_rttm_segment &l, const fa_rttm_segment &r) {
-    const double ld = static_cast<double>(l.end_seconds - l.start_seconds), rd = static_cast<double>(r.end_seconds - r.start_seconds);
-    const double total = ld + rd;
-    if (!(total > 0)) return std::min(std::max((l.quality + r.quality) / 2, 0.0f), 1.0f);
-    const double weighted = static_cast<double>(l.quality) * ld + static_cast<double>(r.quality) * rd;
-    return static_cast<float>(std::min(std::max(weighted / total, 0.0), 1.0));
-}
-
-void stable_by_start(std::vector<fa_rttm_segment> &v) {
-    std::stable_sort(v.begin(), v.end(), [](const fa_rttm_segment &x, const fa_rttm_segment &y) { return x.start_seconds < y.start_seconds; });
-}
-
-// mergeSegments (:431-463) -> sanitize (:481-496) -> excludeOverlaps (:359-398)
-std::vector<fa_rttm_segment> finalize(const fa_reconstruct_config &cfg, std::vector<fa_rttm_segment> raw) {
-    std::vector<fa_rttm_segment> merged;
-    if (!raw.empty()) {
-        const double gap_threshold = std::max(cfg.min_gap_duration, cfg.min_duration_off);
-        stable_by_start(raw);
-        fa_rttm_segment cur = raw[0];
-        for (size_t i = 1; i < raw.size(); ++i) {
-            const fa_rttm_segment &s = raw[i];
-            if (same_speaker(s, cur) && static_cast<double>(s.start_seconds) - static_cast<double>(cur.end_seconds) <= gap_threshold) {
-                const float q = blended_quality(cur, s);
-                cur.end_seconds = std::max(cur.end_seconds, s.end_seconds);
-                cur.quality = q;
-                continue;
-            }
-            merged.push_back(cur);
-            cur = s;
-        }
-        merged.push_back(cur);
-    }
-    stable_by_start(merged);
-    const float min_dur = std::max(static_cast<float>(cfg.min_segment_duration), static_cast<float>(cfg.min_duration_on));
-    std::vector<fa_rttm_segment> kept;
-    for (const auto &s : merged) if (s.end_seconds - s.start_seconds >= min_dur) kept.push_back(s);
-    if (!cfg.exclusive) return kept;
-    std::vector<fa_rttm_segment> out;
-    const float min_seg = static_cast<float>(cfg.min_segment_duration);
-    for (const auto &s : kept) {
-        float start = s.start_seconds;
-        const float end = s.end_seconds;
-        if (!out.empty() && start < out.back().end_seconds) start = out.back().end_seconds;
-        if (start >= end) continue;
-        const float dur = end - start;
-        if (dur < min_seg) continue;
-        const float orig = s.end_seconds - s.start_seconds;
-        const float scale = orig > 0 ? dur / orig : 1.0f;
-        fa_rttm_segment t = s;
-        t.start_seconds = start;
-        t.quality = std::max(0.0f, std::min(1.0f, s.quality * scale));
-        out.push_back(t);
-    }
-    return out;
-}
-
-fa_status write_segments(fa_ctx *ctx, const std::vector<fa_rttm_segment> &segs, fa_rttm_segment *out, int64_t capacity, int64_t *count) {
-    *count = static_cast<int64_t>(segs.size());
-    if (!out) return FA_SUCCESS;
-    if (capacity < *count) return fa::set_error(ctx, FA_OUTPUT_TOO_SMALL, "reconstruct: output holds %lld of %lld segments", (long long)capacity, (long long)*count);
-    std::copy(segs.begin(), segs.end(), out);
-    return FA_SUCCESS;
-}
-
-void set_info(fa_reconstruct_info *info, int64_t T, int64_t raw, double fd) {
-    if (!info) return;
-    info->total_frames = T;
-    info->raw_segments = raw;
-    info->frame_duration = fd;
-    info->zero_vote_run_count = 0;
-    info->frame_slots = 0;
-}
-
-fa_status reconstruct(fa_ctx *ctx, const fa_reconstruct_config *cfg, const float *weights, int64_t C, int32_t F, int32_t S, const double *offsets,
-                      int64_t n_offsets, const int32_t *hard, int32_t K, const int64_t *overrides, int64_t n_overrides, fa_rttm_segment *out,
-                      int64_t capacity, int64_t *count, fa_reconstruct_info *info, bool device_weights) {
-    if (!ctx || !cfg || !count) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "reconstruct: ctx, config and count are required");
-    *count = 0;
-    set_info(info, 0, 0, 0.0);
-    if (C < 0 || F < 0 || S < 0 || K < 0 || n_offsets < 0 || n_overrides < 0 || capacity < 0 || (C > 0 && F > 0 && S > 0 && !weights) ||
-        (n_offsets > 0 && !offsets) || (n_overrides > 0 && !overrides) || S > kSelMask)
-        return fa::set_error(ctx, FA_INVALID_ARGUMENT, "reconstruct: bad arguments");
-    if (C == 0 || F == 0) return FA_SUCCESS;                                   // :30
-    const double fd = cfg->frame_duration > 0 ? cfg->frame_duration : cfg->window_duration / F;   // OfflineSegmentationProcessor.swift:286
-    if (!std::isfinite(fd)) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "reconstruct: frame duration is not finite");
-    if (!(fd > 0)) return FA_SUCCESS;                                          // :33
-    if (C > INT32_MAX) return fa::set_error(ctx, FA_INDEX_OVERFLOW, "reconstruct: more than 2^31 chunks");
-    return fa::no_throw(ctx, "reconstruct", [&]() -> fa_status {
-    // chunk starts (:498-507) and the global frame count (:37-47)
-    std::vector<double> start(static_cast<size_t>(C));
-    double max_time = 0.0;
-    bool sorted = true;
-    for (int64_t c = 0; c < C; ++c) {
-        start[c] = c < n_offsets ? offsets[c] : static_cast<double>(c) * cfg->window_duration;
-        if (!std::isfinite(start[c])) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "reconstruct: chunk %lld starts at a non-finite time", (long long)c);
-        if (c > 0 && start[c] < start[c - 1]) sorted = false;
-        const double end = start[c] + static_cast<double>(F) * fd;
-        if (end > max_time) max_time = end;
-    }
-    const double tf = std::ceil(max_time / fd);
-    const int32_t Kc = std::max(K, 1);
-    const int32_t maxc = std::min(Kc, S), smax = std::max(maxc, 1);
-    if (!(tf < static_cast<double>(INT32_MAX) / smax)) return fa::set_error(ctx, FA_INDEX_OVERFLOW, "reconstruct: %.0f global frames", tf);
-    const int32_t T = std::max(1, static_cast<int32_t>(tf));
-    set_info(info, T, 0, fd);
-    if (info) info->frame_slots = smax;
-    std::vector<int32_t> first_g(static_cast<size_t>(C)), last_g(static_cast<size_t>(C));
-    for (int64_t c = 0; c < C; ++c) { first_g[c] = global_frame(start[c], 0, fd, T); last_g[c] = global_frame(start[c], F - 1, fd, T); }
-    std::vector<int32_t> hard_m(static_cast<size_t>(C * S), -1);
-    if (hard) for (int64_t i = 0; i < C * S; ++i) hard_m[i] = hard[i] >= 0 && hard[i] < Kc ? hard[i] : -1;   // :81-83
-    std::vector<int32_t> ovr;
-    if (n_overrides > 0) {   // :284-286, applied in order
-        ovr.assign(static_cast<size_t>(T), -1);
-        for (int64_t i = 0; i < n_overrides; ++i) {
-            const int64_t lo = overrides[3 * i], hi = overrides[3 * i + 1], k = overrides[3 * i + 2];
-            if (lo < 0 || hi < lo || hi > T || k < 0 || k >= Kc) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "reconstruct: override %lld is out of range", (long long)i);
-            for (int64_t g = lo; g < hi; ++g) ovr[g] = static_cast<int32_t>(k);
-        }
-    }
-
-    fa::DeviceGuard guard(ctx->device);
-    hipStream_t st = ctx->stream;
-    const int64_t items = static_cast<int64_t>(T) * smax;
-    const int64_t nb = (items + kThreads * kScanPer - 1) / (kThreads * kScanPer);
-    const bool want_frames = info && info->frame_capacity >= T && (info->frame_clusters || info->frame_averages || info->expected_count_sums);
-    fa::DevBuf b_w, b_start, b_first, b_last, b_hard, b_ovr, b_word, b_sel, b_avg, b_bsum, b_flags, b_starts, b_esum;
-    auto alloc = [&](fa::DevBuf &b, size_t bytes) { return b.alloc(ctx, bytes) == hipSuccess; };
-    if ((!device_weights && !alloc(b_w, sizeof(float) * C * F * S)) || !alloc(b_start, sizeof(double) * C) || !alloc(b_first, sizeof(int32_t) * C) ||
-        !alloc(b_last, sizeof(int32_t) * C) || !alloc(b_hard, sizeof(int32_t) * C * S) || (!ovr.empty() && !alloc(b_ovr, sizeof(int32_t) * T)) ||
-        !alloc(b_word, sizeof(int32_t) * T) || !alloc(b_sel, sizeof(int32_t) * items) || !alloc(b_avg, sizeof(double) * items) ||
-        !alloc(b_bsum, sizeof(int32_t) * nb) || !alloc(b_flags, sizeof(int32_t) * 2) || !alloc(b_starts, sizeof(int64_t) * items) ||
-        (want_frames && info->expected_count_sums && !alloc(b_esum, sizeof(double) * T))) {
-        (void)hipGetLastError();
-        return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "reconstruct: device allocation failed");
-    }
-    const float *d_w = weights;
-    if (!device_weights) {
-        FA_HIP_TRY(ctx, hipMemcpyAsync(b_w.p, weights, sizeof(float) * C * F * S, hipMemcpyHostToDevice, st));
-        d_w = b_w.as<float>();
-    }
-    FA_HIP_TRY(ctx, hipMemcpyAsync(b_start.p, start.data(), sizeof(double) * C, hipMemcpyHostToDevice, st));
-    FA_HIP_TRY(ctx, hipMemcpyAsync(b_first.p, first_g.data(), sizeof(int32_t) * C, hipMemcpyHostToDevice, st));
-    FA_HIP_TRY(ctx, hipMemcpyAsync(b_last.p, last_g.data(), sizeof(int32_t) * C, hipMemcpyHostToDevice, st));
-    if (C * S > 0) FA_HIP_TRY(ctx, hipMemcpyAsync(b_hard.p, hard_m.data(), sizeof(int32_t) * C * S, hipMemcpyHostToDevice, st));
-    if (!ovr.empty()) FA_HIP_TRY(ctx, hipMemcpyAsync(b_ovr.p, ovr.data(), sizeof(int32_t) * T, hipMemcpyHostToDevice, st));
-    FA_HIP_TRY(ctx, hipMemsetAsync(b_flags.p, 0, sizeof(int32_t) * 2, st));
-
-    FrameArgs fa_args{d_w, b_start.as<double>(), b_first.as<int32_t>(), b_last.as<int32_t>(), b_hard.as<int32_t>(), ovr.empty() ? nullptr : b_ovr.as<int32_t>(),
-                      b_word.as<int32_t>(), b_sel.as<int32_t>(), b_avg.as<double>(), b_flags.as<int32_t>(),
-                      b_esum.p ? b_esum.as<double>() : nullptr, C, F, S, Kc, T, smax, maxc, sorted ? 1 : 0, fd};
-    const unsigned fgrid = grid_for(T, kTileG);
-    if (Kc <= 64) hipLaunchKernelGGL(recon_frames<1>, dim3(fgrid), dim3(kThreads), 0, st, fa_args);
-    else hipLaunchKernelGGL(recon_frames<4>, dim3(fgrid), dim3(kThreads), 0, st, fa_args);
-    hipLaunchKernelGGL(run_count, dim3(static_cast<unsigned>(nb)), dim3(kThreads), 0, st, b_word.as<int32_t>(), b_sel.as<int32_t>(), smax, items, b_bsum.as<int32_t>());
-    hipLaunchKernelGGL(fa::scan::scan_totals<>, dim3(1), dim3(kThreads), 0, st, b_bsum.as<int32_t>(), nb, b_flags.as<int32_t>() + 1);
-    hipLaunchKernelGGL(run_write, dim3(static_cast<unsigned>(nb)), dim3(kThreads), 0, st, b_word.as<int32_t>(), b_sel.as<int32_t>(), smax, items,
-                       b_bsum.as<int32_t>(), b_starts.as<int64_t>());
-    FA_HIP_TRY(ctx, hipGetLastError());
-    int32_t flags[2];
-    FA_HIP_TRY(ctx, hipMemcpyAsync(flags, b_flags.p, sizeof(flags), hipMemcpyDeviceToHost, st));
-    FA_HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (flags[0]) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "reconstruct: a speaker weight is not finite (the reference traps in Int(NaN))");
-    const int64_t n_raw = flags[1];
-    std::vector<RawRun> runs(static_cast<size_t>(n_raw));
-    if (n_raw > 0) {
-        fa::DevBuf b_raw;
-        if (!alloc(b_raw, sizeof(RawRun) * n_raw)) { (void)hipGetLastError(); return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "reconstruct: device allocation failed"); }
-        hipLaunchKernelGGL(run_walk, dim3(std::min<unsigned>(grid_for(n_raw, kThreads), 4096)), dim3(kThreads), 0, st, b_starts.as<int64_t>(), b_flags.as<int32_t>() + 1,
-                           b_word.as<int32_t>(), b_sel.as<int32_t>(), b_avg.as<double>(), smax, T, b_raw.as<RawRun>());
-        FA_HIP_TRY(ctx, hipGetLastError());
-        FA_HIP_TRY(ctx, hipMemcpyAsync(runs.data(), b_raw.p, sizeof(RawRun) * n_raw, hipMemcpyDeviceToHost, st));
-    }
-    const bool want_counts = info && info->speaker_counts && info->speaker_counts_capacity >= T;
-    const bool want_runs = info && info->zero_vote_runs;
-    std::vector<int32_t> words, sel;
-    std::vector<double> avg;
-    if (want_counts || want_runs || want_frames) {
-        words.resize(static_cast<size_t>(T));
-        FA_HIP_TRY(ctx, hipMemcpyAsync(words.data(), b_word.p, sizeof(int32_t) * T, hipMemcpyDeviceToHost, st));
-    }
-    if (want_frames) {
-        if (info->frame_clusters) { sel.resize(static_cast<size_t>(items)); FA_HIP_TRY(ctx, hipMemcpyAsync(sel.data(), b_sel.p, sizeof(int32_t) * items, hipMemcpyDeviceToHost, st)); }
-        if (info->frame_averages) { avg.resize(static_cast<size_t>(items)); FA_HIP_TRY(ctx, hipMemcpyAsync(avg.data(), b_avg.p, sizeof(double) * items, hipMemcpyDeviceToHost, st)); }
-        if (info->expected_count_sums) FA_HIP_TRY(ctx, hipMemcpyAsync(info->expected_count_sums, b_esum.p, sizeof(double) * T, hipMemcpyDeviceToHost, st));
-    }
-    FA_HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (want_frames) {   // slots past a frame's active clusters were never written on the device: -1 / 0 here
-        for (int64_t e = 0; e < items; ++e) {
-            const bool live = e % smax < (words[e / smax] & kSelMask);
-            if (info->frame_clusters) info->frame_clusters[e] = live ? sel[e] : -1;
-            if (info->frame_averages) info->frame_averages[e] = live ? avg[e] : 0.0;
-        }
-    }
-    if (want_counts) for (int32_t g = 0; g < T; ++g) info->speaker_counts[g] = (words[g] >> kSelBits) & kSelMask;
-    if (want_runs) {   // ZeroVoteReembedder.detectRuns (:42-79)
-        int64_t n = 0;
-        auto emit = [&](int64_t lo, int64_t hi) {
-            if (!(static_cast<double>(hi - lo) * fd >= cfg->zero_vote_min_duration)) return;
-            if (n < info->zero_vote_capacity) { info->zero_vote_runs[2 * n] = lo; info->zero_vote_runs[2 * n + 1] = hi; }
-            ++n;
-        };
-        int64_t run0 = -1;
-        for (int32_t g = 0; g < T; ++g) {
-            if (words[g] & kZeroVote) { if (run0 < 0) run0 = g; }
-            else if (run0 >= 0) { emit(run0, g); run0 = -1; }
-        }
-        if (run0 >= 0) emit(run0, T);
-        info->zero_vote_run_count = n;
-    }
-    // raw order: (closing frame, cluster) — see the header comment; then the appendSegment records (:400-429)
-    std::sort(runs.begin(), runs.end(), [](const RawRun &x, const RawRun &y) { return x.g1 != y.g1 ? x.g1 < y.g1 : x.k < y.k; });
-    std::vector<fa_rttm_segment> raw;
-    raw.reserve(runs.size());
-    for (const RawRun &r : runs) {
-        const double s = static_cast<double>(r.g0) * fd;
-        const double e = r.g1 < T ? static_cast<double>(r.g1) * fd : static_cast<double>(T - 1) * fd + fd;
-        if (!(e > s)) continue;
-        fa_rttm_segment seg{};
-        seg.start_seconds = static_cast<float>(s);
-        seg.end_seconds = static_cast<float>(e);
-        seg.quality = static_cast<float>(std::min(std::max(r.score / static_cast<double>(r.frames), 0.0), 1.0));
-        snprintf(seg.speaker_id, sizeof(seg.speaker_id), "S%d", r.k + 1);
-        raw.push_back(seg);
-    }
-    if (info) info->raw_segments = static_cast<int64_t>(raw.size());
-    return write_segments(ctx, finalize(*cfg, std::move(raw)), out, capacity, count);
-    });
-}
-
-fa_status powerset_decode(fa_ctx *ctx, const float *logits, int64_t C, int32_t F, int32_t classes, float *weights, float *log_probs, bool device) {
-    if (!ctx) return FA_INVALID_ARGUMENT;
-    if (C < 0 || F < 0 || classes < 0) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "powerset decode: negative size");
-    const int64_t rows = C * F;
-    if (rows == 0) return FA_SUCCESS;
-    if ((classes > 0 && !logits) || !weights) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "powerset decode: bad arguments");
-    fa::DeviceGuard guard(ctx->device);
-    hipStream_t st = ctx->stream;
-    fa::DevBuf b_x, b_w, b_lp;
-    const float *d_x = logits;
-    float *d_w = weights, *d_lp = log_probs;
-    if (!device) {
-        if (b_x.alloc(ctx, sizeof(float) * rows * std::max(classes, 1)) != hipSuccess || b_w.alloc(ctx, sizeof(float) * rows * 3) != hipSuccess ||
-            (log_probs && b_lp.alloc(ctx, sizeof(float) * rows * std::max(classes, 1)) != hipSuccess)) {
-            (void)hipGetLastError();
-            return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "powerset decode: device allocation failed");
-        }
-        if (classes > 0) FA_HIP_TRY(ctx, hipMemcpyAsync(b_x.p, logits, sizeof(float) * rows * classes, hipMemcpyHostToDevice, st));
-        d_x = b_x.as<float>();
-        d_w = b_w.as<float>();
-        d_lp = log_probs ? b_lp.as<float>() : nullptr;
-    }
-    const auto aligned = [](const void *p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
-    int64_t row0 = 0;
-    if (classes == 7 && aligned(d_x) && aligned(d_w) && aligned(d_lp)) {
-        const int64_t groups = rows / 4;
-        if (groups > 0)
-            hipLaunchKernelGGL(powerset_decode7, dim3(grid_for(groups, kThreads)), dim3(kThreads), 0, st, reinterpret_cast<const float4 *>(d_x), groups,
-                               reinterpret_cast<float4 *>(d_w), reinterpret_cast<float4 *>(d_lp));
-        row0 = groups * 4;
-    }
-    if (row0 < rows)
-        hipLaunchKernelGGL(powerset_decode_rows, dim3(grid_for(rows - row0, kThreads)), dim3(kThreads), 0, st, d_x, row0, rows, classes, d_w, d_lp);
-    FA_HIP_TRY(ctx, hipGetLastError());
-    if (!device) {
-        FA_HIP_TRY(ctx, hipMemcpyAsync(weights, d_w, sizeof(float) * rows * 3, hipMemcpyDeviceToHost, st));
-        if (log_probs && classes > 0) FA_HIP_TRY(ctx, hipMemcpyAsync(log_probs, d_lp, sizeof(float) * rows * classes, hipMemcpyDeviceToHost, st));
-        FA_HIP_TRY(ctx, hipStreamSynchronize(st));
-    }
-    return FA_SUCCESS;
-}
-
 }  // namespace
 
-extern "C" {
+// ---------------------------------------------------------------- launchers (reconstruct_launch.h)
 
-void fa_reconstruct_default_config(fa_reconstruct_config *cfg) {
-    if (!cfg) return;
-    memset(cfg, 0, sizeof(*cfg));
-    cfg->window_duration = 10.0;          // OfflineDiarizerTypes.swift:46-55
-    cfg->frame_duration = 0.0;            // windowDuration / frames
-    cfg->min_duration_on = 0.0;
-    cfg->min_duration_off = 0.0;
-    cfg->min_segment_duration = 1.0;      // :97-103
-    cfg->min_gap_duration = 0.1;          // :204-214
-    cfg->exclusive = 1;
-    cfg->zero_vote_enabled = 0;           // :232-247
-    cfg->zero_vote_min_duration = 0.4;
-}
+namespace fa {
+namespace reconstruct {
 
-fa_status fa_powerset_decode_dev(fa_ctx *ctx, const float *d_logits, int64_t chunks, int32_t frames, int32_t classes, float *d_weights, float *d_log_probs) {
-    return powerset_decode(ctx, d_logits, chunks, frames, classes, d_weights, d_log_probs, true);
-}
-
-fa_status fa_powerset_decode(fa_ctx *ctx, const float *logits, int64_t chunks, int32_t frames, int32_t classes, float *weights, float *log_probs) {
-    return powerset_decode(ctx, logits, chunks, frames, classes, weights, log_probs, false);
-}
-
-fa_status fa_offline_chunk_assignments(int64_t n, const int32_t *chunk_indices, const int32_t *speaker_indices, const int32_t *labels, int32_t cluster_count,
-                                       int32_t chunks, int32_t speakers, int32_t *hard) {
-    if (n < 0 || chunks < 0 || speakers < 0 || (n > 0 && (!chunk_indices || !speaker_indices || !labels)) || (static_cast<int64_t>(chunks) * speakers > 0 && !hard))
-        return FA_INVALID_ARGUMENT;
-    for (int64_t i = 0; i < static_cast<int64_t>(chunks) * speakers; ++i) hard[i] = -2;   // OfflineDiarizerManager.swift:891-894
-    for (int64_t i = 0; i < n; ++i) {                                                       // :896-908, later embeddings overwrite
-        const int32_t c = chunk_indices[i], s = speaker_indices[i], k = labels[i];
-        if (c < 0 || c >= chunks || s < 0 || s >= speakers || k < 0 || k >= cluster_count) continue;
-        hard[static_cast<int64_t>(c) * speakers + s] = k;
+void launch_powerset(hipStream_t st, const float *x, int64_t rows, int32_t classes, float *w, float *lp) {
+    const auto aligned = [](const void *p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
+    int64_t row0 = 0;
+    if (classes == 7 && aligned(x) && aligned(w) && aligned(lp)) {
+        const int64_t groups = rows / 4;
+        if (groups > 0)
+            hipLaunchKernelGGL(powerset_decode7, dim3(grid_for(groups, kThreads)), dim3(kThreads), 0, st, reinterpret_cast<const float4 *>(x), groups,
+                               reinterpret_cast<float4 *>(w), reinterpret_cast<float4 *>(lp));
+        row0 = groups * 4;
     }
-    return FA_SUCCESS;
+    if (row0 < rows) hipLaunchKernelGGL(powerset_decode_rows, dim3(grid_for(rows - row0, kThreads)), dim3(kThreads), 0, st, x, row0, rows, classes, w, lp);
 }
 
-fa_status fa_offline_reconstruct_dev(fa_ctx *ctx, const fa_reconstruct_config *cfg, const float *d_weights, int64_t chunks, int32_t frames, int32_t speakers,
-                                     const double *offsets, int64_t n_offsets, const int32_t *hard, int32_t clusters, const int64_t *overrides,
-                                     int64_t n_overrides, fa_rttm_segment *out, int64_t capacity, int64_t *count, fa_reconstruct_info *info) {
-    return reconstruct(ctx, cfg, d_weights, chunks, frames, speakers, offsets, n_offsets, hard, clusters, overrides, n_overrides, out, capacity, count, info, true);
+int64_t run_blocks(int64_t items) { return (items + kThreads * kScanPer - 1) / (kThreads * kScanPer); }
+
+void launch_frames(hipStream_t st, const FrameArgs &a, int32_t *bsum, int32_t *total, int64_t *starts) {
+    const unsigned fgrid = grid_for(a.T, kTileG);
+    if (a.K <= 64) hipLaunchKernelGGL(recon_frames<1>, dim3(fgrid), dim3(kThreads), 0, st, a);
+    else hipLaunchKernelGGL(recon_frames<4>, dim3(fgrid), dim3(kThreads), 0, st, a);
+    const int64_t items = static_cast<int64_t>(a.T) * a.smax, nb = run_blocks(items);
+    hipLaunchKernelGGL(run_count, dim3(static_cast<unsigned>(nb)), dim3(kThreads), 0, st, a.word, a.sel, a.smax, items, bsum);
+    hipLaunchKernelGGL(fa::scan::scan_totals<>, dim3(1), dim3(kThreads), 0, st, bsum, nb, total);
+    hipLaunchKernelGGL(run_write, dim3(static_cast<unsigned>(nb)), dim3(kThreads), 0, st, a.word, a.sel, a.smax, items, bsum, starts);
 }
 
-fa_status fa_offline_reconstruct(fa_ctx *ctx, const fa_reconstruct_config *cfg, const float *weights, int64_t chunks, int32_t frames, int32_t speakers,
-                                 const double *offsets, int64_t n_offsets, const int32_t *hard, int32_t clusters, const int64_t *overrides,
-                                 int64_t n_overrides, fa_rttm_segment *out, int64_t capacity, int64_t *count, fa_reconstruct_info *info) {
-    return reconstruct(ctx, cfg, weights, chunks, frames, speakers, offsets, n_offsets, hard, clusters, overrides, n_overrides, out, capacity, count, info, false);
+void launch_walk(hipStream_t st, const FrameArgs &a, const int64_t *starts, const int32_t *total, int64_t n_raw, RawRun *out) {
+    hipLaunchKernelGGL(run_walk, dim3(std::min<unsigned>(grid_for(n_raw, kThreads), 4096)), dim3(kThreads), 0, st, starts, total, a.word, a.sel, a.avg, a.smax,
+                       a.T, out);
 }
 
-fa_status fa_segments_finalize(const fa_reconstruct_config *cfg, const fa_rttm_segment *raw, int64_t n, fa_rttm_segment *out, int64_t capacity, int64_t *count) {
-    if (!cfg || !count || n < 0 || capacity < 0 || (n > 0 && !raw)) return FA_INVALID_ARGUMENT;
-    *count = 0;
-    return fa::no_throw(nullptr, "segments finalize", [&]() -> fa_status {
-        return write_segments(nullptr, finalize(*cfg, std::vector<fa_rttm_segment>(raw, raw + n)), out, capacity, count);
-    });
-}
-
-}  // extern "C"
+}  // namespace reconstruct
+}  // namespace fa

@@ -1,4 +1,4 @@
-"""The embedding model's inputs on the device (csrc/embedding.hip): OfflineEmbeddingExtractor.extractEmbeddings up to the networks
+"""The embedding model's inputs on the device (csrc/embedding.hip, csrc/embedding_host.hip): OfflineEmbeddingExtractor.extractEmbeddings up to the networks
 (reference: Sources/FluidAudio/Diarizer/Offline/Extraction/OfflineEmbeddingExtractor.swift:177-711) and WeightInterpolation
 (Diarizer/Offline/Utils/WeightInterpolation.swift:19-116).
 

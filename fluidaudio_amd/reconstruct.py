@@ -1,4 +1,4 @@
-"""Speaker segments from the segmentation output and the per-chunk clusters (csrc/reconstruct.hip): the powerset decode of
+"""Speaker segments from the segmentation output and the per-chunk clusters (csrc/reconstruct.hip, csrc/reconstruct_host.hip): the powerset decode of
 OfflineSegmentationProcessor (reference: Sources/FluidAudio/Diarizer/Offline/Segmentation/OfflineSegmentationProcessor.swift:316-409)
 and OfflineReconstruction.buildSegments / buildSpeakerDatabase (Diarizer/Offline/Utils/OfflineReconstruction.swift:24-357).
 

@@ -1,7 +1,7 @@
 """numpy restatement of OfflineEmbeddingExtractor.extractEmbeddings up to the networks (OfflineEmbeddingExtractor.swift:177-711) and of
 WeightInterpolation (WeightInterpolation.swift:19-116), in the reference's order with scalar fp32 / fp64 semantics: every fp32 sum and dot
 product is sequential in frame order (np.add.accumulate, never numpy's pairwise sum), every fp32 operation rounds on its own (numpy does
-not fuse), sample indices round half away from zero.  The test oracle of csrc/embedding.hip."""
+not fuse), sample indices round half away from zero.  The test oracle of csrc/embedding.hip and csrc/embedding_geom.h."""
 import math
 from dataclasses import dataclass
 
@@ -180,6 +180,8 @@ def span_inputs(audio, spans, cfg: Config):
     spw, W, total = cfg.spw, cfg.weight_frames, a.size
     win, wts, ok = np.zeros((len(spans), spw), f32), np.zeros((len(spans), W), f32), np.zeros(len(spans), bool)
     for i, (t0, t1) in enumerate(spans):
+        if not (math.isfinite(t0) and math.isfinite(t1)):     # the library refuses the span (the reference traps in Int(...))
+            continue
         s = max(0, int(round_half_away(t0 * cfg.sample_rate)))
         e = min(total, int(round_half_away(t1 * cfg.sample_rate)))
         n = min(e - s, spw)

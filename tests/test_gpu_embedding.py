@@ -1,4 +1,4 @@
-"""The embedding model's inputs on the device (csrc/embedding.hip) equal the numpy restatement (tests/embedding_restatement.py) bit for bit:
+"""The embedding model's inputs on the device (csrc/embedding.hip, driven by csrc/embedding_host.hip) equal the numpy restatement (tests/embedding_restatement.py) bit for bit:
 records (times as fp64 bits), run_of_job, window_of_run, the run rows, the mask rows and the counters; fbank windows and span inputs equal
 numpy slicing; the chain powerset decode -> extract_embeddings -> diarize_segments gives the segments of the restatement's plan."""
 import os
@@ -328,3 +328,67 @@ def test_long_chunks_read_in_place(fa, gpu_ctx, F, S):
             w[c, a:a + F // 3 + int(rng.integers(0, F // 10)), s] = rng.uniform(0.5, 1.0)
     _, want = check(fa, gpu_ctx, w, np.arange(6) * 10.0, 16000 * 70, weight_frames=589, skip_threshold=0.5)
     assert len(want["records"]) >= 6 and want["skipped"] > 0
+
+
+@pytest.mark.parametrize("skip", [None, 0.95])
+@pytest.mark.parametrize("C", [512, 513])
+def test_compaction_block_boundary(fa, gpu_ctx, C, skip):
+    """One compaction workgroup covers 256 x 8 = 2048 (window, speaker) items: four speakers and 512 planned chunks fill one exactly, 513 spill
+    four items into a second; both compactions (valid masks -> jobs, jobs that run the model -> runs) cross the boundary."""
+    rng = np.random.default_rng(C)
+    w = (rng.random((C, 8, 4)) < 0.3).astype(f32)
+    w[rng.random(C) < 0.3] = 0                                            # silent chunks: empty masks between the jobs
+    w[-2:] = 0
+    w[-2:, :, 0] = 1                                                      # a lone speaker in the last two chunks: jobs past the boundary when C = 513
+    _, want = check(fa, gpu_ctx, w, np.arange(C) * 1.0, 16000 * (C + 20), weight_frames=5, skip_threshold=skip)
+    assert want["evaluated"] == 4 * C and len(want["windows"]) == C
+    assert 200 < len(want["records"]) < 4 * C and want["empty"] > 200 and want["records"][-1][0] == C - 1
+    if skip is not None:
+        assert 0 < want["skipped"] < len(want["records"])
+
+
+def test_plan_early_exits(fa, gpu_ctx):
+    """The status, the error text and the fa_embedding_info fields at every exit fa_embedding_plan takes before it touches the device, in the
+    order it checks: a call that is wrong in two ways reports the earlier one."""
+    import ctypes as C
+    L = fa._lib
+    f = L.lib().fa_embedding_plan
+    F, S = 4, 3
+    w = np.zeros((2, F, S), f32)
+    rec = np.zeros(8, fa.embedding.RECORD_DTYPE)
+    roj, wor, wch = (np.full(8, -7, np.int32) for _ in range(3))
+    wst = np.full(8, -7, np.int64)
+    rows = np.zeros((8, 589), f32)
+    outs = (rec.ctypes.data, roj.ctypes.data, wor.ctypes.data, wst.ctypes.data, wch.ctypes.data, rows.ctypes.data, None)
+    no_outs = (None,) * 7
+    good = fa.EmbeddingConfig().c_config()
+    bad = fa.EmbeddingConfig(sample_rate=0).c_config()
+    zero = dict.fromkeys((k for k, _ in L.EmbeddingInfo._fields_), 0)
+
+    def call(ctx, cfg, weights, nc, nf, ns, total, outputs):
+        info = L.EmbeddingInfo(*([-7] * len(L.EmbeddingInfo._fields_)))
+        st = f(ctx, C.byref(cfg) if cfg is not None else None, weights, nc, nf, ns, None, 0, total, *outputs, C.byref(info))
+        return st, info.as_dict(), (gpu_ctx.last_error() if st != L.SUCCESS else None)
+
+    untouched = dict.fromkeys(zero, -7)
+    # 1. no context: nothing is written, not even info
+    assert call(None, bad, None, -1, F, S, 1000, no_outs) == (L.INVALID_ARGUMENT, untouched, gpu_ctx.last_error())
+    # 2. a bad config, before the arguments are looked at
+    for cfg in (None, bad):
+        assert call(gpu_ctx.handle, cfg, None, -1, F, S, 1000, no_outs) == (L.INVALID_ARGUMENT, zero, "embedding plan: bad config")
+    # 3. bad arguments (a negative size; weights missing), before the outputs are looked at
+    assert call(gpu_ctx.handle, good, w.ctypes.data, -1, F, S, 1000, no_outs) == (L.INVALID_ARGUMENT, zero, "embedding plan: bad arguments")
+    assert call(gpu_ctx.handle, good, None, 2, F, S, 1000, no_outs) == (L.INVALID_ARGUMENT, zero, "embedding plan: bad arguments")
+    # 4. missing outputs, before the mask limit
+    assert call(gpu_ctx.handle, good, w.ctypes.data, 2 ** 29, F, S, 1000, no_outs) == (
+        L.INVALID_ARGUMENT, zero, "embedding plan: records, run_of_job, window_of_run and run_weights are required")
+    # 5. more than 2^30 (chunk, speaker) or (frame, speaker) pairs; no weight is read
+    assert call(gpu_ctx.handle, good, w.ctypes.data, 2 ** 29, F, S, 1000, outs) == (L.INDEX_OVERFLOW, zero, "embedding plan: more than 2^30 masks")
+    assert call(gpu_ctx.handle, good, w.ctypes.data, 2, 2 ** 29, S, 1000, outs) == (L.INDEX_OVERFLOW, zero, "embedding plan: more than 2^30 masks")
+    # 6. no chunk, or no frame: the config's geometry is reported
+    geom = dict(zero, samples_per_window=160000, batch_size=32)
+    assert call(gpu_ctx.handle, good, None, 0, 589, S, 1000, no_outs) == (L.SUCCESS, dict(geom, frame_duration=10.0 / 589, min_frames=59), None)
+    assert call(gpu_ctx.handle, good, None, 3, 0, S, 1000, no_outs) == (L.SUCCESS, dict(geom, frame_duration=0.0, min_frames=1), None)
+    # 7. no planned window (no audio): the counts of the plan are zero and no output is written
+    assert call(gpu_ctx.handle, good, w.ctypes.data, 2, F, S, 0, outs) == (L.SUCCESS, dict(geom, frame_duration=2.5, min_frames=1), None)
+    assert wst.tolist() == [-7] * 8 and wch.tolist() == [-7] * 8 and roj.tolist() == [-7] * 8

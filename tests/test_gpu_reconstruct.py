@@ -1,4 +1,4 @@
-"""Speaker segments on the device (csrc/reconstruct.hip) equal the numpy restatement (tests/reconstruct_restatement.py) bit for bit:
+"""Speaker segments on the device (csrc/reconstruct.hip, driven by csrc/reconstruct_host.hip) equal the numpy restatement (tests/reconstruct_restatement.py) bit for bit:
 every segment's start / end / quality as fp32 bits and its speaker id, the per-frame speaker counts and the segment count."""
 import ctypes as C
 import os
@@ -256,3 +256,85 @@ def test_diarize_segments_1h(fa, gpu_ctx):
     want = R.build_segments(seg.speaker_weights, hard, cen, off, 0.0, R.config())
     assert bits(out.segments) == bits(want) and len(want) > 100
     assert {k: v.tobytes() for k, v in out.speaker_database.items()} == {k: v.tobytes() for k, v in R.speaker_database(want, cen).items()}
+
+
+@pytest.mark.parametrize("F", [2048, 2049])
+def test_run_compaction_block_boundary(fa, gpu_ctx, F):
+    """One workgroup of the run-start compaction covers 256 x 8 = 2048 (frame, slot) items: one cluster (one slot per frame) and one chunk
+    of 2048 frames fill it exactly, 2049 frames spill one item into a second."""
+    rng = np.random.default_rng(F)
+    w = (rng.random((1, F, 3)) < 0.5).astype(np.float32)
+    w[0, -3:, :] = [[0, 0, 0], [1, 0, 1], [1, 0, 0]]        # a run that starts on the last item but one
+    hard = np.array([[0, -2, 0]], np.int32)
+    _, st = check(fa, gpu_ctx, w, hard, 1, [0.0], 0.0625, min_segment_duration=0.0, min_gap_duration=0.0)
+    assert st["T"] == F and len(st["raw"]) > 100
+    _, st = check(fa, gpu_ctx, w, hard, 1, [0.0], 0.0625)     # defaults: merge, 1 s minimum, exclusive
+    assert st["T"] == F
+
+
+def test_powerset_decode_of_misaligned_logits(fa, gpu_ctx):
+    """7 classes whose logits start one float past a 16-byte boundary take the row kernel and give what the aligned tensor gives; fewer
+    rows than one group of four run as the tail alone."""
+    import torch
+    rng = np.random.default_rng(77)
+    for rows in (4 * 333 + 3, 3):
+        x = (1.5 * rng.standard_normal((1, rows, 7))).astype(np.float32)
+        x[0, ::5, :] = np.round(x[0, ::5, :])
+        x[0, 1, :] = np.nan
+        ww, lp = R.powerset_decode(x)
+        aligned = torch.from_numpy(x).cuda(gpu_ctx.device)
+        store = torch.zeros(rows * 7 + 4, dtype=torch.float32, device=aligned.device)
+        shifted = store[1:1 + rows * 7].view(1, rows, 7)
+        shifted.copy_(aligned)
+        assert aligned.data_ptr() % 16 == 0 and shifted.data_ptr() % 16 == 4 and shifted.is_contiguous()
+        a = fa.powerset_decode(aligned, log_probs=True, ctx=gpu_ctx)
+        b = fa.powerset_decode(shifted, log_probs=True, ctx=gpu_ctx)
+        assert np.array_equal(a.speaker_weights.cpu().numpy(), ww) and np.array_equal(b.speaker_weights.cpu().numpy(), ww)
+        fin = np.isfinite(x).all(axis=2)
+        la, lb = a.log_probs.cpu().numpy(), b.log_probs.cpu().numpy()
+        assert np.array_equal(la[fin].view(np.uint32), lb[fin].view(np.uint32)) and np.abs(lb[fin] - lp[fin]).max() <= 1e-6
+        assert np.array_equal(fa.powerset_decode(shifted, ctx=gpu_ctx).speaker_weights.cpu().numpy(), ww)
+
+
+def test_reconstruct_early_exits(fa, gpu_ctx):
+    """The status, the error text, *count and the fa_reconstruct_info fields at every exit fa_offline_reconstruct takes before it touches
+    the device, in the order it checks: a call that is wrong in two ways reports the earlier one."""
+    L = fa._lib
+    f = L.lib().fa_offline_reconstruct
+    nc, F, S, K = 2, 4, 3, 2
+    w = np.zeros((nc, F, S), np.float32)
+    hard = np.zeros((nc, S), np.int32)
+    fields = ("total_frames", "raw_segments", "frame_duration", "zero_vote_run_count", "frame_slots")
+
+    def cfg_of(**kw):
+        return fa.ReconstructionConfig(**kw).c_config(0.0)
+
+    def call(ctx, cfg, count=True, speakers=S, overrides=()):
+        info = L.ReconstructInfo()
+        for k in fields:
+            setattr(info, k, -7)
+        cnt = C.c_int64(-7)
+        ov = np.asarray(overrides, np.int64).reshape(-1, 3)
+        st = f(ctx, C.byref(cfg) if cfg is not None else None, w.ctypes.data, nc, F, speakers, None, 0, hard.ctypes.data, K,
+               ov.ctypes.data if len(ov) else None, len(ov), None, 0, C.byref(cnt) if count else None, C.byref(info))
+        return st, cnt.value, tuple(getattr(info, k) for k in fields), (gpu_ctx.last_error() if st != L.SUCCESS else None)
+
+    good = cfg_of()
+    untouched, cleared = (-7, -7, -7.0, -7, -7), (0, 0, 0.0, 0, 0)
+    required = "reconstruct: ctx, config and count are required"
+    bad_override = [(0, 8, 1), (0, 9, 0)]                      # the second one ends past the 8 global frames
+    # 1. - 3. no context, no config, no count: nothing is written
+    assert call(None, None, count=False)[:3] == (L.INVALID_ARGUMENT, -7, untouched)
+    assert call(gpu_ctx.handle, None, speakers=2 ** 15) == (L.INVALID_ARGUMENT, -7, untouched, required)
+    assert call(gpu_ctx.handle, good, count=False, speakers=2 ** 15) == (L.INVALID_ARGUMENT, -7, untouched, required)
+    # 4. more local speakers than a frame word counts, before the frame duration is looked at
+    assert call(gpu_ctx.handle, cfg_of(window_duration=np.inf), speakers=2 ** 15) == (L.INVALID_ARGUMENT, 0, cleared, "reconstruct: bad arguments")
+    # 5. a frame duration that is not finite, before the overrides are looked at
+    assert call(gpu_ctx.handle, cfg_of(window_duration=np.inf), overrides=bad_override) == (
+        L.INVALID_ARGUMENT, 0, cleared, "reconstruct: frame duration is not finite")
+    assert call(gpu_ctx.handle, cfg_of(window_duration=np.nan))[0] == L.INVALID_ARGUMENT
+    # 6. a frame duration that is not positive: no segments, like the reference
+    assert call(gpu_ctx.handle, cfg_of(window_duration=-10.0), overrides=bad_override) == (L.SUCCESS, 0, cleared, None)
+    assert call(gpu_ctx.handle, cfg_of(window_duration=0.0)) == (L.SUCCESS, 0, cleared, None)
+    # 7. an override out of range: the frame count, the frame duration and the slots are already reported
+    assert call(gpu_ctx.handle, good, overrides=bad_override) == (L.INVALID_ARGUMENT, 0, (8, 0, 2.5, 0, 2), "reconstruct: override 1 is out of range")
