@@ -10,53 +10,32 @@
 // wins).  Row winners land in LDS; the collapse `id != blank && id != previous id` is a
 // local predicate, so it becomes a block-wide exclusive scan + scatter.  Every logit is read
 // from HBM exactly once: 4*T*V bytes per fp32 matrix.
+//
+// This unit: the kernels and one launcher per kernel family.  Host side (argument checks, staging, C ABI): ctc_host.hip; shared: ctc_launch.h.
 #include <climits>
 
 #include <hip/hip_fp16.h>
 
-#include "fa_common.h"
+#include "ctc_launch.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
+using namespace fa::ctc;
+
 constexpr int kChunk = 2048;  // frames staged in LDS per pass (8 per thread in the scan)
 constexpr int kPerThread = kChunk / kThreads;
 
-struct CtcArgs {
-    const void *logits;
-    const int32_t *valid_frames;
-    int32_t *frame_ids;
-    int32_t *token_ids;
-    int32_t *token_lens;
-    int64_t row_stride, matrix_stride;
-    int32_t frames, vocab, blank_id;
-    int32_t vector_ok;  // rows are 16-byte aligned and vocab is a multiple of the vector width
-    int32_t elem_ok;    // the matrices are aligned to their element type and a row holds two vectors or more: rows of any alignment take the head + 16-byte body + tail path
-};
-
-
-// Every logit is read once: a nontemporal 16-byte load keeps the stream out of the way of the L2 / MALL lines other kernels of the context own.
-#ifndef FA_CTC_NT
-#define FA_CTC_NT 1
-#endif
+// Every logit is read once: a nontemporal 16-byte load keeps the stream out of the way of the L2 / MALL lines other kernels of the context own
+// (A/B against default-policy loads on MI355X: profiles/r04_ctc_ab.txt).
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint4 stream_load(const uint4 *p) {
-#if FA_CTC_NT
     const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p));
     return make_uint4(v.x, v.y, v.z, v.w);
-#else
-    return *p;
-#endif
 }
 __device__ __forceinline__ float4 stream_load(const float4 *p) {
-#if FA_CTC_NT
     const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(p));
     return make_float4(v.x, v.y, v.z, v.w);
-#else
-    return *p;
-#endif
 }
 
 __device__ __forceinline__ void take(float x, int idx, float &best, int &bi) {
@@ -211,10 +190,7 @@ __device__ __forceinline__ void rows_argmax_any(const char *row0, const size_t s
     }
 }
 
-#ifndef FA_CTC_ROWS
-#define FA_CTC_ROWS 4  // A/B of 1 / 2 / 4 rows and of the load policy on MI355X: profiles/r04_ctc_ab.txt
-#endif
-constexpr int kRowsAtOnce = FA_CTC_ROWS;
+constexpr int kRowsAtOnce = 4;  // A/B of 1 / 2 / 4 / 8 rows and of the load policy on MI355X: profiles/r04_ctc_ab.txt
 
 // MODE 0: aligned rows of whole vectors; 1: rows of any alignment (head + body + tail); 2: 4-/2-byte loads (misaligned matrices, rows shorter than
 // two vectors).  Separate builds: the any-alignment path needs 117 registers, the aligned one 74 — sharing a kernel cost it two wavefronts per SIMD
@@ -241,7 +217,7 @@ __global__ __launch_bounds__(kThreads) void ctc_greedy_kernel(const CtcArgs a) {
         const int n = T - c0 < kChunk ? T - c0 : kChunk;
         // phase 1: one row per wavefront
         int r = wave;
-        if (kRowsAtOnce > 1 && MODE == 0) {
+        if (MODE == 0) {
             const size_t step_bytes = static_cast<size_t>(kWaves) * a.row_stride * esz;
             for (; r + (kRowsAtOnce - 1) * kWaves < n; r += kRowsAtOnce * kWaves) {
                 int bi[kRowsAtOnce];
@@ -255,7 +231,7 @@ __global__ __launch_bounds__(kThreads) void ctc_greedy_kernel(const CtcArgs a) {
                 }
             }
         }
-        if (kRowsAtOnce > 1 && MODE == 1) {
+        if (MODE == 1) {
             const size_t step_bytes = static_cast<size_t>(kWaves) * a.row_stride * esz;
             for (; r + (kRowsAtOnce - 1) * kWaves < n; r += kRowsAtOnce * kWaves) {
                 int bi[kRowsAtOnce];
@@ -333,17 +309,6 @@ __global__ __launch_bounds__(kThreads) void ctc_greedy_kernel(const CtcArgs a) {
 // One workgroup per utterance, one wavefront per frame; the frames of utterance u are rows utt_rows[u] .. utt_rows[u + 1] of a flat value array whose
 // row r spans values[row_offsets[r] .. row_offsets[r + 1]).  Frames of eight values or more go through the head + 16-byte body + tail scan above.
 constexpr int32_t kEmptyFrame = INT_MIN;   // LDS marker of an empty frame (a frame id is >= 0)
-
-struct CtcRowsArgs {
-    const float *values;
-    const int64_t *row_offsets;   // [total_rows + 1], non-decreasing
-    const int64_t *utt_rows;      // [batch + 1], non-decreasing; NULL: one utterance of `total_rows` rows
-    int32_t *frame_ids;           // [total_rows] or NULL: argmax per frame, -1 for an empty frame
-    int32_t *token_ids;           // [total_rows]: utterance u writes from token_ids[utt_rows[u]]
-    int32_t *token_lens;          // [batch]
-    int64_t total_rows;
-    int32_t blank_id;
-};
 
 __device__ __forceinline__ int row_argmax_seed_first(const float *row, const int64_t len, const int lane) {
     int bi;
@@ -465,16 +430,6 @@ __global__ __launch_bounds__(kThreads) void ctc_greedy_rows_kernel(const CtcRows
 // x / temperature (only when temperature != 1), max, sum of expf(x - max), (x - max) - logf(sum); then blankBias is
 // subtracted from the blank column.  One wavefront per row; the row is read ONCE from HBM and lives in registers
 // (up to 64 lanes x 32 values), so the kernel moves 2 x 4 T V bytes per matrix.
-constexpr int kLsmRegs = 32;  // values per lane held in registers: V <= 2048 single pass
-
-struct LsmArgs {
-    const void *logits;
-    float *out;
-    int64_t row_stride, matrix_stride, out_row_stride, out_matrix_stride, rows_total;
-    int32_t frames, vocab, blank_id;
-    float inv_temp_unused, temperature, blank_bias;
-};
-
 template <bool F16>
 __device__ __forceinline__ float lsm_load(const void *row, const int i) {
     return F16 ? __half2float(static_cast<const __half *>(row)[i]) : static_cast<const float *>(row)[i];
@@ -580,164 +535,37 @@ __global__ __launch_bounds__(kThreads) void ctc_log_softmax_vec4_kernel(const Ls
     }
 }
 
-fa_status check_args(fa_ctx *ctx, const void *logits, int dtype, int batch, int frames, int vocab, int64_t row_stride,
-                     int64_t matrix_stride, const int32_t *token_ids, const int32_t *token_lens) {
-    if (!ctx || !token_ids || !token_lens) return FA_INVALID_ARGUMENT;
-    if (dtype != FA_DTYPE_F32 && dtype != FA_DTYPE_F16) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "ctc: bad dtype");
-    if (batch < 0 || frames < 0 || vocab < 1 || row_stride < vocab) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "ctc: bad shape");
-    if (batch > 0 && frames > 0 && (!logits || matrix_stride < static_cast<int64_t>(frames - 1) * row_stride + vocab))
-        return fa::set_error(ctx, FA_INVALID_ARGUMENT, "ctc: bad strides");
-    return FA_SUCCESS;
-}
-
 }  // namespace
 
-extern "C" {
+namespace fa {
+namespace ctc {
 
-fa_status fa_ctc_greedy_batch_dev(fa_ctx *ctx, const void *d_logits, int32_t dtype, int32_t batch, int32_t frames,
-                                  int32_t vocab, int64_t row_stride, int64_t matrix_stride,
-                                  const int32_t *d_valid_frames, int32_t blank_id, int32_t *d_frame_ids,
-                                  int32_t *d_token_ids, int32_t *d_token_lens) {
-    FA_TRY(check_args(ctx, d_logits, dtype, batch, frames, vocab, row_stride, matrix_stride, d_token_ids, d_token_lens));
-    if (batch == 0) return FA_SUCCESS;
-    fa::DeviceGuard guard(ctx->device);
-    CtcArgs a;
-    a.logits = d_logits; a.valid_frames = d_valid_frames; a.frame_ids = d_frame_ids; a.token_ids = d_token_ids;
-    a.token_lens = d_token_lens; a.row_stride = row_stride; a.matrix_stride = matrix_stride; a.frames = frames;
-    a.vocab = vocab; a.blank_id = blank_id;
-    const int vw = dtype == FA_DTYPE_F16 ? 8 : 4;
-    a.vector_ok = (vocab % vw == 0) && (row_stride % vw == 0) && (matrix_stride % vw == 0) &&
-                  (reinterpret_cast<uintptr_t>(d_logits) % 16 == 0);
-    a.elem_ok = reinterpret_cast<uintptr_t>(d_logits) % (dtype == FA_DTYPE_F16 ? 2 : 4) == 0 && vocab >= 2 * vw;   // at least one whole 16-byte piece behind any head
-    const int launch_mode = a.vector_ok ? 0 : (a.elem_ok ? 1 : 2);
-    const bool f16 = dtype == FA_DTYPE_F16;
-#define FA_CTC_LAUNCH(F, M) hipLaunchKernelGGL((ctc_greedy_kernel<F, M>), dim3(batch), dim3(kThreads), 0, ctx->stream, a)
-    if (launch_mode == 0) { if (f16) FA_CTC_LAUNCH(true, 0); else FA_CTC_LAUNCH(false, 0); }
-    else if (launch_mode == 1) { if (f16) FA_CTC_LAUNCH(true, 1); else FA_CTC_LAUNCH(false, 1); }
-    else { if (f16) FA_CTC_LAUNCH(true, 2); else FA_CTC_LAUNCH(false, 2); }
-#undef FA_CTC_LAUNCH
-    FA_HIP_TRY(ctx, hipGetLastError());
-    return FA_SUCCESS;
-}
-
-fa_status fa_ctc_greedy_batch(fa_ctx *ctx, const void *logits, int32_t dtype, int32_t batch, int32_t frames, int32_t vocab,
-                              int64_t row_stride, int64_t matrix_stride, const int32_t *valid_frames, int32_t blank_id,
-                              int32_t *frame_ids, int32_t *token_ids, int32_t *token_lens) {
-    FA_TRY(check_args(ctx, logits, dtype, batch, frames, vocab, row_stride, matrix_stride, token_ids, token_lens));
-    if (batch == 0) return FA_SUCCESS;
-    fa::DeviceGuard guard(ctx->device);
-    const size_t esz = dtype == FA_DTYPE_F16 ? 2 : 4;
-    const size_t in_bytes = frames > 0 ? (static_cast<size_t>(batch - 1) * matrix_stride + static_cast<size_t>(frames - 1) * row_stride + vocab) * esz : 0;
-    const size_t id_bytes = sizeof(int32_t) * static_cast<size_t>(batch) * (frames > 0 ? frames : 1);
-    fa::DevBuf d_in, d_valid, d_fid, d_tok, d_len;
-    hipError_t e;
-    fa_status st = FA_SUCCESS;
-    do {
-        if ((e = d_in.alloc(in_bytes)) != hipSuccess) break;
-        if ((e = d_tok.alloc(id_bytes)) != hipSuccess) break;
-        if ((e = d_len.alloc(sizeof(int32_t) * batch)) != hipSuccess) break;
-        if (frame_ids && (e = d_fid.alloc(id_bytes)) != hipSuccess) break;
-        if (valid_frames && (e = d_valid.alloc(sizeof(int32_t) * batch)) != hipSuccess) break;
-        if (in_bytes && (e = hipMemcpyAsync(d_in.p, logits, in_bytes, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) break;
-        if (valid_frames && (e = hipMemcpyAsync(d_valid.p, valid_frames, sizeof(int32_t) * batch, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) break;
-        st = fa_ctc_greedy_batch_dev(ctx, d_in.p, dtype, batch, frames, vocab, row_stride, matrix_stride,
-                                     valid_frames ? d_valid.as<int32_t>() : nullptr, blank_id,
-                                     frame_ids ? d_fid.as<int32_t>() : nullptr, d_tok.as<int32_t>(), d_len.as<int32_t>());
-        if (st != FA_SUCCESS) break;
-        if (frames > 0 && (e = hipMemcpyAsync(token_ids, d_tok.p, id_bytes, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) break;
-        if (frames > 0 && frame_ids && (e = hipMemcpyAsync(frame_ids, d_fid.p, id_bytes, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(token_lens, d_len.p, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) break;
-        e = hipStreamSynchronize(ctx->stream);
-    } while (0);
-    if (st != FA_SUCCESS) return st;
-    return fa::hip_status(ctx, e, "fa_ctc_greedy_batch");
-}
-
-fa_status fa_ctc_greedy_rows_dev(fa_ctx *ctx, const float *d_values, const int64_t *d_row_offsets, int64_t total_rows, const int64_t *d_utt_rows,
-                                 int32_t batch, int32_t blank_id, int32_t *d_frame_ids, int32_t *d_token_ids, int32_t *d_token_lens) {
-    if (!ctx || !d_token_lens) return FA_INVALID_ARGUMENT;
-    if (batch < 0 || total_rows < 0) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "ctc rows: bad shape");
-    if (batch == 0) return FA_SUCCESS;
-    if (!d_utt_rows && batch != 1) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "ctc rows: a batch needs utt_rows");
-    if (total_rows > 0 && (!d_row_offsets || !d_token_ids)) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "ctc rows: null buffer");
-    fa::DeviceGuard guard(ctx->device);
-    CtcRowsArgs a;
-    a.values = d_values; a.row_offsets = d_row_offsets; a.utt_rows = d_utt_rows; a.frame_ids = d_frame_ids; a.token_ids = d_token_ids;
-    a.token_lens = d_token_lens; a.total_rows = total_rows; a.blank_id = blank_id;
-    hipLaunchKernelGGL(ctc_greedy_rows_kernel, dim3(batch), dim3(kThreads), 0, ctx->stream, a);
-    FA_HIP_TRY(ctx, hipGetLastError());
-    return FA_SUCCESS;
-}
-
-fa_status fa_ctc_greedy_rows(fa_ctx *ctx, const float *values, const int64_t *row_offsets, int64_t total_rows, const int64_t *utt_rows, int32_t batch,
-                             int32_t blank_id, int32_t *frame_ids, int32_t *token_ids, int32_t *token_lens) {
-    if (!ctx || !token_lens) return FA_INVALID_ARGUMENT;
-    if (batch < 0 || total_rows < 0) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "ctc rows: bad shape");
-    if (batch == 0) return FA_SUCCESS;
-    if (!utt_rows && batch != 1) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "ctc rows: a batch needs utt_rows");
-    if (total_rows > 0 && (!row_offsets || !token_ids)) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "ctc rows: null buffer");
-    // the offsets are the caller's: a decreasing pair would make the kernel read outside `values`
-    if (total_rows > 0) {
-        if (row_offsets[0] < 0) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "ctc rows: negative offset");
-        for (int64_t r = 0; r < total_rows; ++r)
-            if (row_offsets[r + 1] < row_offsets[r]) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "ctc rows: row_offsets decrease");
+void launch_greedy(hipStream_t stream, const CtcArgs &a, const bool f16, const int batch) {
+    const int mode = greedy_mode(f16, a.vocab, a.row_stride, a.matrix_stride, reinterpret_cast<uintptr_t>(a.logits));
+    const dim3 grid(batch), block(kThreads);
+    if (mode == 0) {
+        if (f16) hipLaunchKernelGGL((ctc_greedy_kernel<true, 0>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((ctc_greedy_kernel<false, 0>), grid, block, 0, stream, a);
+    } else if (mode == 1) {
+        if (f16) hipLaunchKernelGGL((ctc_greedy_kernel<true, 1>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((ctc_greedy_kernel<false, 1>), grid, block, 0, stream, a);
+    } else {
+        if (f16) hipLaunchKernelGGL((ctc_greedy_kernel<true, 2>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((ctc_greedy_kernel<false, 2>), grid, block, 0, stream, a);
     }
-    if (utt_rows) {
-        if (utt_rows[0] < 0 || utt_rows[batch] > total_rows) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "ctc rows: utt_rows out of range");
-        for (int32_t u = 0; u < batch; ++u)
-            if (utt_rows[u + 1] < utt_rows[u]) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "ctc rows: utt_rows decrease");
-    }
-    const int64_t n_values = total_rows > 0 ? row_offsets[total_rows] : 0;
-    if (n_values > 0 && !values) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "ctc rows: null values");
-    fa::DeviceGuard guard(ctx->device);
-    const size_t id_bytes = sizeof(int32_t) * static_cast<size_t>(total_rows > 0 ? total_rows : 1);
-    fa::DevBuf d_val, d_off, d_utt, d_fid, d_tok, d_len;
-    hipError_t e;
-    fa_status st = FA_SUCCESS;
-    do {
-        if ((e = d_val.alloc(sizeof(float) * static_cast<size_t>(n_values > 0 ? n_values : 1))) != hipSuccess) break;
-        if ((e = d_off.alloc(sizeof(int64_t) * static_cast<size_t>(total_rows + 1))) != hipSuccess) break;
-        if ((e = d_tok.alloc(id_bytes)) != hipSuccess) break;
-        if ((e = d_len.alloc(sizeof(int32_t) * batch)) != hipSuccess) break;
-        if (frame_ids && (e = d_fid.alloc(id_bytes)) != hipSuccess) break;
-        if (utt_rows && (e = d_utt.alloc(sizeof(int64_t) * (static_cast<size_t>(batch) + 1))) != hipSuccess) break;
-        if (n_values > 0 && (e = hipMemcpyAsync(d_val.p, values, sizeof(float) * static_cast<size_t>(n_values), hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) break;
-        if (total_rows > 0 && (e = hipMemcpyAsync(d_off.p, row_offsets, sizeof(int64_t) * static_cast<size_t>(total_rows + 1), hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) break;
-        if (utt_rows && (e = hipMemcpyAsync(d_utt.p, utt_rows, sizeof(int64_t) * (static_cast<size_t>(batch) + 1), hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) break;
-        st = fa_ctc_greedy_rows_dev(ctx, d_val.as<float>(), d_off.as<int64_t>(), total_rows, utt_rows ? d_utt.as<int64_t>() : nullptr, batch, blank_id,
-                                    frame_ids ? d_fid.as<int32_t>() : nullptr, d_tok.as<int32_t>(), d_len.as<int32_t>());
-        if (st != FA_SUCCESS) break;
-        if (total_rows > 0 && (e = hipMemcpyAsync(token_ids, d_tok.p, sizeof(int32_t) * static_cast<size_t>(total_rows), hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) break;
-        if (total_rows > 0 && frame_ids && (e = hipMemcpyAsync(frame_ids, d_fid.p, sizeof(int32_t) * static_cast<size_t>(total_rows), hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(token_lens, d_len.p, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) break;
-        e = hipStreamSynchronize(ctx->stream);
-    } while (0);
-    if (st != FA_SUCCESS) return st;
-    return fa::hip_status(ctx, e, "fa_ctc_greedy_rows");
 }
 
-fa_status fa_ctc_log_softmax_batch_dev(fa_ctx *ctx, const void *d_logits, int32_t dtype, int32_t batch, int32_t frames, int32_t vocab,
-                                       int64_t row_stride, int64_t matrix_stride, float temperature, float blank_bias, int32_t blank_id,
-                                       float *d_log_probs) {
-    if (!ctx || !d_log_probs) return FA_INVALID_ARGUMENT;
-    if (dtype != FA_DTYPE_F32 && dtype != FA_DTYPE_F16) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "log_softmax: bad dtype");
-    if (batch < 0 || frames < 0 || vocab < 1 || row_stride < vocab || !(temperature > 0.0f)) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "log_softmax: bad shape");
-    if (batch == 0 || frames == 0) return FA_SUCCESS;
-    if (!d_logits || matrix_stride < static_cast<int64_t>(frames - 1) * row_stride + vocab) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "log_softmax: bad strides");
-    fa::DeviceGuard guard(ctx->device);
-    LsmArgs a{};
-    a.logits = d_logits; a.out = d_log_probs; a.row_stride = row_stride; a.matrix_stride = matrix_stride;
-    a.out_row_stride = vocab; a.out_matrix_stride = static_cast<int64_t>(frames) * vocab;
-    a.rows_total = static_cast<int64_t>(batch) * frames; a.frames = frames; a.vocab = vocab; a.blank_id = blank_id;
-    a.temperature = temperature; a.blank_bias = blank_bias;
-    const unsigned grid = static_cast<unsigned>((a.rows_total + kWaves - 1) / kWaves);
-    const bool vec4 = dtype == FA_DTYPE_F32 && vocab % 4 == 0 && vocab <= 64 * kLsmRegs && row_stride % 4 == 0 && matrix_stride % 4 == 0 &&
-                      reinterpret_cast<uintptr_t>(d_logits) % 16 == 0 && reinterpret_cast<uintptr_t>(d_log_probs) % 16 == 0;
-    if (vec4) hipLaunchKernelGGL(ctc_log_softmax_vec4_kernel, dim3(grid), dim3(kThreads), 0, ctx->stream, a);
-    else if (dtype == FA_DTYPE_F16) hipLaunchKernelGGL(ctc_log_softmax_kernel<true>, dim3(grid), dim3(kThreads), 0, ctx->stream, a);
-    else hipLaunchKernelGGL(ctc_log_softmax_kernel<false>, dim3(grid), dim3(kThreads), 0, ctx->stream, a);
-    FA_HIP_TRY(ctx, hipGetLastError());
-    return FA_SUCCESS;
+void launch_greedy_rows(hipStream_t stream, const CtcRowsArgs &a, const int batch) {
+    hipLaunchKernelGGL(ctc_greedy_rows_kernel, dim3(batch), dim3(kThreads), 0, stream, a);
 }
 
-}  // extern "C"
+void launch_log_softmax(hipStream_t stream, const LsmArgs &a, const bool f16) {
+    const dim3 grid(fa::grid_for(a.rows_total, kWaves)), block(kThreads);
+    if (log_softmax_vec4(f16, a.vocab, a.row_stride, a.matrix_stride, reinterpret_cast<uintptr_t>(a.logits), reinterpret_cast<uintptr_t>(a.out)))
+        hipLaunchKernelGGL(ctc_log_softmax_vec4_kernel, grid, block, 0, stream, a);
+    else if (f16) hipLaunchKernelGGL(ctc_log_softmax_kernel<true>, grid, block, 0, stream, a);
+    else hipLaunchKernelGGL(ctc_log_softmax_kernel<false>, grid, block, 0, stream, a);
+}
+
+}  // namespace ctc
+}  // namespace fa

@@ -80,7 +80,7 @@ def test_walk_on_joint_logits_equals_walk_on_tables(fa, gpu_ctx, oracle_mod, dty
 @pytest.mark.parametrize("dtype", ["float32", "float16"])
 @pytest.mark.parametrize("V1", [5, 64, 130, 1025, 1087, 1088, 1089, 2500])   # fp16 rows of even stride (5, 1025, 1087 + 5 durations) take the pair requests
 def test_logits_walk_every_row_form_and_every_option(fa, gpu_ctx, oracle_mod, dtype, V1):
-    """Round 5: the walk on joint logits is a state machine with one joint evaluation per iteration (tdt_walk_wave); rows of up to 17 x 64 logits
+    """Round 5: the walk on joint logits is a state machine with one joint evaluation per iteration (tdt_walk); rows of up to 17 x 64 logits
     are decided from registers (row maximum + first index holding it, soft-max only when the token is emitted: tdt_logits_fits_kernel), longer
     rows in one streaming pass.  Every row form (1 .. 17 pieces, the 17th piece partly filled, both sides of the 1 088-logit boundary) with every
     per-chunk option of the entry — audio_frames, start frames beyond the chunk, last-chunk flush, global offsets, emit_after, a joint grid too
@@ -130,3 +130,125 @@ def test_logits_walk_every_row_form_and_every_option(fa, gpu_ctx, oracle_mod, dt
         assert 0 in statuses
         if max_out == 64:
             assert sum(g["count"] for g in got) > B // 2        # the rows do produce tokens
+
+
+# ---- the rare rules of the walk, on hand-built tables: one chunk per rule.  Random tables almost never put ten zero-duration tokens on one frame
+# or 150 tokens into a chunk, so the limits are small here: the oracle takes them as max_symbols / max_tokens / blank_limit.
+RARE_B, RARE_U, RARE_T = 10, 16, 24
+RARE_TOKENS, RARE_BLANKS = 4, 2                     # max_tokens_per_chunk, consecutive_blank_limit
+(FORCE, ZERO_AFTER_EMIT, BLANK_ZERO, CAP_LAST, CAP_NOT_LAST, FLUSH_BLANKS, FLUSH_SYMBOLS, FLUSH_EMIT_AFTER, CAP_EXACT, FORCE_LAST) = range(RARE_B)
+
+
+def rare_chunks():
+    """tok [B, U, T] with -1 for the blank, bin [B, U, T] (bin k = duration k), and the per-chunk options.  Everything not set is a blank of
+    duration 1: the walk moves one frame and stays at its u."""
+    B, U, T = RARE_B, RARE_U, RARE_T
+    tok, bn = np.full((B, U, T), -1, np.int32), np.ones((B, U, T), np.int32)
+    enc, t0, last = np.full(B, T, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
+    af, goff, ea = enc.copy(), (10 * np.arange(B)).astype(np.int32), [None] * B
+
+    def put(b, cells):
+        for u, t, k, d in cells:
+            tok[b, u, t], bn[b, u, t] = k, d
+
+    # frame 5 answers a token of duration 0 at every u: the blank-advance loop arrives there, emits (0, 5), stays; the next outer step emits
+    # (1, 5) with its duration raised to 1 (:318-323), which moves the walk to frame 6 — so no third token can share the timestamp, and only
+    # max_symbols_per_step <= 2 reaches the force-advance (:453-462), which skips frame 6: the third token is then frame 7's
+    for b in (FORCE, FORCE_LAST):
+        put(b, [(u, 5, 1 + u % 5, 0) for u in range(U)] + [(2, 6, 5, 1), (2, 7, 6, 1)])
+    last[FORCE_LAST] = 1
+    put(ZERO_AFTER_EMIT, [(0, 3, 2, 0), (1, 3, 3, 0)])       # an outer step emits at frame 3 with duration 0; the next one is at frame 3 again
+    t0[ZERO_AFTER_EMIT] = 3
+    put(BLANK_ZERO, [(0, 0, -1, 0), (0, 1, -1, 0), (0, 2, 4, 2)])   # a blank of duration 0 in the outer step (:327-329) and in the blank-advance loop (:377-379)
+    for b in (CAP_LAST, CAP_NOT_LAST, FLUSH_EMIT_AFTER):     # a fifth token at frame 4: the cap of 4 stops the walk behind it, at frame 5
+        put(b, [(u, u, 1 + u, 1) for u in range(5)])
+    last[CAP_LAST] = last[FLUSH_EMIT_AFTER] = 1
+    put(CAP_LAST, [(4, 5, 6, 0)])                            # the flush starts at frame 5 with the predictor state of four tokens
+    # flush tokens at frames 5, 9, 13 (durations 4, 4, 0 move the flush's frame pointer); emit_after cuts the walk's tokens and the first of them
+    put(FLUSH_EMIT_AFTER, [(4, 5, 6, 4), (5, RARE_T - 1, 1, 4), (6, RARE_T - 2, 2, 0)])
+    ea[FLUSH_EMIT_AFTER] = int(goff[FLUSH_EMIT_AFTER]) + 9
+    # 20 of 24 frames hold audio: the walk ends at frame 20, the flush looks at frames min(20, 23), 19, 18 — a token, then two blanks
+    af[FLUSH_BLANKS], t0[FLUSH_BLANKS], last[FLUSH_BLANKS] = 20, 17, 1
+    put(FLUSH_BLANKS, [(0, 20, 1, 0), (1, 20, 5, 1), (1, 17, 5, 1)])
+    # the walk jumps from frame 22 over the end; the flush finds a token at each of its frames 23, 23, 22
+    t0[FLUSH_SYMBOLS], last[FLUSH_SYMBOLS] = 22, 1
+    put(FLUSH_SYMBOLS, [(0, 22, -1, 2), (0, 23, 1, 3), (1, 23, 2, 0), (2, 22, 3, 1)])
+    put(CAP_EXACT, [(u, 2 * u, 1 + u, 2) for u in range(4)])   # exactly max_tokens_per_chunk tokens: the cap does not fire
+    return tok, bn, enc, af, t0, last, goff, ea
+
+
+def rare_reference(oracle_mod, symbols, blank, prob):
+    """The oracle on every chunk, after a look at ITS output: each table reaches the rule it was built for."""
+    tok, bn, enc, af, t0, last, goff, ea = rare_chunks()
+    tk = np.where(tok < 0, blank, tok).astype(np.int32)
+    ref = [oracle_mod.tdt_greedy(tk[b], bn[b], prob[b], enc[b], af[b], t0[b], bool(last[b]), goff[b], ea[b], blank_id=blank, max_symbols=symbols,
+                                 max_tokens=RARE_TOKENS, blank_limit=RARE_BLANKS, max_out=16) for b in range(RARE_B)]
+    assert all(r["status"] == 0 for r in ref)
+    ts = lambda b: (ref[b]["timestamps"] - goff[b]).tolist()   # noqa: E731
+    T = RARE_T
+    third = 7 if symbols <= 2 else 6                         # the force-advance skips frame 6
+    assert ts(FORCE) == [5, 5, third] and ref[FORCE]["tokens"].tolist() == [1, 2, third - 1] and ref[FORCE]["durations"].tolist() == [0, 1, 1]
+    assert ref[FORCE]["final_time"] == T and ref[FORCE]["joint_calls"] == 5 + 2 + (T - third)
+    assert ts(FORCE_LAST)[:3] == ts(FORCE) and ref[FORCE_LAST]["joint_calls"] == ref[FORCE]["joint_calls"] + min(symbols, RARE_BLANKS)
+    assert ts(ZERO_AFTER_EMIT) == [3, 3] and ref[ZERO_AFTER_EMIT]["durations"].tolist() == [0, 1] and ref[ZERO_AFTER_EMIT]["final_time"] == T
+    assert ts(BLANK_ZERO) == [2] and ref[BLANK_ZERO]["joint_calls"] == 3 + (T - 4)      # frames 0, 1, 2, then 4 .. 23: no frame twice
+    assert ref[CAP_NOT_LAST]["count"] == RARE_TOKENS and ts(CAP_NOT_LAST) == [0, 1, 2, 3]
+    assert ref[CAP_NOT_LAST]["final_time"] == 5 and ref[CAP_NOT_LAST]["final_u"] == 4   # stopped mid-way, behind the fifth token's frame
+    assert ts(CAP_LAST) == [0, 1, 2, 3, 5] and ref[CAP_LAST]["tokens"][4] == 6 and (ref[CAP_LAST]["final_time"], ref[CAP_LAST]["final_u"]) == (5, 5)
+    assert ref[CAP_EXACT]["count"] == RARE_TOKENS and ref[CAP_EXACT]["final_time"] == T
+    # the flush token's timestamp is min(fp, Teff - 1) + offset: frame pointer 20, 20 frames of audio
+    assert ts(FLUSH_BLANKS) == [min(20, 20 - 1)] and ref[FLUSH_BLANKS]["final_time"] == 20
+    assert ref[FLUSH_BLANKS]["joint_calls"] == 3 + min(symbols, 3)          # 3: frames 20, 19, 18 — all three variants —, ended by two blanks in a row
+    assert ts(FLUSH_SYMBOLS) == [T - 1] * symbols and ref[FLUSH_SYMBOLS]["tokens"].tolist() == [1, 2, 3][:symbols]   # ended by max_symbols_per_step: no blank
+    assert ref[FLUSH_SYMBOLS]["joint_calls"] == 1 + symbols and ref[FLUSH_SYMBOLS]["final_time"] == T
+    assert ts(FLUSH_EMIT_AFTER) == [9, 13][:symbols - 1] and ref[FLUSH_EMIT_AFTER]["final_u"] == 4 + symbols          # five tokens cut, the walk's four among them
+    return tk, bn, enc, af, t0, last, goff, ea, ref
+
+
+def rare_compare(got, ref, exact):
+    for b in range(RARE_B):
+        g, r = got[b], ref[b]
+        assert (g["status"], g["count"], g["final_u"], g["final_time"]) == (r["status"], r["count"], r["final_u"], r["final_time"]), b
+        for k in ("tokens", "timestamps", "durations"):
+            np.testing.assert_array_equal(g[k], r[k], err_msg=str(b))
+        if exact:
+            np.testing.assert_array_equal(g["confidences"], r["confidences"], err_msg=str(b))
+        else:
+            np.testing.assert_allclose(g["confidences"], r["confidences"], rtol=3e-5, atol=1e-7, err_msg=str(b))
+
+
+# max_symbols_per_step = 3 with 4 tokens per chunk and 2 blanks in a row; = 2 as well, the largest value at which the force-advance can fire at all
+@pytest.mark.parametrize("symbols", [3, 2])
+def test_rare_rules_on_tables(fa, gpu_ctx, oracle_mod, symbols):
+    import torch
+    rng = np.random.default_rng(5)
+    pr = rng.uniform(-0.2, 1.2, (RARE_B, RARE_U, RARE_T)).astype(np.float32)
+    pr[rng.random(pr.shape) < 0.05] = np.nan
+    tk, bn, enc, af, t0, last, goff, ea, ref = rare_reference(oracle_mod, symbols, 8192, pr)
+    cfg = fa.TdtConfig(max_symbols_per_step=symbols, max_tokens_per_chunk=RARE_TOKENS, consecutive_blank_limit=RARE_BLANKS)
+    got = fa.tdt_decode_tables(torch.from_numpy(tk).cuda(), torch.from_numpy(bn).cuda(), torch.from_numpy(pr).cuda(), enc, af, t0, last, goff, ea,
+                               config=cfg, max_out=16, ctx=gpu_ctx)
+    rare_compare(got, ref, exact=True)
+
+
+# rows of 13 logits: one per request (W = 1); 14 halves: the pair route; 1 105: the streaming kernel
+@pytest.mark.parametrize("V1,dtype", [(8, "float32"), (8, "float16"), (9, "float16"), (1100, "float32")])
+@pytest.mark.parametrize("symbols", [3, 2])
+def test_rare_rules_on_logits(fa, gpu_ctx, oracle_mod, symbols, V1, dtype):
+    """The same decisions as logits: a large value on the chosen token and on the chosen bin, noise below it elsewhere."""
+    import torch
+    nd, blank = 5, V1 - 1
+    tok, bn = rare_chunks()[:2]
+    tk = np.where(tok < 0, blank, tok)
+    rng = np.random.default_rng(V1)
+    lg = (0.5 * rng.standard_normal((RARE_B, RARE_U, RARE_T, V1 + nd))).astype(np.float32)
+    np.put_along_axis(lg, tk[..., None].astype(np.int64), 8.0, axis=-1)
+    np.put_along_axis(lg, (V1 + bn)[..., None].astype(np.int64), 8.0, axis=-1)
+    lg = lg.astype(dtype)
+    x = lg.astype(np.float64)
+    assert (np.argmax(x[..., :V1], -1) == tk).all() and (np.argmax(x[..., V1:], -1) == bn).all()
+    pr = (1.0 / np.exp(x[..., :V1] - 8.0).sum(-1)).astype(np.float32)
+    tk, bn, enc, af, t0, last, goff, ea, ref = rare_reference(oracle_mod, symbols, blank, pr)
+    cfg = fa.TdtConfig(blank_id=blank, max_symbols_per_step=symbols, max_tokens_per_chunk=RARE_TOKENS, consecutive_blank_limit=RARE_BLANKS)
+    got = fa.tdt_decode_logits(torch.from_numpy(lg).cuda(), V1, enc, af, t0, last, goff, ea, config=cfg, max_out=16, ctx=gpu_ctx)
+    rare_compare(got, ref, exact=False)
