@@ -214,17 +214,12 @@ struct VbxDevice {   // buffers of one VBx run; gamma [T][S], pi [S] and hard [T
     int64_t T = 0;
     int32_t D = 0, S = 0;
 };
-fa_status vbx_run_dev(fa_ctx *ctx, const double *d_X, int64_t T, int32_t D, const int32_t *d_labels, int32_t S, const double *phi_host,
-                      double Fa, double Fb, int32_t max_iter, double epsilon, double *elbos_host, int32_t *n_iters, VbxDevice &out);   // vbx.hip
-
-// VBxClustering.refine's catch block (VBxClustering.swift:136-141) on the device: gamma = one-hot labels, pi = 1/S, hard = clamped labels
-fa_status vbx_degrade_dev(fa_ctx *ctx, int64_t T, int32_t S, const int32_t *d_labels, VbxDevice &out);                             // vbx.hip
-
-fa_status centroids_dev(fa_ctx *ctx, const double *d_emb, int64_t n, int32_t d, const double *d_gamma, int32_t S, const int32_t *d_spk, int32_t K,
-                        double *d_cent, bool rows_finite = false);                                                                                             // post.hip
-fa_status scores_dev(fa_ctx *ctx, const double *d_emb, int64_t n, int32_t d, const double *d_cent, int32_t K, double *d_cn, double *d_scores);
-fa_status assign_dev(fa_ctx *ctx, const double *d_emb, int64_t n, int32_t d, const double *d_cent, int32_t K, double *d_cn, int32_t *d_out);
-fa_status constrained_assign_dev(fa_ctx *ctx, const double *d_scores, int64_t n, int32_t K, const int32_t *chunk_indices_host, int32_t *d_out);
+// VBx on device-resident inputs with VBxClustering.refine's degrade rule (VBxClustering.swift:136-141): ALLOCATION_FAILURE / INVALID_ARGUMENT reach
+// the caller; any other failure of the run becomes gamma = one-hot labels, pi = 1/S, hard = clamped labels, no iterations, SUCCESS, *degraded set
+// and "<degraded_text> (<what failed>)" as the context's text.                                                                            vbx_host.hip
+fa_status vbx_refine_dev(fa_ctx *ctx, const double *d_X, int64_t T, int32_t D, const int32_t *d_labels, int32_t S, const double *phi_host,
+                         double Fa, double Fb, int32_t max_iter, double epsilon, double *elbos_host, int32_t *n_iters, VbxDevice &out,
+                         const char *degraded_text, bool *degraded);
 
 fa_status default_pool(fa_pool **out);   // pool.hip: the device set behind the context-free drop-in symbol
 

@@ -7,15 +7,16 @@
 // (sequential in t for the centroid sums, sequential in the dimension for norms and dot products) and are therefore
 // bit-identical to the CPU restatement, not just close: one thread owns one output element and walks the reduction
 // axis; the loads of different iterations are independent, so they pipeline.
-#include <algorithm>
-#include <climits>
 #include <cmath>
-#include <cstdlib>
-#include <vector>
 
-#include "fa_common.h"
+#include "post_launch.h"
 
 namespace {
+
+using fa::kHungInf;
+using fa::post::hung_slab_bytes;
+using fa::post::kCenTile;
+using fa::post::kHungMaxN;
 
 constexpr int kThreads = 256;
 
@@ -55,7 +56,6 @@ __global__ void centroid_kernel(const double *__restrict__ emb, const double *__
 // 16 rows cost a full memory round trip).  Here a workgroup of 4 wavefronts owns (speaker, 64 dimensions): all four fetch tiles of
 // 128 rows (32 requests in flight per thread, coalesced 512-byte rows) into a double-buffered LDS tile while wavefront 0 walks
 // the previous tile in row order.  Same operations in the same order: identical bits.
-constexpr int kCenTile = 128;
 // Round 6 (second half): the kernel was 1.44 ms at the 8 h session and, with one workgroup per CU (133 KB of LDS), 11 of the 17 ms that eight recordings spend
 // behind their merge chains in one fa_offline_cluster_batch call.  The chain of one (speaker, dimension) was 9 vector instructions per row: two additions, a
 // multiplication, a compare and four selects for the reference's `weight <= 0 -> skip` (:655).  Now:
@@ -177,7 +177,8 @@ __global__ void assign_kernel(const double *__restrict__ emb, const double *__re
     out[i] = bi;
 }
 
-// centroidScores (:789-798): scores[i][k] = <normalised e_i, normalised c_k>, same arithmetic as assign_kernel
+// centroidScores (:789-798): scores[i][k] = <normalised e_i, normalised c_k>, same arithmetic as assign_kernel (the loop is a copy: as a shared
+// __device__ helper it compiled to other instructions in both kernels)
 __global__ void scores_kernel(const double *__restrict__ emb, const double *__restrict__ cn, double *__restrict__ scores, int64_t n, int d,
                               int K) {
     const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -203,9 +204,6 @@ __global__ void scores_kernel(const double *__restrict__ emb, const double *__re
 // over the chunk's rows, solved by Kuhn-Munkres with potentials on integer costs (:8-62).  One wavefront per chunk; the
 // potentials / matching / slack arrays (n + 1 <= 257 entries) live in the wavefront's LDS slice and the inner loops over
 // columns j run across the lanes.  Every comparison is on the reference's integers, so assignments are identical.
-constexpr int kHungMaxN = 256;
-constexpr long long kHungInf = 0x7fffffffffffffffLL / 4;  // Int.max / 4 (:14)
-
 struct HungLds {
     long long u[kHungMaxN + 1], v[kHungMaxN + 1], minv[kHungMaxN + 1];
     int p[kHungMaxN + 1], way[kHungMaxN + 1];
@@ -218,10 +216,6 @@ struct HungView {
     int *p, *way;
     unsigned char *used;
 };
-__host__ __device__ inline size_t hung_slab_bytes(const int n) {   // per wavefront, 16-byte aligned
-    const size_t e = static_cast<size_t>(n) + 1;
-    return (e * (3 * sizeof(long long) + 2 * sizeof(int) + 1) + 15) & ~static_cast<size_t>(15);
-}
 
 __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -320,123 +314,12 @@ __global__ __launch_bounds__(256) void hungarian_kernel(const double *__restrict
 
 }  // namespace
 
-extern "C" {
 
-fa_status fa_vbx_weighted_centroids(fa_ctx *ctx, const double *emb, int64_t n, int32_t d, const double *gamma, const double *pi,
-                                    int32_t S, double *centroids, int32_t *map, int32_t *n_centroids) {
-    if (!ctx || !n_centroids || !map || (S > 0 && !pi)) return FA_INVALID_ARGUMENT;
-    *n_centroids = 0;
-    if (n < 0 || d < 1 || S < 0) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "centroids: bad shape");
-    try {
-        std::vector<int32_t> spk;
-        for (int s = 0; s < S; ++s) {  // speakers kept: pi > 1e-7 (:630-640)
-            map[s] = -1;
-            if (pi[s] > 1e-7) { map[s] = static_cast<int32_t>(spk.size()); spk.push_back(s); }
-        }
-        const int K = static_cast<int>(spk.size());
-        *n_centroids = K;
-        if (K == 0) return FA_SUCCESS;
-        if (!centroids || (n > 0 && (!emb || !gamma))) return FA_INVALID_ARGUMENT;
-        fa::DeviceGuard guard(ctx->device);
-        fa::DevBuf d_emb, d_gamma, d_spk, d_cent;
-        hipError_t e;
-        fa_status st = FA_SUCCESS;
-        do {
-            if ((e = d_emb.alloc(sizeof(double) * n * d)) != hipSuccess) break;
-            if ((e = d_gamma.alloc(sizeof(double) * n * S)) != hipSuccess) break;
-            if ((e = d_spk.alloc(sizeof(int32_t) * K)) != hipSuccess) break;
-            if ((e = d_cent.alloc(sizeof(double) * K * d)) != hipSuccess) break;
-            if (n > 0 && (e = hipMemcpyAsync(d_emb.p, emb, sizeof(double) * n * d, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) break;
-            if (n > 0 && (e = hipMemcpyAsync(d_gamma.p, gamma, sizeof(double) * n * S, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) break;
-            if ((e = hipMemcpyAsync(d_spk.p, spk.data(), sizeof(int32_t) * K, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) break;
-            if ((st = fa::centroids_dev(ctx, d_emb.as<double>(), n, d, d_gamma.as<double>(), S, d_spk.as<int32_t>(), K, d_cent.as<double>())) != FA_SUCCESS) break;
-            if ((e = hipMemcpyAsync(centroids, d_cent.p, sizeof(double) * K * d, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) break;
-            e = hipStreamSynchronize(ctx->stream);
-        } while (0);
-        if (st != FA_SUCCESS) return st;
-        return fa::hip_status(ctx, e, "fa_vbx_weighted_centroids");
-    } catch (const std::bad_alloc &) {
-        return FA_ALLOCATION_FAILURE;
-    } catch (...) {
-        return FA_UNKNOWN_ERROR;
-    }
-}
-
-fa_status fa_assign_cosine(fa_ctx *ctx, const double *emb, int64_t n, int32_t d, const double *centroids, int32_t K, int32_t *out) {
-    if (!ctx) return FA_INVALID_ARGUMENT;
-    if (n == 0) return FA_SUCCESS;
-    if (n < 0 || d < 1 || K < 0 || !out || !emb) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "assign: bad arguments");
-    if (K == 0) { for (int64_t i = 0; i < n; ++i) out[i] = 0; return FA_SUCCESS; }  // guard (:795-797)
-    if (!centroids) return FA_INVALID_ARGUMENT;
-    fa::DeviceGuard guard(ctx->device);
-    fa::DevBuf d_emb, d_c, d_cn, d_out;
-    hipError_t e;
-    fa_status st = FA_SUCCESS;
-    do {
-        if ((e = d_emb.alloc(sizeof(double) * n * d)) != hipSuccess) break;
-        if ((e = d_c.alloc(sizeof(double) * K * d)) != hipSuccess) break;
-        if ((e = d_cn.alloc(sizeof(double) * K * d)) != hipSuccess) break;
-        if ((e = d_out.alloc(sizeof(int32_t) * n)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(d_emb.p, emb, sizeof(double) * n * d, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(d_c.p, centroids, sizeof(double) * K * d, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) break;
-        if ((st = fa::assign_dev(ctx, d_emb.as<double>(), n, d, d_c.as<double>(), K, d_cn.as<double>(), d_out.as<int32_t>())) != FA_SUCCESS) break;
-        if ((e = hipMemcpyAsync(out, d_out.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) break;
-        e = hipStreamSynchronize(ctx->stream);
-    } while (0);
-    if (st != FA_SUCCESS) return st;
-    return fa::hip_status(ctx, e, "fa_assign_cosine");
-}
-
-fa_status fa_centroid_scores(fa_ctx *ctx, const double *emb, int64_t n, int32_t d, const double *centroids, int32_t K, double *scores) {
-    if (!ctx) return FA_INVALID_ARGUMENT;
-    if (n == 0 || K == 0) return FA_SUCCESS;
-    if (n < 0 || d < 1 || K < 0 || !emb || !centroids || !scores) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "scores: bad arguments");
-    fa::DeviceGuard guard(ctx->device);
-    fa::DevBuf d_emb, d_c, d_cn, d_s;
-    hipError_t e;
-    fa_status st = FA_SUCCESS;
-    do {
-        if ((e = d_emb.alloc(sizeof(double) * n * d)) != hipSuccess) break;
-        if ((e = d_c.alloc(sizeof(double) * K * d)) != hipSuccess) break;
-        if ((e = d_cn.alloc(sizeof(double) * K * d)) != hipSuccess) break;
-        if ((e = d_s.alloc(sizeof(double) * n * K)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(d_emb.p, emb, sizeof(double) * n * d, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(d_c.p, centroids, sizeof(double) * K * d, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) break;
-        if ((st = fa::scores_dev(ctx, d_emb.as<double>(), n, d, d_c.as<double>(), K, d_cn.as<double>(), d_s.as<double>())) != FA_SUCCESS) break;
-        if ((e = hipMemcpyAsync(scores, d_s.p, sizeof(double) * n * K, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) break;
-        e = hipStreamSynchronize(ctx->stream);
-    } while (0);
-    if (st != FA_SUCCESS) return st;
-    return fa::hip_status(ctx, e, "fa_centroid_scores");
-}
-
-fa_status fa_constrained_assign(fa_ctx *ctx, const double *scores, int64_t n, int32_t K, const int32_t *chunk_indices, int32_t *out) {
-    if (!ctx) return FA_INVALID_ARGUMENT;
-    if (n == 0) return FA_SUCCESS;
-    if (n < 0 || n > INT32_MAX || K < 0 || !chunk_indices || !out || (K > 0 && !scores)) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "constrained assign: bad arguments");
-    fa::DeviceGuard guard(ctx->device);
-    fa::DevBuf d_s, d_out;
-    hipError_t e;
-    fa_status st = FA_SUCCESS;
-    do {
-        if ((e = d_s.alloc(sizeof(double) * n * (K > 0 ? K : 1))) != hipSuccess) break;
-        if ((e = d_out.alloc(sizeof(int32_t) * n)) != hipSuccess) break;
-        if (K > 0 && (e = hipMemcpyAsync(d_s.p, scores, sizeof(double) * n * K, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) break;
-        if ((st = fa::constrained_assign_dev(ctx, d_s.as<double>(), n, K, chunk_indices, d_out.as<int32_t>())) != FA_SUCCESS) break;
-        if ((e = hipMemcpyAsync(out, d_out.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) break;
-        e = hipStreamSynchronize(ctx->stream);
-    } while (0);
-    if (st != FA_SUCCESS) return st;
-    return fa::hip_status(ctx, e, "fa_constrained_assign");
-}
-
-}  // extern "C"
-
-// ---- device-level cores (fa_common.h): inputs and outputs are device pointers, work is enqueued on ctx->stream
+// ---- launchers (post_launch.h)
 fa_status fa::centroids_dev(fa_ctx *ctx, const double *d_emb, int64_t n, int32_t d, const double *d_gamma, int32_t S, const int32_t *d_spk, int32_t K,
                             double *d_cent, const bool rows_finite) {
     if (K <= 0) return FA_SUCCESS;
-    if (n >= 4 * kCenTile) {
+    if (fa::post::centroids_tiled(n)) {
         const size_t lds = sizeof(double) * (2 * kCenTile * 64 + 2 * kCenTile + 2);   // + the denominator and the two tile flags
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(centroid_tiled_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
         hipLaunchKernelGGL(centroid_tiled_kernel, dim3((d + 63) / 64, K), dim3(256), lds, ctx->stream, d_emb, d_gamma, d_spk, d_cent, n, d, S, K, rows_finite ? 1 : 0);
@@ -449,7 +332,7 @@ fa_status fa::centroids_dev(fa_ctx *ctx, const double *d_emb, int64_t n, int32_t
 fa_status fa::scores_dev(fa_ctx *ctx, const double *d_emb, int64_t n, int32_t d, const double *d_cent, int32_t K, double *d_cn, double *d_scores) {
     if (n <= 0 || K <= 0) return FA_SUCCESS;
     hipLaunchKernelGGL(normalize_rows, dim3((K + 63) / 64), dim3(64), 0, ctx->stream, d_cent, d_cn, static_cast<int64_t>(K), d);
-    hipLaunchKernelGGL(scores_kernel, dim3(static_cast<unsigned>((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, ctx->stream, d_emb, d_cn, d_scores, n, d, K);
+    hipLaunchKernelGGL(scores_kernel, dim3(fa::grid_for(n, kThreads)), dim3(kThreads), 0, ctx->stream, d_emb, d_cn, d_scores, n, d, K);
     FA_HIP_TRY(ctx, hipGetLastError());
     return FA_SUCCESS;
 }
@@ -458,49 +341,16 @@ fa_status fa::assign_dev(fa_ctx *ctx, const double *d_emb, int64_t n, int32_t d,
     if (n <= 0) return FA_SUCCESS;
     if (K <= 0) { FA_HIP_TRY(ctx, hipMemsetAsync(d_out, 0, sizeof(int32_t) * n, ctx->stream)); return FA_SUCCESS; }   // guard (:795-797)
     hipLaunchKernelGGL(normalize_rows, dim3((K + 63) / 64), dim3(64), 0, ctx->stream, d_cent, d_cn, static_cast<int64_t>(K), d);
-    hipLaunchKernelGGL(assign_kernel, dim3(static_cast<unsigned>((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, ctx->stream, d_emb, d_cn, d_out, n, d, K);
+    hipLaunchKernelGGL(assign_kernel, dim3(fa::grid_for(n, kThreads)), dim3(kThreads), 0, ctx->stream, d_emb, d_cn, d_out, n, d, K);
     FA_HIP_TRY(ctx, hipGetLastError());
     return FA_SUCCESS;
 }
 
-// chunk_indices is a HOST array (it is the caller's bookkeeping, not a device product): the grouping of rows by chunk is host
-// work, the tables go up (8 n bytes) and stay alive until the kernel has run (the call synchronises the stream before it returns).
-fa_status fa::constrained_assign_dev(fa_ctx *ctx, const double *d_scores, int64_t n, int32_t K, const int32_t *chunk_indices, int32_t *d_out) {
-    if (n <= 0) return FA_SUCCESS;
-    try {
-        // rows grouped by chunk, ascending row order inside a chunk (rowsByChunk[chunk].append(row), :27-30)
-        std::vector<int32_t> order(static_cast<size_t>(n));
-        for (int64_t i = 0; i < n; ++i) order[i] = static_cast<int32_t>(i);
-        std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return chunk_indices[a] < chunk_indices[b]; });
-        std::vector<int32_t> starts;
-        int max_rows = 0;
-        for (int64_t i = 0; i < n; ++i)
-            if (i == 0 || chunk_indices[order[i]] != chunk_indices[order[i - 1]]) starts.push_back(static_cast<int32_t>(i));
-        starts.push_back(static_cast<int32_t>(n));
-        const int n_chunks = static_cast<int>(starts.size()) - 1;
-        for (int c = 0; c < n_chunks; ++c) max_rows = std::max(max_rows, starts[c + 1] - starts[c]);
-        const int n_max = std::max(max_rows, static_cast<int>(K));
-        const bool big = n_max > kHungMaxN;   // potentials / matching in HBM slabs instead of LDS (rare: more than 256 clusters survive VBx)
-        fa::DevBuf d_start, d_rows, d_slabs;
-        if (big && d_slabs.alloc(ctx, hung_slab_bytes(n_max) * static_cast<size_t>(n_chunks)) != hipSuccess) {
-            (void)hipGetLastError();
-            return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "constrained assign: device allocation failed");
-        }
-        if (d_start.alloc(ctx, sizeof(int32_t) * starts.size()) != hipSuccess || d_rows.alloc(ctx, sizeof(int32_t) * n) != hipSuccess) {
-            (void)hipGetLastError();
-            return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "constrained assign: device allocation failed");
-        }
-        FA_HIP_TRY(ctx, hipMemcpyAsync(d_start.p, starts.data(), sizeof(int32_t) * starts.size(), hipMemcpyHostToDevice, ctx->stream));
-        FA_HIP_TRY(ctx, hipMemcpyAsync(d_rows.p, order.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, ctx->stream));
-        FA_HIP_TRY(ctx, hipMemsetAsync(d_out, 0xfe, sizeof(int32_t) * n, ctx->stream));  // placeholder, every row is written
-        if (big) hipLaunchKernelGGL(hungarian_kernel<true>, dim3((n_chunks + 3) / 4), dim3(256), 0, ctx->stream, d_scores, d_start.as<int32_t>(), d_rows.as<int32_t>(), d_out, n_chunks, K, d_slabs.as<unsigned char>(), n_max);
-        else hipLaunchKernelGGL(hungarian_kernel<false>, dim3((n_chunks + 3) / 4), dim3(256), 0, ctx->stream, d_scores, d_start.as<int32_t>(), d_rows.as<int32_t>(), d_out, n_chunks, K, static_cast<unsigned char *>(nullptr), 0);
-        FA_HIP_TRY(ctx, hipGetLastError());
-        FA_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // the tables above are released on return
-        return FA_SUCCESS;
-    } catch (const std::bad_alloc &) {
-        return FA_ALLOCATION_FAILURE;
-    } catch (...) {
-        return FA_UNKNOWN_ERROR;
-    }
+fa_status fa::hungarian_dev(fa_ctx *ctx, const double *d_scores, const int32_t *d_start, const int32_t *d_rows, int32_t *d_out, const int n_chunks, const int32_t K,
+                            unsigned char *d_slabs, const int side) {
+    const dim3 grid(fa::grid_for(n_chunks, 4));
+    if (fa::post::hung_in_slabs(side)) hipLaunchKernelGGL(hungarian_kernel<true>, grid, dim3(256), 0, ctx->stream, d_scores, d_start, d_rows, d_out, n_chunks, K, d_slabs, side);
+    else hipLaunchKernelGGL(hungarian_kernel<false>, grid, dim3(256), 0, ctx->stream, d_scores, d_start, d_rows, d_out, n_chunks, K, static_cast<unsigned char *>(nullptr), 0);
+    FA_HIP_TRY(ctx, hipGetLastError());
+    return FA_SUCCESS;
 }

@@ -1,7 +1,7 @@
 """The arithmetic of ``OfflineDiarizerManager.cluster`` (reference:
 Sources/FluidAudio/Diarizer/Offline/Core/OfflineDiarizerManager.swift:270-375) on precomputed embeddings — the "embeddings in
 -> final per-embedding cluster ids out" path of BASELINE config 5.  ``cluster_embeddings`` is ONE call into the library
-(``fa_offline_cluster``, csrc/offline.hip: inputs go up once, the intermediates stay in HBM); ``cluster_embeddings_stagewise``
+(``fa_offline_cluster``, csrc/offline_host.hip: inputs go up once, the intermediates stay in HBM); ``cluster_embeddings_stagewise``
 is the same composition made of the single-stage entries (every intermediate crosses PCIe), kept because it exposes the
 intermediate results (AHC labels, VBx posteriors) the tests compare with the CPU restatement:
 

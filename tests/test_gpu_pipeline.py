@@ -102,3 +102,47 @@ def test_batched_recordings_equal_single_calls(fa, gpu_ctx):
     for (e, r, c), got in zip(recs[:2], out2):
         one = fa.cluster_embeddings(e, r, c, phi, cfg, ctx=gpu_ctx)
         assert st2 == [0, 0] and got.assignments == one.assignments and got.info["was_adjusted"] == one.info["was_adjusted"] == 1
+
+
+def test_stage_branches_on_short_recordings(fa, gpu_ctx, oracle_mod):
+    """The steps of the stage's second half (offline_host.hip: cut, refine, enforce the speaker count, centroids from one of three sources,
+    assign, deliver) on recordings of at most 300 embeddings, in the combinations the tests above leave out."""
+    emb, rho, chunks, phi, _ = synth_session(90, 4, 7)
+    emb[[3, 100, 101]] = np.inf
+    emb[200, 5] = np.nan                                       # some rows are not finite: the training rows are gathered
+    ok = np.isfinite(emb).all(axis=1)
+    # the extras of fa_offline_cluster_ex against the plain call and the restatement
+    plain = fa.cluster_embeddings(emb, rho, chunks, phi, ctx=gpu_ctx)
+    ex = fa.cluster_embeddings(emb, rho, chunks, phi, ctx=gpu_ctx, intermediates=True)
+    ref = oracle_mod.cluster_embeddings(emb, rho, chunks, phi)
+    assert np.asarray(ex.assignments).tolist() == plain.assignments == ref["assignments"].tolist()
+    np.testing.assert_array_equal(ex.centroids, plain.centroids)
+    for key in ("training_rows", "initial_clusters", "vbx_iterations", "was_adjusted", "constrained", "vbx_degraded", "ahc_degraded"):
+        assert ex.info[key] == plain.info[key], key
+    assert plain.info["training_rows"] == int(ok.sum()) == len(emb) - 4
+    assert np.array_equal(ex.initial_clusters, ref["initial"]) and np.array_equal(ex.info["vbx_hard"], ref["hard"])
+    assert len(ex.info["elbos"]) == plain.info["vbx_iterations"] == len(ref["elbos"])
+    np.testing.assert_allclose(ex.info["elbos"], ref["elbos"], rtol=1e-9)
+    np.testing.assert_allclose(plain.centroids, ref["centroids"], rtol=0, atol=1e-9)
+    # a forced speaker count with rows left out of training: the K-Means centroids as they are, plain cosine assignment
+    cfg = fa.OfflineClusteringConfig(num_speakers=2)
+    forced = fa.cluster_embeddings(emb, rho, chunks, phi, cfg, ctx=gpu_ctx)
+    fref = oracle_mod.cluster_embeddings(emb, rho, chunks, phi, num_speakers=2)
+    assert forced.info["was_adjusted"] == int(fref["was_adjusted"]) == 1 and forced.info["constrained"] == 0
+    assert forced.assignments == fref["assignments"].tolist() and forced.centroids.shape == (2, 256)
+    # no PLDA features and rows left out of training: per-cluster means of the AHC labels of the gathered rows
+    bare = fa.cluster_embeddings(emb, np.zeros((len(emb), 0)), chunks, phi, ctx=gpu_ctx, intermediates=True)
+    e64 = emb.astype(np.float64)
+    init = oracle_mod.ahc_cluster(e64[ok], 0.6)
+    cen = np.stack([np.cumsum(e64[ok][init == k], axis=0)[-1] / (init == k).sum() for k in sorted(set(init.tolist()))])
+    assert np.array_equal(bare.initial_clusters, init) and bare.info["vbx_iterations"] == 0 and len(bare.info["elbos"]) == 0
+    np.testing.assert_array_equal(bare.centroids, cen)
+    assert np.asarray(bare.assignments).tolist() == oracle_mod.constrained_assign(oracle_mod.centroid_scores(e64, cen), chunks).tolist()
+    # unconstrained assignment behind VBx
+    free = fa.cluster_embeddings(emb, rho, chunks, phi, fa.OfflineClusteringConfig(constrained_assignment=False), ctx=gpu_ctx)
+    assert free.info["constrained"] == 0 and free.assignments == oracle_mod.cluster_embeddings(emb, rho, chunks, phi, constrained=False)["assignments"].tolist()
+    np.testing.assert_array_equal(free.centroids, plain.centroids)
+    # n = 1 without PLDA features: the row is its own cluster mean
+    solo = fa.cluster_embeddings(emb[:1], np.zeros((1, 0)), chunks[:1], phi, ctx=gpu_ctx, intermediates=True)
+    assert np.asarray(solo.assignments).tolist() == [0] and solo.info["training_rows"] == 1 and solo.initial_clusters.tolist() == [0]
+    np.testing.assert_array_equal(solo.centroids, e64[:1])

@@ -6,7 +6,8 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("n,d,S,seed", [(500, 256, 7, 0), (1, 16, 3, 1), (3000, 128, 40, 2), (257, 33, 5, 3),
-                                        (512, 100, 4, 4), (641, 64, 3, 5), (5000, 256, 12, 6), (1153, 70, 9, 7)])   # n >= 512: the tiled kernel
+                                        (512, 100, 4, 4), (641, 64, 3, 5), (5000, 256, 12, 6), (1153, 70, 9, 7),
+                                        (511, 65, 3, 8), (513, 64, 2, 9), (640, 8, 3, 10)])   # n >= 512: the tiled kernel (511: the last n below it; d = 65: a second column block of one)
 def test_centroids_and_assignment_match_oracle(fa, gpu_ctx, oracle_mod, n, d, S, seed):
     rng = np.random.default_rng(seed)
     emb = rng.standard_normal((n, d))
@@ -96,3 +97,16 @@ def test_constrained_assignment_beyond_256_clusters(fa, gpu_ctx, oracle_mod):
         want = oracle_mod.constrained_assign(scores, chunks)
         got = fa.ConstrainedClusterAssignment.assign(scores, chunks, ctx=gpu_ctx)
         np.testing.assert_array_equal(np.asarray(got), want)
+
+
+@pytest.mark.parametrize("per,K,chunks", [(256, 4, 2), (257, 4, 2), (2, 256, 5)])
+def test_constrained_assignment_at_the_lds_limit(fa, gpu_ctx, oracle_mod, per, K, chunks):
+    """The Hungarian arrays of a chunk live in LDS up to a problem side (rows of the largest chunk, or clusters) of 256 and in HBM slabs from 257 on
+    (post_geom.h: hung_in_slabs).  Same integers on both sides of the limit -> the reference's assignment."""
+    rng = np.random.default_rng(per + K)
+    n = per * chunks
+    scores = rng.standard_normal((n, K))
+    ids = np.repeat(np.arange(chunks), per)[rng.permutation(n)].astype(np.int32)      # rows of a chunk are not adjacent
+    want = oracle_mod.constrained_assign(scores, ids)
+    got = fa.ConstrainedClusterAssignment.assign(scores, ids, ctx=gpu_ctx)
+    np.testing.assert_array_equal(np.asarray(got), want)

@@ -155,3 +155,54 @@ def test_tiled_kernels_of_many_speakers_keep_the_bits(fa, gpu_ctx, oracle_mod, s
         np.testing.assert_allclose(tiled.elbos, elbos, rtol=1e-9)
         np.testing.assert_allclose(tiled.gamma, gamma, atol=1e-9)
         assert tiled.hard_clusters[0] == hard.tolist()
+
+
+def _against_oracle(out, oracle_mod, x, init, phi, K):
+    gamma, pi, hard, elbos = oracle_mod.vbx_refine(x, init, phi)
+    assert out.num_clusters == K and len(out.elbos) == len(elbos)
+    np.testing.assert_allclose(out.elbos, elbos, rtol=1e-9)
+    np.testing.assert_allclose(out.gamma, gamma, atol=1e-9)
+    np.testing.assert_allclose(out.pi, pi, atol=1e-9)
+    assert out.hard_clusters[0] == hard.tolist()
+
+
+def _every_label(T, D, K, seed):
+    x, init, phi = make_problem(T, D, K, seed)
+    init[:K] = np.arange(K)                     # every one of the K labels occurs: S = K
+    return x, init, phi
+
+
+@pytest.mark.parametrize("T,D,K,seed", [(1, 8, 1, 10), (63, 16, 3, 11), (65, 16, 3, 12)])
+def test_vbx_fewer_frames_than_slices(fa, gpu_ctx, oracle_mod, T, D, K, seed):
+    """The frame axis is cut into 64 slices of ceil(T / 64) frames (vbx_geom.h: slice_range).  T = 63: slices of one frame and an empty one;
+    T = 65: 32 slices of two frames, one of one frame, 31 empty ones; T = 1: one frame in the first slice."""
+    x, init, phi = _every_label(T, D, K, seed)
+    _against_oracle(fa.VBxClustering(phi, ctx=gpu_ctx).refine(x, init), oracle_mod, x, init, phi, K)
+
+
+@pytest.mark.parametrize("K", [47, 48])
+def test_vbx_on_both_sides_of_the_tiled_route(fa, gpu_ctx, oracle_mod, switch, K):
+    """47 speakers: the one-speaker-per-wavefront kernels; 48: the tiled products — whose bits are those of the other kernels (FA_VBX_NO_TILED)."""
+    x, init, phi = _every_label(130, 24, K, 20 + K)
+    out = fa.VBxClustering(phi, ctx=gpu_ctx).refine(x, init)
+    _against_oracle(out, oracle_mod, x, init, phi, K)
+    switch("FA_VBX_NO_TILED", "1")
+    plain = fa.VBxClustering(phi, ctx=gpu_ctx).refine(x, init)
+    switch("FA_VBX_NO_TILED", None)
+    assert out.elbos == plain.elbos and out.hard_clusters == plain.hard_clusters
+    np.testing.assert_array_equal(out.gamma, plain.gamma)
+    np.testing.assert_array_equal(out.pi, plain.pi)
+
+
+@pytest.mark.parametrize("D", [63, 64])
+def test_vbx_count_column_at_a_tile_edge(fa, gpu_ctx, oracle_mod, switch, D):
+    """The records carry sum_t gamma in column D: the last column of the first 64-column tile (D = 63) or the first of the second (D = 64)."""
+    K = 48
+    x, init, phi = _every_label(200, D, K, 30 + D)
+    out = fa.VBxClustering(phi, ctx=gpu_ctx).refine(x, init)
+    _against_oracle(out, oracle_mod, x, init, phi, K)
+    switch("FA_VBX_NO_TILED", "1")
+    plain = fa.VBxClustering(phi, ctx=gpu_ctx).refine(x, init)
+    switch("FA_VBX_NO_TILED", None)
+    assert out.elbos == plain.elbos
+    np.testing.assert_array_equal(out.gamma, plain.gamma)
