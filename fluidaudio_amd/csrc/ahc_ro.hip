@@ -1,5 +1,5 @@
 // ahc_ro.hip — the reference's selection order, matrix-free (ahc_ws.h: the map; ahc_reforder.h: the selection).
-#include "ahc_ws.h"
+#include "ahc_launch.h"
 
 using namespace fa_ahc;
 
@@ -289,13 +289,7 @@ fa_status ro_run_device_mf(fa_ctx *ctx, const double *d_data, size_t N, size_t d
     FA_HIP_TRY(ctx, hipMemcpyAsync(d_Z, w.Z, sizeof(double) * 4 * (N - 1), z_on_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
     FA_HIP_TRY(ctx, hipEventRecord(ev[2], st));
     FA_HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (stats) {
-        float t01 = 0, t12 = 0;
-        (void)hipEventElapsedTime(&t01, ev[0], ev[1]);
-        (void)hipEventElapsedTime(&t12, ev[1], ev[2]);
-        stats->merges = hd.merges; stats->rounds += hd.scans; if (!stats->reference_order) stats->reference_order = 1;
-        stats->init_ms += t01; stats->merge_ms += t12; stats->total_ms += t01 + t12;
-    }
+    if (stats) stats_add(*stats, hd.merges, hd.scans, 0, 0, intervals_of(ev));
     return FA_SUCCESS;
 }
 

@@ -1,5 +1,5 @@
 // ahc_rom.hip — the reference's selection order with the Lance-Williams matrix as the filter of its scans (ahc_ws.h: the map).
-#include "ahc_ws.h"
+#include "ahc_launch.h"
 
 using namespace fa_ahc;
 
@@ -714,12 +714,8 @@ fa_status rom_run_device(fa_ctx *ctx, const double *d_data, size_t N, size_t d, 
                 fprintf(stderr, "ahc (reference order, matrix filter): N %zu handed over to the rounds after %d rows (%lld scans), last tie at row %d; %lld rounds\n", N, hd.merges,
                         hd.scans, hd.last_tie, static_cast<long long>(p.h.rounds));
             if (stats) {
-                float t01 = 0, t12 = 0;
-                (void)hipEventElapsedTime(&t01, ev[0], ev[1]);
-                (void)hipEventElapsedTime(&t12, ev[1], ev[2]);
-                stats->merges = p.h.step; stats->rounds += hd.scans + hd.exact_scans + p.h.rounds; if (!stats->reference_order) stats->reference_order = 1;
-                stats->rescans += hd.exact_scans + p.h.rescans; stats->windows += p.h.windows; stats->handed_over_at = hd.merges;
-                stats->init_ms += t01; stats->merge_ms += t12; stats->total_ms += t01 + t12;
+                stats_add(*stats, p.h.step, hd.scans + hd.exact_scans + p.h.rounds, hd.exact_scans + p.h.rescans, p.h.windows, intervals_of(ev));
+                stats->handed_over_at = hd.merges;
             }
             return FA_SUCCESS;
         }
@@ -741,14 +737,8 @@ fa_status rom_run_device(fa_ctx *ctx, const double *d_data, size_t N, size_t d, 
 #endif
     if (fa::sw(fa::Sw::AHC_DEBUG))
         fprintf(stderr, "ahc (reference order, matrix filter): N %zu scans %lld exact re-evaluations %lld candidates %lld eps %.3e\n", N, hd.scans, hd.exact_scans, hd.cands, hd.eps);
-    if (stats) {
-        float t01 = 0, t12 = 0;
-        (void)hipEventElapsedTime(&t01, ev[0], ev[1]);
-        (void)hipEventElapsedTime(&t12, ev[1], ev[2]);
-        stats->merges = hd.merges; stats->rounds += hd.scans + hd.exact_scans; if (!stats->reference_order) stats->reference_order = 1;
-        stats->rescans += hd.exact_scans;   // rows whose candidates were too many for one wavefront: scanned again with exact sums
-        stats->init_ms += t01; stats->merge_ms += t12; stats->total_ms += t01 + t12;
-    }
+    // re-scans: rows whose candidates were too many for one wavefront, scanned again with exact sums
+    if (stats) stats_add(*stats, hd.merges, hd.scans + hd.exact_scans, hd.exact_scans, 0, intervals_of(ev));
     return FA_SUCCESS;
 }
 

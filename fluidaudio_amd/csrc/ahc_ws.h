@@ -1,13 +1,17 @@
 // ahc_ws.h — what the translation units of the linkage share: constants, the device state and block records, the workspace descriptor (Ws) and
 // its layout in the context's cached allocation (Layout / make_layout: THE one place that says where an array lives), wave helpers (DPP),
-// the host-side record of a problem (Prob), the graph of round launches, and the functions one unit offers the others.
-//   ahc_startup.hip   start-up kernels: transpose, Gram-form matrix on the fp64 matrix cores (+ per-tile row minima), exact pairwise matrix, eps
-//   ahc_round_body.h  the round (block records, decision, merge / re-scan / window phases) as a template over the launch forms
-//   ahc_rounds.hip    one problem: entry kernels, set-up / replay / finish, fa::ahc_run_device
-//   ahc_batch.hip     several problems per launch: uniform-layout batches, argument-table batches, groups side by side, fa::ahc_run_device_batch
-//   ahc_ro.hip        the reference's selection order, matrix-free (O(N d) memory)
-//   ahc_rom.hip       the reference's selection order with the matrix as the filter of its scans
-//   ahc_api.hip       normalisation, the C entries, the dendrogram cut, the shardable nearest-neighbour table
+// the host-side record of a problem (Prob), and the functions one unit offers the others.
+//   ahc_route.h          the host's decisions as plain C++: slots per thread, round forms, budgets, the uniform kernel, the dispatcher's route
+//   ahc_launch.h         what kernel units and host units share: launchers, their operands, the graph of round launches, the drive loop, the stats fill
+//   ahc_startup.hip      start-up kernels: transpose, Gram-form matrix on the fp64 matrix cores (+ per-tile row minima), exact pairwise matrix, eps
+//   ahc_round_body.h     the round (block records, decision, merge / re-scan / window phases) as a template over the launch forms
+//   ahc_rounds.hip       kernels of one problem: the round's single-problem builds, records, heights, adoption; their launchers
+//   ahc_rounds_host.hip  one problem on the host: set-up / replay / finish, the cached graph, fa::ahc_run_device
+//   ahc_batch.hip        kernels of several problems per launch: uniform-layout, block-map and argument-table rounds; their launchers
+//   ahc_batch_host.hip   batches on the host: block-map and uniform forms, groups side by side, chains in flight, fa::ahc_run_device_batch
+//   ahc_ro.hip           the reference's selection order, matrix-free (O(N d) memory)
+//   ahc_rom.hip          the reference's selection order with the matrix as the filter of its scans
+//   ahc_api.hip          normalisation, the C entries, the dendrogram cut, the shardable nearest-neighbour table
 #pragma once
 #include <algorithm>
 #include <climits>
@@ -19,22 +23,14 @@
 
 #include "fa_common.h"
 #include "ahc_reforder.h"
+#include "ahc_route.h"
 
 namespace fa_ahc {
 
 #ifndef FA_AHC_SPECULATE
 #define FA_AHC_SPECULATE 1   // the operands of the presumptive merge are requested before the decision is complete (0: after it, as in round 2)
 #endif
-#ifndef FA_AHC_BLK
-#define FA_AHC_BLK 256
-#endif
-constexpr int kBlk = FA_AHC_BLK;   // rows per block record == threads per round workgroup (512 measured: see profiles/r03_ahc_variants.txt)
 constexpr int kWaves = kBlk / 64;
-constexpr int kMaxBlocks = 768;    // N <= 196 608 (N^2 * 8 B = 288 GB is reached at N ~ 190 000)
-#ifndef FA_AHC_ROUNDS_PER_GRAPH
-#define FA_AHC_ROUNDS_PER_GRAPH 512
-#endif
-constexpr int kRoundsPerGraph = FA_AHC_ROUNDS_PER_GRAPH;  // multiple of 4 (counter rotation) and of 2 (parity)
 constexpr int kMaxCand = 64;       // candidate rows inside an ambiguity window
 constexpr int kMaxPairs = 1024;    // matrix entries inside an ambiguity window
 constexpr int kDead = INT_MAX;     // node id of an empty slot
@@ -309,39 +305,6 @@ struct Prob {   // one linkage problem: its workspace, its copy of the device st
     bool needs_ro = false;   // an exact tie at the minimum (or a window overflowing with near-ties): to be recomputed in reference order
 };
 
-// rounds per replay for a problem of n points: one replay should finish a small problem (one round per merge + a few re-scans /
-// window rounds) without hundreds of idle rounds behind it — at n = 50 the fixed 512-round graph cost 2.7 ms per call, five times the
-// reference on a host core; large problems use the full length.  Multiple of 4 (counter rotation and parity).
-inline int rounds_for(size_t n) {
-    const size_t want = n + n / 8 + 8;
-    const size_t r = want < static_cast<size_t>(kRoundsPerGraph) ? want : static_cast<size_t>(kRoundsPerGraph);
-    return static_cast<int>((r + 3) & ~static_cast<size_t>(3));
-}
-
-struct RoundGraph {   // `rounds` rounds captured once, replayed until every problem reports done
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    bool ok = false;
-    int rounds = kRoundsPerGraph;
-    ~RoundGraph() { if (exec) (void)hipGraphExecDestroy(exec); if (graph) (void)hipGraphDestroy(graph); }
-    template <class Launch> void capture(fa_ctx *ctx, Launch &&launch, const int n_rounds) {
-        ok = true;
-        rounds = n_rounds;
-        if (hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            for (int i = 0; i < rounds; ++i) launch(i & 3);
-            if (hipStreamEndCapture(ctx->stream, &graph) != hipSuccess || !graph) ok = false;
-            else if (hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) ok = false;
-        } else ok = false;
-        (void)hipGetLastError();
-    }
-    template <class Launch> fa_status replay(fa_ctx *ctx, Launch &&launch) {
-        if (ok) FA_HIP_TRY(ctx, hipGraphLaunch(exec, ctx->stream));
-        else for (int i = 0; i < rounds; ++i) launch(i & 3);
-        return FA_SUCCESS;
-    }
-};
-
-
 // ---- the reference-order runs: device records shared by ahc_ro.hip and ahc_rom.hip
 struct RoPart { double v; int32_t node, pad; };
 struct RoDev {                       // scalars of fa_ro::Sel between launches + flags
@@ -362,7 +325,7 @@ struct RoWs {
 void startup_filter(hipStream_t st, const Ws &w, const Layout &L, char *base, int dev_mode, const double *d_data, size_t N, size_t Np, size_t d);   // state, rows, transpose, matrix, row minima, eps
 void startup_transpose(hipStream_t st, const double *d_data, double *XT, int N, int Np, int d);
 fa_status startup_gram(fa_ctx *ctx, hipStream_t st, const Ws &gw, double *d_norms);   // norms + Gram-form matrix of gw (no row minima): the matrix-filtered reference-order run
-// ahc_rounds.hip
+// ahc_rounds_host.hip
 void window_counter_init(WinCounters (&c)[4]);
 fa_status prob_check_shape(fa_ctx *ctx, size_t N, size_t d);
 void prob_bind(Prob &p, char *base);                      // p.w = the arrays of p.L at `base` (no device work)
@@ -376,15 +339,6 @@ fa_status prob_run_rounds(fa_ctx *ctx, Prob &p);
 fa_status prob_adopt(fa_ctx *ctx, Prob &p, int merges, double eps, const double *pair_a, const double *pair_b);
 fa_status prob_after_replay(fa_ctx *ctx, Prob &p);
 fa_status prob_finish(fa_ctx *ctx, Prob &p);
-struct CachedGraph {   // the round launches of one problem shape, kept in the context between calls
-    RoundGraph rg;
-    const void *base = nullptr;
-    size_t N = 0, d = 0;
-    int cpt = 1;
-    bool spec = false;            // the speculative round (FA_AHC_SPEC)
-    int grid_y = 0, kernel = 0;   // uniform batches: problems in the grid and which build of the round serves them
-};
-void cached_graph_free(void *p);
 fa_status ctx_events(fa_ctx *ctx, hipEvent_t (&ev)[3]);   // the three timing events a context keeps
 // ahc_ro.hip / ahc_rom.hip
 fa_status ro_run_device_mf(fa_ctx *ctx, const double *d_data, size_t N, size_t d, double *d_Z, fa_ahc_stats *stats, bool z_on_host = false);
@@ -396,9 +350,10 @@ fa_status ro_run_device(fa_ctx *ctx, const double *d_data, size_t N, size_t d, d
 size_t rom_total_bytes(size_t N, size_t Np, size_t d);   // workspace of the matrix-filtered reference-order run
 void ro_launch_init(hipStream_t st, const RoWs &w, size_t threads);
 void ro_launch_finish(hipStream_t st, const RoWs &w);
-// ahc_batch.hip
+// ahc_batch_host.hip: ahc_route.h's answers under the process's switches
 bool uniform_eligible(int count, const size_t *n, int mode);
 int uniform_groups(int count, const size_t *n);                  // uniform batches side by side a dispatch of `count` problems uses
 size_t uniform_stride(int count, size_t Nmax, size_t d);         // bytes per problem slot of a uniform batch
+// kernel launchers, the graph of round launches, the drive loop and the stats fill: ahc_launch.h
 
 }  // namespace fa_ahc

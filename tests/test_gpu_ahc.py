@@ -518,3 +518,54 @@ def test_register_path_boundary_equals_the_reference_build(fa, gpu_ctx, oracle_m
     bad = np.nonzero((z != zr).any(axis=1))[0]
     assert bad.size == 0, f"first differing row {bad[0]} of {n - 1}: device {z[bad[0]]} reference {zr[bad[0]]} ({stats})"
     assert stats["merges"] == n - 1 and stats["reference_order"] == 0
+
+
+def test_centroid_buffer_above_48_kb(fa, gpu_ctx, oracle_mod):
+    """d = 6 400: the round's centroid buffer in LDS is 51 200 B, above the 48 KB a kernel may use without its dynamic limit being raised — and the limit is
+    raised for the kernel that was chosen only.  One problem through the single-launch form (300 points: two slots per thread) and through the multi-block
+    round (600), a batch through the uniform kernel ([600, 500]) and one through the argument kernel ([600, 200]: padded sizes more than a factor of two
+    apart): every dendrogram is the reference build's, row for row (every height of these inputs is distinct)."""
+    rng = np.random.default_rng(5)
+    x = {n: oracle_mod.ahc_normalize(rng.standard_normal((n, 6400))) for n in (300, 600, 500, 200)}
+    ref = {}
+    for n, v in x.items():
+        sr, ref[n] = oracle_mod.linkage_ref(v)
+        assert sr == 0
+    for n in (300, 600):
+        st, z = fa.linkage(x[n], ctx=gpu_ctx)
+        assert st == 0, gpu_ctx.last_error()
+        np.testing.assert_array_equal(z, ref[n])
+    for sizes in ([600, 500], [600, 200]):
+        st, zs = fa.linkage_batch([x[n] for n in sizes], ctx=gpu_ctx)
+        assert list(st) == [0, 0], (sizes, gpu_ctx.last_error())
+        for n, z in zip(sizes, zs):
+            np.testing.assert_array_equal(z, ref[n])
+
+
+def test_uniform_batch_placement_order_and_shrinking_grid(fa, gpu_ctx, oracle_mod):
+    """A uniform batch of [720, 1400, 720, 720] points (padded 768 and 1 536): placed largest first, so the placement order differs from the caller's; the
+    short problems finish in the second replay of 512 rounds and the long one needs a third, so the grid is captured again at one problem.  Per caller
+    index: the reference build's dendrogram, status 0, the problem's own merge count, and the batch's times.  Then the long problem with every row twice:
+    only that index is recomputed in reference order, as the single call computes it."""
+    sizes = [720, 1400, 720, 720]
+    probs = [speaker_mixture(n, 32, 5 + k, 0.05, 90 + k) for k, n in enumerate(sizes)]
+    st, zs, stats = fa.linkage_batch(probs, ctx=gpu_ctx, return_stats=True)
+    assert list(st) == [0] * 4, gpu_ctx.last_error()
+    for k, (x, z) in enumerate(zip(probs, zs)):
+        sr, zr = oracle_mod.linkage_ref(x)
+        assert sr == 0
+        np.testing.assert_array_equal(z, zr, err_msg=f"problem {k}")
+        assert stats[k]["merges"] == sizes[k] - 1 and stats[k]["reference_order"] == 0
+        assert stats[k]["init_ms"] == stats[0]["init_ms"] and stats[k]["merge_ms"] == stats[0]["merge_ms"]      # the batch's times
+        # total_ms == init_ms + merge_ms, exactly: the intervals are hipEventElapsedTime's floats and the library adds them as floats
+        assert stats[k]["total_ms"] == float(np.float32(stats[k]["init_ms"]) + np.float32(stats[k]["merge_ms"]))
+    tied = probs[1].copy()
+    tied[700:1400] = tied[0:700]
+    st, zs2, stats = fa.linkage_batch([probs[0], tied, probs[2], probs[3]], ctx=gpu_ctx, return_stats=True)
+    assert list(st) == [0] * 4, gpu_ctx.last_error()
+    assert [s["reference_order"] for s in stats] == [0, 1, 0, 0]
+    st1, z1 = fa.linkage(tied, ctx=gpu_ctx)
+    assert st1 == 0
+    np.testing.assert_array_equal(zs2[1], z1)
+    for k in (0, 2, 3):
+        np.testing.assert_array_equal(zs2[k], zs[k])

@@ -1,4 +1,4 @@
-"""AUTO's tie route hands the problem back to the filter-based rounds once the ties have stopped (round 6; csrc/ahc_rom.hip, prob_adopt in csrc/ahc_rounds.hip).
+"""AUTO's tie route hands the problem back to the filter-based rounds once the ties have stopped (round 6; csrc/ahc_rom.hip, prob_adopt in csrc/ahc_rounds_host.hip).
 Ties at distance 0 only (duplicated rows): the rows behind the last tie have a unique closest pair, so the rounds produce what the reference's heap produces.
 Whatever happens — handed over, handed over and a later tie met (everything again in reference order), never handed over — the dendrogram is the reference
 build's (oracle/_ref) row for row."""
