@@ -14,6 +14,8 @@ from .embedding import EmbeddingConfig, EmbeddingPlan, plan_embeddings, span_inp
 from .formats import AudioWAV, RTTMParser, RTTMParserError, TimedSpeakerSegment, export_embeddings_json  # noqa: F401
 from .kmeans import KMeansClustering, SeededRNG, SpeakerCountConstraints  # noqa: F401
 from .mel import AudioMelSpectrogram, LuxTtsMelExtractor, MelPlan, UnifiedMelExtractor  # noqa: F401
+from .paraformer import (PARAFORMER_SPAN_DTYPE, CifResult, ParaformerConfig, TimestampedSegment, cif_batch, cif_batch_dev, decode_tokens,  # noqa: F401
+                         keep_table, segments_from_spans, timestamps_batch, timestamps_batch_dev)
 from .pipeline import (ClusteringResult, OfflineClusteringConfig, cluster_embeddings, cluster_embeddings_batch, cluster_embeddings_stagewise, diarize_segments,  # noqa: F401
                        extract_embeddings, select_training_embeddings, span_embedder)
 from .pool import Pool, device_count  # noqa: F401

@@ -60,6 +60,7 @@ EXPORTED_SYMBOLS = [
     "fa_der_default_config", "fa_der_score_batch",
     "fa_edit_distance_batch", "fa_edit_distance_batch_dev",
     "fa_kws_adjusted_threshold", "fa_ctc_kws_spot_batch_dev", "fa_ctc_kws_spot_batch", "fa_ctc_kws_score_windows_dev", "fa_ctc_kws_score_windows",
+    "fa_paraformer_cif_default_config", "fa_paraformer_cif_dev", "fa_paraformer_cif", "fa_paraformer_timestamps_dev", "fa_paraformer_timestamps",
 ]
 
 
@@ -176,6 +177,14 @@ class KwsDetection(C.Structure):
 
 class KwsWindow(C.Structure):
     _fields_ = [("utterance", C.c_int32), ("keyword", C.c_int32), ("start_frame", C.c_int32), ("end_frame", C.c_int32)]
+
+
+class ParaformerCifConfig(C.Structure):
+    _fields_ = [("threshold", C.c_float), ("tail_threshold", C.c_float), ("max_tokens", C.c_int32), ("enc_frames", C.c_int32)]
+
+
+class ParaformerSpan(C.Structure):
+    _fields_ = [("utterance", C.c_int32), ("token_index", C.c_int32), ("start", C.c_double), ("end", C.c_double)]
 
 
 def build(force: bool = False) -> str:
@@ -405,6 +414,12 @@ def lib() -> C.CDLL:
     L.fa_ctc_kws_spot_batch.argtypes = L.fa_ctc_kws_spot_batch_dev.argtypes
     L.fa_ctc_kws_score_windows_dev.argtypes = [vp, vp, i32, i32, i32, i64, i64, vp, vp, vp, i32, vp, i64, i32, vp]
     L.fa_ctc_kws_score_windows.argtypes = L.fa_ctc_kws_score_windows_dev.argtypes
+    L.fa_paraformer_cif_default_config.argtypes = [C.POINTER(ParaformerCifConfig)]
+    L.fa_paraformer_cif_default_config.restype = None
+    L.fa_paraformer_cif_dev.argtypes = [vp, C.POINTER(ParaformerCifConfig), vp, i32, i32, i32, i32, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp]
+    L.fa_paraformer_cif.argtypes = L.fa_paraformer_cif_dev.argtypes
+    L.fa_paraformer_timestamps_dev.argtypes = [vp, C.POINTER(ParaformerCifConfig), vp, i64, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i64, C.POINTER(i64), vp]
+    L.fa_paraformer_timestamps.argtypes = L.fa_paraformer_timestamps_dev.argtypes
     _lib = L
     return L
 

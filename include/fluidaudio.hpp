@@ -996,4 +996,158 @@ private:
     }
 };
 
+// ------------------------------------------------------------------------------------------------------------------ Paraformer
+// ParaformerConfig (Sources/FluidAudio/ASR/Paraformer/ParaformerConfig.swift:8-39)
+struct ParaformerConfig {
+    static constexpr int featureDim = 560, encoderDim = 512;
+    static constexpr int decoderEncFrames = 512, decoderMaxTokens = 128;
+    static constexpr int blankId = 0, sosId = 1, eosId = 2;
+    static constexpr float cifThreshold = 1.0f, cifTailThreshold = 0.45f;
+    static constexpr int sampleRate = 16000;
+    static constexpr float waveformScale = 32768.0f;
+    static int pickEncoderBucket(int frames) {
+        for (const int b : {128, 256, 512, 1024, 1800})
+            if (b >= frames) return b;
+        return 1800;
+    }
+};
+
+// ParaformerCif (Sources/FluidAudio/ASR/Paraformer/ParaformerCif.swift:19-55) over fa_paraformer_cif: one utterance, every token (the
+// token budget of the call is the frame count + 1, so nothing is clamped), as the Swift routine returns them.
+struct ParaformerCif {
+    using Rows = std::vector<std::vector<float>>;
+    struct Fired {
+        Rows embeds;
+        std::vector<int> fireFrames;
+    };
+    static Fired integrateAndFireWithFireFrames(fa_ctx *ctx, const Rows &encRows, const std::vector<float> &alphas) {
+        const int32_t T = static_cast<int32_t>(encRows.size());
+        const int32_t dim = T > 0 ? static_cast<int32_t>(encRows[0].size()) : ParaformerConfig::encoderDim;
+        if (alphas.size() < encRows.size() || dim < 1) throw Error(FA_INVALID_ARGUMENT, "ParaformerCif: an alpha per row and rows of one length >= 1 are required");
+        std::vector<float> flat;
+        flat.reserve(static_cast<size_t>(T) * static_cast<size_t>(dim));
+        for (const auto &row : encRows) {
+            if (static_cast<int32_t>(row.size()) != dim) throw Error(FA_INVALID_ARGUMENT, "ParaformerCif: rows of different lengths");
+            flat.insert(flat.end(), row.begin(), row.end());
+        }
+        fa_paraformer_cif_config cfg;
+        fa_paraformer_cif_default_config(&cfg);
+        cfg.max_tokens = T + 1;
+        cfg.enc_frames = 0;
+        std::vector<float> ac(static_cast<size_t>(T + 1) * static_cast<size_t>(dim));
+        std::vector<int32_t> frames(static_cast<size_t>(T) + 1);
+        int32_t tokens = 0, fires = 0;
+        static const float none = 0.0f;   // an utterance without frames still gets arrays
+        const fa_status st = fa_paraformer_cif(ctx, &cfg, T > 0 ? flat.data() : &none, FA_DTYPE_F32, 1, T, dim, dim, static_cast<int64_t>(T) * dim,
+                                               T > 0 ? alphas.data() : &none, T, nullptr, ac.data(), nullptr, &tokens, &fires, frames.data());
+        if (st != FA_SUCCESS) throw Error(st, "fa_paraformer_cif", ctx ? fa_ctx_last_error(ctx) : nullptr);
+        Fired out;
+        for (int32_t l = 0; l < fires; ++l) {
+            out.embeds.emplace_back(ac.begin() + static_cast<int64_t>(l) * dim, ac.begin() + static_cast<int64_t>(l + 1) * dim);
+            out.fireFrames.push_back(frames[static_cast<size_t>(l)]);
+        }
+        return out;
+    }
+    static Rows integrateAndFire(fa_ctx *ctx, const Rows &encRows, const std::vector<float> &alphas) { return integrateAndFireWithFireFrames(ctx, encRows, alphas).embeds; }
+    static Fired integrateAndFireWithFireFrames(Context &ctx, const Rows &encRows, const std::vector<float> &alphas) { return integrateAndFireWithFireFrames(ctx.handle(), encRows, alphas); }
+    static Rows integrateAndFire(Context &ctx, const Rows &encRows, const std::vector<float> &alphas) { return integrateAndFire(ctx.handle(), encRows, alphas); }
+};
+
+// TimestampedSegment (Sources/FluidAudio/ASR/Paraformer/ParaformerManager.swift:12-22)
+struct TimestampedSegment {
+    double startTime = 0.0, endTime = 0.0;
+    std::string text;
+};
+
+// The host side of ParaformerManager behind the decoder's argmax (ParaformerManager.swift): decode (:450-463) and decodeWithTimestamps
+// (:134-257) over fa_paraformer_timestamps — the fires, the envelope and the walk run on the device; the charList filter becomes the
+// keep table, and the BPE merge of the emission (:228-256) runs here on the raw spans.  The vocabulary maps an id to its piece.
+struct ParaformerManager {
+    using Vocabulary = std::map<int, std::string>;
+    static bool special(int id) { return id == ParaformerConfig::blankId || id == ParaformerConfig::sosId || id == ParaformerConfig::eosId; }
+    // decode (:450-463): pieces joined, U+2581 -> blank, blanks and tabs trimmed
+    static std::string decode(const std::vector<int> &ids, const Vocabulary &vocabulary) {
+        std::string joined;
+        for (const int id : ids) {
+            if (special(id)) continue;
+            const auto it = vocabulary.find(id);
+            if (it != vocabulary.end()) joined += it->second;
+        }
+        const std::string boundary = "\xE2\x96\x81";
+        std::string out;
+        for (size_t i = 0; i < joined.size();) {
+            if (joined.compare(i, boundary.size(), boundary) == 0) { out += ' '; i += boundary.size(); }
+            else out += joined[i++];
+        }
+        const size_t a = out.find_first_not_of(" \t");
+        return a == std::string::npos ? std::string() : out.substr(a, out.find_last_not_of(" \t") - a + 1);
+    }
+    // the charList filter (:146-156) as a table over the ids 0 ... size - 1
+    static std::vector<uint8_t> keepTable(const Vocabulary &vocabulary, int size) {
+        std::vector<uint8_t> keep(static_cast<size_t>(size > 0 ? size : 0), 0);
+        for (const auto &kv : vocabulary)
+            if (kv.first >= 0 && kv.first < size && !special(kv.first) && !kv.second.empty()) keep[static_cast<size_t>(kv.first)] = 1;
+        return keep;
+    }
+    // the raw spans (:141-226) of one utterance: tokenIds is the argmax of the decoder's tokenCount positions
+    static std::vector<fa_paraformer_span> rawSpans(fa_ctx *ctx, const std::vector<int> &tokenIds, const Vocabulary &vocabulary, const std::vector<float> &alphas,
+                                                    const std::vector<float> &audio) {
+        fa_paraformer_cif_config cfg;
+        fa_paraformer_cif_default_config(&cfg);
+        cfg.max_tokens = static_cast<int32_t>(tokenIds.size() > 0 ? tokenIds.size() : 1);
+        int size = 0;
+        for (const int id : tokenIds) size = id >= size ? id + 1 : size;
+        const std::vector<uint8_t> keep = keepTable(vocabulary, size);
+        std::vector<int32_t> ids(static_cast<size_t>(cfg.max_tokens), 0);
+        for (size_t i = 0; i < tokenIds.size(); ++i) ids[i] = tokenIds[i];
+        const int32_t n = static_cast<int32_t>(tokenIds.size());
+        const int64_t off[2] = {0, static_cast<int64_t>(audio.size())};
+        std::vector<fa_paraformer_span> spans(tokenIds.size());
+        int64_t count = 0;
+        static const float none = 0.0f;
+        static const uint8_t no_keep = 0;
+        const fa_status st = fa_paraformer_timestamps(ctx, &cfg, alphas.empty() ? &none : alphas.data(), static_cast<int64_t>(alphas.size()), 1,
+                                                      static_cast<int32_t>(alphas.size()), nullptr, ids.data(), &n, keep.empty() ? &no_keep : keep.data(), size,
+                                                      audio.empty() ? &none : audio.data(), off, spans.data(), static_cast<int64_t>(spans.size()), &count, nullptr);
+        if (st != FA_SUCCESS) throw Error(st, "fa_paraformer_timestamps", ctx ? fa_ctx_last_error(ctx) : nullptr);
+        spans.resize(static_cast<size_t>(count));
+        return spans;
+    }
+    // the emission (:228-256): pieces[i] is the text of span i
+    static std::vector<TimestampedSegment> segments(const std::vector<std::string> &pieces, const std::vector<fa_paraformer_span> &spans) {
+        const std::string boundary = "\xE2\x96\x81", cont = "@@";
+        const auto has_prefix = [](const std::string &s, const std::string &p) { return s.compare(0, p.size(), p) == 0; };
+        const auto has_suffix = [](const std::string &s, const std::string &p) { return s.size() >= p.size() && s.compare(s.size() - p.size(), p.size(), p) == 0; };
+        std::vector<TimestampedSegment> out;
+        for (size_t i = 0; i < spans.size(); ++i) {
+            std::string text = pieces[i];
+            double end = spans[i].end;
+            const double start = spans[i].start;
+            while (has_suffix(text, cont)) {
+                text.resize(text.size() - cont.size());
+                ++i;
+                if (i < spans.size()) {
+                    text += has_prefix(pieces[i], boundary) ? pieces[i].substr(boundary.size()) : pieces[i];
+                    end = spans[i].end;
+                }
+            }
+            if (has_prefix(text, boundary)) text = text.substr(boundary.size());
+            if (!text.empty()) out.push_back(TimestampedSegment{start >= 0 ? start : 0.0, end, text});
+        }
+        return out;
+    }
+    // decodeWithTimestamps (:134-257) behind the argmax
+    static std::vector<TimestampedSegment> decodeWithTimestamps(fa_ctx *ctx, const std::vector<int> &tokenIds, const Vocabulary &vocabulary, const std::vector<float> &alphas,
+                                                                const std::vector<float> &audio) {
+        const std::vector<fa_paraformer_span> spans = rawSpans(ctx, tokenIds, vocabulary, alphas, audio);
+        std::vector<std::string> pieces;
+        for (const fa_paraformer_span &s : spans) pieces.push_back(vocabulary.at(tokenIds[static_cast<size_t>(s.token_index)]));
+        return segments(pieces, spans);
+    }
+    static std::vector<TimestampedSegment> decodeWithTimestamps(Context &ctx, const std::vector<int> &tokenIds, const Vocabulary &vocabulary, const std::vector<float> &alphas,
+                                                                const std::vector<float> &audio) {
+        return decodeWithTimestamps(ctx.handle(), tokenIds, vocabulary, alphas, audio);
+    }
+};
+
 }  // namespace fluidaudio

@@ -126,7 +126,7 @@ fa_status fa_debug_ahc_spec_hits(const fa_ctx *ctx, int64_t *hits);
  *   FA_FAULT_AHC            the linkage of fa_offline_cluster fails -> singletons (AHCClustering.swift:52-55) */
 enum { FA_FAULT_VBX = 0, FA_FAULT_THREAD_START = 1, FA_FAULT_DEVBUF_MALLOC = 2, FA_FAULT_WS_MALLOC = 3, FA_FAULT_AHC = 4, FA_FAULT_SITES = 5 };
 void fa_debug_inject_fault(int32_t site, int32_t count);
-/* Measurement support.  fa_ctx_set_timing(1): entries that support it (fa_ctc_beam_search_batch_dev, fa_edit_distance_batch(_dev)) bracket the DEVICE work of a call —
+/* Measurement support.  fa_ctx_set_timing(1): entries that support it (fa_ctc_beam_search_batch_dev, fa_edit_distance_batch(_dev), fa_paraformer_cif(_dev), fa_paraformer_timestamps(_dev)) bracket the DEVICE work of a call —
  * behind its allocations — with two events on the context's stream; fa_ctx_last_device_ms returns that time (< 0: none recorded), so a
  * caller can tell kernel time from host-side allocation time.  fa_debug_sclk_mhz: the shader clock right now (one wavefront counts
  * s_memtime cycles over spin_us microseconds of the constant 100 MHz s_memrealtime counter). */
@@ -943,6 +943,62 @@ fa_status fa_edit_distance_batch(fa_ctx *ctx, const int32_t *hyp, const int64_t 
                                  int64_t n_pairs, fa_edit_counts *out);
 fa_status fa_edit_distance_batch_dev(fa_ctx *ctx, const int32_t *d_hyp, const int64_t *hyp_range, const int32_t *d_ref, const int64_t *ref_range,
                                      int64_t n_pairs, fa_edit_counts *out);
+
+/* ------------------------------------------------------------------ Paraformer: CIF, token timestamps ------ */
+/* The host loop between Paraformer's networks, batched over utterances: ParaformerCif.integrateAndFireWithFireFrames
+ * (FluidAudio/ASR/Paraformer/ParaformerCif.swift:19-50) with the decoder's input packing of ParaformerManager.runDecoder
+ * (ParaformerManager.swift:416-448, rows(of:) :465-486), and the raw token spans of decodeWithTimestamps (:134-226).  Every fp32
+ * chain is evaluated in the reference's order and the time arithmetic is fp64: the outputs are the reference's bit for bit.
+ * The networks (preprocessor, encoder, CifAlphas, decoder) and the vocabulary are the caller's.  The reference has no unit test of
+ * these routines: parity is pinned by the restatement of tests/paraformer_restatement.py. */
+typedef struct {
+    float threshold;                 /* ParaformerConfig.cifThreshold */
+    float tail_threshold;            /* ParaformerConfig.cifTailThreshold: the alpha of the tail frame */
+    int32_t max_tokens;              /* ParaformerConfig.decoderMaxTokens: rows of ac, columns of token_ids */
+    int32_t enc_frames;              /* ParaformerConfig.decoderEncFrames: rows of enc_packed */
+} fa_paraformer_cif_config;
+void fa_paraformer_cif_default_config(fa_paraformer_cif_config *cfg);   /* 1.0, 0.45, 128, 512 */
+/* enc: batch matrices addressed like the logits of fa_ctc_greedy_batch_dev (dtype FA_DTYPE_F32 or FA_DTYPE_F16, widened on load; `dim`
+ * elements of a row are read, never the padding).  alphas float[batch][alpha_stride].  valid_frames HOST int32[batch] (nullable: all
+ * frames; clamped to [0, frames] — the caller clamps to decoderEncFrames as transcribe does).  cfg nullable: the defaults.
+ * Per utterance, over t = 0 ... T with the tail frame (alpha = tail_threshold, a zero row) at t = T: at most one fire per frame,
+ * alphas above the threshold fire on consecutive frames, T == 0 yields no token.
+ * ac float[batch][max_tokens][dim]: the first min(L, max_tokens) tokens, zeros behind them.  enc_packed (nullable)
+ * float[batch][enc_frames][dim]: rows below min(T, enc_frames) widened, zeros behind them.  token_counts HOST int32[batch]:
+ * min(L, max_tokens); fire_counts HOST int32[batch]: L; fire_frames HOST int32[batch][frames + 1]: all L fire frames, -1 behind them.
+ * _dev: enc, alphas, ac, enc_packed are DEVICE pointers, read and written in stream order; otherwise HOST pointers.  INVALID_ARGUMENT
+ * for a NULL pointer, a negative size, a stride below its row, a dtype or config out of range; INDEX_OVERFLOW for a batch of more than
+ * INT32_MAX frames or tokens — decided before any device work, nothing written.  batch == 0: SUCCESS.  One host synchronisation. */
+fa_status fa_paraformer_cif_dev(fa_ctx *ctx, const fa_paraformer_cif_config *cfg, const void *d_enc, int32_t dtype, int32_t batch,
+                                int32_t frames, int32_t dim, int64_t row_stride, int64_t matrix_stride, const float *d_alphas,
+                                int64_t alpha_stride, const int32_t *valid_frames, float *d_ac, float *d_enc_packed,
+                                int32_t *token_counts, int32_t *fire_counts, int32_t *fire_frames);
+fa_status fa_paraformer_cif(fa_ctx *ctx, const fa_paraformer_cif_config *cfg, const void *enc, int32_t dtype, int32_t batch,
+                            int32_t frames, int32_t dim, int64_t row_stride, int64_t matrix_stride, const float *alphas,
+                            int64_t alpha_stride, const int32_t *valid_frames, float *ac, float *enc_packed, int32_t *token_counts,
+                            int32_t *fire_counts, int32_t *fire_frames);
+/* A raw span of decodeWithTimestamps (its `raw` array, :203-226): token_index is the position of the token in the utterance's row of
+ * token_ids; the text and the merge of BPE pieces (:228-256) are the wrappers'. */
+typedef struct { int32_t utterance, token_index; double start, end; } fa_paraformer_span;
+/* alphas and valid_frames as above (only tail_threshold and max_tokens of cfg matter).  token_ids int32[batch][max_tokens]: the argmax
+ * of the decoder's logits; token_counts HOST int32[batch], each in [0, max_tokens].  keep HOST uint8[vocab]: 0 for the ids the
+ * reference drops (:146-156: blank, <s>, </s>, ids without a vocabulary entry, empty strings); an id outside [0, vocab) is dropped.
+ * audio: the utterances' 16 kHz samples one after the other, utterance b at audio_offsets[b] ... audio_offsets[b + 1] (HOST
+ * int64[batch + 1]); finite samples (the reference sorts them: the order of NaN is unspecified there; here such input ends without a
+ * fault).  spans HOST [capacity], by utterance and token; *count is set even when spans is NULL (SUCCESS) or too small
+ * (OUTPUT_TOO_SMALL, the first `capacity` records are written); utterance_counts HOST int64[batch] (nullable).  An utterance without a
+ * kept token or with fewer than two fires yields none.  _dev: alphas, token_ids and audio are DEVICE pointers.  Argument errors as
+ * above; one host synchronisation behind the uploads. */
+fa_status fa_paraformer_timestamps_dev(fa_ctx *ctx, const fa_paraformer_cif_config *cfg, const float *d_alphas, int64_t alpha_stride,
+                                       int32_t batch, int32_t frames, const int32_t *valid_frames, const int32_t *d_token_ids,
+                                       const int32_t *token_counts, const uint8_t *keep, int32_t vocab, const float *d_audio,
+                                       const int64_t *audio_offsets, fa_paraformer_span *spans, int64_t capacity, int64_t *count,
+                                       int64_t *utterance_counts);
+fa_status fa_paraformer_timestamps(fa_ctx *ctx, const fa_paraformer_cif_config *cfg, const float *alphas, int64_t alpha_stride,
+                                   int32_t batch, int32_t frames, const int32_t *valid_frames, const int32_t *token_ids,
+                                   const int32_t *token_counts, const uint8_t *keep, int32_t vocab, const float *audio,
+                                   const int64_t *audio_offsets, fa_paraformer_span *spans, int64_t capacity, int64_t *count,
+                                   int64_t *utterance_counts);
 
 /* ------------------------------------------------------------------ resampling ------ */
 /* AudioConverter.linearResample (FluidAudio/Shared/AudioConverter.swift:388-442): planar float[channels][frames] ->
