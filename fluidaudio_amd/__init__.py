@@ -28,6 +28,8 @@ from .sharding import gather_ragged_int32, shard_offsets, shard_range  # noqa: F
 from .sortformer import OfflineSortformerConfig, OfflineSortformerDiarizer, offline_windows, pack_windows, stitch, stitcher_alignment  # noqa: F401
 from .tdt import (TdtConfig, TdtDurationMapping, TdtFrameNavigation, decode_logits as tdt_decode_logits,  # noqa: F401
                   decode_tables as tdt_decode_tables)
+from .tdt_merge import (MERGE_NO_SEAM, MergedWindows, merge_capacity, merge_route_name, merge_windows, merge_windows_dev,  # noqa: F401
+                        splice_safe_table, case_canon_table)
 from .timeline import DiarizerSegment, DiarizerTimeline, DiarizerTimelineConfig, timeline_segments  # noqa: F401
 from .vbx import VBxClustering, VBxOutput  # noqa: F401
 from .wer import (EDIT_COUNTS_DTYPE, CorpusErrorRate, WERAndCER, WERMetrics, edit_distance_batch, edit_distance_batch_dev, levenshtein_distance,  # noqa: F401

@@ -61,6 +61,7 @@ EXPORTED_SYMBOLS = [
     "fa_edit_distance_batch", "fa_edit_distance_batch_dev",
     "fa_kws_adjusted_threshold", "fa_ctc_kws_spot_batch_dev", "fa_ctc_kws_spot_batch", "fa_ctc_kws_score_windows_dev", "fa_ctc_kws_score_windows",
     "fa_paraformer_cif_default_config", "fa_paraformer_cif_dev", "fa_paraformer_cif", "fa_paraformer_timestamps_dev", "fa_paraformer_timestamps",
+    "fa_tdt_merge_default_config", "fa_tdt_merge_windows_dev", "fa_tdt_merge_windows",
 ]
 
 
@@ -185,6 +186,10 @@ class ParaformerCifConfig(C.Structure):
 
 class ParaformerSpan(C.Structure):
     _fields_ = [("utterance", C.c_int32), ("token_index", C.c_int32), ("start", C.c_double), ("end", C.c_double)]
+
+
+class TdtMergeConfig(C.Structure):
+    _fields_ = [("frame_seconds", C.c_double), ("overlap_seconds", C.c_double)]
 
 
 def build(force: bool = False) -> str:
@@ -420,6 +425,10 @@ def lib() -> C.CDLL:
     L.fa_paraformer_cif.argtypes = L.fa_paraformer_cif_dev.argtypes
     L.fa_paraformer_timestamps_dev.argtypes = [vp, C.POINTER(ParaformerCifConfig), vp, i64, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i64, C.POINTER(i64), vp]
     L.fa_paraformer_timestamps.argtypes = L.fa_paraformer_timestamps_dev.argtypes
+    L.fa_tdt_merge_default_config.argtypes = [C.POINTER(TdtMergeConfig)]
+    L.fa_tdt_merge_default_config.restype = None
+    L.fa_tdt_merge_windows_dev.argtypes = [vp, C.POINTER(TdtMergeConfig), vp, vp, vp, vp, vp, i32, vp, i64, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.fa_tdt_merge_windows.argtypes = L.fa_tdt_merge_windows_dev.argtypes
     _lib = L
     return L
 

@@ -895,6 +895,80 @@ struct StringUtils {
     static int levenshteinDistance(Context &ctx, const std::vector<int> &a, const std::vector<int> &b) { return levenshteinDistance(ctx.handle(), a, b); }
 };
 
+// ------------------------------------------------------------------------------------------------------------------ TDT long-form merging
+// ChunkProcessor's fold of mergeChunks over a recording's windows and enforceMonotonicTimestamps (Sources/FluidAudio/ASR/Parakeet/
+// SlidingWindow/TDT/ChunkProcessor.swift:843-855, 952-1219) over fa_tdt_merge_windows: the windows of one or more recordings in one
+// device call.  The safe set and the case table (spliceSafeTokenIds, caseVariantCanonicalIds) are the caller's, as tables over the
+// vocabulary; collapseSeamWordDuplicates, repairSeamGaps and the planning of chunk starts are out of scope.
+struct ChunkProcessor {
+    struct TokenWindow {          // ChunkProcessor.TokenWindow
+        int token = 0, timestamp = 0, duration = 0;
+        float confidence = 0.0f;
+    };
+    using Window = std::vector<TokenWindow>;
+    struct Merged {
+        std::vector<TokenWindow> tokens;
+        fa_status status = FA_SUCCESS;          // FA_OUTPUT_TOO_SMALL cannot happen here: the slices get the safe bound
+        std::vector<int32_t> seamRoutes;        // one per window, FA_TDT_MERGE_NO_SEAM for the first
+    };
+    double frameSeconds = 1280.0 / 16000.0, overlapSeconds = 2.0;
+    std::vector<uint8_t> spliceSafe;            // with hasSpliceSafe: uint8[vocab]
+    std::vector<int32_t> caseCanon;             // with hasCaseCanon: int32[vocab], -1 without an entry
+    bool hasSpliceSafe = false, hasCaseCanon = false;
+
+    // every recording's windows (global timestamps) in one call; answers in input order
+    std::vector<Merged> mergeRecordings(fa_ctx *ctx, const std::vector<std::vector<Window>> &recordings) const {
+        const int64_t n = static_cast<int64_t>(recordings.size());
+        std::vector<Merged> out(recordings.size());
+        if (n == 0) return out;
+        size_t maxOut = 1, windows = 0;
+        for (const auto &r : recordings)
+            for (const Window &w : r) { maxOut = std::max(maxOut, w.size()); ++windows; }
+        std::vector<int32_t> tok(windows * maxOut), time(windows * maxOut), dur(windows * maxOut), count(windows);
+        std::vector<float> conf(windows * maxOut);
+        std::vector<int64_t> windowRange{0}, outRange{0};
+        size_t at = 0;
+        for (const auto &r : recordings) {
+            int64_t cap = 0;
+            for (size_t k = 0; k < r.size(); ++k, ++at) {
+                for (size_t i = 0; i < r[k].size(); ++i) {
+                    tok[at * maxOut + i] = r[k][i].token; time[at * maxOut + i] = r[k][i].timestamp;
+                    dur[at * maxOut + i] = r[k][i].duration; conf[at * maxOut + i] = r[k][i].confidence;
+                }
+                count[at] = static_cast<int32_t>(r[k].size());
+                cap += static_cast<int64_t>(r[k].size()) * (k == 0 ? 1 : 2);   // a right token is emitted at most twice
+            }
+            windowRange.push_back(static_cast<int64_t>(at));
+            outRange.push_back(outRange.back() + cap);
+        }
+        const size_t total = static_cast<size_t>(outRange.back());
+        std::vector<int32_t> oTok(total + 1), oTime(total + 1), oDur(total + 1), counts(recordings.size()), statuses(recordings.size()), routes(windows + 1);
+        std::vector<float> oConf(total + 1);
+        const size_t vocab = hasSpliceSafe ? spliceSafe.size() : (hasCaseCanon ? caseCanon.size() : 0);
+        if (hasSpliceSafe && hasCaseCanon && spliceSafe.size() != caseCanon.size()) throw Error(FA_INVALID_ARGUMENT, "fa_tdt_merge_windows", "the tables disagree about the vocabulary");
+        static const uint8_t noSafe = 0;
+        static const int32_t noCanon = -1;
+        const fa_tdt_merge_config cfg{frameSeconds, overlapSeconds};
+        const fa_status st = fa_tdt_merge_windows(ctx, &cfg, tok.data(), time.data(), dur.data(), conf.data(), count.data(), static_cast<int32_t>(maxOut), windowRange.data(), n,
+                                                  hasSpliceSafe ? (spliceSafe.empty() ? &noSafe : spliceSafe.data()) : nullptr,
+                                                  hasCaseCanon ? (caseCanon.empty() ? &noCanon : caseCanon.data()) : nullptr, static_cast<int32_t>(vocab), oTok.data(),
+                                                  oTime.data(), oDur.data(), oConf.data(), outRange.data(), counts.data(), statuses.data(), routes.data());
+        if (st != FA_SUCCESS) throw Error(st, "fa_tdt_merge_windows", ctx ? fa_ctx_last_error(ctx) : nullptr);
+        for (size_t r = 0; r < recordings.size(); ++r) {
+            out[r].status = static_cast<fa_status>(statuses[r]);
+            for (int32_t i = 0; i < counts[r]; ++i) {
+                const size_t q = static_cast<size_t>(outRange[r]) + static_cast<size_t>(i);
+                out[r].tokens.push_back(TokenWindow{oTok[q], oTime[q], oDur[q], oConf[q]});
+            }
+            out[r].seamRoutes.assign(routes.begin() + windowRange[r], routes.begin() + windowRange[r + 1]);
+        }
+        return out;
+    }
+    // mergeChunks(left, right) alone, without the clamp's effect on later seams: a recording of two windows
+    Merged mergeRecording(fa_ctx *ctx, const std::vector<Window> &windows) const { return mergeRecordings(ctx, {windows})[0]; }
+    Merged mergeRecording(Context &ctx, const std::vector<Window> &windows) const { return mergeRecording(ctx.handle(), windows); }
+};
+
 // ------------------------------------------------------------------------------------------------------------------ CTC word spotting
 // CtcKeywordSpotter.spotKeywordsFromLogProbs (…/WordSpotting/CtcKeywordSpotter.swift:191-254) and the two scans of CtcDPAlgorithm it and
 // the rescorer call (CtcDPAlgorithm.swift:250-392), over fa_ctc_kws_spot_batch / fa_ctc_kws_score_windows.  A term carries its token ids

@@ -99,6 +99,8 @@ const char *fa_version(void);
  *   FA_RESAMPLE_SIMPLE, _NO_DECIM, _NO_DECIM_TILES, _NO_ROWS, _NO_WIDE, FA_RESAMPLE_WIDE=rows:waves (16:8, 16:10, 32:8, 32:10)   polyphase kernel family
  *   FA_KWS_ARENA=records                     the candidate arena of a word-spotting call (never less than one job can need): a small one forces the
  *                                            passes that walk overflowed jobs again
+ *   FA_TDT_MERGE_LDS_SIDE=tokens             the longest overlap side a seam of fa_tdt_merge_windows keeps in LDS (at most 128, the default): a
+ *                                            small one sends short sides through the workspace route
  * fa_debug_set_switch(name, value): value NULL = unset.  Changes what the NEXT calls see (process-wide; not for use while calls are in flight
  * on other threads).  RUNTIME_ERROR without FLUIDAUDIO_HIP_DEBUG_HOOKS=1, INVALID_ARGUMENT for an unknown name. */
 fa_status fa_debug_set_switch(const char *name, const char *value);
@@ -126,7 +128,7 @@ fa_status fa_debug_ahc_spec_hits(const fa_ctx *ctx, int64_t *hits);
  *   FA_FAULT_AHC            the linkage of fa_offline_cluster fails -> singletons (AHCClustering.swift:52-55) */
 enum { FA_FAULT_VBX = 0, FA_FAULT_THREAD_START = 1, FA_FAULT_DEVBUF_MALLOC = 2, FA_FAULT_WS_MALLOC = 3, FA_FAULT_AHC = 4, FA_FAULT_SITES = 5 };
 void fa_debug_inject_fault(int32_t site, int32_t count);
-/* Measurement support.  fa_ctx_set_timing(1): entries that support it (fa_ctc_beam_search_batch_dev, fa_edit_distance_batch(_dev), fa_paraformer_cif(_dev), fa_paraformer_timestamps(_dev)) bracket the DEVICE work of a call —
+/* Measurement support.  fa_ctx_set_timing(1): entries that support it (fa_ctc_beam_search_batch_dev, fa_edit_distance_batch(_dev), fa_paraformer_cif(_dev), fa_paraformer_timestamps(_dev), fa_tdt_merge_windows(_dev)) bracket the DEVICE work of a call —
  * behind its allocations — with two events on the context's stream; fa_ctx_last_device_ms returns that time (< 0: none recorded), so a
  * caller can tell kernel time from host-side allocation time.  fa_debug_sclk_mhz: the shader clock right now (one wavefront counts
  * s_memtime cycles over spin_us microseconds of the constant 100 MHz s_memrealtime counter). */
@@ -999,6 +1001,63 @@ fa_status fa_paraformer_timestamps(fa_ctx *ctx, const fa_paraformer_cif_config *
                                    const int32_t *token_counts, const uint8_t *keep, int32_t vocab, const float *audio,
                                    const int64_t *audio_offsets, fa_paraformer_span *spans, int64_t capacity, int64_t *count,
                                    int64_t *utterance_counts);
+
+/* ------------------------------------------------------------------ TDT long-form: merging the windows' tokens ------ */
+/* What ChunkProcessor does with the tokens of a recording's overlapping windows (FluidAudio/ASR/Parakeet/SlidingWindow/TDT/
+ * ChunkProcessor.swift): merged = w[0]; merged = mergeChunks(merged, w[k]) for every further window (:952-1219 with tokensMatch,
+ * tokenIdsMatch, mergeUsingMatches, wordInitialIndex, popSeamWord, mergeByMidpoint; SequenceMatcher.findContiguousMatches and
+ * findLongestCommonSubsequence, TokenDeduplication/SequenceMatcher.swift:127-225), then enforceMonotonicTimestamps (:843-855) —
+ * batched over recordings, one wavefront per recording, on the arrays the greedy walk leaves on the device.  Integer rules and the
+ * reference's own fp64 time expressions, evaluated without contraction: the merged stream is the reference's bit for bit (pinned by
+ * its 17 literal mergeTokenWindowsForTesting cases).  OUT OF SCOPE: collapseSeamWordDuplicates (Unicode strings), repairSeamGaps
+ * (needs the networks), the planning of chunk starts, the streaming removeDuplicateTokenSequence. */
+typedef struct {
+    double frame_seconds;            /* ASRConstants.secondsPerEncoderFrame */
+    double overlap_seconds;          /* ChunkProcessor.overlapSeconds */
+} fa_tdt_merge_config;
+void fa_tdt_merge_default_config(fa_tdt_merge_config *cfg);   /* Double(1280) / Double(16000), 2.0 */
+/* A seam's route: base strategy | tail handling << 4; FA_TDT_MERGE_NO_SEAM for a recording's first window and for seams not done. */
+#define FA_TDT_MERGE_EMPTY 0            /* a side without tokens (:958-959) */
+#define FA_TDT_MERGE_CONCAT 1           /* left ends before right starts (:976-978) */
+#define FA_TDT_MERGE_CONTIGUOUS 2       /* the longest contiguous run holds minimumPairs (:1015-1024) */
+#define FA_TDT_MERGE_LCS 3              /* the LCS fallback (:1026-1050) */
+#define FA_TDT_MERGE_MIDPOINT 4         /* mergeByMidpoint (:993-997, :1033-1037) */
+#define FA_TDT_MERGE_TAIL_VERBATIM 0    /* right's tail as it is */
+#define FA_TDT_MERGE_TAIL_ADOPT_RIGHT 1 /* the seam word popped, right's segmentation of it adopted (:1123-1128) */
+#define FA_TDT_MERGE_TAIL_KEEP_LEFT 2   /* left keeps its word, right resumes at its next word-initial piece (:1129-1146) */
+#define FA_TDT_MERGE_NO_SEAM (-1)
+/* d_tok, d_time, d_dur, d_conf [windows][max_out] and d_count [windows]: what fa_tdt_greedy_tables_dev / fa_tdt_greedy_logits_dev
+ * wrote (global timestamps); min(count, max_out) tokens of a window are used, a negative count as 0.  window_range HOST
+ * int64[n_recordings + 1]: recording r owns the windows [window_range[r], window_range[r + 1]), in order; windows without tokens are
+ * legal anywhere.  cfg nullable: the defaults.
+ * splice_safe HOST uint8[vocab] (nullable = spliceSafeTokenIds == nil, the legacy splices; an all-zero table is the EMPTY set, which
+ * is not the same) and case_canon HOST int32[vocab] (nullable = caseVariantIds == nil; -1: no entry): the tables the reference
+ * builds from its vocabulary (spliceSafeTokenIds, caseVariantCanonicalIds) stay the caller's.  An id outside [0, vocab) is unsafe and
+ * has no entry.
+ * Outputs are flat: recording r's merged stream goes to [out_range[r], out_range[r + 1]) of d_out_tok / d_out_time / d_out_dur /
+ * d_out_conf (out_range HOST int64[n_recordings + 1]); out_counts HOST int32[n_recordings]: its length; statuses HOST
+ * int32[n_recordings]: FA_SUCCESS, or FA_OUTPUT_TOO_SMALL for a recording whose slice ran out (its count is 0, its slice unspecified;
+ * the other recordings are untouched by it).  A merge emits a token of the right window at most twice (a right-side gap adopted, then
+ * the seam word spliced again from its start), so |w0| + 2 sum_{k >= 1} |wk| tokens are always enough.  seam_routes (nullable) HOST
+ * int32, indexed like the windows: entries [window_range[0], window_range[n_recordings]) are written.
+ * _dev: the window arrays and the four output arrays are DEVICE pointers on the context's device, read and written in stream order;
+ * otherwise HOST pointers.  INVALID_ARGUMENT for a NULL or descending range, a range starting below 0, a missing array, a negative
+ * size, a frame that is not positive or an overlap that is negative (or either not finite); INDEX_OVERFLOW for a slice longer than
+ * INT32_MAX or 2^31 - 1 recordings or more — decided before any device work, nothing written.  n_recordings == 0: SUCCESS.  One host
+ * synchronisation per call; fa_ctx_set_timing brackets the kernel.  Overlap sides of any length are served (beyond 128 tokens a
+ * side through a workspace of (largest slice) x max_out bits per wavefront in flight: ALLOCATION_FAILURE when that cannot be had). */
+fa_status fa_tdt_merge_windows_dev(fa_ctx *ctx, const fa_tdt_merge_config *cfg, const int32_t *d_tok, const int32_t *d_time,
+                                   const int32_t *d_dur, const float *d_conf, const int32_t *d_count, int32_t max_out,
+                                   const int64_t *window_range, int64_t n_recordings, const uint8_t *splice_safe,
+                                   const int32_t *case_canon, int32_t vocab, int32_t *d_out_tok, int32_t *d_out_time,
+                                   int32_t *d_out_dur, float *d_out_conf, const int64_t *out_range, int32_t *out_counts,
+                                   int32_t *statuses, int32_t *seam_routes);
+fa_status fa_tdt_merge_windows(fa_ctx *ctx, const fa_tdt_merge_config *cfg, const int32_t *tok, const int32_t *time,
+                               const int32_t *dur, const float *conf, const int32_t *count, int32_t max_out,
+                               const int64_t *window_range, int64_t n_recordings, const uint8_t *splice_safe,
+                               const int32_t *case_canon, int32_t vocab, int32_t *out_tok, int32_t *out_time, int32_t *out_dur,
+                               float *out_conf, const int64_t *out_range, int32_t *out_counts, int32_t *statuses,
+                               int32_t *seam_routes);
 
 /* ------------------------------------------------------------------ resampling ------ */
 /* AudioConverter.linearResample (FluidAudio/Shared/AudioConverter.swift:388-442): planar float[channels][frames] ->
