@@ -251,7 +251,8 @@ fa_status fa_ctc_beam_search_batch_dev(fa_ctx *ctx, const float *d_log_probs, in
     ta.logp = d_log_probs; ta.valid = d_valid_frames; ta.tok = a.tok; ta.top = d_top.as<TopEntry>();
     ta.row_stride = row_stride; ta.matrix_stride = matrix_stride; ta.frames = frames; ta.vocab = vocab; ta.blank = blank_id;
     ta.top_k = token_candidates; ta.use_lm = a.use_lm;
-    if (ctx->timing) FA_HIP_TRY(ctx, hipEventRecord(ctx->tim_ev[0], ctx->stream));   // device work of the call: behind the allocations
+    fa::DeviceTiming tim{ctx};   // device work of the call: behind the allocations
+    FA_TRY(tim.begin());
     for (int first = 0; first < batch; first += plan.chunk) {
         const int now = std::min(plan.chunk, batch - first);
         a.first = first;
@@ -264,9 +265,9 @@ fa_status fa_ctc_beam_search_batch_dev(fa_ctx *ctx, const float *d_log_probs, in
         launch_walk(ctx->stream, a, now, plan.ntop);
         FA_HIP_TRY(ctx, hipGetLastError());
     }
-    if (ctx->timing) FA_HIP_TRY(ctx, hipEventRecord(ctx->tim_ev[1], ctx->stream));
+    FA_TRY(tim.end());
     FA_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // the arena and the tables go back to the context's cache on return
-    if (ctx->timing) { float ms = -1.0f; FA_HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->tim_ev[0], ctx->tim_ev[1])); ctx->last_device_ms = ms; }
+    FA_TRY(tim.read());
     return FA_SUCCESS;
 }
 

@@ -1,4 +1,5 @@
-// der.hip — frame-wise diarization error rate with the optimal speaker mapping, batched over recordings: DiarizationDER.compute
+// der.hip — the kernels of the frame-wise diarization error rate with the optimal speaker mapping, batched over recordings (entries:
+// der_host.hip, argument pass and plan: der_geom.h, operands: der_launch.h): DiarizationDER.compute
 // (Sources/FluidAudio/Diarizer/DiarizationDER.swift:52-231) and the integer Kuhn-Munkres it calls (Diarizer/HungarianAssignment.swift:8-61).
 // Every quantity is an integer count, so the result is pinned bit for bit; the fp64 arithmetic is one division, one subtraction and a
 // ceil / floor per range end (this unit is built with -ffp-contract=off like the other restatements).
@@ -11,41 +12,11 @@
 //   der_accumulate  lane = frame: miss / false alarm / confusion / reference counts -> int64 atomicAdd
 // The geometry (label counts, maxEnd, numFrames, word offsets) is decided by the host in the pass that validates the arguments: that
 // pass has to read every segment before any device work anyway, and the planes have to be sized before the call's one synchronisation.
-#include <algorithm>
-#include <cmath>
-
-#include "fa_common.h"
+#include "der_launch.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWave = 64;
-constexpr int kMaxLabels = FA_DER_MAX_LABELS;
-constexpr int kRasterLanes = 8;          // lanes that share one range in der_raster
-constexpr int kOverlapTileWords = 256;   // words per workgroup of der_overlap: one 64-word chunk per wavefront
-constexpr int kAccWordsPerWave = 8;      // consecutive words a wavefront of der_accumulate sums before it reduces
-constexpr int kAccTileWords = kAccWordsPerWave * (kThreads / kWave);
-
-static_assert(kMaxLabels == kWave, "der_assign gives every column a lane and der_accumulate keeps a label set in one 64-bit word");
-
-struct DerRec {
-    int64_t ref_begin, ref_end, hyp_begin, hyp_end;   // the recording's segments in the concatenated lists
-    int64_t plane_off;                                // first word of its planes: R ref planes, H hyp planes, the excluded plane
-    int64_t ov_off;                                   // first entry of its [H][R] overlap table
-    int32_t words, num_frames, R, H;
-};
-
-struct DerArgs {
-    const fa_der_segment *ref, *hyp;
-    const DerRec *rec;
-    unsigned long long *planes;
-    unsigned long long *overlap;   // int64 counts, added as unsigned
-    unsigned long long *acc;       // [B][4]: miss, false alarm, confusion, ref
-    int32_t *mapping;              // [B][kMaxLabels]
-    int64_t n_ref, n_hyp;
-    int32_t B;
-    double step, collar;
-};
+using namespace fa::der;
 
 // max(0, min(limit, Int(x))) for an x that is already integral (a ceil or a floor) or infinite, without converting what does not fit
 __device__ inline int32_t clamp_frame(const double x, const int32_t limit) {
@@ -251,135 +222,25 @@ __global__ __launch_bounds__(kThreads) void der_accumulate(const DerArgs a) {
     }
 }
 
-// The argument pass: labels, times, and with them the geometry of :61-86.  Nothing here touches the device.
-fa_status der_geometry(fa_ctx *ctx, const fa_der_config *cfg, const fa_der_segment *ref, const int64_t *ref_range, const fa_der_segment *hyp,
-                       const int64_t *hyp_range, int32_t B, std::vector<DerRec> &rec, int64_t &plane_words, int64_t &ov_entries) {
-    plane_words = 0;
-    ov_entries = 0;
-    for (int32_t b = 0; b < B; ++b) {
-        DerRec &r = rec[b];
-        r = DerRec{ref_range[b], ref_range[b + 1], hyp_range[b], hyp_range[b + 1], plane_words, ov_entries, 0, 0, 0, 0};
-        if (r.ref_begin < 0 || r.ref_end < r.ref_begin || r.hyp_begin < 0 || r.hyp_end < r.hyp_begin)
-            return fa::set_error(ctx, FA_INVALID_ARGUMENT, "der: the segment ranges of recording %d do not ascend", b);
-        if ((r.ref_end > r.ref_begin && !ref) || (r.hyp_end > r.hyp_begin && !hyp)) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "der: segments are required");
-        double max_end = 0.0;
-        int32_t labels[2] = {0, 0};
-        for (int side = 0; side < 2; ++side) {
-            const fa_der_segment *s = side ? hyp : ref;
-            for (int64_t i = side ? r.hyp_begin : r.ref_begin, e = side ? r.hyp_end : r.ref_end; i < e; ++i) {
-                if (!std::isfinite(s[i].start) || !std::isfinite(s[i].end))
-                    return fa::set_error(ctx, FA_INVALID_ARGUMENT, "der: recording %d has a segment with a non-finite time", b);
-                if (s[i].label < 0 || s[i].label >= kMaxLabels)
-                    return fa::set_error(ctx, FA_INVALID_ARGUMENT, "der: recording %d has label %d; a side holds at most %d labels, numbered from 0", b, s[i].label,
-                                         kMaxLabels);
-                labels[side] = std::max(labels[side], s[i].label + 1);
-                max_end = std::max(max_end, s[i].end);   // degenerate segments count too (:72, :79)
-            }
-        }
-        r.R = labels[0];
-        r.H = labels[1];
-        if (r.R == 0 && r.H == 0) continue;   // :82-86: every output is zero
-        const double frames = std::ceil(max_end / cfg->frame_step) + 1.0;
-        if (!(frames < 2147483584.0)) return fa::set_error(ctx, FA_INDEX_OVERFLOW, "der: recording %d has 2^31 frames or more", b);
-        r.num_frames = static_cast<int32_t>(frames);
-        r.words = (r.num_frames + 63) / 64;
-        plane_words += static_cast<int64_t>(r.words) * (r.R + r.H + 1);
-        ov_entries += static_cast<int64_t>(r.R) * r.H;
-    }
-    return FA_SUCCESS;
-}
-
-fa_status der_score(fa_ctx *ctx, const fa_der_config *cfg, const fa_der_segment *ref, const int64_t *ref_range, const fa_der_segment *hyp,
-                    const int64_t *hyp_range, int32_t B, fa_der_counts *counts, int32_t *mapping, const int64_t *mapping_range, int64_t *overlap,
-                    int64_t overlap_capacity) {
-    if (!ctx || !cfg) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "der: ctx and config are required");
-    if (!(cfg->frame_step > 0.0) || !std::isfinite(cfg->frame_step) || !(cfg->collar >= 0.0) || !std::isfinite(cfg->collar))
-        return fa::set_error(ctx, FA_INVALID_ARGUMENT, "der: frame_step must be positive and finite, collar non-negative and finite");
-    if (B < 0 || overlap_capacity < 0 || (B > 0 && (!ref_range || !hyp_range || !counts || !mapping_range)))
-        return fa::set_error(ctx, FA_INVALID_ARGUMENT, "der: bad arguments");
-    if (B == 0) return FA_SUCCESS;
-    return fa::no_throw(ctx, "der", [&]() -> fa_status {
-    std::vector<DerRec> rec(static_cast<size_t>(B));
-    int64_t plane_words = 0, ov_entries = 0;
-    FA_TRY(der_geometry(ctx, cfg, ref, ref_range, hyp, hyp_range, B, rec, plane_words, ov_entries));
-    int32_t max_words = 0;
-    for (int32_t b = 0; b < B; ++b) {
-        const int64_t room = mapping_range[b + 1] - mapping_range[b];
-        if (mapping_range[b] < 0 || room < 0) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "der: the mapping range of recording %d does not ascend", b);
-        if (room < rec[b].H) return fa::set_error(ctx, FA_OUTPUT_TOO_SMALL, "der: recording %d has %d hypothesis labels, its mapping range holds %lld", b, rec[b].H, (long long)room);
-        if (room > 0 && !mapping) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "der: mapping is required");
-        max_words = std::max(max_words, rec[b].words);
-    }
-    if (overlap && overlap_capacity < ov_entries)
-        return fa::set_error(ctx, FA_OUTPUT_TOO_SMALL, "der: the overlap tables take %lld entries, the output holds %lld", (long long)ov_entries, (long long)overlap_capacity);
-    const int64_t n_ref = ref_range[B], n_hyp = hyp_range[B], r0 = ref_range[0], h0 = hyp_range[0];
-    for (int32_t b = 0; b < B; ++b) {
-        counts[b] = fa_der_counts{rec[b].num_frames, 0, 0, 0, 0, rec[b].R, rec[b].H};
-        for (int64_t i = mapping_range[b]; i < mapping_range[b + 1]; ++i) mapping[i] = -1;
-        rec[b].ref_begin -= r0; rec[b].ref_end -= r0; rec[b].hyp_begin -= h0; rec[b].hyp_end -= h0;   // the upload starts at the first segment used
-    }
-    if (plane_words == 0) return FA_SUCCESS;   // no recording has a label
-    const int64_t items = (n_ref - r0) + (n_hyp - h0) + (cfg->collar > 0.0 ? 2 * (n_ref - r0) : 0);
-    const int64_t raster_blocks = (items * kRasterLanes + kThreads - 1) / kThreads;
-    if (raster_blocks >= INT32_MAX) return fa::set_error(ctx, FA_INDEX_OVERFLOW, "der: %lld segments", (long long)items);
-
-    fa::DeviceGuard guard(ctx->device);
-    hipStream_t st = ctx->stream;
-    fa::DevBuf b_ref, b_hyp, b_rec, b_planes, b_work;
-    auto alloc = [&](fa::DevBuf &b, size_t bytes) { return b.alloc(ctx, bytes) == hipSuccess; };
-    // b_work: the overlap tables, the accumulators, then the mappings — what comes back to the host, in one buffer
-    const size_t ov_bytes = sizeof(int64_t) * ov_entries, acc_bytes = sizeof(int64_t) * 4 * B, map_bytes = sizeof(int32_t) * kMaxLabels * static_cast<size_t>(B);
-    if (!alloc(b_ref, sizeof(fa_der_segment) * (n_ref - r0)) || !alloc(b_hyp, sizeof(fa_der_segment) * (n_hyp - h0)) || !alloc(b_rec, sizeof(DerRec) * B) ||
-        !alloc(b_planes, sizeof(uint64_t) * plane_words) || !alloc(b_work, ov_bytes + acc_bytes + map_bytes)) {
-        (void)hipGetLastError();
-        return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "der: device allocation failed");
-    }
-    if (n_ref > r0) FA_HIP_TRY(ctx, hipMemcpyAsync(b_ref.p, ref + r0, sizeof(fa_der_segment) * (n_ref - r0), hipMemcpyHostToDevice, st));
-    if (n_hyp > h0) FA_HIP_TRY(ctx, hipMemcpyAsync(b_hyp.p, hyp + h0, sizeof(fa_der_segment) * (n_hyp - h0), hipMemcpyHostToDevice, st));
-    FA_HIP_TRY(ctx, hipMemcpyAsync(b_rec.p, rec.data(), sizeof(DerRec) * B, hipMemcpyHostToDevice, st));
-    FA_HIP_TRY(ctx, hipMemsetAsync(b_planes.p, 0, sizeof(uint64_t) * plane_words, st));
-    FA_HIP_TRY(ctx, hipMemsetAsync(b_work.p, 0, ov_bytes + acc_bytes, st));   // der_assign writes every mapping entry it owns
-    char *work = b_work.as<char>();
-    DerArgs a{b_ref.as<fa_der_segment>(), b_hyp.as<fa_der_segment>(), b_rec.as<DerRec>(), b_planes.as<unsigned long long>(),
-              reinterpret_cast<unsigned long long *>(work), reinterpret_cast<unsigned long long *>(work + ov_bytes),
-              reinterpret_cast<int32_t *>(work + ov_bytes + acc_bytes), n_ref - r0, n_hyp - h0, B, cfg->frame_step, cfg->collar};
-    if (items > 0) hipLaunchKernelGGL(der_raster, dim3(static_cast<unsigned>(raster_blocks)), dim3(kThreads), 0, st, a, items);
-    if (ov_entries > 0)
-        hipLaunchKernelGGL(der_overlap, dim3((max_words + kOverlapTileWords - 1) / kOverlapTileWords, B), dim3(kThreads), 0, st, a);
-    hipLaunchKernelGGL(der_assign, dim3(B), dim3(kWave), 0, st, a);
-    hipLaunchKernelGGL(der_accumulate, dim3((max_words + kAccTileWords - 1) / kAccTileWords, B), dim3(kThreads), 0, st, a);
-    FA_HIP_TRY(ctx, hipGetLastError());
-    std::vector<int64_t> h_acc(static_cast<size_t>(4) * B);
-    std::vector<int32_t> h_map(static_cast<size_t>(kMaxLabels) * B);
-    if (overlap && ov_entries > 0) FA_HIP_TRY(ctx, hipMemcpyAsync(overlap, work, ov_bytes, hipMemcpyDeviceToHost, st));
-    FA_HIP_TRY(ctx, hipMemcpyAsync(h_acc.data(), work + ov_bytes, acc_bytes, hipMemcpyDeviceToHost, st));
-    FA_HIP_TRY(ctx, hipMemcpyAsync(h_map.data(), work + ov_bytes + acc_bytes, map_bytes, hipMemcpyDeviceToHost, st));
-    FA_HIP_TRY(ctx, hipStreamSynchronize(st));   // the call's one synchronisation
-    for (int32_t b = 0; b < B; ++b) {
-        counts[b].miss = h_acc[4 * b + 0];
-        counts[b].false_alarm = h_acc[4 * b + 1];
-        counts[b].confusion = h_acc[4 * b + 2];
-        counts[b].ref = h_acc[4 * b + 3];
-        for (int32_t h = 0; h < rec[b].H; ++h) mapping[mapping_range[b] + h] = h_map[static_cast<size_t>(kMaxLabels) * b + h];
-    }
-    return FA_SUCCESS;
-    });
-}
-
 }  // namespace
 
-extern "C" {
+namespace fa {
+namespace der {
 
-void fa_der_default_config(fa_der_config *cfg) {
-    if (!cfg) return;
-    cfg->frame_step = 0.01;   // DiarizationDER.compute's defaults (:55-56)
-    cfg->collar = 0.0;
+void launch_raster(hipStream_t stream, const DerArgs &a, const Plan &plan) {
+    if (plan.items > 0) hipLaunchKernelGGL(der_raster, dim3(static_cast<unsigned>(plan.raster_blocks)), dim3(kThreads), 0, stream, a, plan.items);
 }
 
-fa_status fa_der_score_batch(fa_ctx *ctx, const fa_der_config *cfg, const fa_der_segment *ref_segs, const int64_t *ref_range, const fa_der_segment *hyp_segs,
-                             const int64_t *hyp_range, int32_t batch, fa_der_counts *counts, int32_t *mapping, const int64_t *mapping_range, int64_t *overlap,
-                             int64_t overlap_capacity) {
-    return der_score(ctx, cfg, ref_segs, ref_range, hyp_segs, hyp_range, batch, counts, mapping, mapping_range, overlap, overlap_capacity);
+void launch_overlap(hipStream_t stream, const DerArgs &a, const Plan &plan) {
+    if (plan.ov_entries > 0)
+        hipLaunchKernelGGL(der_overlap, dim3((plan.max_words + kOverlapTileWords - 1) / kOverlapTileWords, a.B), dim3(kThreads), 0, stream, a);
 }
 
-}  // extern "C"
+void launch_assign(hipStream_t stream, const DerArgs &a) { hipLaunchKernelGGL(der_assign, dim3(a.B), dim3(kWave), 0, stream, a); }
+
+void launch_accumulate(hipStream_t stream, const DerArgs &a, const Plan &plan) {
+    hipLaunchKernelGGL(der_accumulate, dim3((plan.max_words + kAccTileWords - 1) / kAccTileWords, a.B), dim3(kThreads), 0, stream, a);
+}
+
+}  // namespace der
+}  // namespace fa

@@ -232,4 +232,27 @@ struct DeviceGuard {
     ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 
+// The bracket of fa_ctx_set_timing round the launches of a call: begin() and end() record the context's two events on its stream, read()
+// — behind the synchronisation that follows end() — puts the elapsed milliseconds into ctx->last_device_ms, or (an entry of several
+// passes) adds them to *sum and stores the sum.  Nothing happens while ctx->timing is off.  None of the three looks at hipGetLastError:
+// the entry's own check stays between its launches and end().
+struct DeviceTiming {
+    fa_ctx *ctx;
+    fa_status begin() {
+        if (ctx->timing) FA_HIP_TRY(ctx, hipEventRecord(ctx->tim_ev[0], ctx->stream));
+        return FA_SUCCESS;
+    }
+    fa_status end() {
+        if (ctx->timing) FA_HIP_TRY(ctx, hipEventRecord(ctx->tim_ev[1], ctx->stream));
+        return FA_SUCCESS;
+    }
+    fa_status read(double *sum = nullptr) {
+        if (!ctx->timing) return FA_SUCCESS;
+        float ms = 0.0f;
+        FA_HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->tim_ev[0], ctx->tim_ev[1]));
+        ctx->last_device_ms = sum ? (*sum += ms) : ms;
+        return FA_SUCCESS;
+    }
+};
+
 }  // namespace fa

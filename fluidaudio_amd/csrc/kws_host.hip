@@ -108,7 +108,7 @@ void order_by_class(const Problem &p, const std::vector<Job> &jobs, std::vector<
 
 // the launches of one job list that is ordered by class; the bracket for fa_ctx_set_timing adds up over the passes of a call
 fa_status launch_classes(fa_ctx *ctx, WalkArgs a, const Job *d_jobs, const int32_t (&n)[3]) {
-    if (ctx->timing) FA_HIP_TRY(ctx, hipEventRecord(ctx->tim_ev[0], ctx->stream));
+    FA_TRY(fa::DeviceTiming{ctx}.begin());
     int32_t base = 0;
     for (int c = 0; c < 3; ++c) {
         a.jobs = d_jobs + base; a.n_jobs = n[c]; a.job_base = base;
@@ -116,17 +116,7 @@ fa_status launch_classes(fa_ctx *ctx, WalkArgs a, const Job *d_jobs, const int32
         base += n[c];
     }
     FA_HIP_TRY(ctx, hipGetLastError());
-    if (ctx->timing) FA_HIP_TRY(ctx, hipEventRecord(ctx->tim_ev[1], ctx->stream));
-    return FA_SUCCESS;
-}
-
-fa_status add_elapsed(fa_ctx *ctx, double &device_ms) {   // after a synchronisation behind launch_classes
-    if (!ctx->timing) return FA_SUCCESS;
-    float ms = 0.0f;
-    FA_HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->tim_ev[0], ctx->tim_ev[1]));
-    device_ms += ms;
-    ctx->last_device_ms = device_ms;
-    return FA_SUCCESS;
+    return fa::DeviceTiming{ctx}.end();
 }
 
 // mergeOverlap (:374-391) on one job's candidates, which arrive in the order of their end samples
@@ -219,7 +209,7 @@ fa_status spot(fa_ctx *ctx, const float *lp, bool device, int32_t batch, int32_t
         state.resize(sizeof(unsigned long long) + sizeof(int32_t) * take);
         FA_HIP_TRY(ctx, hipMemcpyAsync(state.data(), b_state.p, state.size(), hipMemcpyDeviceToHost, st));
         FA_HIP_TRY(ctx, hipStreamSynchronize(st));
-        FA_TRY(add_elapsed(ctx, device_ms));
+        FA_TRY(fa::DeviceTiming{ctx}.read(&device_ms));
         unsigned long long cursor;
         std::memcpy(&cursor, state.data(), sizeof(cursor));
         const int32_t *status = reinterpret_cast<const int32_t *>(state.data() + sizeof(unsigned long long));
@@ -324,7 +314,7 @@ fa_status score_windows(fa_ctx *ctx, const float *lp, bool device, int32_t batch
     std::vector<Record> recs(J);
     FA_HIP_TRY(ctx, hipMemcpyAsync(recs.data(), b_out.p, sizeof(Record) * J, hipMemcpyDeviceToHost, st));
     FA_HIP_TRY(ctx, hipStreamSynchronize(st));   // the call's one synchronisation behind the uploads
-    FA_TRY(add_elapsed(ctx, device_ms));
+    FA_TRY(fa::DeviceTiming{ctx}.read(&device_ms));
     for (size_t i = 0; i < J; ++i) {
         fa_kws_detection &d = out[window_of[ids[i]]];
         d.score = recs[i].score; d.start_frame = recs[i].start; d.end_frame = recs[i].end;

@@ -9,26 +9,6 @@ namespace {
 
 namespace pf = fa::paraformer;
 
-struct Timing {   // fa_ctx_set_timing: the bracket round the kernels of a call
-    fa_ctx *ctx;
-    fa_status begin() {
-        if (ctx->timing) FA_HIP_TRY(ctx, hipEventRecord(ctx->tim_ev[0], ctx->stream));
-        return FA_SUCCESS;
-    }
-    fa_status end() {
-        FA_HIP_TRY(ctx, hipGetLastError());
-        if (ctx->timing) FA_HIP_TRY(ctx, hipEventRecord(ctx->tim_ev[1], ctx->stream));
-        return FA_SUCCESS;
-    }
-    fa_status read() {   // behind the synchronisation
-        if (!ctx->timing) return FA_SUCCESS;
-        float ms = 0.0f;
-        FA_HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->tim_ev[0], ctx->tim_ev[1]));
-        ctx->last_device_ms = ms;
-        return FA_SUCCESS;
-    }
-};
-
 std::vector<int32_t> clamped(const int32_t *valid_frames, const int32_t batch, const int32_t frames) {
     std::vector<int32_t> v(static_cast<size_t>(batch), frames);
     if (valid_frames)
@@ -80,9 +60,10 @@ fa_status cif(fa_ctx *ctx, const fa_paraformer_cif_config *cfg, const void *enc,
     a.w = b_w.as<float>(); a.seed = b_seed.as<float>(); a.fires = b_fires.as<int32_t>(); a.counts = b_counts.as<int32_t>();
     a.ac = device ? ac : b_ac.as<float>();
     a.enc_packed = !enc_packed ? nullptr : (device ? enc_packed : b_packed.as<float>());
-    Timing tim{ctx};
+    fa::DeviceTiming tim{ctx};
     FA_TRY(tim.begin());
     pf::launch_cif(st, a, pf::vector_width(s, a.enc, a.ac, a.enc_packed), dtype == FA_DTYPE_F16);
+    FA_HIP_TRY(ctx, hipGetLastError());
     FA_TRY(tim.end());
     std::vector<int32_t> counts(2 * B);
     FA_HIP_TRY(ctx, hipMemcpyAsync(counts.data(), b_counts.p, sizeof(int32_t) * 2 * B, hipMemcpyDeviceToHost, st));
@@ -162,9 +143,10 @@ fa_status timestamps(fa_ctx *ctx, const fa_paraformer_cif_config *cfg, const flo
     a.env_raw = b_raw.as<float>(); a.env = b_env.as<float>(); a.threshold = b_thr.as<float>();
     a.kept = b_kept.as<int32_t>(); a.fires = b_fires.as<int32_t>(); a.spacing = b_spacing.as<float>();
     a.spans = b_spans.as<pf::Span>(); a.span_counts = b_counts.as<int32_t>();
-    Timing tim{ctx};
+    fa::DeviceTiming tim{ctx};
     FA_TRY(tim.begin());
     pf::launch_stamps(st, a);
+    FA_HIP_TRY(ctx, hipGetLastError());
     FA_TRY(tim.end());
     std::vector<int32_t> counts(B);
     std::vector<pf::Span> got(B * mt);

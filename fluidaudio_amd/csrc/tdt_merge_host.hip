@@ -82,10 +82,11 @@ fa_status merge(fa_ctx *ctx, const fa_tdt_merge_config *cfg, const int32_t *tok,
     a.out_counts = b_res.as<int32_t>();
     a.statuses = a.out_counts + N;
 
-    if (ctx->timing) FA_HIP_TRY(ctx, hipEventRecord(ctx->tim_ev[0], st));
+    fa::DeviceTiming tim{ctx};
+    FA_TRY(tim.begin());
     mg::launch(st, a, plan.slots);
     FA_HIP_TRY(ctx, hipGetLastError());
-    if (ctx->timing) FA_HIP_TRY(ctx, hipEventRecord(ctx->tim_ev[1], st));
+    FA_TRY(tim.end());
     std::vector<int32_t> res(2 * N);
     FA_HIP_TRY(ctx, hipMemcpyAsync(res.data(), b_res.p, sizeof(int32_t) * 2 * N, hipMemcpyDeviceToHost, st));
     if (seam_routes && W) FA_HIP_TRY(ctx, hipMemcpyAsync(seam_routes + w0, b_routes.p, sizeof(int32_t) * W, hipMemcpyDeviceToHost, st));
@@ -96,11 +97,7 @@ fa_status merge(fa_ctx *ctx, const fa_tdt_merge_config *cfg, const int32_t *tok,
         FA_HIP_TRY(ctx, hipMemcpyAsync(out_conf + o0, a.out.conf, 4 * T, hipMemcpyDeviceToHost, st));
     }
     FA_HIP_TRY(ctx, hipStreamSynchronize(st));   // the call's one synchronisation
-    if (ctx->timing) {
-        float ms = 0.0f;
-        FA_HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->tim_ev[0], ctx->tim_ev[1]));
-        ctx->last_device_ms = ms;
-    }
+    FA_TRY(tim.read());
     std::copy(res.begin(), res.begin() + n, out_counts);
     std::copy(res.begin() + n, res.end(), statuses);
     return FA_SUCCESS;

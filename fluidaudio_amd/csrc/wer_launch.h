@@ -1,7 +1,8 @@
-// wer_launch.h — the host plan of the edit-distance kernel (wer.hip): the argument pass over the ranges, each pair's class and panel
-// count, the job list by class, the layout of the boundary workspace, and where in the wavefront a pair's answer ends up.  Plain C++
-// without a HIP call, shared by wer.hip and by tests/cpu/wer_emul.cpp, which walks the kernel's schedule on the host.  Internal; not
-// part of the C ABI.
+// wer_launch.h — the host plan of the edit-distance kernel (kernel: wer.hip, entries: wer_host.hip): the argument pass over the ranges,
+// each pair's class and panel count, the job list by class, the layout of the boundary workspace, where in the wavefront a pair's
+// answer ends up, and the kernel's operands.  Plain C++ without a HIP call, shared by the two units and by tests/cpu/wer_emul.cpp,
+// which walks the kernel's schedule on the host; only the launcher's declaration at the end is for hipcc alone.  Internal; not part
+// of the C ABI.
 //
 // One wavefront walks one pair.  Lane l owns a strip of C = 1, 2, 4, 8 or 16 consecutive reference columns (class 0 ... 4, the smallest
 // that covers the reference in one pass: up to 64 C columns); a reference of more than 1024 columns is walked panel by panel, 1024
@@ -101,6 +102,18 @@ inline void make_plan(const int64_t *hyp_range, const int64_t *ref_range, const 
                 plan.ws_ints += boundary_ints(j.m, j.panels);
             }
 }
+
+struct WalkArgs {               // the kernel's operands
+    const int32_t *hyp, *ref;
+    const Job *jobs;
+    int32_t n_jobs;
+    int32_t *ws;       // boundary buffers
+    int32_t *out;      // [n_jobs][4]: total, insertions, deletions, substitutions
+};
+
+#if defined(__HIPCC__)
+void launch_walk(hipStream_t stream, const WalkArgs &a, int cls);   // wer.hip: the jobs of class cls, strip_of(cls) columns per lane
+#endif
 
 }  // namespace wer
 }  // namespace fa

@@ -1,4 +1,4 @@
-"""Frame-wise diarization error rate with the optimal speaker mapping (csrc/der.hip): DiarizationDER.compute (reference:
+"""Frame-wise diarization error rate with the optimal speaker mapping (csrc/der.hip, csrc/der_host.hip): DiarizationDER.compute (reference:
 Sources/FluidAudio/Diarizer/DiarizationDER.swift:52-231, Diarizer/HungarianAssignment.swift:8-61), batched over recordings — the
 score the reference's Sortformer and LS-EEND benchmarks print (Sources/FluidAudioCLI/Commands/SortformerBenchmark.swift:622-640).
 

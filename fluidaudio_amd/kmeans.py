@@ -1,6 +1,6 @@
 """Host-side mirror of ``KMeansClustering`` and ``SpeakerCountConstraints`` (reference:
 Sources/FluidAudio/Diarizer/Offline/Clustering/KMeansClustering.swift:39-224, SpeakerCountConstraints.swift:6-77) over the HIP
-C ABI (csrc/kmeans.hip).  The n_init runs advance together on the device; the random draws are the reference's LCG through
+C ABI (csrc/kmeans.hip, csrc/kmeans_host.hip).  The n_init runs advance together on the device; the random draws are the reference's LCG through
 the Swift standard library's bounded draw (restated in the library, see include/fluidaudio_hip.h)."""
 from __future__ import annotations
 

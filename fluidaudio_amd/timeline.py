@@ -1,4 +1,4 @@
-"""The diarizer timeline (csrc/timeline.hip): DiarizerTimeline.rebuild (reference: Sources/FluidAudio/Diarizer/DiarizerTimeline.swift:945-1003,
+"""The diarizer timeline (csrc/timeline.hip, csrc/timeline_host.hip): DiarizerTimeline.rebuild (reference: Sources/FluidAudio/Diarizer/DiarizerTimeline.swift:945-1003,
 1169-1336), batched over recordings.  The offline Sortformer diarizer (sortformer.py) ends in it, the streaming Sortformer and LS-EEND
 diarizers call it as well, and der.py scores its records.
 

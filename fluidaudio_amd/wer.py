@@ -1,4 +1,4 @@
-"""Word and character error rates (csrc/wer.hip): WERCalculator.editDistance with its insertion / deletion / substitution breakdown
+"""Word and character error rates (csrc/wer.hip, csrc/wer_host.hip): WERCalculator.editDistance with its insertion / deletion / substitution breakdown
 (reference: Sources/FluidAudioCLI/Utils/WERCalculator.swift:178-239), StringUtils.levenshteinDistance (Sources/FluidAudio/Shared/
 StringUtils.swift:12-40) and the metrics the ASR benchmarks print from them (WERCalculator.swift:7-56), batched over (hypothesis,
 reference) pairs: one device call for a whole corpus, words and characters together.

@@ -1,4 +1,4 @@
-"""The offline Sortformer / timeline mirrors of include/fluidaudio.hpp (csrc/sortformer_host.hip, csrc/timeline.hip) from a C++ host built
+"""The offline Sortformer / timeline mirrors of include/fluidaudio.hpp (csrc/sortformer_host.hip, csrc/timeline_host.hip) from a C++ host built
 with g++ -Werror (tests/cabi/sortformer_host.cpp), against the numpy restatement (tests/sortformer_restatement.py): geometry, alignment,
 rounding and statuses on the CPU tier; DiarizerTimeline::rebuild on the GPU tier."""
 import os

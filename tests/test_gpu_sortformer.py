@@ -1,4 +1,4 @@
-"""csrc/sortformer.hip, csrc/sortformer_host.hip and csrc/timeline.hip on the device against tests/sortformer_restatement.py, bit for bit: np.array_equal on the fp32 arrays viewed as
+"""csrc/sortformer.hip, csrc/sortformer_host.hip, csrc/timeline.hip and csrc/timeline_host.hip on the device against tests/sortformer_restatement.py, bit for bit: np.array_equal on the fp32 arrays viewed as
 uint32 and on every integer field.  There are no tolerances here."""
 import ctypes as C
 import os

@@ -1,4 +1,4 @@
-"""fa_edit_distance_batch / fa_edit_distance_batch_dev (csrc/wer.hip) on the device against the restatement with the full table and the
+"""fa_edit_distance_batch / fa_edit_distance_batch_dev (csrc/wer.hip, csrc/wer_host.hip) on the device against the restatement with the full table and the
 traceback (tests/wer_restatement.py).  No tolerances: all four integers and both lengths of every pair.  The same file is run on the
 poisoned-workspace library (make POISON=1).  The restatement fills fewer than 3e6 table cells for the whole file, once."""
 import os
