@@ -129,12 +129,14 @@ def ctc_greedy_decode(log_probs, vocabulary: dict[int, str], blank_id: int = 102
 def ctc_log_probs_dev(ctx, d_logits, temperature: float = 1.0, blank_bias: float = 0.0, blank_id: int = -1, d_out=None,
                       order: bool = True):
     """makeLogProbs (CtcKeywordSpotter+Inference.swift:350-405) for a batch: d_logits torch CUDA [B, T, V] fp32/fp16
-    (last dim contiguous) -> float32 CUDA tensor [B, T, V].  Enqueues on ctx.stream."""
+    (last dim contiguous) -> float32 CUDA tensor [B, T, V]: d_out (contiguous, on the logits' device) or a new one.  Enqueues on ctx.stream."""
     import torch
     B, T, V = d_logits.shape
-    assert d_logits.stride(2) == 1
+    assert d_logits.stride(2) == 1 and d_logits.dtype in (torch.float32, torch.float16)
     if d_out is None:
         d_out = torch.empty((B, T, V), dtype=torch.float32, device=d_logits.device)
+    assert d_out.dtype == torch.float32 and d_out.shape == (B, T, V) and d_out.is_contiguous() and d_out.device == d_logits.device, \
+        "d_out must be a contiguous float32 [B, T, V] tensor on the logits' device (the kernels write B * T * V floats behind its pointer)"
     dt = L.DTYPE_F16 if d_logits.dtype == torch.float16 else L.DTYPE_F32
     with ctx.torch_ordered(order):
         ctx.check(L.lib().fa_ctc_log_softmax_batch_dev(ctx.handle, C.c_void_p(d_logits.data_ptr()), dt, B, T, V, d_logits.stride(1),
