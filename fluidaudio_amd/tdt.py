@@ -71,13 +71,21 @@ class TdtDurationMapping:
 
 def decode_logits(d_logits, vocab_with_blank: int, enc_len, audio_frames=None, t0=None, is_last=None, global_offset=None, emit_after=None,
                   config: TdtConfig | None = None, max_out: int = 256, ctx: L.Context | None = None):
-    """Batched greedy walk on joint LOGITS: d_logits torch CUDA tensor [B, U, T, W] (fp32 / fp16, last dim contiguous, W >=
-    vocab_with_blank + number of duration bins).  Same result structure as decode_tables."""
+    """Batched greedy walk on joint LOGITS.  d_logits: a contiguous torch CUDA tensor [B, U, T, W] of float32 or float16 — any other dtype
+    is refused, the entry has no code for it — with W >= vocab_with_blank + len(config.duration_bins): a row holds the token logits, the
+    duration logits behind them, and W - that many elements of padding the walk never reads.  Its first element may lie at any address a
+    tensor of its dtype can have (a view into a larger allocation is fine).  Same result structure as decode_tables."""
     import torch
     ctx = ctx or L.default_context()
-    cfg = (config or TdtConfig()).c()
+    config = config or TdtConfig()
+    cfg = config.c()
+    assert isinstance(d_logits, torch.Tensor) and d_logits.is_cuda, "decode_logits: d_logits must be a CUDA tensor"
+    assert d_logits.dtype in (torch.float16, torch.float32), f"decode_logits: d_logits must be float16 or float32, not {d_logits.dtype}"
+    assert d_logits.dim() == 4, f"decode_logits: d_logits must be [B, U, T, W], not {tuple(d_logits.shape)}"
     B, U, T, W = d_logits.shape
-    assert d_logits.is_contiguous()
+    assert W >= int(vocab_with_blank) + len(config.duration_bins), \
+        f"decode_logits: rows of {W} logits cannot hold {int(vocab_with_blank)} token and {len(config.duration_bins)} duration logits"
+    assert d_logits.is_contiguous(), "decode_logits: d_logits must be contiguous"
     dev = d_logits.device
 
     def vec(v):

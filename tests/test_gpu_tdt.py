@@ -1,8 +1,23 @@
 """TDT greedy control loop on the device vs the CPU restatement, over random joint-decision tables."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import tdt_logits_restatement as R  # noqa: E402
+
 pytestmark = pytest.mark.gpu
+
+
+def within_bound(got, ref, V1, W, dtype):
+    """The elementwise bound of tests/tdt_logits_restatement.py beside the flat rtol: |confidence - reference| <= tolerance, for a contiguous,
+    16-byte aligned matrix of rows of W logits (fp16 rows of even W are read as pairs); half an ulp more for the float32 table the oracle
+    reads its probability from.  A reference of 0 (an undefined probability after the clamp) has to be met exactly."""
+    form = "streaming" if V1 > R.FITS_LOGITS else ("pairs" if dtype == "float16" and W % 2 == 0 else "registers")
+    ref = np.asarray(ref, np.float64)
+    return bool((np.abs(np.asarray(got, np.float64) - ref) <= R.tolerance(ref, V1, form) + 2.0 ** -25 * ref).all())
 
 
 @pytest.mark.parametrize("B,U,T,p_blank,seed", [(64, 40, 60, 0.7, 0), (200, 160, 188, 0.85, 1), (32, 12, 30, 0.3, 2)])
@@ -74,6 +89,7 @@ def test_walk_on_joint_logits_equals_walk_on_tables(fa, gpu_ctx, oracle_mod, dty
         for k in ("tokens", "timestamps", "durations"):
             np.testing.assert_array_equal(g[k], ref[k])
         np.testing.assert_allclose(g["confidences"], ref["confidences"], rtol=2e-5, atol=1e-7)
+        assert within_bound(g["confidences"], ref["confidences"], V1, V1 + nd, dtype), b
     assert sum(g["count"] for g in got) > B
 
 
@@ -127,6 +143,7 @@ def test_logits_walk_every_row_form_and_every_option(fa, gpu_ctx, oracle_mod, dt
             for k in ("tokens", "timestamps", "durations"):
                 np.testing.assert_array_equal(g[k], ref[k])
             np.testing.assert_allclose(g["confidences"], ref["confidences"], rtol=3e-5, atol=1e-7)
+            assert within_bound(g["confidences"], ref["confidences"], V1, V1 + nd, dtype), (b, max_out)
         assert 0 in statuses
         if max_out == 64:
             assert sum(g["count"] for g in got) > B // 2        # the rows do produce tokens
@@ -205,7 +222,7 @@ def rare_reference(oracle_mod, symbols, blank, prob):
     return tk, bn, enc, af, t0, last, goff, ea, ref
 
 
-def rare_compare(got, ref, exact):
+def rare_compare(got, ref, exact, bound=None):
     for b in range(RARE_B):
         g, r = got[b], ref[b]
         assert (g["status"], g["count"], g["final_u"], g["final_time"]) == (r["status"], r["count"], r["final_u"], r["final_time"]), b
@@ -215,6 +232,7 @@ def rare_compare(got, ref, exact):
             np.testing.assert_array_equal(g["confidences"], r["confidences"], err_msg=str(b))
         else:
             np.testing.assert_allclose(g["confidences"], r["confidences"], rtol=3e-5, atol=1e-7, err_msg=str(b))
+            assert within_bound(g["confidences"], r["confidences"], *bound), b
 
 
 # max_symbols_per_step = 3 with 4 tokens per chunk and 2 blanks in a row; = 2 as well, the largest value at which the force-advance can fire at all
@@ -251,4 +269,4 @@ def test_rare_rules_on_logits(fa, gpu_ctx, oracle_mod, symbols, V1, dtype):
     tk, bn, enc, af, t0, last, goff, ea, ref = rare_reference(oracle_mod, symbols, blank, pr)
     cfg = fa.TdtConfig(blank_id=blank, max_symbols_per_step=symbols, max_tokens_per_chunk=RARE_TOKENS, consecutive_blank_limit=RARE_BLANKS)
     got = fa.tdt_decode_logits(torch.from_numpy(lg).cuda(), V1, enc, af, t0, last, goff, ea, config=cfg, max_out=16, ctx=gpu_ctx)
-    rare_compare(got, ref, exact=False)
+    rare_compare(got, ref, exact=False, bound=(V1, V1 + nd, dtype))
