@@ -90,8 +90,8 @@ fa_status fa_ahc_linkage_batch(fa_ctx *ctx, int32_t count, const double *const *
             if (st[k] != FA_SUCCESS || trivial) continue;
             nn[k] = n[k];
             if (device_pointers) { d_in[k] = data[k]; d_z[k] = dendrograms[k]; continue; }
-            if (bufs[2 * k].alloc(sizeof(double) * n[k] * d) != hipSuccess || bufs[2 * k + 1].alloc(sizeof(double) * 4 * (n[k] - 1)) != hipSuccess) {
-                (void)hipGetLastError();
+            // a problem without room fails alone; a failing upload below ends the call
+            if (fa::take_once(ctx, "linkage batch", {{&bufs[2 * k], sizeof(double) * n[k] * d}, {&bufs[2 * k + 1], sizeof(double) * 4 * (n[k] - 1)}}) != FA_SUCCESS) {
                 st[k] = FA_ALLOCATION_FAILURE; nn[k] = 0;
                 continue;
             }
@@ -360,11 +360,7 @@ extern "C" fa_status fa_ahc_row_minima(fa_ctx *ctx, const double *x, size_t n, s
     double *d_m = mins;
     int32_t *d_a = args;
     if (!device_pointers) {
-        if (bx.alloc(sizeof(double) * n * d) != hipSuccess || bm.alloc(sizeof(double) * rows) != hipSuccess || ba.alloc(sizeof(int32_t) * rows) != hipSuccess) {
-            (void)hipGetLastError();
-            return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "row minima: device allocation failed");
-        }
-        FA_HIP_TRY(ctx, hipMemcpyAsync(bx.p, x, sizeof(double) * n * d, hipMemcpyHostToDevice, ctx->stream));
+        FA_TRY(fa::take_once(ctx, "row minima", {{&bx, sizeof(double) * n * d, true, x}, {&bm, sizeof(double) * rows}, {&ba, sizeof(int32_t) * rows}}));
         d_x = bx.as<double>(); d_m = bm.as<double>(); d_a = ba.as<int32_t>();
     }
     hipLaunchKernelGGL(slab_row_minima_kernel, dim3(static_cast<unsigned>((rows + kSlabT - 1) / kSlabT)), dim3(256), 0, ctx->stream, d_x, static_cast<int>(n),

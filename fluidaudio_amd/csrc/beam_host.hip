@@ -239,13 +239,12 @@ fa_status fa_ctc_beam_search_batch_dev(fa_ctx *ctx, const float *d_log_probs, in
     a.row_stride = row_stride; a.matrix_stride = matrix_stride; a.arena_stride = plan.stride;
     a.frames = frames; a.vocab = vocab; a.blank = blank_id; a.beam_width = beam_width; a.top_k = token_candidates;
     a.use_lm = lm != nullptr; a.lm_weight = lm_weight; a.word_bonus = word_bonus;
-    fa::DevBuf d_arena;   // the tries of one launch
-    FA_HIP_TRY(ctx, d_arena.alloc(ctx, static_cast<size_t>(plan.per) * plan.chunk));   // the context's buffer cache: a second call pays no hipMalloc
-    a.arena = d_arena.as<unsigned long long>();
-    // the pre-pass' table of one launch: K (token, log-prob) pairs + the blank's log-prob per frame
-    fa::DevBuf d_top;
+    // d_arena: the tries of one launch; d_top: the pre-pass' table of one launch, K (token, log-prob) pairs + the blank's log-prob per frame.
+    // From the context's buffer cache: a second call pays no hipMalloc
+    fa::DevBuf d_arena, d_top;
     const size_t rows_max = static_cast<size_t>(plan.chunk) * std::max(frames, 1);
-    FA_HIP_TRY(ctx, d_top.alloc(ctx, sizeof(TopEntry) * rows_max * (token_candidates + 1)));
+    FA_TRY(fa::take(ctx, "beam search", {{&d_arena, static_cast<size_t>(plan.per) * plan.chunk}, {&d_top, sizeof(TopEntry) * rows_max * (token_candidates + 1)}}));
+    a.arena = d_arena.as<unsigned long long>();
     a.top = d_top.as<TopEntry>();
     TopArgs ta{};
     ta.logp = d_log_probs; ta.valid = d_valid_frames; ta.tok = a.tok; ta.top = d_top.as<TopEntry>();
@@ -289,15 +288,9 @@ fa_status fa_ctc_beam_search_batch(fa_ctx *ctx, const float *log_probs, int32_t 
     fa::DeviceGuard guard(ctx->device);
     const size_t n = static_cast<size_t>(batch) * frames * vocab;
     fa::DevBuf d_lp, d_valid, d_tok, d_len, d_sc;
-    FA_HIP_TRY(ctx, d_lp.alloc(sizeof(float) * n));
-    FA_HIP_TRY(ctx, d_tok.alloc(sizeof(int32_t) * static_cast<size_t>(batch) * std::max(frames, 1)));
-    FA_HIP_TRY(ctx, d_len.alloc(sizeof(int32_t) * batch));
-    FA_HIP_TRY(ctx, d_sc.alloc(sizeof(float) * batch));
-    if (n) FA_HIP_TRY(ctx, hipMemcpyAsync(d_lp.p, log_probs, sizeof(float) * n, hipMemcpyHostToDevice, ctx->stream));
-    if (valid_frames) {
-        FA_HIP_TRY(ctx, d_valid.alloc(sizeof(int32_t) * batch));
-        FA_HIP_TRY(ctx, hipMemcpyAsync(d_valid.p, valid_frames, sizeof(int32_t) * batch, hipMemcpyHostToDevice, ctx->stream));
-    }
+    FA_TRY(fa::take_once(ctx, "beam search", {{&d_lp, sizeof(float) * n, true, log_probs}, {&d_tok, sizeof(int32_t) * static_cast<size_t>(batch) * std::max(frames, 1)},
+                                              {&d_len, sizeof(int32_t) * batch}, {&d_sc, sizeof(float) * batch},
+                                              {&d_valid, sizeof(int32_t) * batch, valid_frames != nullptr, valid_frames}}));
     FA_TRY(fa_ctc_beam_search_batch_dev(ctx, d_lp.as<float>(), batch, frames, vocab, vocab, static_cast<int64_t>(frames) * vocab,
                                         valid_frames ? d_valid.as<int32_t>() : nullptr, vocabulary, lm, beam_width, lm_weight, word_bonus, blank_id,
                                         token_candidates, d_tok.as<int32_t>(), d_len.as<int32_t>(), d_sc.as<float>()));

@@ -7,7 +7,7 @@ namespace {
 
 using namespace fa::ctc;
 
-// a HIP call of a host-pointer entry: failures are reported under the entry's name
+// a copy or synchronisation of a host-pointer entry: failures are reported under the entry's name
 #define FA_CTC_HIP(ctx, entry, expr) FA_TRY(::fa::hip_status((ctx), (expr), (entry)))
 
 fa_status check_args(fa_ctx *ctx, const void *logits, int dtype, int batch, int frames, int vocab, int64_t row_stride,
@@ -41,11 +41,8 @@ fa_status stage_batch(fa_ctx *ctx, const char *entry, const void *logits, int32_
     b.in_bytes = frames > 0 ? (static_cast<size_t>(batch - 1) * matrix_stride + static_cast<size_t>(frames - 1) * row_stride + vocab) * esz : 0;
     b.id_bytes = sizeof(int32_t) * static_cast<size_t>(batch) * (frames > 0 ? frames : 1);
     b.len_bytes = sizeof(int32_t) * batch;
-    FA_CTC_HIP(ctx, entry, b.in.alloc(b.in_bytes));
-    FA_CTC_HIP(ctx, entry, b.tok.alloc(b.id_bytes));
-    FA_CTC_HIP(ctx, entry, b.len.alloc(b.len_bytes));
-    if (want_frame_ids) FA_CTC_HIP(ctx, entry, b.fid.alloc(b.id_bytes));
-    if (valid_frames) FA_CTC_HIP(ctx, entry, b.valid.alloc(b.len_bytes));
+    FA_TRY(fa::take_once(ctx, entry, {{&b.in, b.in_bytes}, {&b.tok, b.id_bytes}, {&b.len, b.len_bytes}, {&b.fid, b.id_bytes, want_frame_ids},
+                                      {&b.valid, b.len_bytes, valid_frames != nullptr}}));
     if (b.in_bytes) FA_CTC_HIP(ctx, entry, hipMemcpyAsync(b.in.p, logits, b.in_bytes, hipMemcpyHostToDevice, ctx->stream));
     if (valid_frames) FA_CTC_HIP(ctx, entry, hipMemcpyAsync(b.valid.p, valid_frames, b.len_bytes, hipMemcpyHostToDevice, ctx->stream));
     return FA_SUCCESS;
@@ -69,12 +66,8 @@ fa_status stage_rows(fa_ctx *ctx, const char *entry, const float *values, int64_
                      const int64_t *utt_rows, int32_t batch, bool want_frame_ids, RowsBuffers &b) {
     const size_t id_bytes = sizeof(int32_t) * static_cast<size_t>(total_rows > 0 ? total_rows : 1);
     const size_t off_bytes = sizeof(int64_t) * static_cast<size_t>(total_rows + 1), utt_bytes = sizeof(int64_t) * (static_cast<size_t>(batch) + 1);
-    FA_CTC_HIP(ctx, entry, b.val.alloc(sizeof(float) * static_cast<size_t>(n_values > 0 ? n_values : 1)));
-    FA_CTC_HIP(ctx, entry, b.off.alloc(off_bytes));
-    FA_CTC_HIP(ctx, entry, b.tok.alloc(id_bytes));
-    FA_CTC_HIP(ctx, entry, b.len.alloc(sizeof(int32_t) * batch));
-    if (want_frame_ids) FA_CTC_HIP(ctx, entry, b.fid.alloc(id_bytes));
-    if (utt_rows) FA_CTC_HIP(ctx, entry, b.utt.alloc(utt_bytes));
+    FA_TRY(fa::take_once(ctx, entry, {{&b.val, sizeof(float) * static_cast<size_t>(n_values > 0 ? n_values : 1)}, {&b.off, off_bytes}, {&b.tok, id_bytes},
+                                      {&b.len, sizeof(int32_t) * batch}, {&b.fid, id_bytes, want_frame_ids}, {&b.utt, utt_bytes, utt_rows != nullptr}}));
     if (n_values > 0) FA_CTC_HIP(ctx, entry, hipMemcpyAsync(b.val.p, values, sizeof(float) * static_cast<size_t>(n_values), hipMemcpyHostToDevice, ctx->stream));
     if (total_rows > 0) FA_CTC_HIP(ctx, entry, hipMemcpyAsync(b.off.p, row_offsets, off_bytes, hipMemcpyHostToDevice, ctx->stream));
     if (utt_rows) FA_CTC_HIP(ctx, entry, hipMemcpyAsync(b.utt.p, utt_rows, utt_bytes, hipMemcpyHostToDevice, ctx->stream));

@@ -168,7 +168,7 @@ hipError_t devbuf_take(fa_ctx *ctx, size_t bytes, void **p, size_t *cap) {
     if (e != hipSuccess) {   // HBM pressure: every idle byte the library holds on this device goes (the caches of ALL its contexts, idle linkage workspaces)
         (void)hipGetLastError();
         (void)release_idle_device_memory(ctx, ctx->device);
-        e = hipMalloc(p, want);
+        e = fault_hit(FA_FAULT_DEVBUF_MALLOC) ? hipErrorOutOfMemory : hipMalloc(p, want);   // armed twice: the request fails for good
     }
     *cap = want;
     if (e == hipSuccess) poison(ctx, *p, want);

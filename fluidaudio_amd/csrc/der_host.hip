@@ -29,17 +29,11 @@ fa_status der_score(fa_ctx *ctx, const fa_der_config *cfg, const fa_der_segment 
     fa::DeviceGuard guard(ctx->device);
     hipStream_t st = ctx->stream;
     fa::DevBuf b_ref, b_hyp, b_rec, b_planes, b_work;
-    auto alloc = [&](fa::DevBuf &b, size_t bytes) { return b.alloc(ctx, bytes) == hipSuccess; };
     // b_work: the overlap tables, the accumulators, then the mappings — what comes back to the host, in one buffer
     const size_t ov_bytes = sizeof(int64_t) * ov_entries, acc_bytes = sizeof(int64_t) * 4 * B, map_bytes = sizeof(int32_t) * kMaxLabels * static_cast<size_t>(B);
-    if (!alloc(b_ref, sizeof(fa_der_segment) * n_ref) || !alloc(b_hyp, sizeof(fa_der_segment) * n_hyp) || !alloc(b_rec, sizeof(DerRec) * B) ||
-        !alloc(b_planes, sizeof(uint64_t) * plane_words) || !alloc(b_work, ov_bytes + acc_bytes + map_bytes)) {
-        (void)hipGetLastError();
-        return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "der: device allocation failed");
-    }
-    if (n_ref > 0) FA_HIP_TRY(ctx, hipMemcpyAsync(b_ref.p, ref + plan.r0, sizeof(fa_der_segment) * n_ref, hipMemcpyHostToDevice, st));
-    if (n_hyp > 0) FA_HIP_TRY(ctx, hipMemcpyAsync(b_hyp.p, hyp + plan.h0, sizeof(fa_der_segment) * n_hyp, hipMemcpyHostToDevice, st));
-    FA_HIP_TRY(ctx, hipMemcpyAsync(b_rec.p, rec.data(), sizeof(DerRec) * B, hipMemcpyHostToDevice, st));
+    FA_TRY(fa::take(ctx, "der", {{&b_ref, sizeof(fa_der_segment) * n_ref, true, ref + plan.r0}, {&b_hyp, sizeof(fa_der_segment) * n_hyp, true, hyp + plan.h0},
+                                 {&b_rec, sizeof(DerRec) * B, true, rec.data()}, {&b_planes, sizeof(uint64_t) * plane_words},
+                                 {&b_work, ov_bytes + acc_bytes + map_bytes}}));
     FA_HIP_TRY(ctx, hipMemsetAsync(b_planes.p, 0, sizeof(uint64_t) * plane_words, st));
     FA_HIP_TRY(ctx, hipMemsetAsync(b_work.p, 0, ov_bytes + acc_bytes, st));   // der_assign writes every mapping entry it owns
     char *work = b_work.as<char>();

@@ -5,7 +5,6 @@
 // one body each; `device` says which of the caller's pointers are device memory.
 #include <algorithm>
 #include <cstring>
-#include <initializer_list>
 #include <vector>
 
 #include "embedding_launch.h"
@@ -13,21 +12,6 @@
 namespace {
 
 using namespace fa::embedding;
-
-// buffers of one call, taken from the context in the order listed; the one allocation-failure branch of this unit
-struct Take {
-    fa::DevBuf *buf;
-    size_t bytes;
-    bool wanted = true;
-};
-fa_status take(fa_ctx *ctx, const char *what, std::initializer_list<Take> list) {
-    for (const Take &t : list) {
-        if (!t.wanted || t.buf->alloc(ctx, t.bytes) == hipSuccess) continue;
-        (void)hipGetLastError();
-        return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "%s: device allocation failed", what);
-    }
-    return FA_SUCCESS;
-}
 
 // ---------------------------------------------------------------- fa_embedding_plan
 
@@ -96,16 +80,12 @@ struct PlanBuffers {
 fa_status stage_plan(fa_ctx *ctx, const PlanCall &c, const Plan &p, PlanBuffers &b) {
     hipStream_t st = ctx->stream;
     const size_t wbytes = sizeof(float) * c.C * c.F * c.S, idx = sizeof(int32_t) * p.items;
-    FA_TRY(take(ctx, "embedding plan", {{&b.w, wbytes, !c.device}, {&b.chunk, sizeof(int32_t) * p.nw}, {&b.rec, sizeof(ItemRec) * p.items},
-                                        {&b.masks, sizeof(float) * p.items * c.F, c.cfg->skip_enabled != 0}, {&b.flags, sizeof(int32_t) * 4},
-                                        {&b.bsum, sizeof(int32_t) * select_blocks(p.items)}, {&b.job_of_item, idx}, {&b.item_of_job, idx}, {&b.is_run, idx},
-                                        {&b.src, idx}, {&b.run_of_src, idx}, {&b.job_of_run, idx}, {&b.run_of_job, idx}, {&b.window_of_run, idx}}));
-    b.d_w = c.weights;
-    if (!c.device) {
-        FA_HIP_TRY(ctx, hipMemcpyAsync(b.w.p, c.weights, wbytes, hipMemcpyHostToDevice, st));
-        b.d_w = b.w.as<float>();
-    }
-    FA_HIP_TRY(ctx, hipMemcpyAsync(b.chunk.p, p.win.chunk.data(), sizeof(int32_t) * p.nw, hipMemcpyHostToDevice, st));
+    FA_TRY(fa::take(ctx, "embedding plan", {{&b.w, wbytes, !c.device, c.weights}, {&b.chunk, sizeof(int32_t) * p.nw, true, p.win.chunk.data()},
+                                            {&b.rec, sizeof(ItemRec) * p.items}, {&b.masks, sizeof(float) * p.items * c.F, c.cfg->skip_enabled != 0},
+                                            {&b.flags, sizeof(int32_t) * 4}, {&b.bsum, sizeof(int32_t) * select_blocks(p.items)}, {&b.job_of_item, idx},
+                                            {&b.item_of_job, idx}, {&b.is_run, idx}, {&b.src, idx}, {&b.run_of_src, idx}, {&b.job_of_run, idx},
+                                            {&b.run_of_job, idx}, {&b.window_of_run, idx}}));
+    b.d_w = c.device ? c.weights : b.w.as<float>();
     FA_HIP_TRY(ctx, hipMemsetAsync(b.flags.p, 0, sizeof(int32_t) * 4, st));
     return FA_SUCCESS;
 }
@@ -135,7 +115,7 @@ fa_status write_rows(fa_ctx *ctx, const PlanCall &c, const Plan &p, PlanBuffers 
     b.d_rows = c.run_weights;
     b.d_mrows = c.mask_rows;
     if (!c.device) {
-        FA_TRY(take(ctx, "embedding plan", {{&b.rows, sizeof(float) * runs * p.g.W, runs > 0}, {&b.mrows, sizeof(float) * jobs * c.F, c.mask_rows && jobs > 0}}));
+        FA_TRY(fa::take(ctx, "embedding plan", {{&b.rows, sizeof(float) * runs * p.g.W, runs > 0}, {&b.mrows, sizeof(float) * jobs * c.F, c.mask_rows && jobs > 0}}));
         b.d_rows = b.rows.as<float>();
         b.d_mrows = c.mask_rows ? b.mrows.as<float>() : nullptr;
     }
@@ -235,15 +215,12 @@ fa_status span_inputs(fa_ctx *ctx, const fa_embedding_config *cfg, const float *
     fa::DeviceGuard guard(ctx->device);
     hipStream_t st = ctx->stream;
     fa::DevBuf b_audio, b_start, b_len, b_active, b_win, b_w;
-    FA_TRY(take(ctx, "span inputs", {{&b_audio, sizeof(float) * total_samples, !device && total_samples > 0}, {&b_start, sizeof(int64_t) * n},
-                                     {&b_len, sizeof(int64_t) * n}, {&b_active, sizeof(int32_t) * n}, {&b_win, sizeof(float) * n * g.spw, !device},
-                                     {&b_w, sizeof(float) * n * g.W, !device}}));
+    FA_TRY(fa::take(ctx, "span inputs", {{&b_audio, sizeof(float) * total_samples, !device && total_samples > 0, audio},
+                                         {&b_start, sizeof(int64_t) * n, true, start.data()}, {&b_len, sizeof(int64_t) * n, true, len.data()},
+                                         {&b_active, sizeof(int32_t) * n, true, active.data()}, {&b_win, sizeof(float) * n * g.spw, !device},
+                                         {&b_w, sizeof(float) * n * g.W, !device}}));
     const float *d_audio = device ? audio : b_audio.as<float>();
     float *d_win = device ? windows : b_win.as<float>(), *d_w = device ? weights : b_w.as<float>();
-    if (!device && total_samples > 0) FA_HIP_TRY(ctx, hipMemcpyAsync(b_audio.p, audio, sizeof(float) * total_samples, hipMemcpyHostToDevice, st));
-    FA_HIP_TRY(ctx, hipMemcpyAsync(b_start.p, start.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice, st));
-    FA_HIP_TRY(ctx, hipMemcpyAsync(b_len.p, len.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice, st));
-    FA_HIP_TRY(ctx, hipMemcpyAsync(b_active.p, active.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
     launch_windows(st, d_audio, b_start.as<int64_t>(), b_len.as<int64_t>(), n, g.spw, d_win);
     launch_spans(st, b_active.as<int32_t>(), n, g.W, d_w);
     FA_HIP_TRY(ctx, hipGetLastError());
@@ -269,8 +246,7 @@ fa_status weight_resample(fa_ctx *ctx, const float *in, int64_t rows, int32_t n_
     const float *d_in = in;
     float *d_out = out;
     if (!device) {
-        FA_TRY(take(ctx, "weight resample", {{&b_in, sizeof(float) * rows * n_in}, {&b_out, sizeof(float) * rows * n_out}}));
-        FA_HIP_TRY(ctx, hipMemcpyAsync(b_in.p, in, sizeof(float) * rows * n_in, hipMemcpyHostToDevice, st));
+        FA_TRY(fa::take(ctx, "weight resample", {{&b_in, sizeof(float) * rows * n_in, true, in}, {&b_out, sizeof(float) * rows * n_out}}));
         d_in = b_in.as<float>();
         d_out = b_out.as<float>();
     }
@@ -337,8 +313,7 @@ fa_status fa_embedding_windows_dev(fa_ctx *ctx, const float *d_audio, int64_t to
         fa::DeviceGuard guard(ctx->device);
         hipStream_t st = ctx->stream;
         fa::DevBuf b;
-        FA_TRY(take(ctx, "embedding windows", {{&b, sizeof(int64_t) * 2 * count}}));
-        FA_HIP_TRY(ctx, hipMemcpyAsync(b.p, sl.data(), sizeof(int64_t) * 2 * count, hipMemcpyHostToDevice, st));
+        FA_TRY(fa::take(ctx, "embedding windows", {{&b, sizeof(int64_t) * 2 * count, true, sl.data()}}));
         launch_windows(st, d_audio, b.as<int64_t>(), b.as<int64_t>() + count, count, samples_per_window, d_out);
         FA_HIP_TRY(ctx, hipGetLastError());
         FA_HIP_TRY(ctx, hipStreamSynchronize(st));   // the pageable staging above lives until the copy has been read

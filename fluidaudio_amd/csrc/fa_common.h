@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <new>
 #include <string>
@@ -186,6 +187,28 @@ struct DevBuf {
     }
     template <class T> T *as() const { return static_cast<T *>(p); }
 };
+
+// The device buffers a host entry takes, as one ordered list: take() (the context's buffer cache) and take_once() (one-call hipMalloc)
+// take the wanted ones in list order and hold the one allocation-failure branch of the library; with the whole list taken, every entry
+// with a host source and bytes != 0 is filled from it on ctx->stream — the source has to live until the call's synchronisation.
+struct Take {
+    DevBuf *buf;
+    size_t bytes;
+    bool wanted = true;
+    const void *host = nullptr;
+};
+inline fa_status take_list(fa_ctx *ctx, const char *what, std::initializer_list<Take> list, const bool cached) {
+    for (const Take &t : list) {
+        if (!t.wanted || (cached ? t.buf->alloc(ctx, t.bytes) : t.buf->alloc(t.bytes)) == hipSuccess) continue;
+        (void)hipGetLastError();
+        return set_error(ctx, FA_ALLOCATION_FAILURE, "%s: device allocation failed", what);
+    }
+    for (const Take &t : list)
+        if (t.wanted && t.host && t.bytes) FA_TRY(hip_status(ctx, hipMemcpyAsync(t.buf->p, t.host, t.bytes, hipMemcpyHostToDevice, ctx->stream), what));
+    return FA_SUCCESS;
+}
+inline fa_status take(fa_ctx *ctx, const char *what, std::initializer_list<Take> list) { return take_list(ctx, what, list, true); }
+inline fa_status take_once(fa_ctx *ctx, const char *what, std::initializer_list<Take> list) { return take_list(ctx, what, list, false); }
 
 fa_status ensure_scratch(fa_ctx *ctx, size_t bytes);
 

@@ -34,7 +34,7 @@ fa_status lloyd_batch(fa_ctx *ctx, LloydArgs a, int max_iter, const uint64_t *se
     for (int r = 0; r < runs; ++r) draw_picks(rng[r], n, h_picks.data() + static_cast<size_t>(r) * kPicks);
     fa::DevBuf d_book;
     const size_t book_ints = static_cast<size_t>(3) * runs + 2;
-    FA_HIP_TRY(ctx, d_book.alloc(sizeof(int32_t) * (book_ints + h_picks.size())));
+    FA_TRY(fa::take_once(ctx, "kmeans", {{&d_book, sizeof(int32_t) * (book_ints + h_picks.size())}}));
     a.done = d_book.as<int32_t>();
     a.iters = a.done + runs;
     a.cursor = a.iters + runs;
@@ -83,15 +83,9 @@ fa_status kmeans_device(fa_ctx *ctx, const double *emb, int64_t n, int d, int k,
     for (int r0 = 0; r0 < runs; r0 += kMaxRuns) {
         const int nr = std::min(kMaxRuns, runs - r0);
         Buffers b;
-        FA_HIP_TRY(ctx, b.x.alloc(sizeof(double) * n * d));
-        FA_HIP_TRY(ctx, b.xn.alloc(sizeof(double) * n * d));
-        FA_HIP_TRY(ctx, b.xt.alloc(sizeof(double) * n * d));
-        FA_HIP_TRY(ctx, b.cen.alloc(sizeof(double) * nr * k * d));
-        FA_HIP_TRY(ctx, b.assign.alloc(sizeof(int32_t) * nr * n));
-        FA_HIP_TRY(ctx, b.changed.alloc(sizeof(int32_t) * nr));
-        FA_HIP_TRY(ctx, b.counts.alloc(sizeof(int32_t) * nr * k));
-        FA_HIP_TRY(ctx, b.list.alloc(sizeof(int32_t) * nr * n));
-        FA_HIP_TRY(ctx, hipMemcpyAsync(b.x.p, emb, sizeof(double) * n * d, hipMemcpyHostToDevice, st));
+        FA_TRY(fa::take_once(ctx, "kmeans", {{&b.x, sizeof(double) * n * d, true, emb}, {&b.xn, sizeof(double) * n * d}, {&b.xt, sizeof(double) * n * d},
+                                             {&b.cen, sizeof(double) * nr * k * d}, {&b.assign, sizeof(int32_t) * nr * n}, {&b.changed, sizeof(int32_t) * nr},
+                                             {&b.counts, sizeof(int32_t) * nr * k}, {&b.list, sizeof(int32_t) * nr * n}}));
         launch_normalize(st, b.x.as<double>(), b.xn.as<double>(), b.xt.as<double>(), n, d);
         LloydArgs a{};
         a.xn = b.xn.as<double>(); a.xt = b.xt.as<double>(); a.cen = b.cen.as<double>();
@@ -101,7 +95,7 @@ fa_status kmeans_device(fa_ctx *ctx, const double *emb, int64_t n, int d, int k,
         FA_TRY(lloyd_batch(ctx, a, max_iter, seeds + r0, res));
         std::vector<double> h_dist;
         if (want_inertia) {
-            FA_HIP_TRY(ctx, b.dist.alloc(sizeof(double) * nr * n));
+            FA_TRY(fa::take_once(ctx, "kmeans", {{&b.dist, sizeof(double) * nr * n}}));
             launch_own_distance(st, a, b.dist.as<double>());
             FA_HIP_TRY(ctx, hipGetLastError());
             h_dist.resize(static_cast<size_t>(nr) * n);

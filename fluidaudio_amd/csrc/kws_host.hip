@@ -60,29 +60,21 @@ struct DeviceKeywords {
 };
 
 fa_status upload_keywords(fa_ctx *ctx, const Problem &p, const float *min_scores, DeviceKeywords &d) {
-    hipStream_t st = ctx->stream;
     const int64_t n_tok = p.off[p.keywords] - p.off[0];
     std::vector<int64_t> off(static_cast<size_t>(p.keywords) + 1);
     for (int32_t k = 0; k <= p.keywords; ++k) off[k] = p.off[k] - p.off[0];
     std::vector<float> mins(static_cast<size_t>(p.keywords), kDefaultMinScore);
     if (min_scores) std::copy(min_scores, min_scores + p.keywords, mins.begin());
-    if (d.tokens.alloc(ctx, sizeof(int32_t) * n_tok) != hipSuccess || d.off.alloc(ctx, sizeof(int64_t) * off.size()) != hipSuccess ||
-        d.min_score.alloc(ctx, sizeof(float) * mins.size()) != hipSuccess) {
-        (void)hipGetLastError();
-        return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "kws: device allocation failed");
-    }
-    if (n_tok > 0) FA_HIP_TRY(ctx, hipMemcpyAsync(d.tokens.p, p.tokens + p.off[0], sizeof(int32_t) * n_tok, hipMemcpyHostToDevice, st));
-    FA_HIP_TRY(ctx, hipMemcpyAsync(d.off.p, off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice, st));
-    FA_HIP_TRY(ctx, hipMemcpyAsync(d.min_score.p, mins.data(), sizeof(float) * mins.size(), hipMemcpyHostToDevice, st));
-    FA_HIP_TRY(ctx, hipStreamSynchronize(st));   // the staging vectors end with this scope
+    FA_TRY(fa::take(ctx, "kws", {{&d.tokens, sizeof(int32_t) * n_tok, true, n_tok > 0 ? p.tokens + p.off[0] : nullptr},
+                                 {&d.off, sizeof(int64_t) * off.size(), true, off.data()}, {&d.min_score, sizeof(float) * mins.size(), true, mins.data()}}));
+    FA_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // the staging vectors end with this scope
     return FA_SUCCESS;
 }
 
 // the host-pointer entries: the matrices as they are laid out, up to the last column read (there is a job, so batch, frames >= 1)
 fa_status upload_log_probs(fa_ctx *ctx, const Problem &p, const float *lp, fa::DevBuf &buf, const float *&d_lp) {
     const size_t n = static_cast<size_t>(p.batch - 1) * p.matrix_stride + static_cast<size_t>(p.frames - 1) * p.row_stride + p.vocab;
-    if (buf.alloc(ctx, sizeof(float) * n) != hipSuccess) { (void)hipGetLastError(); return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "kws: device allocation failed"); }
-    FA_HIP_TRY(ctx, hipMemcpyAsync(buf.p, lp, sizeof(float) * n, hipMemcpyHostToDevice, ctx->stream));
+    FA_TRY(fa::take(ctx, "kws", {{&buf, sizeof(float) * n, true, lp}}));
     d_lp = buf.as<float>();
     return FA_SUCCESS;
 }
@@ -179,10 +171,7 @@ fa_status spot(fa_ctx *ctx, const float *lp, bool device, int32_t batch, int32_t
     FA_TRY(upload_keywords(ctx, p, min_scores, dk));
     fa::DevBuf b_jobs, b_arena, b_state;   // b_state: the cursor, then a status per job of the pass
     const size_t state_bytes = sizeof(unsigned long long) + sizeof(int32_t) * static_cast<size_t>(J);
-    if (b_jobs.alloc(ctx, sizeof(Job) * J) != hipSuccess || b_arena.alloc(ctx, sizeof(Record) * cap) != hipSuccess || b_state.alloc(ctx, state_bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "kws_spot: device allocation failed");
-    }
+    FA_TRY(fa::take(ctx, "kws_spot", {{&b_jobs, sizeof(Job) * J}, {&b_arena, sizeof(Record) * cap}, {&b_state, state_bytes}}));
     WalkArgs a = walk_args(p, d_lp, dk);
     a.arena = b_arena.as<Record>(); a.arena_cap = cap; a.cursor = b_state.as<unsigned long long>();
     a.status = reinterpret_cast<int32_t *>(b_state.as<char>() + sizeof(unsigned long long));
@@ -301,11 +290,7 @@ fa_status score_windows(fa_ctx *ctx, const float *lp, bool device, int32_t batch
     DeviceKeywords dk;
     FA_TRY(upload_keywords(ctx, p, nullptr, dk));
     fa::DevBuf b_jobs, b_out;
-    if (b_jobs.alloc(ctx, sizeof(Job) * J) != hipSuccess || b_out.alloc(ctx, sizeof(Record) * J) != hipSuccess) {
-        (void)hipGetLastError();
-        return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "kws_windows: device allocation failed");
-    }
-    FA_HIP_TRY(ctx, hipMemcpyAsync(b_jobs.p, pass_jobs.data(), sizeof(Job) * J, hipMemcpyHostToDevice, st));
+    FA_TRY(fa::take(ctx, "kws_windows", {{&b_jobs, sizeof(Job) * J, true, pass_jobs.data()}, {&b_out, sizeof(Record) * J}}));
     WalkArgs a = walk_args(p, d_lp, dk);
     a.constrained = 1;
     a.out = b_out.as<Record>();

@@ -514,11 +514,9 @@ fa_status fa_mel_batch(fa_ctx *ctx, const fa_mel_config *cfg, const float *pcm, 
             return fa::hip_status(ctx, e, "fa_mel_batch");
         }
         fa::DevBuf d_pcm, d_last, d_out, d_len;
-        e = d_pcm.alloc(sizeof(float) * static_cast<size_t>(ns));
-        if (e == hipSuccess) e = d_out.alloc(sizeof(float) * out_floats);
-        if (e == hipSuccess) e = d_len.alloc(sizeof(int32_t) * batch);
-        if (e == hipSuccess && last_samples) e = d_last.alloc(sizeof(float) * batch);
-        if (e != hipSuccess) { (void)hipGetLastError(); return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "fa_mel_batch: device allocation failed"); }
+        // the samples go up slice by slice below
+        FA_TRY(fa::take_once(ctx, "fa_mel_batch", {{&d_pcm, sizeof(float) * static_cast<size_t>(ns)}, {&d_out, sizeof(float) * out_floats}, {&d_len, sizeof(int32_t) * batch},
+                                                   {&d_last, sizeof(float) * batch, last_samples != nullptr}}));
         if (owner.own) { fa_mel_plan_destroy(whole); whole = nullptr; }   // only its geometry was needed: every slice gets its own plan
         hipStream_t down = nullptr;
         FA_HIP_TRY(ctx, hipStreamCreateWithFlags(&down, hipStreamNonBlocking));

@@ -21,8 +21,8 @@ fa_status cif(fa_ctx *ctx, const fa_paraformer_cif_config *cfg, const void *enc,
               int32_t *fire_counts, int32_t *fire_frames, const bool device) {
     const fa_paraformer_cif_config c = pf::config_or_default(cfg);
     const pf::CifShape s{dtype, batch, frames, dim, row_stride, matrix_stride, alpha_stride};
-    const pf::Verdict v = pf::check_cif(c, s, enc, alphas, ac, token_counts, fire_counts, fire_frames);
-    if (v.status != FA_SUCCESS) return fa::set_error(ctx, v.status, "paraformer_cif: %s", v.what);
+    const fa::Verdict v = pf::check_cif(c, s, enc, alphas, ac, token_counts, fire_counts, fire_frames);
+    if (v.status != FA_SUCCESS) return fa::set_error(ctx, v.status, "paraformer_cif: %s", v.text);
     // a workgroup per (utterance, row, slice of 64 elements) at the narrowest load
     const int64_t rows = static_cast<int64_t>(batch) * std::max(c.max_tokens, enc_packed ? c.enc_frames : 0);
     if (rows * ((dim + pf::kWave - 1) / pf::kWave) > INT32_MAX) return fa::set_error(ctx, FA_INDEX_OVERFLOW, "paraformer_cif: more than INT32_MAX workgroups");
@@ -39,16 +39,9 @@ fa_status cif(fa_ctx *ctx, const fa_paraformer_cif_config *cfg, const void *enc,
     fa::DeviceGuard guard(ctx->device);
     hipStream_t st = ctx->stream;
     fa::DevBuf b_valid, b_w, b_seed, b_fires, b_counts, b_enc, b_alphas, b_ac, b_packed;
-    const auto alloc = [&](fa::DevBuf &b, const size_t bytes) { return b.alloc(ctx, bytes) == hipSuccess; };
-    if (!alloc(b_valid, sizeof(int32_t) * B) || !alloc(b_w, sizeof(float) * B * per_utt) || !alloc(b_seed, sizeof(float) * B * per_utt) ||
-        !alloc(b_fires, sizeof(int32_t) * B * per_utt) || !alloc(b_counts, sizeof(int32_t) * 2 * B) ||
-        (!device && (!alloc(b_enc, enc_bytes) || !alloc(b_alphas, alpha_bytes) || !alloc(b_ac, ac_bytes) || (enc_packed && !alloc(b_packed, packed_bytes))))) {
-        (void)hipGetLastError();
-        return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "paraformer_cif: device allocation failed");
-    }
-    FA_HIP_TRY(ctx, hipMemcpyAsync(b_valid.p, valid.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, st));
-    if (enc_bytes) FA_HIP_TRY(ctx, hipMemcpyAsync(b_enc.p, enc, enc_bytes, hipMemcpyHostToDevice, st));
-    if (alpha_bytes) FA_HIP_TRY(ctx, hipMemcpyAsync(b_alphas.p, alphas, alpha_bytes, hipMemcpyHostToDevice, st));
+    FA_TRY(fa::take(ctx, "paraformer_cif", {{&b_valid, sizeof(int32_t) * B, true, valid.data()}, {&b_w, sizeof(float) * B * per_utt}, {&b_seed, sizeof(float) * B * per_utt},
+                                            {&b_fires, sizeof(int32_t) * B * per_utt}, {&b_counts, sizeof(int32_t) * 2 * B}, {&b_enc, enc_bytes, !device, enc},
+                                            {&b_alphas, alpha_bytes, !device, alphas}, {&b_ac, ac_bytes, !device}, {&b_packed, packed_bytes, !device && enc_packed}}));
 
     pf::CifArgs a{};
     a.enc = device ? enc : b_enc.p;
@@ -85,8 +78,8 @@ fa_status timestamps(fa_ctx *ctx, const fa_paraformer_cif_config *cfg, const flo
                      const int64_t *audio_offsets, fa_paraformer_span *spans, int64_t capacity, int64_t *count, int64_t *utterance_counts, const bool device) {
     const fa_paraformer_cif_config c = pf::config_or_default(cfg);
     const pf::StampShape s{batch, frames, vocab, alpha_stride};
-    const pf::Verdict v = pf::check_stamps(c, s, alphas, token_ids, token_counts, keep, audio, audio_offsets, capacity, count);
-    if (v.status != FA_SUCCESS) return fa::set_error(ctx, v.status, "paraformer_timestamps: %s", v.what);
+    const fa::Verdict v = pf::check_stamps(c, s, alphas, token_ids, token_counts, keep, audio, audio_offsets, capacity, count);
+    if (v.status != FA_SUCCESS) return fa::set_error(ctx, v.status, "paraformer_timestamps: %s", v.text);
     int64_t max_env = 0;
     for (int32_t b = 0; b < batch; ++b) max_env = std::max(max_env, pf::env_frames(audio_offsets[b + 1] - audio_offsets[b]));
     const int64_t env_blocks = (max_env + pf::kEnvBlock - 1) / pf::kEnvBlock;
@@ -111,23 +104,12 @@ fa_status timestamps(fa_ctx *ctx, const fa_paraformer_cif_config *cfg, const flo
     fa::DeviceGuard guard(ctx->device);
     hipStream_t st = ctx->stream;
     fa::DevBuf b_valid, b_tc, b_keep, b_aoff, b_eoff, b_raw, b_env, b_thr, b_kept, b_fires, b_spacing, b_spans, b_counts, b_audio, b_alphas, b_ids;
-    const auto alloc = [&](fa::DevBuf &b, const size_t bytes) { return b.alloc(ctx, bytes) == hipSuccess; };
-    if (!alloc(b_valid, sizeof(int32_t) * B) || !alloc(b_tc, sizeof(int32_t) * B) || !alloc(b_keep, static_cast<size_t>(vocab)) || !alloc(b_aoff, sizeof(int64_t) * (B + 1)) ||
-        !alloc(b_eoff, sizeof(int64_t) * (B + 1)) || !alloc(b_raw, sizeof(float) * n_env) || !alloc(b_env, sizeof(float) * n_env) || !alloc(b_thr, sizeof(float) * B) ||
-        !alloc(b_kept, sizeof(int32_t) * B * mt) || !alloc(b_fires, sizeof(int32_t) * n_fires) || !alloc(b_spacing, sizeof(float) * B * mt) ||
-        !alloc(b_spans, sizeof(pf::Span) * B * mt) || !alloc(b_counts, sizeof(int32_t) * B) ||
-        (!device && (!alloc(b_audio, audio_bytes) || !alloc(b_alphas, alpha_bytes) || !alloc(b_ids, ids_bytes)))) {
-        (void)hipGetLastError();
-        return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "paraformer_timestamps: device allocation failed");
-    }
-    FA_HIP_TRY(ctx, hipMemcpyAsync(b_valid.p, valid.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, st));
-    FA_HIP_TRY(ctx, hipMemcpyAsync(b_tc.p, token_counts, sizeof(int32_t) * B, hipMemcpyHostToDevice, st));
-    if (vocab > 0) FA_HIP_TRY(ctx, hipMemcpyAsync(b_keep.p, keep, static_cast<size_t>(vocab), hipMemcpyHostToDevice, st));
-    FA_HIP_TRY(ctx, hipMemcpyAsync(b_aoff.p, audio_off.data(), sizeof(int64_t) * (B + 1), hipMemcpyHostToDevice, st));
-    FA_HIP_TRY(ctx, hipMemcpyAsync(b_eoff.p, env_off.data(), sizeof(int64_t) * (B + 1), hipMemcpyHostToDevice, st));
-    if (audio_bytes) FA_HIP_TRY(ctx, hipMemcpyAsync(b_audio.p, audio + a0, audio_bytes, hipMemcpyHostToDevice, st));
-    if (alpha_bytes) FA_HIP_TRY(ctx, hipMemcpyAsync(b_alphas.p, alphas, alpha_bytes, hipMemcpyHostToDevice, st));
-    if (ids_bytes) FA_HIP_TRY(ctx, hipMemcpyAsync(b_ids.p, token_ids, ids_bytes, hipMemcpyHostToDevice, st));
+    FA_TRY(fa::take(ctx, "paraformer_timestamps",
+                    {{&b_valid, sizeof(int32_t) * B, true, valid.data()}, {&b_tc, sizeof(int32_t) * B, true, token_counts}, {&b_keep, static_cast<size_t>(vocab), true, keep},
+                     {&b_aoff, sizeof(int64_t) * (B + 1), true, audio_off.data()}, {&b_eoff, sizeof(int64_t) * (B + 1), true, env_off.data()}, {&b_raw, sizeof(float) * n_env},
+                     {&b_env, sizeof(float) * n_env}, {&b_thr, sizeof(float) * B}, {&b_kept, sizeof(int32_t) * B * mt}, {&b_fires, sizeof(int32_t) * n_fires},
+                     {&b_spacing, sizeof(float) * B * mt}, {&b_spans, sizeof(pf::Span) * B * mt}, {&b_counts, sizeof(int32_t) * B}, {&b_audio, audio_bytes, !device, audio + a0},
+                     {&b_alphas, alpha_bytes, !device, alphas}, {&b_ids, ids_bytes, !device, token_ids}}));
 
     pf::StampArgs a{};
     a.alphas = device ? alphas : b_alphas.as<float>();

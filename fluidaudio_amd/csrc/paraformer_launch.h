@@ -14,6 +14,7 @@
 #include <algorithm>
 
 #include "fa_common.h"
+#include "fa_verdict.h"
 
 namespace fa {
 namespace paraformer {
@@ -25,11 +26,6 @@ constexpr int kEnvChunk = 32;        // samples of every frame staged through LD
 constexpr int kUpsample = 3;
 constexpr int kMinRun = 3;
 static_assert(kHop % kEnvChunk == 0, "the envelope kernel stages whole chunks");
-
-struct Verdict {
-    fa_status status = FA_SUCCESS;
-    const char *what = "";
-};
 
 inline fa_paraformer_cif_config config_or_default(const fa_paraformer_cif_config *cfg) {
     return cfg ? *cfg : fa_paraformer_cif_config{1.0f, 0.45f, 128, 512};   // ParaformerConfig.swift:19-20, 28-29
@@ -48,15 +44,15 @@ inline int64_t enc_extent(const CifShape &s) {
 
 inline Verdict check_cif(const fa_paraformer_cif_config &c, const CifShape &s, const void *enc, const void *alphas, const void *ac, const void *token_counts,
                          const void *fire_counts, const void *fire_frames) {
-    if (s.batch < 0 || s.frames < 0 || s.dim < 1 || s.row_stride < s.dim || s.alpha_stride < s.frames) return Verdict{FA_INVALID_ARGUMENT, "bad shape"};
-    if (s.dtype != FA_DTYPE_F32 && s.dtype != FA_DTYPE_F16) return Verdict{FA_INVALID_ARGUMENT, "dtype is FA_DTYPE_F32 or FA_DTYPE_F16"};
-    if (c.max_tokens < 1 || c.enc_frames < 0) return Verdict{FA_INVALID_ARGUMENT, "bad config"};
-    if (s.batch > 1 && s.frames > 0 && s.matrix_stride < static_cast<int64_t>(s.frames - 1) * s.row_stride + s.dim) return Verdict{FA_INVALID_ARGUMENT, "matrices overlap"};
-    if (s.batch > 0 && (!ac || !token_counts || !fire_counts || !fire_frames)) return Verdict{FA_INVALID_ARGUMENT, "an output is NULL"};
-    if (s.batch > 0 && s.frames > 0 && (!enc || !alphas)) return Verdict{FA_INVALID_ARGUMENT, "an input is NULL"};
+    if (s.batch < 0 || s.frames < 0 || s.dim < 1 || s.row_stride < s.dim || s.alpha_stride < s.frames) return refuse(FA_INVALID_ARGUMENT, "bad shape");
+    if (s.dtype != FA_DTYPE_F32 && s.dtype != FA_DTYPE_F16) return refuse(FA_INVALID_ARGUMENT, "dtype is FA_DTYPE_F32 or FA_DTYPE_F16");
+    if (c.max_tokens < 1 || c.enc_frames < 0) return refuse(FA_INVALID_ARGUMENT, "bad config");
+    if (s.batch > 1 && s.frames > 0 && s.matrix_stride < static_cast<int64_t>(s.frames - 1) * s.row_stride + s.dim) return refuse(FA_INVALID_ARGUMENT, "matrices overlap");
+    if (s.batch > 0 && (!ac || !token_counts || !fire_counts || !fire_frames)) return refuse(FA_INVALID_ARGUMENT, "an output is NULL");
+    if (s.batch > 0 && s.frames > 0 && (!enc || !alphas)) return refuse(FA_INVALID_ARGUMENT, "an input is NULL");
     const int64_t b = s.batch;
     if (b * (static_cast<int64_t>(s.frames) + 1) > INT32_MAX || b * c.max_tokens > INT32_MAX || b * std::max(c.enc_frames, 1) > INT32_MAX)
-        return Verdict{FA_INDEX_OVERFLOW, "more than INT32_MAX frames or tokens in the batch"};
+        return refuse(FA_INDEX_OVERFLOW, "more than INT32_MAX frames or tokens in the batch");
     return Verdict{};
 }
 
@@ -100,21 +96,21 @@ struct StampShape {
 
 inline Verdict check_stamps(const fa_paraformer_cif_config &c, const StampShape &s, const void *alphas, const void *token_ids, const int32_t *token_counts,
                             const void *keep, const void *audio, const int64_t *audio_offsets, const int64_t capacity, const void *count) {
-    if (s.batch < 0 || s.frames < 0 || s.vocab < 0 || s.alpha_stride < s.frames || capacity < 0 || !count) return Verdict{FA_INVALID_ARGUMENT, "bad shape, or count is NULL"};
-    if (c.max_tokens < 1) return Verdict{FA_INVALID_ARGUMENT, "bad config"};
-    if (s.batch > 0 && (!token_counts || !audio_offsets || (s.vocab > 0 && !keep) || (s.frames > 0 && !alphas))) return Verdict{FA_INVALID_ARGUMENT, "an input is NULL"};
-    if (s.batch > 0 && audio_offsets[0] < 0) return Verdict{FA_INVALID_ARGUMENT, "audio_offsets starts below 0"};
+    if (s.batch < 0 || s.frames < 0 || s.vocab < 0 || s.alpha_stride < s.frames || capacity < 0 || !count) return refuse(FA_INVALID_ARGUMENT, "bad shape, or count is NULL");
+    if (c.max_tokens < 1) return refuse(FA_INVALID_ARGUMENT, "bad config");
+    if (s.batch > 0 && (!token_counts || !audio_offsets || (s.vocab > 0 && !keep) || (s.frames > 0 && !alphas))) return refuse(FA_INVALID_ARGUMENT, "an input is NULL");
+    if (s.batch > 0 && audio_offsets[0] < 0) return refuse(FA_INVALID_ARGUMENT, "audio_offsets starts below 0");
     bool tokens = false;
     for (int32_t b = 0; b < s.batch; ++b) {
-        if (token_counts[b] < 0 || token_counts[b] > c.max_tokens) return Verdict{FA_INVALID_ARGUMENT, "a token count outside [0, max_tokens]"};
-        if (audio_offsets[b + 1] < audio_offsets[b]) return Verdict{FA_INVALID_ARGUMENT, "audio_offsets does not ascend"};
-        if (audio_offsets[b + 1] - audio_offsets[b] > INT32_MAX) return Verdict{FA_INDEX_OVERFLOW, "an utterance of more than INT32_MAX samples"};
+        if (token_counts[b] < 0 || token_counts[b] > c.max_tokens) return refuse(FA_INVALID_ARGUMENT, "a token count outside [0, max_tokens]");
+        if (audio_offsets[b + 1] < audio_offsets[b]) return refuse(FA_INVALID_ARGUMENT, "audio_offsets does not ascend");
+        if (audio_offsets[b + 1] - audio_offsets[b] > INT32_MAX) return refuse(FA_INDEX_OVERFLOW, "an utterance of more than INT32_MAX samples");
         tokens = tokens || token_counts[b] > 0;
     }
-    if (tokens && !token_ids) return Verdict{FA_INVALID_ARGUMENT, "token_ids is NULL"};
-    if (s.batch > 0 && audio_offsets[s.batch] > audio_offsets[0] && !audio) return Verdict{FA_INVALID_ARGUMENT, "audio is NULL"};
+    if (tokens && !token_ids) return refuse(FA_INVALID_ARGUMENT, "token_ids is NULL");
+    if (s.batch > 0 && audio_offsets[s.batch] > audio_offsets[0] && !audio) return refuse(FA_INVALID_ARGUMENT, "audio is NULL");
     const int64_t b = s.batch;
-    if (b * (static_cast<int64_t>(kUpsample) * s.frames + 1) > INT32_MAX || b * c.max_tokens > INT32_MAX) return Verdict{FA_INDEX_OVERFLOW, "more than INT32_MAX frames or tokens in the batch"};
+    if (b * (static_cast<int64_t>(kUpsample) * s.frames + 1) > INT32_MAX || b * c.max_tokens > INT32_MAX) return refuse(FA_INDEX_OVERFLOW, "more than INT32_MAX frames or tokens in the batch");
     return Verdict{};
 }
 

@@ -41,13 +41,8 @@ fa_status fa::constrained_assign_dev(fa_ctx *ctx, const double *d_scores, int64_
     const fa::post::ChunkGroups g = fa::post::group_by_chunk(chunk_indices, n);
     const int side = fa::post::hung_side(g.max_rows, K);
     fa::DevBuf d_start, d_rows, d_slabs;
-    if ((fa::post::hung_in_slabs(side) && d_slabs.alloc(ctx, fa::post::hung_slab_bytes(side) * static_cast<size_t>(g.n_chunks())) != hipSuccess) ||
-        d_start.alloc(ctx, sizeof(int32_t) * g.starts.size()) != hipSuccess || d_rows.alloc(ctx, sizeof(int32_t) * n) != hipSuccess) {
-        (void)hipGetLastError();
-        return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "constrained assign: device allocation failed");
-    }
-    FA_HIP_TRY(ctx, hipMemcpyAsync(d_start.p, g.starts.data(), sizeof(int32_t) * g.starts.size(), hipMemcpyHostToDevice, ctx->stream));
-    FA_HIP_TRY(ctx, hipMemcpyAsync(d_rows.p, g.order.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, ctx->stream));
+    FA_TRY(fa::take(ctx, "constrained assign", {{&d_slabs, fa::post::hung_slab_bytes(side) * static_cast<size_t>(g.n_chunks()), fa::post::hung_in_slabs(side)},
+                                                {&d_start, sizeof(int32_t) * g.starts.size(), true, g.starts.data()}, {&d_rows, sizeof(int32_t) * n, true, g.order.data()}}));
     FA_HIP_TRY(ctx, hipMemsetAsync(d_out, 0xfe, sizeof(int32_t) * n, ctx->stream));  // placeholder, every row is written
     FA_TRY(fa::hungarian_dev(ctx, d_scores, d_start.as<int32_t>(), d_rows.as<int32_t>(), d_out, g.n_chunks(), K, d_slabs.as<unsigned char>(), side));
     FA_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // the tables above are released on return

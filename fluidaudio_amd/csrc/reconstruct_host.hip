@@ -153,33 +153,18 @@ struct Buffers {
     FrameArgs args;   // the frame kernel's operands over them
 };
 
-fa_status alloc_failed(fa_ctx *ctx) {
-    (void)hipGetLastError();
-    return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "reconstruct: device allocation failed");
-}
-
 // the buffers of the frame stage, the plan's H2D copies, flags ([0] bad, [1] raw runs) zeroed
 fa_status stage(fa_ctx *ctx, const Call &c, const FramePlan &p, double fd, bool want_esum, Buffers &b) {
     hipStream_t st = ctx->stream;
     const int64_t C = c.C, T = p.T, items = T * p.smax;
     const size_t wbytes = sizeof(float) * C * c.F * c.S;
-    auto alloc = [&](fa::DevBuf &buf, size_t bytes) { return buf.alloc(ctx, bytes) == hipSuccess; };
-    if ((!c.device_weights && !alloc(b.w, wbytes)) || !alloc(b.start, sizeof(double) * C) || !alloc(b.first, sizeof(int32_t) * C) ||
-        !alloc(b.last, sizeof(int32_t) * C) || !alloc(b.hard, sizeof(int32_t) * C * c.S) || (!p.ovr.empty() && !alloc(b.ovr, sizeof(int32_t) * T)) ||
-        !alloc(b.word, sizeof(int32_t) * T) || !alloc(b.sel, sizeof(int32_t) * items) || !alloc(b.avg, sizeof(double) * items) ||
-        !alloc(b.bsum, sizeof(int32_t) * run_blocks(items)) || !alloc(b.flags, sizeof(int32_t) * 2) || !alloc(b.starts, sizeof(int64_t) * items) ||
-        (want_esum && !alloc(b.esum, sizeof(double) * T)))
-        return alloc_failed(ctx);
-    const float *d_w = c.weights;
-    if (!c.device_weights) {
-        FA_HIP_TRY(ctx, hipMemcpyAsync(b.w.p, c.weights, wbytes, hipMemcpyHostToDevice, st));
-        d_w = b.w.as<float>();
-    }
-    FA_HIP_TRY(ctx, hipMemcpyAsync(b.start.p, p.start.data(), sizeof(double) * C, hipMemcpyHostToDevice, st));
-    FA_HIP_TRY(ctx, hipMemcpyAsync(b.first.p, p.first_g.data(), sizeof(int32_t) * C, hipMemcpyHostToDevice, st));
-    FA_HIP_TRY(ctx, hipMemcpyAsync(b.last.p, p.last_g.data(), sizeof(int32_t) * C, hipMemcpyHostToDevice, st));
-    if (C * c.S > 0) FA_HIP_TRY(ctx, hipMemcpyAsync(b.hard.p, p.hard.data(), sizeof(int32_t) * C * c.S, hipMemcpyHostToDevice, st));
-    if (!p.ovr.empty()) FA_HIP_TRY(ctx, hipMemcpyAsync(b.ovr.p, p.ovr.data(), sizeof(int32_t) * T, hipMemcpyHostToDevice, st));
+    FA_TRY(fa::take(ctx, "reconstruct", {{&b.w, wbytes, !c.device_weights, c.weights}, {&b.start, sizeof(double) * C, true, p.start.data()},
+                                         {&b.first, sizeof(int32_t) * C, true, p.first_g.data()}, {&b.last, sizeof(int32_t) * C, true, p.last_g.data()},
+                                         {&b.hard, sizeof(int32_t) * C * c.S, true, p.hard.data()}, {&b.ovr, sizeof(int32_t) * T, !p.ovr.empty(), p.ovr.data()},
+                                         {&b.word, sizeof(int32_t) * T}, {&b.sel, sizeof(int32_t) * items}, {&b.avg, sizeof(double) * items},
+                                         {&b.bsum, sizeof(int32_t) * run_blocks(items)}, {&b.flags, sizeof(int32_t) * 2}, {&b.starts, sizeof(int64_t) * items},
+                                         {&b.esum, sizeof(double) * T, want_esum}}));
+    const float *d_w = c.device_weights ? c.weights : b.w.as<float>();
     FA_HIP_TRY(ctx, hipMemsetAsync(b.flags.p, 0, sizeof(int32_t) * 2, st));
     b.args = FrameArgs{d_w, b.start.as<double>(), b.first.as<int32_t>(), b.last.as<int32_t>(), b.hard.as<int32_t>(), p.ovr.empty() ? nullptr : b.ovr.as<int32_t>(),
                        b.word.as<int32_t>(), b.sel.as<int32_t>(), b.avg.as<double>(), b.flags.as<int32_t>(), b.esum.p ? b.esum.as<double>() : nullptr,
@@ -211,7 +196,7 @@ fa_status walk_and_fetch(fa_ctx *ctx, const Call &c, const Wanted &want, Buffers
     const int64_t T = b.args.T, items = T * b.args.smax;
     runs.resize(static_cast<size_t>(n_raw));
     if (n_raw > 0) {
-        if (b.raw.alloc(ctx, sizeof(RawRun) * n_raw) != hipSuccess) return alloc_failed(ctx);
+        FA_TRY(fa::take(ctx, "reconstruct", {{&b.raw, sizeof(RawRun) * n_raw}}));
         launch_walk(st, b.args, b.starts.as<int64_t>(), b.flags.as<int32_t>() + 1, n_raw, b.raw.as<RawRun>());
         FA_HIP_TRY(ctx, hipGetLastError());
         FA_HIP_TRY(ctx, hipMemcpyAsync(runs.data(), b.raw.p, sizeof(RawRun) * n_raw, hipMemcpyDeviceToHost, st));
@@ -316,12 +301,8 @@ fa_status powerset_decode(fa_ctx *ctx, const float *logits, int64_t C, int32_t F
     const float *d_x = logits;
     float *d_w = weights, *d_lp = log_probs;
     if (!device) {
-        if (b_x.alloc(ctx, sizeof(float) * rows * std::max(classes, 1)) != hipSuccess || b_w.alloc(ctx, sizeof(float) * rows * 3) != hipSuccess ||
-            (log_probs && b_lp.alloc(ctx, sizeof(float) * rows * std::max(classes, 1)) != hipSuccess)) {
-            (void)hipGetLastError();
-            return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "powerset decode: device allocation failed");
-        }
-        if (classes > 0) FA_HIP_TRY(ctx, hipMemcpyAsync(b_x.p, logits, sizeof(float) * rows * classes, hipMemcpyHostToDevice, st));
+        const size_t xbytes = sizeof(float) * rows * std::max(classes, 1);   // without classes one float a row, never read: no upload then
+        FA_TRY(fa::take(ctx, "powerset decode", {{&b_x, xbytes, true, classes > 0 ? logits : nullptr}, {&b_w, sizeof(float) * rows * 3}, {&b_lp, xbytes, log_probs != nullptr}}));
         d_x = b_x.as<float>();
         d_w = b_w.as<float>();
         d_lp = log_probs ? b_lp.as<float>() : nullptr;

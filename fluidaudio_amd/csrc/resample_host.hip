@@ -196,12 +196,9 @@ fa_status fa_resample_linear(fa_ctx *ctx, const float *planar, int32_t channels,
     if (!planar || !out) return FA_INVALID_ARGUMENT;
     fa::DeviceGuard guard(ctx->device);
     fa::DevBuf d_in, d_mono, d_out;
+    FA_TRY(fa::take_once(ctx, "fa_resample_linear", {{&d_in, sizeof(float) * frames * channels, true, planar}, {&d_mono, sizeof(float) * frames}, {&d_out, sizeof(float) * n_out}}));
     hipError_t e;
     do {
-        if ((e = d_in.alloc(sizeof(float) * frames * channels)) != hipSuccess) break;
-        if ((e = d_mono.alloc(sizeof(float) * frames)) != hipSuccess) break;
-        if ((e = d_out.alloc(sizeof(float) * n_out)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(d_in.p, planar, sizeof(float) * frames * channels, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) break;
         hipLaunchKernelGGL(mixdown_kernel, dim3(static_cast<unsigned>((frames + kThreads - 1) / kThreads)), dim3(kThreads), 0, ctx->stream, d_in.as<float>(), d_mono.as<float>(), channels, frames);
         const float *src = d_mono.as<float>();
         if (in_rate != out_rate) {
@@ -302,11 +299,7 @@ fa_status fa_resample_poly(fa_ctx *ctx, const float *x, int64_t frames, int32_t 
     if (!x || !out) return FA_INVALID_ARGUMENT;
     fa::DeviceGuard guard(ctx->device);
     fa::DevBuf d_x, d_y;
-    if (d_x.alloc(sizeof(float) * frames) != hipSuccess || d_y.alloc(sizeof(float) * n_out) != hipSuccess) {
-        (void)hipGetLastError();
-        return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "resample_poly: device allocation failed");
-    }
-    FA_HIP_TRY(ctx, hipMemcpyAsync(d_x.p, x, sizeof(float) * frames, hipMemcpyHostToDevice, ctx->stream));
+    FA_TRY(fa::take_once(ctx, "resample_poly", {{&d_x, sizeof(float) * frames, true, x}, {&d_y, sizeof(float) * n_out}}));
     int64_t got = 0;
     FA_TRY(fa_resample_poly_dev(ctx, d_x.as<float>(), frames, up, down, d_y.as<float>(), n_out, &got));
     FA_HIP_TRY(ctx, hipMemcpyAsync(out, d_y.p, sizeof(float) * n_out, hipMemcpyDeviceToHost, ctx->stream));

@@ -99,18 +99,8 @@ struct WindowTables { fa::DevBuf win, range, gofs, corr, ov; };   // pack takes 
 fa_status stage_windows(fa_ctx *ctx, const WindowPlan &p, WindowTables &t) {
     const bool stitch = !p.gofs.empty();
     const size_t win_bytes = sizeof(fa_sortformer_window) * p.W, rec_bytes = sizeof(int64_t) * p.geo.range.size();
-    const auto take = [&](fa::DevBuf &b, size_t bytes) { return b.alloc(ctx, bytes) == hipSuccess; };
-    if (!take(t.win, win_bytes) ||
-        (stitch && (!take(t.range, rec_bytes) || !take(t.gofs, rec_bytes) || !take(t.corr, sizeof(float) * p.W * p.speakers * p.speakers) ||
-                    !take(t.ov, sizeof(int32_t) * p.W)))) {
-        (void)hipGetLastError();
-        return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "%s: device allocation failed", p.what);
-    }
-    FA_HIP_TRY(ctx, hipMemcpyAsync(t.win.p, p.geo.win.data(), win_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (!stitch) return FA_SUCCESS;
-    FA_HIP_TRY(ctx, hipMemcpyAsync(t.range.p, p.geo.range.data(), rec_bytes, hipMemcpyHostToDevice, ctx->stream));
-    FA_HIP_TRY(ctx, hipMemcpyAsync(t.gofs.p, p.gofs.data(), rec_bytes, hipMemcpyHostToDevice, ctx->stream));
-    return FA_SUCCESS;
+    return fa::take(ctx, p.what, {{&t.win, win_bytes, true, p.geo.win.data()}, {&t.range, rec_bytes, stitch, p.geo.range.data()}, {&t.gofs, rec_bytes, stitch, p.gofs.data()},
+                                  {&t.corr, sizeof(float) * p.W * p.speakers * p.speakers, stitch}, {&t.ov, sizeof(int32_t) * p.W, stitch}});
 }
 
 // ---------------------------------------------------------------- the stitcher's host side

@@ -21,8 +21,8 @@ fa_status merge(fa_ctx *ctx, const fa_tdt_merge_config *cfg, const int32_t *tok,
                 int32_t *out_tok, int32_t *out_time, int32_t *out_dur, float *out_conf, const int64_t *out_range, int32_t *out_counts, int32_t *statuses,
                 int32_t *seam_routes, const bool device) {
     const fa_tdt_merge_config c = mg::config_or_default(cfg);
-    const mg::Verdict v = mg::check(c, tok, time, dur, conf, count, max_out, window_range, n, vocab, out_tok, out_time, out_dur, out_conf, out_range, out_counts, statuses);
-    if (v.status != FA_SUCCESS) return fa::set_error(ctx, v.status, "tdt_merge_windows: %s", v.what);
+    const fa::Verdict v = mg::check(c, tok, time, dur, conf, count, max_out, window_range, n, vocab, out_tok, out_time, out_dur, out_conf, out_range, out_counts, statuses);
+    if (v.status != FA_SUCCESS) return fa::set_error(ctx, v.status, "tdt_merge_windows: %s", v.text);
     if (!ctx) return FA_INVALID_ARGUMENT;
     if (n == 0) return FA_SUCCESS;
     return fa::no_throw(ctx, "tdt_merge_windows", [&]() -> fa_status {
@@ -35,18 +35,16 @@ fa_status merge(fa_ctx *ctx, const fa_tdt_merge_config *cfg, const int32_t *tok,
     fa::DeviceGuard guard(ctx->device);
     hipStream_t st = ctx->stream;
     fa::DevBuf b_recs, b_safe, b_canon, b_runmax, b_ws, b_routes, b_res, b_win, b_cnt, b_out;
-    const auto alloc = [&](fa::DevBuf &b, const size_t bytes) { return b.alloc(ctx, bytes) == hipSuccess; };
-    if (!alloc(b_recs, sizeof(mg::Rec) * N) || !alloc(b_safe, safe && tables ? static_cast<size_t>(vocab) : 0) ||
-        !alloc(b_canon, canon && tables ? sizeof(int32_t) * static_cast<size_t>(vocab) : 0) || !alloc(b_runmax, sizeof(int32_t) * T) ||
-        !alloc(b_ws, static_cast<size_t>(plan.slot_bytes) * static_cast<size_t>(plan.slots)) || !alloc(b_routes, sizeof(int32_t) * W) ||
-        !alloc(b_res, sizeof(int32_t) * 2 * N) || (!device && (!alloc(b_win, 16 * cells) || !alloc(b_cnt, sizeof(int32_t) * W) || !alloc(b_out, 16 * T)))) {
-        (void)hipGetLastError();
-        return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "tdt_merge_windows: device allocation failed (%lld wave slots of %lld bytes)", (long long)plan.slots,
-                             (long long)plan.slot_bytes);
-    }
-    FA_HIP_TRY(ctx, hipMemcpyAsync(b_recs.p, plan.recs.data(), sizeof(mg::Rec) * N, hipMemcpyHostToDevice, st));
-    if (safe && tables) FA_HIP_TRY(ctx, hipMemcpyAsync(b_safe.p, safe, static_cast<size_t>(vocab), hipMemcpyHostToDevice, st));
-    if (canon && tables) FA_HIP_TRY(ctx, hipMemcpyAsync(b_canon.p, canon, sizeof(int32_t) * static_cast<size_t>(vocab), hipMemcpyHostToDevice, st));
+    // the window arrays go up below, four to a buffer; a null table has 0 bytes and no upload
+    const fa_status taken = fa::take(ctx, "tdt_merge_windows", {{&b_recs, sizeof(mg::Rec) * N, true, plan.recs.data()},
+                                                                {&b_safe, safe && tables ? static_cast<size_t>(vocab) : 0, true, safe},
+                                                                {&b_canon, canon && tables ? sizeof(int32_t) * static_cast<size_t>(vocab) : 0, true, canon},
+                                                                {&b_runmax, sizeof(int32_t) * T}, {&b_ws, static_cast<size_t>(plan.slot_bytes) * static_cast<size_t>(plan.slots)},
+                                                                {&b_routes, sizeof(int32_t) * W}, {&b_res, sizeof(int32_t) * 2 * N}, {&b_win, 16 * cells, !device},
+                                                                {&b_cnt, sizeof(int32_t) * W, !device, count + w0}, {&b_out, 16 * T, !device}});
+    if (taken == FA_ALLOCATION_FAILURE)   // the workspace is what grows with the input
+        return fa::set_error(ctx, taken, "tdt_merge_windows: device allocation failed (%lld wave slots of %lld bytes)", (long long)plan.slots, (long long)plan.slot_bytes);
+    FA_TRY(taken);
 
     mg::Args a{};
     if (device) {
@@ -66,7 +64,6 @@ fa_status merge(fa_ctx *ctx, const fa_tdt_merge_config *cfg, const int32_t *tok,
             FA_HIP_TRY(ctx, hipMemcpyAsync(a.win.dur, dur + at, 4 * cells, hipMemcpyHostToDevice, st));
             FA_HIP_TRY(ctx, hipMemcpyAsync(a.win.conf, conf + at, 4 * cells, hipMemcpyHostToDevice, st));
         }
-        if (W) FA_HIP_TRY(ctx, hipMemcpyAsync(b_cnt.p, count + w0, sizeof(int32_t) * W, hipMemcpyHostToDevice, st));
     }
     a.max_out = max_out;
     a.recs = b_recs.as<mg::Rec>();

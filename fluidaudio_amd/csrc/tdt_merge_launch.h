@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/fluidaudio_hip.h"
+#include "fa_verdict.h"
 #include "tdt_merge_core.h"
 
 namespace fa {
@@ -61,31 +62,26 @@ inline fa_tdt_merge_config config_or_default(const fa_tdt_merge_config *cfg) {
     return fa_tdt_merge_config{static_cast<double>(1280) / static_cast<double>(16000), 2.0};   // ASRConstants.secondsPerEncoderFrame, overlapSeconds
 }
 
-struct Verdict {
-    fa_status status = FA_SUCCESS;
-    const char *what = "";
-};
-
 // The argument pass: nothing is written, no device is touched.
 inline Verdict check(const fa_tdt_merge_config &c, const void *tok, const void *time, const void *dur, const void *conf, const void *count, const int32_t max_out,
                      const int64_t *window_range, const int64_t n, const int32_t vocab, const void *out_tok, const void *out_time, const void *out_dur,
                      const void *out_conf, const int64_t *out_range, const void *out_counts, const void *statuses) {
-    if (n < 0 || max_out < 0 || vocab < 0) return Verdict{FA_INVALID_ARGUMENT, "a negative size"};
+    if (n < 0 || max_out < 0 || vocab < 0) return refuse(FA_INVALID_ARGUMENT, "a negative size");
     if (!(c.frame_seconds > 0.0) || !std::isfinite(c.frame_seconds) || !(c.overlap_seconds >= 0.0) || !std::isfinite(c.overlap_seconds))
-        return Verdict{FA_INVALID_ARGUMENT, "the frame must be positive and the overlap non-negative, both finite"};
+        return refuse(FA_INVALID_ARGUMENT, "the frame must be positive and the overlap non-negative, both finite");
     if (n == 0) return Verdict{};
-    if (n >= INT32_MAX) return Verdict{FA_INDEX_OVERFLOW, "2^31 - 1 recordings or more"};
-    if (!window_range || !out_range || !out_counts || !statuses) return Verdict{FA_INVALID_ARGUMENT, "the ranges, out_counts and statuses are required"};
-    if (window_range[0] < 0 || out_range[0] < 0) return Verdict{FA_INVALID_ARGUMENT, "a range starts below 0"};
+    if (n >= INT32_MAX) return refuse(FA_INDEX_OVERFLOW, "2^31 - 1 recordings or more");
+    if (!window_range || !out_range || !out_counts || !statuses) return refuse(FA_INVALID_ARGUMENT, "the ranges, out_counts and statuses are required");
+    if (window_range[0] < 0 || out_range[0] < 0) return refuse(FA_INVALID_ARGUMENT, "a range starts below 0");
     for (int64_t r = 0; r < n; ++r) {
-        if (window_range[r + 1] < window_range[r] || out_range[r + 1] < out_range[r]) return Verdict{FA_INVALID_ARGUMENT, "the ranges do not ascend"};
-        if (out_range[r + 1] - out_range[r] > INT32_MAX) return Verdict{FA_INDEX_OVERFLOW, "an output slice is longer than INT32_MAX"};
+        if (window_range[r + 1] < window_range[r] || out_range[r + 1] < out_range[r]) return refuse(FA_INVALID_ARGUMENT, "the ranges do not ascend");
+        if (out_range[r + 1] - out_range[r] > INT32_MAX) return refuse(FA_INDEX_OVERFLOW, "an output slice is longer than INT32_MAX");
     }
     const int64_t windows = window_range[n] - window_range[0];
-    if (windows > 0 && !count) return Verdict{FA_INVALID_ARGUMENT, "the windows' counts are required"};
-    if (windows > 0 && max_out > 0 && (!tok || !time || !dur || !conf)) return Verdict{FA_INVALID_ARGUMENT, "the windows' arrays are required"};
-    if (window_range[n] > INT64_MAX / std::max(max_out, 1)) return Verdict{FA_INDEX_OVERFLOW, "the windows' arrays are beyond int64"};
-    if (out_range[n] > out_range[0] && (!out_tok || !out_time || !out_dur || !out_conf)) return Verdict{FA_INVALID_ARGUMENT, "the output arrays are required"};
+    if (windows > 0 && !count) return refuse(FA_INVALID_ARGUMENT, "the windows' counts are required");
+    if (windows > 0 && max_out > 0 && (!tok || !time || !dur || !conf)) return refuse(FA_INVALID_ARGUMENT, "the windows' arrays are required");
+    if (window_range[n] > INT64_MAX / std::max(max_out, 1)) return refuse(FA_INDEX_OVERFLOW, "the windows' arrays are beyond int64");
+    if (out_range[n] > out_range[0] && (!out_tok || !out_time || !out_dur || !out_conf)) return refuse(FA_INVALID_ARGUMENT, "the output arrays are required");
     return Verdict{};
 }
 

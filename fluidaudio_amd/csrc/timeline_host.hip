@@ -30,20 +30,10 @@ fa_status timeline_segments(fa_ctx *ctx, const fa_timeline_config *cfg, const fl
     fa::DeviceGuard guard(ctx->device);
     hipStream_t st = ctx->stream;
     fa::DevBuf b_fin, b_tent, b_rec, b_tile, b_bsum, b_starts, b_runs, b_count, b_off, b_total, b_out;
-    auto alloc = [&](fa::DevBuf &b, size_t bytes) { return b.alloc(ctx, bytes) == hipSuccess; };
-    const auto fail = [&]() { (void)hipGetLastError(); return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "timeline: device allocation failed"); };
-    if (!alloc(b_rec, sizeof(TlRec) * B) || !alloc(b_tile, static_cast<size_t>(blocks)) || !alloc(b_bsum, sizeof(int32_t) * (blocks + 1)) ||
-        !alloc(b_count, sizeof(int32_t) * Q) || !alloc(b_off, sizeof(int32_t) * Q) || !alloc(b_total, sizeof(int32_t)))
-        return fail();
-    const float *d_fin = finalized, *d_tent = tentative;
-    if (!device) {
-        if ((fsum > 0 && !alloc(b_fin, sizeof(float) * fsum * S)) || (tsum > 0 && !alloc(b_tent, sizeof(float) * tsum * S))) return fail();
-        if (fsum > 0) FA_HIP_TRY(ctx, hipMemcpyAsync(b_fin.p, finalized, sizeof(float) * fsum * S, hipMemcpyHostToDevice, st));
-        if (tsum > 0) FA_HIP_TRY(ctx, hipMemcpyAsync(b_tent.p, tentative, sizeof(float) * tsum * S, hipMemcpyHostToDevice, st));
-        d_fin = b_fin.as<float>();
-        d_tent = b_tent.as<float>();
-    }
-    FA_HIP_TRY(ctx, hipMemcpyAsync(b_rec.p, plan.rec.data(), sizeof(TlRec) * B, hipMemcpyHostToDevice, st));
+    FA_TRY(fa::take(ctx, "timeline", {{&b_rec, sizeof(TlRec) * B, true, plan.rec.data()}, {&b_tile, static_cast<size_t>(blocks)}, {&b_bsum, sizeof(int32_t) * (blocks + 1)},
+                                      {&b_count, sizeof(int32_t) * Q}, {&b_off, sizeof(int32_t) * Q}, {&b_total, sizeof(int32_t)},
+                                      {&b_fin, sizeof(float) * fsum * S, !device && fsum > 0, finalized}, {&b_tent, sizeof(float) * tsum * S, !device && tsum > 0, tentative}}));
+    const float *d_fin = device ? finalized : b_fin.as<float>(), *d_tent = device ? tentative : b_tent.as<float>();
     TlArgs ta{d_fin, d_tent, b_rec.as<TlRec>(), b_tile.as<uint8_t>(), b_bsum.as<int32_t>(), S, max_tiles, cfg->onset_threshold, cfg->offset_threshold};
     launch_tiles(st, ta, blocks, 0, nullptr);
     launch_tile_state(st, ta, Q);
@@ -53,7 +43,7 @@ fa_status timeline_segments(fa_ctx *ctx, const fa_timeline_config *cfg, const fl
     int32_t n_runs = 0;
     FA_HIP_TRY(ctx, hipMemcpyAsync(&n_runs, b_bsum.as<int32_t>() + blocks, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     FA_HIP_TRY(ctx, hipStreamSynchronize(st));   // the raw run count sizes the run buffers
-    if (!alloc(b_starts, sizeof(int32_t) * std::max(n_runs, 1)) || !alloc(b_runs, sizeof(TlRun) * std::max(n_runs, 1))) return fail();
+    FA_TRY(fa::take(ctx, "timeline", {{&b_starts, sizeof(int32_t) * std::max(n_runs, 1)}, {&b_runs, sizeof(TlRun) * std::max(n_runs, 1)}}));
     if (n_runs > 0) {
         launch_tiles(st, ta, blocks, 2, b_starts.as<int32_t>());
         launch_run_walk(st, ta, b_starts.as<int32_t>(), Q, n_runs, b_runs.as<TlRun>());
@@ -76,7 +66,7 @@ fa_status timeline_segments(fa_ctx *ctx, const fa_timeline_config *cfg, const fl
     if (!segs || total == 0) return FA_SUCCESS;
     const int64_t n_out = std::min(total, capacity);
     if (n_out > 0) {
-        if (!alloc(b_out, sizeof(fa_diarizer_segment) * n_out)) return fail();
+        FA_TRY(fa::take(ctx, "timeline", {{&b_out, sizeof(fa_diarizer_segment) * n_out}}));
         wa.out = b_out.as<fa_diarizer_segment>();
         wa.capacity = n_out;
         launch_segment_walk(st, wa, 1);

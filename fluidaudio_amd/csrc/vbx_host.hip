@@ -22,15 +22,13 @@ fa_status vbx_setup(fa_ctx *ctx, const double *d_X, int64_t T, int64_t Tg, int64
     const size_t Tn = static_cast<size_t>(T > 0 ? T : 1);
     const size_t TD = Tn * D, TS = Tn * S, SD = static_cast<size_t>(S) * D;
     const int64_t stride = fa::vbx::record_stride(S, D);
-    hipError_t e = hipSuccess;
-    auto A = [&](fa::DevBuf &b, size_t bytes) { if (e == hipSuccess) e = b.alloc(ctx, bytes); };   // from the context's buffer cache: 13 buffers per refinement
-    A(o.phi, 8 * D); A(o.rho, 8 * TD); A(o.G, 8 * Tn); A(o.gamma, 8 * TS); A(o.pi, 8 * S); A(o.logpi, 8 * S);
-    A(o.part, 8 * static_cast<size_t>(kSplit) * stride); A(o.alpha, 8 * SD); A(o.invL, 8 * SD); A(o.phiT, 8 * S);
-    A(o.ll, 8 * Tn); A(o.scal, 64); A(o.hard, 4 * Tn);
-    if (e != hipSuccess) { (void)hipGetLastError(); return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "vbx: device allocation failed"); }
+    const size_t sD = static_cast<size_t>(D), sS = static_cast<size_t>(S);
+    // from the context's buffer cache: 13 buffers per refinement
+    FA_TRY(fa::take(ctx, "vbx", {{&o.phi, 8 * sD, true, phic.data()}, {&o.rho, 8 * TD}, {&o.G, 8 * Tn}, {&o.gamma, 8 * TS}, {&o.pi, 8 * sS}, {&o.logpi, 8 * sS},
+                                 {&o.part, 8 * static_cast<size_t>(kSplit) * stride}, {&o.alpha, 8 * SD}, {&o.invL, 8 * SD}, {&o.phiT, 8 * sS}, {&o.ll, 8 * Tn}, {&o.scal, 64},
+                                 {&o.hard, 4 * Tn}}));
     o.T = T; o.D = D; o.S = S;
     hipStream_t st = ctx->stream;
-    FA_HIP_TRY(ctx, hipMemcpyAsync(o.phi.p, phic.data(), 8 * D, hipMemcpyHostToDevice, st));
     FA_HIP_TRY(ctx, hipMemsetAsync(o.ll.p, 0, 8 * Tn, st));   // the records written before the first E-step carry a zero log-likelihood
     w = VbxWs{};
     w.X = d_X; w.phi = o.phi.as<double>(); w.rho = o.rho.as<double>(); w.G = o.G.as<double>();
@@ -106,10 +104,10 @@ fa_status vbx_degrade(fa_ctx *ctx, int64_t T, int32_t S, const int32_t *d_labels
     (void)hipGetLastError();
     if (T < 0 || S < 1) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "vbx degrade: bad shape");
     const size_t Tn = static_cast<size_t>(T > 0 ? T : 1);
-    hipError_t e = hipSuccess;
-    auto need = [&](fa::DevBuf &b, size_t bytes) { if (e == hipSuccess && (!b.p || b.cap < bytes)) { b.reset(); e = b.alloc(ctx, bytes); } };
-    need(o.gamma, 8 * Tn * S); need(o.pi, 8 * static_cast<size_t>(S)); need(o.hard, 4 * Tn);
-    if (e != hipSuccess) { (void)hipGetLastError(); return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "vbx degrade: device allocation failed"); }
+    // a buffer the failed run left large enough is kept; any other is released and wanted again
+    const auto need = [](fa::DevBuf &b, size_t bytes) { if (b.p && b.cap >= bytes) return false; b.reset(); return true; };
+    const size_t gamma_bytes = 8 * Tn * S, pi_bytes = 8 * static_cast<size_t>(S), hard_bytes = 4 * Tn;
+    FA_TRY(fa::take(ctx, "vbx degrade", {{&o.gamma, gamma_bytes, need(o.gamma, gamma_bytes)}, {&o.pi, pi_bytes, need(o.pi, pi_bytes)}, {&o.hard, hard_bytes, need(o.hard, hard_bytes)}}));
     o.T = T; o.S = S;
     fa::vbx::launch_degrade(ctx->stream, d_labels, o.gamma.as<double>(), o.pi.as<double>(), o.hard.as<int32_t>(), T, S);
     FA_HIP_TRY(ctx, hipGetLastError());
@@ -160,15 +158,8 @@ fa_status shard_fill(fa_vbx_shard *h, const double *rho_local, int64_t T_total, 
     const int64_t T = h->t_hi - h->t_lo;
     if (T > 0 && (!rho_local || !labels_local)) return FA_INVALID_ARGUMENT;
     const size_t Tn = static_cast<size_t>(T > 0 ? T : 1);
-    if (h->X.alloc(8 * Tn * D) != hipSuccess || h->labels.alloc(4 * Tn) != hipSuccess) {
-        (void)hipGetLastError();
-        return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "vbx shard: device allocation failed");
-    }
-    if (T > 0) {
-        hipError_t e = hipMemcpyAsync(h->X.p, rho_local, 8 * static_cast<size_t>(T) * D, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(h->labels.p, labels_local, 4 * static_cast<size_t>(T), hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) return fa::hip_status(ctx, e, "vbx shard upload");
-    }
+    // a rank without frames keeps one placeholder frame and uploads nothing
+    FA_TRY(fa::take_once(ctx, "vbx shard", {{&h->X, 8 * Tn * D, true, T > 0 ? rho_local : nullptr}, {&h->labels, 4 * Tn, true, T > 0 ? labels_local : nullptr}}));
     const int32_t zn = kSplit / h->world;
     return vbx_setup(ctx, h->X.as<double>(), T, T_total, h->t_lo, D, h->labels.as<int32_t>(), S, phi, Fa, Fb, h->rank * zn, zn, h->dev, h->w);
 }
@@ -204,10 +195,8 @@ fa_status fa_vbx_refine(fa_ctx *ctx, const double *rho, int64_t T, int32_t D, co
     return fa::no_throw(ctx, "vbx", [&]() -> fa_status {
         const size_t TD = static_cast<size_t>(T) * D, TS = static_cast<size_t>(T) * S;
         fa::DevBuf bX, blab;
-        if (bX.alloc(8 * TD) != hipSuccess || blab.alloc(4 * T) != hipSuccess) { (void)hipGetLastError(); return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "vbx: device allocation failed"); }
+        FA_TRY(fa::take_once(ctx, "vbx", {{&bX, 8 * TD, true, rho}, {&blab, 4 * static_cast<size_t>(T), true, initial}}));
         hipStream_t st = ctx->stream;
-        FA_HIP_TRY(ctx, hipMemcpyAsync(bX.p, rho, 8 * TD, hipMemcpyHostToDevice, st));
-        FA_HIP_TRY(ctx, hipMemcpyAsync(blab.p, initial, 4 * T, hipMemcpyHostToDevice, st));
         fa::VbxDevice dev;
         bool degraded = false;
         FA_TRY(fa::vbx_refine_dev(ctx, bX.as<double>(), T, D, blab.as<int32_t>(), S, phi, Fa, Fb, max_iter, epsilon, elbos, n_iters, dev,

@@ -31,17 +31,9 @@ fa_status edit_distance(fa_ctx *ctx, const int32_t *hyp, const int64_t *hyp_rang
     fa::DevBuf b_hyp, b_ref, b_jobs, b_out, b_ws;
     const size_t hyp_bytes = device ? 0 : sizeof(int32_t) * static_cast<size_t>(hyp_range[n_pairs] - h0);
     const size_t ref_bytes = device ? 0 : sizeof(int32_t) * static_cast<size_t>(ref_range[n_pairs] - r0);
-    auto alloc = [&](fa::DevBuf &b, size_t bytes) { return b.alloc(ctx, bytes) == hipSuccess; };
-    if (!alloc(b_hyp, hyp_bytes) || !alloc(b_ref, ref_bytes) || !alloc(b_jobs, sizeof(Job) * J) || !alloc(b_out, sizeof(int32_t) * 4 * J) ||
-        !alloc(b_ws, sizeof(int32_t) * static_cast<size_t>(plan.ws_ints))) {
-        (void)hipGetLastError();
-        return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "edit_distance: device allocation failed");
-    }
-    if (!device) {
-        FA_HIP_TRY(ctx, hipMemcpyAsync(b_hyp.p, hyp + h0, hyp_bytes, hipMemcpyHostToDevice, st));
-        FA_HIP_TRY(ctx, hipMemcpyAsync(b_ref.p, ref + r0, ref_bytes, hipMemcpyHostToDevice, st));
-    }
-    FA_HIP_TRY(ctx, hipMemcpyAsync(b_jobs.p, plan.jobs.data(), sizeof(Job) * J, hipMemcpyHostToDevice, st));
+    // hyp_bytes and ref_bytes are 0 for the device entry: nothing is uploaded then
+    FA_TRY(fa::take(ctx, "edit_distance", {{&b_hyp, hyp_bytes, true, hyp + h0}, {&b_ref, ref_bytes, true, ref + r0}, {&b_jobs, sizeof(Job) * J, true, plan.jobs.data()},
+                                           {&b_out, sizeof(int32_t) * 4 * J}, {&b_ws, sizeof(int32_t) * static_cast<size_t>(plan.ws_ints)}}));
     WalkArgs a{device ? hyp : b_hyp.as<int32_t>(), device ? ref : b_ref.as<int32_t>(), nullptr, 0, b_ws.as<int32_t>(), nullptr};
     fa::DeviceTiming tim{ctx};
     FA_TRY(tim.begin());

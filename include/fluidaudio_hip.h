@@ -123,7 +123,8 @@ fa_status fa_debug_ahc_spec_hits(const fa_ctx *ctx, int64_t *hits);
  * fault-injection tests of the degrade contracts:
  *   FA_FAULT_VBX            fa::vbx_run_dev returns RUNTIME_ERROR  -> VBxClustering.refine's catch block (VBxClustering.swift:136-141)
  *   FA_FAULT_THREAD_START   no host thread to be had (std::system_error) -> the share runs on the calling thread
- *   FA_FAULT_DEVBUF_MALLOC  the first hipMalloc of a cached-buffer request fails -> idle caches of the device released, retried
+ *   FA_FAULT_DEVBUF_MALLOC  the first hipMalloc of a cached-buffer request fails -> idle caches of the device released, retried; the retry
+ *                           is a pass too, so count 2 fails one request for good -> the entry returns ALLOCATION_FAILURE
  *   FA_FAULT_WS_MALLOC      the first hipMalloc of a linkage workspace fails     -> the same
  *   FA_FAULT_AHC            the linkage of fa_offline_cluster fails -> singletons (AHCClustering.swift:52-55) */
 enum { FA_FAULT_VBX = 0, FA_FAULT_THREAD_START = 1, FA_FAULT_DEVBUF_MALLOC = 2, FA_FAULT_WS_MALLOC = 3, FA_FAULT_AHC = 4, FA_FAULT_SITES = 5 };

@@ -91,9 +91,9 @@ int main(int argc, char **argv) {
 
     const fa_tdt_merge_config cfg{frame, overlap};
     int32_t none = 0;
-    const mg::Verdict v = mg::check(cfg, w_tok, w_tim, w_dur, w_conf, w_cnt, max_out, window_range.data(), n, vocab, &none, &none, &none, &none, out_range.data(), &none, &none);
+    const fa::Verdict v = mg::check(cfg, w_tok, w_tim, w_dur, w_conf, w_cnt, max_out, window_range.data(), n, vocab, &none, &none, &none, &none, out_range.data(), &none, &none);
     if (v.status != FA_SUCCESS) {
-        std::printf("CHECK %d %s\n", static_cast<int>(v.status), v.what);
+        std::printf("CHECK %d %s\n", static_cast<int>(v.status), v.text);
         std::free(w_tok); std::free(w_tim); std::free(w_dur); std::free(w_conf); std::free(w_cnt);
         return 0;
     }
