@@ -48,7 +48,7 @@ EXPORTED_SYMBOLS = [
     "fa_ctc_vocab_create", "fa_ctc_vocab_destroy", "fa_ctc_beam_search_batch_dev", "fa_ctc_beam_search_batch",
     "fa_wav_pcm16_size", "fa_wav_encode_pcm16", "fa_wav_decode", "fa_rttm_parse", "fa_rttm_format", "fa_export_embeddings_json",
     "fa_seeded_rng_next", "fa_seeded_rng_below", "fa_kmeans_cluster", "fa_kmeans_cluster_ninit", "fa_speaker_constraints_resolve",
-    "fa_resample_linear_frames", "fa_resample_linear", "fa_resample_poly_frames", "fa_resample_poly_taps", "fa_resample_poly", "fa_resample_poly_dev",
+    "fa_resample_linear_frames", "fa_resample_linear", "fa_resample_poly_frames", "fa_resample_poly_taps", "fa_resample_poly", "fa_resample_poly_dev", "fa_debug_resample_route",
     "fa_device_count", "fa_pool_create", "fa_pool_destroy", "fa_pool_size", "fa_pool_context", "fa_ctx_device", "fa_pool_acquire", "fa_pool_release",
     "fa_mel_batch_sharded", "fa_ctc_greedy_batch_sharded", "fa_ahc_linkage_many",
     "fa_powerset_decode_dev", "fa_powerset_decode", "fa_offline_chunk_assignments", "fa_reconstruct_default_config",
@@ -190,6 +190,14 @@ class ParaformerSpan(C.Structure):
 
 class TdtMergeConfig(C.Structure):
     _fields_ = [("frame_seconds", C.c_double), ("overlap_seconds", C.c_double)]
+
+
+RESAMPLE_ROUTE_KINDS = ("DECIM", "INTERP", "ROWS", "LDS", "SIMPLE")    # FA_RESAMPLE_ROUTE_*
+
+
+class ResampleRoute(C.Structure):                                      # fa_resample_route (fa_debug_resample_route: tests)
+    _fields_ = [("lo", C.c_int64), ("hi", C.c_int64), ("split", C.c_int64), ("count", C.c_int64), ("kind", C.c_int32), ("wide", C.c_int32),
+                ("tile_rows", C.c_int32), ("wide_waves", C.c_int32), ("nv", C.c_int32), ("share", C.c_int32), ("groups", C.c_int32)]
 
 
 def build(force: bool = False) -> str:
@@ -362,6 +370,7 @@ def lib() -> C.CDLL:
     L.fa_resample_poly_taps.argtypes = [i32, i32, vp, i64, C.POINTER(i64), C.POINTER(i64)]
     L.fa_resample_poly.argtypes = [vp, vp, i64, i32, i32, vp, i64, C.POINTER(i64)]
     L.fa_resample_poly_dev.argtypes = [vp, vp, i64, i32, i32, vp, i64, C.POINTER(i64)]
+    L.fa_debug_resample_route.argtypes = [vp, vp, i64, i32, i32, vp, C.POINTER(ResampleRoute)]
     L.fa_offline_cluster_batch.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, C.POINTER(OfflineClusterConfig), vp, vp, i32, vp, vp, vp]
     L.fa_offline_cluster_batch_dev.argtypes = L.fa_offline_cluster_batch.argtypes
     L.fa_device_count.argtypes = [C.POINTER(i32)]

@@ -1,5 +1,6 @@
 // resample_host.hip — host side of the sample-rate converter (polyphase kernels and their launchers: resample.hip; shared: resample_launch.h,
-// resample_geom.h): the Kaiser taps, the plan a context keeps for its last rate pair, the route a call takes through the kernels, and the C ABI.
+// resample_geom.h): the Kaiser taps, the plan a context keeps for its last rate pair, the route a call takes through the kernels (chosen by
+// pick_route of resample_route.h, plain C++ that the CPU tests walk), and the C ABI.
 //
 // (1) fa_resample_linear replaces AudioConverter.linearResample
 //     (reference: Sources/FluidAudio/Shared/AudioConverter.swift:388-442): mix N planar channels down to mono with
@@ -14,6 +15,7 @@
 #include <vector>
 
 #include "resample_launch.h"
+#include "resample_route.h"
 
 namespace {
 
@@ -52,13 +54,9 @@ int64_t gcd64(int64_t a, int64_t b) { while (b) { const int64_t t = a % b; a = b
 // ------------------------------------------------------------------------------ the plan of a rate pair
 // What a context keeps for its last (up, down): everything a call needs that does not depend on the call.  Built by the first call of a pair
 // (plan_get), with the taps; a repeated call with the same pair finds it and enqueues its kernels without host work, allocation or synchronisation.
-struct ResamplePlan {
-    int up = 0, down = 0;                       // reduced by their greatest common divisor
-    int64_t n_taps = 0, pre_remove = 0;         // fa_resample_poly_taps
+struct ResamplePlan : PlanFacts {               // (resample_route.h: the pair, its filter, the families with an instance for it — what the route reads)
     float *d_taps = nullptr;
-    RowsTables rows;                            // rows.d_tables set: the row kernels serve the pair (rows.wide: a wide one)
-    bool decim_tiles = false, decim_regs = false, interp = false;   // the other families with an instance for the pair ...
-    size_t lds_bytes = 0;                       // ... and what poly_lds_kernel needs for it: served up to 150 KB
+    RowsTables rows;                            // rows.d_tables set (has_rows): the row kernels serve the pair (rows.wide: a wide one)
     ~ResamplePlan() { (void)hipFree(d_taps); (void)hipFree(rows.d_tables); }
 };
 void plan_free(void *p) { delete static_cast<ResamplePlan *>(p); }
@@ -133,6 +131,7 @@ fa_status plan_get(fa_ctx *ctx, const int up, const int down, const ResamplePlan
             R.d_tables = nullptr;
         }
     }
+    P->has_rows = R.d_tables != nullptr; P->rows_geom = R.g; P->tile_rows = R.tile_rows();
     const bool decim_pair = up == 1 && P->n_taps == 21 * down + 1 && P->pre_remove == 11;   // the geometry the decimation kernels are written for
     P->decim_tiles = decim_pair && decim_tiles_instance(down);
     P->decim_regs = decim_pair && decim_instance(down);
@@ -145,33 +144,13 @@ fa_status plan_get(fa_ctx *ctx, const int up, const int down, const ResamplePlan
 }
 
 // ------------------------------------------------------------------------------ the route of a call
-// The kernel-choice switches of the tests, read ONCE per call (the forms fixed with a plan's tables — FA_RESAMPLE_WIDE, _NO_WIDE — are read when it is built).
-struct Switches { bool simple, no_decim, no_decim_tiles, no_rows; };
-// One family serves the interior outputs [lo, hi), poly_kernel the edges [0, lo) and [hi, n_out).  DECIM: tiles on [lo, split), the register-tiled kernel on
-// [split, hi).  INTERP: `count` threads from phase cycle `split` on.  ROWS: `count` tiles.  LDS: everything.  SIMPLE: nothing — all outputs are edges.
-enum class Kind { DECIM, INTERP, ROWS, LDS, SIMPLE };
-struct Route { Kind kind; int64_t lo, hi, split, count; };
-
-// The first family, in this order, that has an instance for the pair, is not switched off and finds whole work items inside the signal.
-Route pick_route(const ResamplePlan &P, const Switches &sw, const uintptr_t x_addr, const uintptr_t y_addr, const int64_t frames, const int64_t n_out) {
-    if (sw.simple) return {Kind::SIMPLE, 0, 0, 0, 0};
-    if (P.decim_tiles && !sw.no_decim && (x_addr & 15) == 0 && (y_addr & 7) == 0) {   // 16-byte loads, 8-byte stores
-        fa::DecimSplit s = fa::decim_split(P.down, frames, n_out, !sw.no_decim_tiles);
-        if (!P.decim_regs) s.m_regs = s.m_tiles;         // (192 kHz has tiles only: what they leave goes to the edges)
-        if (s.m_regs > s.m_begin) return {Kind::DECIM, s.m_begin, s.m_regs, s.m_tiles, 0};
-    }
-    if (P.interp) {
-        int64_t m_begin = 0, q_begin = 0, groups = 0;
-        fa::interp_geometry(P.up, P.down, static_cast<int>(P.n_taps), fa::kInterpR, frames, n_out, P.pre_remove, m_begin, q_begin, groups);
-        if (groups > 0) return {Kind::INTERP, m_begin, m_begin + groups * fa::kInterpR * P.up, q_begin, groups};
-    }
-    if (P.rows.d_tables && !sw.no_rows) {
-        const fa::PolyRowsGeom &G = P.rows.g;
-        const int64_t tiles = fa::rows_tiles(G, frames, n_out, P.rows.tile_rows());       // tiles whose staged inputs all exist
-        if (tiles > 0 && (tiles + 8) * G.groups < (1LL << 31)) return {Kind::ROWS, G.m_begin, std::min(n_out, G.m_begin + tiles * P.rows.tile_rows() * G.up), 0, tiles};
-    }
-    if (P.lds_bytes <= 150 * 1024) return {Kind::LDS, 0, n_out, 0, 0};
-    return {Kind::SIMPLE, 0, 0, 0, 0};                   // very long filters (extreme rate ratios)
+// The context's plan for the pair and the family that serves this call (pick_route of resample_route.h), with the switches as they stand now.
+fa_status route_get(fa_ctx *ctx, const float *d_x, const int64_t frames, const int32_t up, const int32_t down, const float *d_y, const int64_t n_out, const ResamplePlan *&P, Route &r) {
+    const int64_t g = gcd64(up, down);
+    FA_TRY(plan_get(ctx, static_cast<int>(up / g), static_cast<int>(down / g), P));
+    const Switches sw = {fa::sw_on(fa::Sw::RESAMPLE_SIMPLE), fa::sw_on(fa::Sw::RESAMPLE_NO_DECIM), fa::sw_on(fa::Sw::RESAMPLE_NO_DECIM_TILES), fa::sw_on(fa::Sw::RESAMPLE_NO_ROWS)};
+    r = pick_route(*P, sw, reinterpret_cast<uintptr_t>(d_x), reinterpret_cast<uintptr_t>(d_y), frames, n_out);
+    return FA_SUCCESS;
 }
 
 }  // namespace
@@ -263,11 +242,9 @@ fa_status fa_resample_poly_dev(fa_ctx *ctx, const float *d_x, int64_t frames, in
     if (!d_x || !d_y) return FA_INVALID_ARGUMENT;
     try {
         fa::DeviceGuard guard(ctx->device);
-        const int64_t g = gcd64(up, down);
         const ResamplePlan *P = nullptr;
-        FA_TRY(plan_get(ctx, static_cast<int>(up / g), static_cast<int>(down / g), P));
-        const Switches sw = {fa::sw_on(fa::Sw::RESAMPLE_SIMPLE), fa::sw_on(fa::Sw::RESAMPLE_NO_DECIM), fa::sw_on(fa::Sw::RESAMPLE_NO_DECIM_TILES), fa::sw_on(fa::Sw::RESAMPLE_NO_ROWS)};
-        const Route r = pick_route(*P, sw, reinterpret_cast<uintptr_t>(d_x), reinterpret_cast<uintptr_t>(d_y), frames, n_out);
+        Route r{};
+        FA_TRY(route_get(ctx, d_x, frames, up, down, d_y, n_out, P, r));
         const Job job = {ctx->stream, d_x, P->d_taps, d_y, frames, n_out, P->n_taps, P->pre_remove, P->up, P->down};
         switch (r.kind) {
             case Kind::DECIM: launch_decim_tiles(P->down, job, r.lo, r.split); launch_decim(P->down, job, r.split, r.hi); break;
@@ -279,6 +256,35 @@ fa_status fa_resample_poly_dev(fa_ctx *ctx, const float *d_x, int64_t frames, in
         launch_edges(job, 0, r.lo);
         launch_edges(job, r.hi, n_out);
         FA_HIP_TRY(ctx, hipGetLastError());
+        return FA_SUCCESS;
+    } catch (const std::bad_alloc &) {
+        return FA_ALLOCATION_FAILURE;
+    } catch (...) {
+        return FA_UNKNOWN_ERROR;
+    }
+}
+
+fa_status fa_debug_resample_route(fa_ctx *ctx, const float *d_x, int64_t frames, int32_t up, int32_t down, const float *d_y, fa_resample_route *out) {
+    if (!ctx || !out) return FA_INVALID_ARGUMENT;
+    if (!fa_debug_hooks_enabled()) return FA_RUNTIME_ERROR;
+    *out = fa_resample_route{};
+    out->kind = FA_RESAMPLE_ROUTE_SIMPLE;
+    if (frames < 0 || up < 1 || down < 1) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "resample_route: bad arguments");
+    if (frames == 0) return FA_SUCCESS;       // (such a call launches nothing and builds no plan)
+    try {
+        fa::DeviceGuard guard(ctx->device);
+        const ResamplePlan *P = nullptr;
+        Route r{};
+        FA_TRY(route_get(ctx, d_x, frames, up, down, d_y, fa_resample_poly_frames(frames, up, down), P, r));
+        static_assert(static_cast<int>(Kind::DECIM) == FA_RESAMPLE_ROUTE_DECIM && static_cast<int>(Kind::INTERP) == FA_RESAMPLE_ROUTE_INTERP &&
+                      static_cast<int>(Kind::ROWS) == FA_RESAMPLE_ROUTE_ROWS && static_cast<int>(Kind::LDS) == FA_RESAMPLE_ROUTE_LDS &&
+                      static_cast<int>(Kind::SIMPLE) == FA_RESAMPLE_ROUTE_SIMPLE, "the header's numbering");
+        out->kind = static_cast<int32_t>(r.kind);
+        out->lo = r.lo; out->hi = r.hi; out->split = r.split; out->count = r.count;
+        if (r.kind == Kind::ROWS) {
+            const RowsTables &R = P->rows;
+            out->wide = R.wide ? 1 : 0; out->tile_rows = R.tile_rows(); out->wide_waves = R.wide_waves; out->nv = R.nv; out->share = R.g.share; out->groups = R.g.groups;
+        }
         return FA_SUCCESS;
     } catch (const std::bad_alloc &) {
         return FA_ALLOCATION_FAILURE;

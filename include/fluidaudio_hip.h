@@ -1078,6 +1078,23 @@ fa_status fa_resample_poly(fa_ctx *ctx, const float *x, int64_t frames, int32_t 
  * tables on the device): the first call of a pair builds it and synchronises the stream, a repeated call does neither. */
 fa_status fa_resample_poly_dev(fa_ctx *ctx, const float *d_x, int64_t frames, int32_t up, int32_t down, float *d_y,
                                int64_t out_capacity, int64_t *out_frames);
+/* Test hook: which kernel family a fa_resample_poly_dev call with these arguments would take.  It gets or builds the context's plan for the pair
+ * exactly as the call would (the first time for a pair: taps and tables go to the device and the stream is synchronised), reads the same
+ * FA_RESAMPLE_* switches and launches no kernel; d_x and d_y are looked at as addresses only.  One family serves the interior outputs [lo, hi),
+ * the one-thread-per-output kernel the edges [0, lo) and [hi, n_out):
+ *   DECIM   integer decimation: LDS tiles on [lo, split), the register-tiled kernel on [split, hi)
+ *   INTERP  `count` threads of the register-tiled interpolation kernel from phase cycle `split` on
+ *   ROWS    `count` tiles of a row kernel — wide: a persistent one (tile_rows 16 / 32, wide_waves wavefronts), else the 64-row kernel —
+ *           with windows of nv 16-byte reads shared by `share` phases, in `groups` phase groups (these six are 0 for the other kinds)
+ *   LDS     the LDS-staged kernel on every output;  SIMPLE: nothing but edges (frames == 0 reports SIMPLE and builds no plan)
+ * RUNTIME_ERROR without FLUIDAUDIO_HIP_DEBUG_HOOKS=1; INVALID_ARGUMENT for a NULL ctx / out, frames < 0, up < 1 or down < 1. */
+enum { FA_RESAMPLE_ROUTE_DECIM = 0, FA_RESAMPLE_ROUTE_INTERP = 1, FA_RESAMPLE_ROUTE_ROWS = 2, FA_RESAMPLE_ROUTE_LDS = 3, FA_RESAMPLE_ROUTE_SIMPLE = 4 };
+typedef struct {
+    int64_t lo, hi, split, count;
+    int32_t kind;
+    int32_t wide, tile_rows, wide_waves, nv, share, groups;
+} fa_resample_route;
+fa_status fa_debug_resample_route(fa_ctx *ctx, const float *d_x, int64_t frames, int32_t up, int32_t down, const float *d_y, fa_resample_route *out);
 
 /* ------------------------------------------------------------------ device set ------ */
 /* Multi-GPU for a single-process host (the reference has no multi-device notion; SURVEY §8e: utterances, logit matrices and

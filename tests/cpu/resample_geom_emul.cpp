@@ -153,6 +153,17 @@ int rows_emulate(const float *x, int64_t n_in, const float *h, int64_t h_len, in
     return 0;
 }
 
+// fa::rows_geometry alone, for the tests that restate the route of a call: out = m_begin, k_begin, groups, ppg, sld, smax, share, nv; 0, or -1: pair not served
+int rows_geom_of(const float *h, int64_t h_len, int up, int down, int64_t pre_remove, int share_max, int64_t lds_budget, int64_t *out) {
+    fa::PolyRowsGeom g{};
+    int nv = 0;
+    std::vector<int> gtab;
+    std::vector<float> tt;
+    if (!fa::rows_geometry(g, nv, std::vector<float>(h, h + h_len), up, down, pre_remove, gtab, tt, static_cast<size_t>(lds_budget), share_max)) return -1;
+    out[0] = g.m_begin; out[1] = g.k_begin; out[2] = g.groups; out[3] = g.ppg; out[4] = g.sld; out[5] = g.smax; out[6] = g.share; out[7] = nv;
+    return 0;
+}
+
 // poly_interp_kernel<up, down, nt>, R = 4
 int interp_emulate(const float *x, int64_t n_in, const float *h, int nt, int up, int down, int64_t pre_remove, int64_t n_out, float *y, int64_t *m_lo, int64_t *m_hi) {
     const int R = fa::kInterpR, NO = R * up, KB = (nt - 1) / up, NIN = ((NO - 1) * down) / up + KB + 1, NV = (NIN + 3) / 4;

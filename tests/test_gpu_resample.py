@@ -1,6 +1,12 @@
 """Resampling kernels: AudioConverter.linearResample bit-exact vs the oracle; polyphase extension vs scipy."""
+import os
+import sys
+
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import resample_restatement as R  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -34,6 +40,11 @@ def test_polyphase_extension_vs_scipy(fa, gpu_ctx, up, down, n):
     got = fa.resample_poly(x, up, down, ctx=gpu_ctx)
     assert got.size == ref.size
     np.testing.assert_allclose(got, ref, rtol=0, atol=2e-5)
+    # the kernels' arithmetic alone, with the library's own float32 taps: the float64 restatement and its derived bound (tests/resample_restatement.py)
+    taps, pre = fa.poly_taps(up, down)
+    problems, worst = R.compare(got, *R.reference(x, taps, up, down, pre))
+    print(f"resample-ratio host-entry {worst:.3f} vs_scipy_{up}_{down}_n{n}")
+    assert problems == [], problems
 
 
 @pytest.mark.parametrize("up,down,n", [(1, 3, 250001), (160, 441, 132300), (2, 1, 40000), (640, 441, 33075), (1, 6, 96000), (1, 1, 5000), (3, 2, 5), (160, 147, 14700),
@@ -85,6 +96,9 @@ def test_rows_kernel_actually_serves_the_common_non_integer_pairs(fa, gpu_ctx, s
             e1.record(stream)
             gpu_ctx.synchronize()
             return e0.elapsed_time(e1) / 3
+        route = fa._lib.ResampleRoute()                                   # the route itself, before the stopwatch: a wide row kernel serves the call
+        gpu_ctx.check(fa.lib().fa_debug_resample_route(gpu_ctx.handle, C.c_void_p(x.data_ptr()), n, up, down, C.c_void_p(y.data_ptr()), C.byref(route)), "route")
+        assert fa._lib.RESAMPLE_ROUTE_KINDS[route.kind] == "ROWS" and route.wide == 1 and route.hi - route.lo > 0.99 * n_out, (up, down, route.kind, route.wide)
         t_rows = timed(y)
         switch("FA_RESAMPLE_NO_ROWS", "1")
         t_lds = timed(y2)
