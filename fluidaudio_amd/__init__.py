@@ -31,6 +31,8 @@ from .tdt import (TdtConfig, TdtDurationMapping, TdtFrameNavigation, decode_logi
 from .tdt_merge import (MERGE_NO_SEAM, MergedWindows, merge_capacity, merge_route_name, merge_windows, merge_windows_dev,  # noqa: F401
                         splice_safe_table, case_canon_table)
 from .timeline import DiarizerSegment, DiarizerTimeline, DiarizerTimelineConfig, timeline_segments  # noqa: F401
+from .vad import (VAD_SEGMENT_DTYPE, VAD_STREAM_EVENT_DTYPE, VAD_STREAM_STATE_DTYPE, gather_segments, gather_segments_dev, initial_stream_states,  # noqa: F401
+                  pack_chunks, pack_chunks_dev, segment_speech_batch, segment_speech_batch_dev, stream_advance, stream_advance_dev, vad_config)
 from .vbx import VBxClustering, VBxOutput  # noqa: F401
 from .wer import (EDIT_COUNTS_DTYPE, CorpusErrorRate, WERAndCER, WERMetrics, edit_distance_batch, edit_distance_batch_dev, levenshtein_distance,  # noqa: F401
                   wer_and_cer_batch, wer_metrics_batch)

@@ -62,6 +62,8 @@ EXPORTED_SYMBOLS = [
     "fa_kws_adjusted_threshold", "fa_ctc_kws_spot_batch_dev", "fa_ctc_kws_spot_batch", "fa_ctc_kws_score_windows_dev", "fa_ctc_kws_score_windows",
     "fa_paraformer_cif_default_config", "fa_paraformer_cif_dev", "fa_paraformer_cif", "fa_paraformer_timestamps_dev", "fa_paraformer_timestamps",
     "fa_tdt_merge_default_config", "fa_tdt_merge_windows_dev", "fa_tdt_merge_windows",
+    "fa_vad_default_config", "fa_vad_chunk_count", "fa_vad_segments_dev", "fa_vad_segments", "fa_vad_pack_chunks_dev", "fa_vad_pack_chunks",
+    "fa_vad_gather_segments_dev", "fa_vad_gather_segments", "fa_vad_stream_advance_dev", "fa_vad_stream_advance",
 ]
 
 
@@ -190,6 +192,26 @@ class ParaformerSpan(C.Structure):
 
 class TdtMergeConfig(C.Structure):
     _fields_ = [("frame_seconds", C.c_double), ("overlap_seconds", C.c_double)]
+
+
+class VadSegmentationConfig(C.Structure):
+    _fields_ = [("default_threshold", C.c_float), ("reserved0", C.c_int32), ("min_speech_duration", C.c_double), ("min_silence_duration", C.c_double),
+                ("max_speech_duration", C.c_double), ("speech_padding", C.c_double), ("silence_threshold_for_split", C.c_float),
+                ("has_negative_threshold", C.c_int32), ("negative_threshold", C.c_float), ("negative_threshold_offset", C.c_float),
+                ("min_silence_at_max_speech", C.c_double), ("use_max_possible_silence_at_max_speech", C.c_int32), ("reserved1", C.c_int32)]
+
+
+class VadSegmentRecord(C.Structure):
+    _fields_ = [("recording", C.c_int32), ("reserved", C.c_int32), ("start_sample", C.c_int64), ("end_sample", C.c_int64),
+                ("start_time", C.c_double), ("end_time", C.c_double)]
+
+
+class VadStreamStateRecord(C.Structure):
+    _fields_ = [("triggered", C.c_int32), ("has_temp_end", C.c_int32), ("temp_end_sample", C.c_int64), ("processed_samples", C.c_int64)]
+
+
+class VadStreamEventRecord(C.Structure):
+    _fields_ = [("stream", C.c_int32), ("chunk", C.c_int32), ("kind", C.c_int32), ("reserved", C.c_int32), ("sample_index", C.c_int64), ("time", C.c_double)]
 
 
 RESAMPLE_ROUTE_KINDS = ("DECIM", "INTERP", "ROWS", "LDS", "SIMPLE")    # FA_RESAMPLE_ROUTE_*
@@ -438,6 +460,18 @@ def lib() -> C.CDLL:
     L.fa_tdt_merge_default_config.restype = None
     L.fa_tdt_merge_windows_dev.argtypes = [vp, C.POINTER(TdtMergeConfig), vp, vp, vp, vp, vp, i32, vp, i64, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.fa_tdt_merge_windows.argtypes = L.fa_tdt_merge_windows_dev.argtypes
+    L.fa_vad_default_config.argtypes = [C.POINTER(VadSegmentationConfig)]
+    L.fa_vad_default_config.restype = None
+    L.fa_vad_chunk_count.argtypes = [i64]
+    L.fa_vad_chunk_count.restype = i64
+    L.fa_vad_segments_dev.argtypes = [vp, C.POINTER(VadSegmentationConfig), vp, vp, vp, i32, vp, i64, C.POINTER(i64), vp]
+    L.fa_vad_segments.argtypes = L.fa_vad_segments_dev.argtypes
+    L.fa_vad_pack_chunks_dev.argtypes = [vp, vp, vp, i32, vp, i64, vp]
+    L.fa_vad_pack_chunks.argtypes = L.fa_vad_pack_chunks_dev.argtypes
+    L.fa_vad_gather_segments_dev.argtypes = [vp, vp, vp, i32, vp, i64, vp, i64, vp]
+    L.fa_vad_gather_segments.argtypes = L.fa_vad_gather_segments_dev.argtypes
+    L.fa_vad_stream_advance_dev.argtypes = [vp, C.POINTER(VadSegmentationConfig), vp, vp, vp, i32, i32, vp, i32, i32, vp, i64, C.POINTER(i64)]
+    L.fa_vad_stream_advance.argtypes = L.fa_vad_stream_advance_dev.argtypes
     _lib = L
     return L
 

@@ -1224,4 +1224,113 @@ struct ParaformerManager {
     }
 };
 
+// ------------------------------------------------------------------------------------------------------------------ VAD
+// VadConfig (Sources/FluidAudio/VAD/VadTypes.swift:4-21) without the CoreML fields
+struct VadConfig {
+    float defaultThreshold = 0.85f;
+};
+
+// VadSegmentationConfig (VadTypes.swift:24-91).  The preconditions of its init are the refusals of the entries it is handed to.
+struct VadSegmentationConfig {
+    double minSpeechDuration = 0.15, minSilenceDuration = 0.75, maxSpeechDuration = 14.0, speechPadding = 0.1;
+    float silenceThresholdForSplit = 0.3f;
+    std::optional<float> negativeThreshold;
+    float negativeThresholdOffset = 0.15f;
+    double minSilenceAtMaxSpeech = 0.098;
+    bool useMaxPossibleSilenceAtMaxSpeech = true;
+    float effectiveNegativeThreshold(float baseThreshold) const {
+        if (negativeThreshold) return *negativeThreshold;
+        const float x = baseThreshold - negativeThresholdOffset;
+        return 0.01f >= x ? 0.01f : x;
+    }
+    fa_vad_segmentation_config abi(const VadConfig &vad = VadConfig{}) const {
+        fa_vad_segmentation_config c{};
+        c.default_threshold = vad.defaultThreshold;
+        c.min_speech_duration = minSpeechDuration; c.min_silence_duration = minSilenceDuration; c.max_speech_duration = maxSpeechDuration; c.speech_padding = speechPadding;
+        c.silence_threshold_for_split = silenceThresholdForSplit;
+        c.has_negative_threshold = negativeThreshold ? 1 : 0; c.negative_threshold = negativeThreshold.value_or(0.0f); c.negative_threshold_offset = negativeThresholdOffset;
+        c.min_silence_at_max_speech = minSilenceAtMaxSpeech;
+        c.use_max_possible_silence_at_max_speech = useMaxPossibleSilenceAtMaxSpeech ? 1 : 0;
+        return c;
+    }
+};
+
+// VadSegment (VadTypes.swift:137-164)
+struct VadSegment {
+    double startTime = 0.0, endTime = 0.0;
+    double duration() const { return endTime - startTime; }
+    int64_t startSample(int sampleRate) const { return static_cast<int64_t>(startTime * static_cast<double>(sampleRate)); }
+    int64_t endSample(int sampleRate) const { return static_cast<int64_t>(endTime * static_cast<double>(sampleRate)); }
+    int64_t sampleCount(int sampleRate) const { return endSample(sampleRate) - startSample(sampleRate); }
+};
+
+// VadStreamState (VadTypes.swift:166-187) without the model's state, which stays with whoever runs the network
+struct VadStreamState {
+    bool triggered = false;
+    std::optional<int64_t> tempEndSample;
+    int64_t processedSamples = 0;
+    static VadStreamState initial() { return VadStreamState{}; }
+    fa_vad_stream_state abi() const { return fa_vad_stream_state{triggered ? 1 : 0, tempEndSample ? 1 : 0, tempEndSample.value_or(0), processedSamples}; }
+    static VadStreamState from(const fa_vad_stream_state &s) {
+        VadStreamState r;
+        r.triggered = s.triggered != 0;
+        if (s.has_temp_end) r.tempEndSample = s.temp_end_sample;
+        r.processedSamples = s.processed_samples;
+        return r;
+    }
+};
+
+// VadStreamEvent (VadTypes.swift:189-207)
+struct VadStreamEvent {
+    enum class Kind { speechStart = FA_VAD_SPEECH_START, speechEnd = FA_VAD_SPEECH_END };
+    Kind kind = Kind::speechStart;
+    int64_t sampleIndex = 0;
+    std::optional<double> time;
+    bool isStart() const { return kind == Kind::speechStart; }
+    bool isEnd() const { return kind == Kind::speechEnd; }
+};
+
+// The host arithmetic of VadManager round the network (VadManager+SpeechSegmentation.swift, VadManager+Streaming.swift, VadManager.swift)
+// for ONE recording or stream; the batched forms are the C entries.
+struct VadManager {
+    static constexpr int chunkSize = 4096, contextLength = 64, sampleRate = 16000, modelInputSize = 4160;
+    VadConfig config;
+    // segmentSpeech(from:totalSamples:config:) on the probabilities the network gave, one per chunk
+    std::vector<VadSegment> segmentSpeech(Context &ctx, const std::vector<float> &probabilities, int64_t totalSamples, const VadSegmentationConfig &cfg = {}) const {
+        const fa_vad_segmentation_config c = cfg.abi(config);
+        const int64_t range[2] = {0, static_cast<int64_t>(probabilities.size())};
+        std::vector<fa_vad_segment> segs(probabilities.size());                  // at most one segment per frame
+        int64_t count = 0;
+        ctx.check(fa_vad_segments(ctx.handle(), &c, probabilities.data(), range, &totalSamples, 1, segs.data(), static_cast<int64_t>(segs.size()), &count, nullptr), "fa_vad_segments");
+        std::vector<VadSegment> out;
+        for (int64_t i = 0; i < count; ++i) out.push_back(VadSegment{segs[static_cast<size_t>(i)].start_time, segs[static_cast<size_t>(i)].end_time});
+        return out;
+    }
+    // the audio_input rows of processAudioSamples: [chunks][4160]
+    static std::vector<float> modelInputs(Context &ctx, const std::vector<float> &samples) {
+        const int64_t offsets[2] = {0, static_cast<int64_t>(samples.size())};
+        int64_t range[2] = {0, 0};
+        std::vector<float> rows(static_cast<size_t>(fa_vad_chunk_count(offsets[1])) * modelInputSize);
+        ctx.check(fa_vad_pack_chunks(ctx.handle(), samples.data(), offsets, 1, rows.data(), fa_vad_chunk_count(offsets[1]), range), "fa_vad_pack_chunks");
+        return rows;
+    }
+    // streamingStateMachine for one chunk
+    std::optional<VadStreamEvent> streamingStateMachine(Context &ctx, float probability, int32_t chunkSampleCount, VadStreamState &state, const VadSegmentationConfig &cfg = {},
+                                                        bool returnSeconds = false, int timeResolution = 1) const {
+        const fa_vad_segmentation_config c = cfg.abi(config);
+        fa_vad_stream_state st = state.abi();
+        fa_vad_stream_event ev{};
+        const int32_t one = 1;
+        int64_t count = 0;
+        ctx.check(fa_vad_stream_advance(ctx.handle(), &c, &probability, &one, &chunkSampleCount, 1, 1, &st, returnSeconds ? 1 : 0, timeResolution, &ev, 1, &count), "fa_vad_stream_advance");
+        state = VadStreamState::from(st);
+        if (count == 0) return std::nullopt;
+        VadStreamEvent out;
+        out.kind = static_cast<VadStreamEvent::Kind>(ev.kind);
+        out.sampleIndex = ev.sample_index;
+        if (returnSeconds) out.time = ev.time;
+        return out;
+    }
+};
+
 }  // namespace fluidaudio

@@ -1060,6 +1060,83 @@ fa_status fa_tdt_merge_windows(fa_ctx *ctx, const fa_tdt_merge_config *cfg, cons
                                float *out_conf, const int64_t *out_range, int32_t *out_counts, int32_t *statuses,
                                int32_t *seam_routes);
 
+/* ------------------------------------------------------------------ VAD: speech segments, model rows, streaming events ------ */
+/* The host arithmetic round the Silero network (FluidAudio/VAD), batched over recordings: segmentSpeech(from:totalSamples:config:)
+ * with detectSpeechSampleRanges (VadManager+SpeechSegmentation.swift:22-51, 71-234), the model's input rows of processAudioSamples /
+ * processChunk (VadManager.swift:162-206, 352-376), the audio of segmentSpeechAudio (:55-67) and streamingStateMachine
+ * (VadManager+Streaming.swift:31-107).  Integers, fp32 comparisons and fp64 divisions in the reference's order: the outputs are the
+ * reference's bit for bit (pinned by its VadSegmentationTests / VadStreamingTests through tests/vad_restatement.py).  Frames are
+ * chunks of 4096 samples at 16 kHz; a model row is 64 context samples and 4096 chunk samples.  OUT OF SCOPE: the Silero network and its
+ * LSTM state (the caller's), isSilentAudio, FSMN-VAD (VAD/Fsmn/).
+ * Conventions of the four entries: cfg nullable = the defaults; _dev takes DEVICE pointers where it says so and reads them in stream
+ * order; *count is set even when the output is NULL (SUCCESS) or too small (OUTPUT_TOO_SMALL, the first `capacity` records written);
+ * every refusal is decided before any device work; batch == 0: SUCCESS; one host synchronisation unless stated otherwise. */
+typedef struct {
+    float default_threshold;                          /* VadConfig.defaultThreshold */
+    int32_t reserved0;
+    double min_speech_duration, min_silence_duration, max_speech_duration, speech_padding;   /* seconds; max_speech_duration may be +inf */
+    float silence_threshold_for_split;
+    int32_t has_negative_threshold;                   /* negativeThreshold != nil */
+    float negative_threshold;
+    float negative_threshold_offset;
+    double min_silence_at_max_speech;
+    int32_t use_max_possible_silence_at_max_speech;
+    int32_t reserved1;
+} fa_vad_segmentation_config;
+void fa_vad_default_config(fa_vad_segmentation_config *cfg);   /* 0.85; 0.15, 0.75, 14.0, 0.1; 0.3; nil, 0.15; 0.098; true */
+typedef struct { int32_t recording, reserved; int64_t start_sample, end_sample; double start_time, end_time; } fa_vad_segment;
+/* probs float[sum frames]: recording b's probabilities at frame_range[b] ... frame_range[b + 1] (HOST int64[batch + 1]);
+ * total_samples HOST int64[batch].  A recording without frames or with total_samples <= 0 yields nothing; NaN probabilities are in
+ * neither class.  segs HOST [capacity], by recording and time: the times are Double(sample) / 16000.0.  recording_counts HOST
+ * int64[batch] (nullable).  INVALID_ARGUMENT for the reference's preconditions on the config, a NaN duration, a duration whose
+ * sample count does not fit int64 (Swift traps there), a NULL, descending or negative range; INDEX_OVERFLOW for a recording of 2^31
+ * frames or more.  _dev: probs is a DEVICE pointer. */
+fa_status fa_vad_segments_dev(fa_ctx *ctx, const fa_vad_segmentation_config *cfg, const float *d_probs, const int64_t *frame_range,
+                              const int64_t *total_samples, int32_t batch, fa_vad_segment *segs, int64_t capacity, int64_t *count,
+                              int64_t *recording_counts);
+fa_status fa_vad_segments(fa_ctx *ctx, const fa_vad_segmentation_config *cfg, const float *probs, const int64_t *frame_range,
+                          const int64_t *total_samples, int32_t batch, fa_vad_segment *segs, int64_t capacity, int64_t *count,
+                          int64_t *recording_counts);
+int64_t fa_vad_chunk_count(int64_t samples);          /* ceil(samples / 4096); 0 for samples <= 0 */
+/* audio: the recordings' samples one after the other, recording b at audio_offsets[b] ... audio_offsets[b + 1] (HOST
+ * int64[batch + 1]).  rows float[row_capacity][4160]: recording b's fa_vad_chunk_count rows from chunk_range[b] on (HOST
+ * int64[batch + 1], written whenever the offsets are sound).  A row is the last 64 samples of the padded chunk before it (zeros
+ * for a recording's first) and the chunk, a short one filled with its last sample; samples are copied as bits.  OUTPUT_TOO_SMALL
+ * when row_capacity is below chunk_range[batch]: nothing is packed.  _dev: audio and rows are DEVICE pointers and the entry does NOT
+ * synchronise. */
+fa_status fa_vad_pack_chunks_dev(fa_ctx *ctx, const float *d_audio, const int64_t *audio_offsets, int32_t batch, float *d_rows,
+                                 int64_t row_capacity, int64_t *chunk_range);
+fa_status fa_vad_pack_chunks(fa_ctx *ctx, const float *audio, const int64_t *audio_offsets, int32_t batch, float *rows,
+                             int64_t row_capacity, int64_t *chunk_range);
+/* The speech audio of every segment, packed: segment i goes to out[out_range[i] ... out_range[i + 1]) (HOST int64[n_segments + 1],
+ * written whenever the arguments are sound).  The bounds are the reference's Int(start_time * 16000.0) and Int(end_time * 16000.0),
+ * clamped to the recording — NOT start_sample / end_sample, from which the trip through fp64 seconds can differ by one.  segs HOST
+ * (the records of fa_vad_segments, or hand-made times).  INVALID_ARGUMENT for a recording outside the batch or a time that does not
+ * fit int64; OUTPUT_TOO_SMALL when out_capacity is below out_range[n_segments]: nothing is copied.  _dev: audio and out are DEVICE
+ * pointers. */
+fa_status fa_vad_gather_segments_dev(fa_ctx *ctx, const float *d_audio, const int64_t *audio_offsets, int32_t batch,
+                                     const fa_vad_segment *segs, int64_t n_segments, float *d_out, int64_t out_capacity,
+                                     int64_t *out_range);
+fa_status fa_vad_gather_segments(fa_ctx *ctx, const float *audio, const int64_t *audio_offsets, int32_t batch,
+                                 const fa_vad_segment *segs, int64_t n_segments, float *out, int64_t out_capacity, int64_t *out_range);
+typedef struct { int32_t triggered, has_temp_end; int64_t temp_end_sample, processed_samples; } fa_vad_stream_state;
+#define FA_VAD_SPEECH_START 0
+#define FA_VAD_SPEECH_END 1
+typedef struct { int32_t stream, chunk, kind, reserved; int64_t sample_index; double time; } fa_vad_stream_event;
+/* `streams` state machines advanced by chunk_counts[s] (HOST int32[streams], each in [0, max_chunks]) chunks each: probs
+ * float[streams][max_chunks], chunk_samples int32[streams][max_chunks] (nullable: 4096 each).  states HOST [streams], in and out.
+ * events HOST [capacity], by stream and chunk, at most one per chunk; time is NaN unless return_seconds, else
+ * (seconds * 10^time_resolution).rounded() / 10^time_resolution (halves away from zero).  INVALID_ARGUMENT for a time_resolution
+ * outside 0 ... 22, where the power is not exact.  _dev: probs and chunk_samples are DEVICE pointers. */
+fa_status fa_vad_stream_advance_dev(fa_ctx *ctx, const fa_vad_segmentation_config *cfg, const float *d_probs, const int32_t *chunk_counts,
+                                    const int32_t *d_chunk_samples, int32_t streams, int32_t max_chunks, fa_vad_stream_state *states,
+                                    int32_t return_seconds, int32_t time_resolution, fa_vad_stream_event *events, int64_t capacity,
+                                    int64_t *count);
+fa_status fa_vad_stream_advance(fa_ctx *ctx, const fa_vad_segmentation_config *cfg, const float *probs, const int32_t *chunk_counts,
+                                const int32_t *chunk_samples, int32_t streams, int32_t max_chunks, fa_vad_stream_state *states,
+                                int32_t return_seconds, int32_t time_resolution, fa_vad_stream_event *events, int64_t capacity,
+                                int64_t *count);
+
 /* ------------------------------------------------------------------ resampling ------ */
 /* AudioConverter.linearResample (FluidAudio/Shared/AudioConverter.swift:388-442): planar float[channels][frames] ->
  * mono mix (weight 1/channels) -> linear interpolation to out_rate.  HOST pointers.  Bit-exact restatement. */
