@@ -26,8 +26,9 @@ from .post import (ConstrainedClusterAssignment, HungarianAssignment, assign_emb
 from .resample import linear_resample, poly_taps, resample_poly  # noqa: F401
 from .sharding import gather_ragged_int32, shard_offsets, shard_range  # noqa: F401
 from .sortformer import OfflineSortformerConfig, OfflineSortformerDiarizer, offline_windows, pack_windows, stitch, stitcher_alignment  # noqa: F401
-from .tdt import (TdtConfig, TdtDurationMapping, TdtFrameNavigation, decode_logits as tdt_decode_logits,  # noqa: F401
-                  decode_tables as tdt_decode_tables)
+from .tdt import (Language, Script, TdtConfig, TdtDurationMapping, TdtFrameNavigation, decode_logits as tdt_decode_logits,  # noqa: F401
+                  decode_logits_lang as tdt_decode_logits_lang, decode_tables as tdt_decode_tables, matches as tdt_matches,
+                  token_classes as tdt_token_classes, topk_rows as tdt_topk_rows)
 from .tdt_merge import (MERGE_NO_SEAM, MergedWindows, merge_capacity, merge_route_name, merge_windows, merge_windows_dev,  # noqa: F401
                         splice_safe_table, case_canon_table)
 from .timeline import DiarizerSegment, DiarizerTimeline, DiarizerTimelineConfig, timeline_segments  # noqa: F401

@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = [
     "fa_ctc_greedy_batch_dev", "fa_ctc_greedy_batch", "fa_ctc_greedy_rows_dev", "fa_ctc_greedy_rows", "fa_ctc_log_softmax_batch_dev",
     "fa_tdt_default_config", "fa_tdt_initial_time_index", "fa_tdt_navigation_state", "fa_tdt_final_time_jump",
     "fa_tdt_map_duration_bin", "fa_tdt_clamp_probability", "fa_tdt_greedy_tables_dev", "fa_tdt_greedy_logits_dev",
+    "fa_tdt_token_classes", "fa_tdt_topk_rows_dev", "fa_tdt_greedy_logits_lang_dev",
     "fastcluster_compute_centroid_linkage", "fa_ahc_linkage", "fa_ahc_linkage_batch", "fa_ahc_row_minima", "fa_ahc_cluster", "fa_ahc_cut",
     "fa_vbx_speaker_count", "fa_vbx_refine",
     "fa_vbx_shard_slices", "fa_vbx_shard_range", "fa_vbx_shard_chunk_doubles", "fa_vbx_shard_create", "fa_vbx_shard_destroy",
@@ -318,6 +319,9 @@ def lib() -> C.CDLL:
     L.fa_tdt_clamp_probability.restype = f32
     L.fa_tdt_greedy_tables_dev.argtypes = [vp, C.POINTER(TdtConfig), vp, vp, vp, i32, i32, i32] + [vp] * 6 + [i32] + [vp] * 8
     L.fa_tdt_greedy_logits_dev.argtypes = [vp, C.POINTER(TdtConfig), vp, i32, i32, i32, i32, i32, i64] + [vp] * 6 + [i32] + [vp] * 8
+    L.fa_tdt_token_classes.argtypes = [vp, vp, i32, vp, i32, vp]
+    L.fa_tdt_topk_rows_dev.argtypes = [vp, vp, i32, i64, i32, i64, i32, vp, vp, vp]
+    L.fa_tdt_greedy_logits_lang_dev.argtypes = L.fa_tdt_greedy_logits_dev.argtypes + [vp, i32, i32, i32, vp, vp]
     L.fastcluster_compute_centroid_linkage.argtypes = [vp, sz, sz, vp, sz]
     L.fastcluster_compute_centroid_linkage.restype = C.c_int
     L.fa_ahc_linkage.argtypes = [vp, vp, sz, sz, vp, sz, i32, i32, C.POINTER(AhcStats)]

@@ -20,6 +20,7 @@
 // integers: scalar registers and scalar branches where a wavefront walks a chunk, no scratch where a thread does.
 //
 // This unit: the kernels and one launcher per kernel family.  Host side (navigation helpers, argument checks, C ABI): tdt_host.hip; shared: tdt_launch.h.
+// The language mode (transcribe(..., language:): the script filter and the blocklist at the walk's decision site, the top-K list): tdt_lang.h, included below.
 #include <hip/hip_fp16.h>
 
 #include <type_traits>
@@ -39,8 +40,12 @@ struct ThreadWalk { static __device__ __forceinline__ int uni(const int x) { ret
 // cell —, `prob_of_last()` the probability of the token of the MOST RECENT decision, asked for only when that token is emitted (the reference's
 // joint returns it with every decision, TdtModelInference.swift:107-138, but only an emitted token's confidence is ever used, :409-463): three of
 // four decisions are blanks, and the soft-max denominator is most of a decision's arithmetic.  `writer` is true for the thread that stores the outputs.
-template <class Walker, class Decide, class Prob>
-__device__ __forceinline__ void tdt_walk(const TdtArgs &a, const int b, const bool writer, Decide &&decide, Prob &&prob_of_last) {
+// LANG (the language mode, tdt_lang.h): `filter(u, frame, tok, score)` sees every main-loop and blank-advance decision — never a flush decision
+// (TdtDecoderV3.swift:602-605) — before anything is derived from its token; it returns FA_TDT_ROUTE_* bits and, where one is set, has replaced
+// tok and set score, the replaced token's confidence.  out_route [max_out] takes the bits of every emitted token.  Without LANG there is no hook.
+template <class Walker, bool LANG = false, class Decide, class Prob, class Filter = int>
+__device__ __forceinline__ void tdt_walk(const TdtArgs &a, const int b, const bool writer, Decide &&decide, Prob &&prob_of_last, Filter &&filter = 0,
+                                         int32_t *out_route = nullptr) {
     auto uni = [](const int x) { return Walker::uni(x); };
     const fa_tdt_config &c = a.cfg;
     int32_t *otok = a.out_tok + static_cast<int64_t>(b) * a.max_out, *otime = a.out_time + static_cast<int64_t>(b) * a.max_out;
@@ -61,11 +66,16 @@ __device__ __forceinline__ void tdt_walk(const TdtArgs &a, const int b, const bo
     enum { OUTER = 0, INNER = 1, FLUSH = 2 };
     int phase = OUTER, last_emit_t = -1, n_at_t = 0, processed = 0, t_label = t;
     int steps = 0, blanks = 0, fp = 0;                             // last-chunk flush (:472-571)
+    int route = 0;                                                 // LANG: what the filters did to the present decision
+    float filtered_score = 0.0f;
     auto emit = [&](const int ts, const int tok, const int dur) {
         if (emit_after >= 0 && ts < emit_after) return;           // shouldEmitToken (:600-606)
         if (count < a.max_out) {
-            const float score = clamp_probability(prob_of_last());
+            float score;
+            if constexpr (LANG) score = route ? filtered_score : clamp_probability(prob_of_last());
+            else score = clamp_probability(prob_of_last());
             if (writer) { otok[count] = tok; otime[count] = ts; odur[count] = dur; oconf[count] = score; }
+            if constexpr (LANG) { if (writer) out_route[count] = route; }
         } else st = FA_OUTPUT_TOO_SMALL;
         ++count;
     };
@@ -84,6 +94,10 @@ __device__ __forceinline__ void tdt_walk(const TdtArgs &a, const int b, const bo
         int tok = 0, bi = 0;
         decide(u, frame, tok, bi);
         tok = uni(tok); bi = uni(bi);
+        if constexpr (LANG) {
+            route = 0;
+            if (phase != FLUSH) { route = uni(filter(u, frame, tok, filtered_score)); tok = uni(tok); }
+        }
         if (bi < 0 || bi >= c.n_duration_bins) { st = FA_RUNTIME_ERROR; finish(); return; }  // mapDurationBin throws (TdtDurationMapping.swift:17-22)
         int dur = 0;
 #pragma unroll
@@ -211,6 +225,8 @@ __device__ __forceinline__ void tdt_wave_softmax(float &m, float &s) {
     s = tdt_reduce<64>(t, 0.0f, [](const float x, const float o) { return x + o; });
 }
 
+#include "tdt_lang.h"   // the language mode's filters and the top-K kernel, on the helpers above
+
 // ---- rows of at most 17 x 64 logits (Parakeet-TDT's 1 025 + 5, the CTC-sized heads): the row stays in registers, in its own element type, from
 // the decision until the next one.  A decision is: 17 + 1 requests from a scalar row address (the lane's byte offsets are loop invariants; offsets
 // beyond the row are clamped to its last element — a duplicate of a real element can tie with it but never beat it, and the true holder has the
@@ -227,8 +243,8 @@ __device__ __forceinline__ void tdt_wave_softmax(float &m, float &s) {
 // 512 bytes and more per wavefront (fp32 pairs / quads, fp16 quads / octets) measured SLOWER than 256: profiles/r06_tdt_piece_probe.txt.
 typedef unsigned tdt_v2u __attribute__((ext_vector_type(2)));
 typedef unsigned tdt_v4u __attribute__((ext_vector_type(4)));
-template <bool F16, int W = 1>
-__global__ __launch_bounds__(64) void tdt_logits_fits_kernel(const TdtArgs a, const TdtLogitArgs g) {
+template <bool F16, int W, bool LANG>
+__device__ __forceinline__ void tdt_logits_fits_body(const TdtArgs &a, const TdtLogitArgs &g, const TdtLangArgs &l) {
     using E = std::conditional_t<F16, __half, float>;
     constexpr int kBytes = W * static_cast<int>(sizeof(E));   // per request and lane
     static_assert(W == 1 || kBytes == 4 || kBytes == 8 || kBytes == 16, "a request is one element or 1 / 2 / 4 dwords");
@@ -247,9 +263,14 @@ __global__ __launch_bounds__(64) void tdt_logits_fits_kernel(const TdtArgs a, co
     }
     const unsigned doff = static_cast<unsigned>(g.V1 + (lane < g.nd ? lane : g.nd - 1)) * static_cast<unsigned>(sizeof(E));
     const int row_bytes = (g.V1 + g.nd) * static_cast<int>(sizeof(E));
+    int n_script = 0, n_block = 0;   // LANG: decisions the script filter / the blocklist replaced
+    auto filter = [&](const int u, const int frame, int &tok, float &score) -> int {
+        const void *row = static_cast<const char *>(g.logits) + (tb + static_cast<int64_t>(u) * a.T + frame) * g.row_stride * static_cast<int64_t>(sizeof(E));
+        return tdt_lang_filter<F16>(l, row, g.V1, a.cfg.blank_id, tok, score, n_script, n_block);
+    };
     float v[kP];   // fp16 rows are widened as they arrive (LogitsArgmax.swift:31-55 widens fp16 logits before the scan): one conversion per element —
                    // half-precision maxima (__hmax) compile to a NaN-handling branch per element
-    tdt_walk<WaveWalk>(a, b, lane == 0, [&](const int u, const int frame, int &tok, int &bin) {
+    tdt_walk<WaveWalk, LANG>(a, b, lane == 0, [&](const int u, const int frame, int &tok, int &bin) {
         // the row through a buffer descriptor: scalar base (the walk's state is scalar) + the lane's 32-bit byte offset = ONE instruction per
         // request (a flat global load of scalar base + lane offset is compiled as a 64-bit per-lane add and the load)
         char *rp = const_cast<char *>(static_cast<const char *>(g.logits)) + (tb + static_cast<int64_t>(u) * a.T + frame) * g.row_stride * static_cast<int64_t>(sizeof(E));
@@ -309,13 +330,18 @@ __global__ __launch_bounds__(64) void tdt_logits_fits_kernel(const TdtArgs a, co
         for (int j = 0; j < kP; ++j) { const float e = __expf(v[j] - m); ssum += (finite_max & (index_of(j) <= last_k)) ? e : 0.0f; }
         tdt_wave_softmax(m, ssum);
         return __builtin_amdgcn_ballot_w64(nan_seen) ? NAN : 1.0f / ssum;
-    });
+    }, filter, LANG ? l.out_route + static_cast<int64_t>(b) * a.max_out : nullptr);
+    if constexpr (LANG) { if (lane == 0) { l.swap_counts[2 * static_cast<int64_t>(b)] = n_script; l.swap_counts[2 * static_cast<int64_t>(b) + 1] = n_block; } }
 }
+template <bool F16, int W = 1>
+__global__ __launch_bounds__(64) void tdt_logits_fits_kernel(const TdtArgs a, const TdtLogitArgs g) { tdt_logits_fits_body<F16, W, false>(a, g, TdtLangArgs{}); }
+template <bool F16, int W = 1>
+__global__ __launch_bounds__(64) void tdt_logits_fits_lang_kernel(const TdtArgs a, const TdtLogitArgs g, const TdtLangArgs l) { tdt_logits_fits_body<F16, W, true>(a, g, l); }
 
 // ---- longer rows (8 198 logits: Parakeet-TDT v3): one pass, the soft-max partials (m, ssum) accumulated against the running maximum while the
 // row streams through sixteen 256-byte pieces at a time, the NEXT sixteen requested before the present ones are looked at
-template <bool F16>
-__global__ __launch_bounds__(64) void tdt_logits_kernel(const TdtArgs a, const TdtLogitArgs g) {
+template <bool F16, bool LANG>
+__device__ __forceinline__ void tdt_logits_body(const TdtArgs &a, const TdtLogitArgs &g, const TdtLangArgs &l) {
     const int b = blockIdx.x, lane = threadIdx.x;
     const int64_t tb = static_cast<int64_t>(b) * a.U * a.T;
     auto at = [&](const int64_t row, const int k) -> float {   // row: wave-uniform (a scalar base address), k: the lane's element
@@ -325,7 +351,12 @@ __global__ __launch_bounds__(64) void tdt_logits_kernel(const TdtArgs a, const T
     constexpr int kBatch = 16;
     float m_on = -INFINITY, s_on = 0.0f;              // one-pass partials of the present row
     bool nan_seen = false;                            // a NaN logit anywhere in the row: probability 0 after the clamp (what the two-pass sum of round 3 gave)
-    tdt_walk<WaveWalk>(a, b, lane == 0, [&](const int u, const int frame, int &tok, int &bin) {
+    int n_script = 0, n_block = 0;                    // LANG: decisions the script filter / the blocklist replaced
+    auto filter = [&](const int u, const int frame, int &tok, float &score) -> int {
+        const void *row = static_cast<const char *>(g.logits) + (tb + static_cast<int64_t>(u) * a.T + frame) * g.row_stride * static_cast<int64_t>(F16 ? 2 : 4);
+        return tdt_lang_filter<F16>(l, row, g.V1, a.cfg.blank_id, tok, score, n_script, n_block);
+    };
+    tdt_walk<WaveWalk, LANG>(a, b, lane == 0, [&](const int u, const int frame, int &tok, int &bin) {
         const int64_t row = tb + static_cast<int64_t>(u) * a.T + frame;
         float dvl = lane < g.nd ? at(row, g.V1 + lane) : -INFINITY;            // the duration logits travel with the first batch of the row
         if (dvl != dvl) dvl = -INFINITY;                                       // NaN never wins the first-maximum scan
@@ -377,8 +408,13 @@ __global__ __launch_bounds__(64) void tdt_logits_kernel(const TdtArgs a, const T
         float m = m_on, ssum = s_on;
         tdt_wave_softmax(m, ssum);
         return __builtin_amdgcn_ballot_w64(nan_seen) ? NAN : 1.0f / ssum;
-    });
+    }, filter, LANG ? l.out_route + static_cast<int64_t>(b) * a.max_out : nullptr);
+    if constexpr (LANG) { if (lane == 0) { l.swap_counts[2 * static_cast<int64_t>(b)] = n_script; l.swap_counts[2 * static_cast<int64_t>(b) + 1] = n_block; } }
 }
+template <bool F16>
+__global__ __launch_bounds__(64) void tdt_logits_kernel(const TdtArgs a, const TdtLogitArgs g) { tdt_logits_body<F16, false>(a, g, TdtLangArgs{}); }
+template <bool F16>
+__global__ __launch_bounds__(64) void tdt_logits_lang_kernel(const TdtArgs a, const TdtLogitArgs g, const TdtLangArgs l) { tdt_logits_body<F16, true>(a, g, l); }
 
 }  // namespace
 
@@ -398,6 +434,25 @@ void launch_logits(hipStream_t stream, const TdtArgs &a, const TdtLogitArgs &g) 
         if (route == kStream) hipLaunchKernelGGL(tdt_logits_kernel<false>, grid, block, 0, stream, a, g);
         else hipLaunchKernelGGL((tdt_logits_fits_kernel<false, 1>), grid, block, 0, stream, a, g);
     }
+}
+
+void launch_logits_lang(hipStream_t stream, const TdtArgs &a, const TdtLogitArgs &g, const TdtLangArgs &l) {
+    const Route route = logits_route(g.f16 != 0, g.V1, g.row_stride, reinterpret_cast<uintptr_t>(g.logits));
+    const dim3 grid(a.B), block(64);
+    if (g.f16) {
+        if (route == kStream) hipLaunchKernelGGL(tdt_logits_lang_kernel<true>, grid, block, 0, stream, a, g, l);
+        else if (route == kFitsPairs) hipLaunchKernelGGL((tdt_logits_fits_lang_kernel<true, 2>), grid, block, 0, stream, a, g, l);
+        else hipLaunchKernelGGL((tdt_logits_fits_lang_kernel<true, 1>), grid, block, 0, stream, a, g, l);
+    } else {
+        if (route == kStream) hipLaunchKernelGGL(tdt_logits_lang_kernel<false>, grid, block, 0, stream, a, g, l);
+        else hipLaunchKernelGGL((tdt_logits_fits_lang_kernel<false, 1>), grid, block, 0, stream, a, g, l);
+    }
+}
+
+void launch_topk(hipStream_t stream, const TdtTopkArgs &k) {
+    const dim3 grid(static_cast<unsigned>(k.R)), block(64);
+    if (k.f16) hipLaunchKernelGGL(tdt_topk_kernel<true>, grid, block, 0, stream, k);
+    else hipLaunchKernelGGL(tdt_topk_kernel<false>, grid, block, 0, stream, k);
 }
 
 }  // namespace tdt

@@ -895,6 +895,84 @@ struct StringUtils {
     static int levenshteinDistance(Context &ctx, const std::vector<int> &a, const std::vector<int> &b) { return levenshteinDistance(ctx.handle(), a, b); }
 };
 
+// ------------------------------------------------------------------------------------------------------------------ TDT language mode
+// Language / Script / TokenLanguageFilter (Sources/FluidAudio/Shared/TokenLanguageFilter.swift:4-134) and the decoding entry of
+// TdtDecoderV3.decodeWithTimings(..., language:) (TdtDecoderV3.swift:103-607, the filters :284-299, 371-387, 635-703) over
+// fa_tdt_token_classes and fa_tdt_greedy_logits(_lang)_dev.  The joint logits and every per-chunk array live on the device.
+enum class Script : int32_t { latin = FA_TDT_SCRIPT_LATIN, cyrillic = FA_TDT_SCRIPT_CYRILLIC, greek = FA_TDT_SCRIPT_GREEK };
+enum class Language {
+    english, spanish, french, german, italian, portuguese, romanian, dutch, danish, swedish, finnish, hungarian, estonian, latvian, lithuanian, maltese,
+    polish, czech, slovak, slovenian, croatian, bosnian, russian, ukrainian, belarusian, bulgarian, serbian, greek
+};
+inline const char *rawValue(Language l) {
+    static const char *const codes[] = {"en", "es", "fr", "de", "it", "pt", "ro", "nl", "da", "sv", "fi", "hu", "et", "lv", "lt", "mt",
+                                        "pl", "cs", "sk", "sl", "hr", "bs", "ru", "uk", "be", "bg", "sr", "el"};
+    return codes[static_cast<int>(l)];
+}
+inline Script script(Language l) {
+    if (l == Language::greek) return Script::greek;
+    return l >= Language::russian && l <= Language::serbian ? Script::cyrillic : Script::latin;
+}
+
+struct TokenLanguageFilter {
+    // The class bytes of a vocabulary (FA_TDT_CLASS_*): vocabulary[i] empty optional = id i is not in the vocabulary
+    static std::vector<uint8_t> tokenClasses(const std::vector<std::optional<std::string>> &vocabulary, const std::vector<int32_t> &blocklistIds = {}) {
+        std::vector<const char *> texts(vocabulary.size());
+        for (size_t i = 0; i < vocabulary.size(); ++i) {
+            if (vocabulary[i] && vocabulary[i]->find('\0') != std::string::npos) throw Error(FA_INVALID_ARGUMENT, "fa_tdt_token_classes", "a token text holds a NUL");
+            texts[i] = vocabulary[i] ? vocabulary[i]->c_str() : nullptr;
+        }
+        std::vector<uint8_t> classes(vocabulary.size());
+        const fa_status st = fa_tdt_token_classes(texts.data(), nullptr, static_cast<int32_t>(vocabulary.size()), blocklistIds.data(),
+                                                  static_cast<int32_t>(blocklistIds.size()), classes.data());
+        if (st != FA_SUCCESS) throw Error(st, "fa_tdt_token_classes", "text that is not UTF-8, or a blocklist id outside the vocabulary");
+        return classes;
+    }
+    // matches(_:script:) (:81-134).  U+2581 is stripped wherever it stands, also in front of a combining mark, where Foundation's
+    // string search may leave it: the reference's tests pin no such token.
+    static bool matches(const std::string &text, Script script) {
+        return (tokenClasses({text})[0] & (FA_TDT_CLASS_LATIN_OK << static_cast<int32_t>(script))) != 0;
+    }
+};
+
+struct TdtDecoderV3 {
+    static bool englishBlocklistApplies(std::optional<Language> language) { return language && *language == Language::french; }   // :623-625
+    struct Chunks {              // DEVICE pointers; the operands of fa_tdt_greedy_logits_dev
+        const void *logits = nullptr;
+        int32_t dtype = FA_DTYPE_F32, batch = 0, U = 0, T = 0, vocabWithBlank = 0;
+        int64_t rowStride = 0;
+        const int32_t *encLen = nullptr, *audioFrames = nullptr, *t0 = nullptr, *isLast = nullptr, *globalOffset = nullptr, *emitAfter = nullptr;
+        int32_t maxOut = 0;
+        int32_t *tokens = nullptr, *timestamps = nullptr, *durations = nullptr;
+        float *confidences = nullptr;
+        int32_t *counts = nullptr, *finalTime = nullptr, *finalU = nullptr, *status = nullptr;
+    };
+    struct LanguageMode {        // what transcribe(..., language:) adds: DEVICE class bytes of TokenLanguageFilter::tokenClasses, DEVICE outputs
+        Language language = Language::english;
+        const uint8_t *classes = nullptr;
+        bool useBlocklist = false;      // the caller's decision: englishBlocklistApplies(language) and a blocklist in the class bytes
+        int32_t topK = FA_TDT_MAX_TOP_K;
+        int32_t *routes = nullptr;      // [batch][maxOut] FA_TDT_ROUTE_*
+        int32_t *swapCounts = nullptr;  // [batch][2]
+    };
+    fa_tdt_config config{};
+    TdtDecoderV3() { fa_tdt_default_config(&config); }
+    // decodeWithTimings for a batch of chunks; language == nil is the plain walk
+    void decodeWithTimings(Context &ctx, const Chunks &c, const std::optional<LanguageMode> &language = std::nullopt) const {
+        if (!language) {
+            ctx.check(fa_tdt_greedy_logits_dev(ctx.handle(), &config, c.logits, c.dtype, c.batch, c.U, c.T, c.vocabWithBlank, c.rowStride, c.encLen, c.audioFrames, c.t0,
+                                               c.isLast, c.globalOffset, c.emitAfter, c.maxOut, c.tokens, c.timestamps, c.durations, c.confidences, c.counts,
+                                               c.finalTime, c.finalU, c.status), "fa_tdt_greedy_logits_dev");
+            return;
+        }
+        ctx.check(fa_tdt_greedy_logits_lang_dev(ctx.handle(), &config, c.logits, c.dtype, c.batch, c.U, c.T, c.vocabWithBlank, c.rowStride, c.encLen, c.audioFrames,
+                                                c.t0, c.isLast, c.globalOffset, c.emitAfter, c.maxOut, c.tokens, c.timestamps, c.durations, c.confidences, c.counts,
+                                                c.finalTime, c.finalU, c.status, language->classes, static_cast<int32_t>(script(language->language)),
+                                                language->useBlocklist ? 1 : 0, language->topK, language->routes, language->swapCounts),
+                  "fa_tdt_greedy_logits_lang_dev");
+    }
+};
+
 // ------------------------------------------------------------------------------------------------------------------ TDT long-form merging
 // ChunkProcessor's fold of mergeChunks over a recording's windows and enforceMonotonicTimestamps (Sources/FluidAudio/ASR/Parakeet/
 // SlidingWindow/TDT/ChunkProcessor.swift:843-855, 952-1219) over fa_tdt_merge_windows: the windows of one or more recordings in one

@@ -363,6 +363,51 @@ fa_status fa_tdt_greedy_logits_dev(fa_ctx *ctx, const fa_tdt_config *cfg, const 
                                    int32_t *d_out_tok, int32_t *d_out_time, int32_t *d_out_dur, float *d_out_conf,
                                    int32_t *d_out_count, int32_t *d_final_time, int32_t *d_final_u, int32_t *d_status);
 
+/* ---- language-aware decoding: transcribe(..., language:) (TdtDecoderV3.swift:284-299, 371-387, 635-703;
+ * Shared/TokenLanguageFilter.swift:81-186).  One byte of class bits per token: */
+#define FA_TDT_CLASS_LATIN_OK 1     /* TokenLanguageFilter.matches(text, .latin) */
+#define FA_TDT_CLASS_CYRILLIC_OK 2  /* ... .cyrillic */
+#define FA_TDT_CLASS_GREEK_OK 4     /* ... .greek */
+#define FA_TDT_CLASS_IN_VOCAB 8     /* vocabulary[id] exists */
+#define FA_TDT_CLASS_BLOCKLISTED 16 /* the id is on the caller's blocklist (the reference's englishBlocklistIds, French only) */
+enum { FA_TDT_SCRIPT_LATIN = 0, FA_TDT_SCRIPT_CYRILLIC = 1, FA_TDT_SCRIPT_GREEK = 2 };
+#define FA_TDT_ROUTE_SCRIPT_SWAP 1     /* the script filter replaced the joint's winner */
+#define FA_TDT_ROUTE_BLOCKLIST_SWAP 2  /* the blocklist pass replaced the (possibly already replaced) label */
+#define FA_TDT_MAX_TOP_K 64            /* the reference's joint hands back K = 64 candidates */
+/* The class bytes of a vocabulary.  HOST pointers, no context, no GPU.  utf8_tokens[i]: the NUL-terminated UTF-8 text of token i;
+ * NULL, or present[i] == 0 where present is not NULL, leaves IN_VOCAB clear (the script bits are then those of the empty text).
+ * matches (TokenLanguageFilter.swift:81-134): every U+2581 scalar is stripped, an empty remainder matches every script, the rest
+ * is checked scalar by scalar against the script's ranges.  INVALID_ARGUMENT for text that is not UTF-8 (overlong forms,
+ * surrogates and scalars above U+10FFFF included) and for a blocklist id outside [0, vocab_with_blank). */
+fa_status fa_tdt_token_classes(const char *const *utf8_tokens, const int32_t *present, int32_t vocab_with_blank,
+                               const int32_t *blocklist_ids, int32_t n_block, uint8_t *classes);
+/* What the joint's two top-K outputs hold, as THIS LIBRARY defines them (CoreML's order among equal logits is unspecified):
+ * per row the min(K, vocab_with_blank) tokens in order of descending key, then ascending id; key = the logit widened to float32,
+ * NaN counting as -inf; comparison by value (-0.0 == +0.0).  d_rows[R][row_stride] (fp32 / fp16), 1 <= K <= 64.  d_ids and
+ * d_logits [R][K] (the reported logit is the widened value, NaN reported as -inf; unused slots: id -1, logit -inf), d_counts [R]
+ * (NULL: not wanted).  One wavefront per row. */
+fa_status fa_tdt_topk_rows_dev(fa_ctx *ctx, const void *d_rows, int32_t dtype, int64_t R, int32_t vocab_with_blank,
+                               int64_t row_stride, int32_t K, int32_t *d_ids, float *d_logits, int32_t *d_counts);
+/* fa_tdt_greedy_logits_dev with the reference's language mode at the main-loop and the blank-advance decisions (never in the
+ * last-chunk flush, :602-605).  d_classes[vocab_with_blank]: the bytes of fa_tdt_token_classes on the device; script: FA_TDT_SCRIPT_*.
+ * Script filter (:676-703): a non-blank winner that is IN_VOCAB and does not match the script is replaced by the first entry of
+ * the row's top-K list (fa_tdt_topk_rows_dev's definition, K = top_k) that is IN_VOCAB and matches; blank is a legal candidate;
+ * confidence = clamp(exp(x_best - M) / sum over the list of exp(x_j - M)), 0 where the list's maximum M is not finite.
+ * Blocklist (:635-667), when use_blocklist != 0, on the possibly replaced label: a non-blank BLOCKLISTED label is replaced by the
+ * first list entry that is not blank, not BLOCKLISTED, IN_VOCAB and LATIN_OK, with the same confidence formula.  Without such an
+ * entry a filter changes nothing.  Duration, blank test, inner loop and emission follow on the filtered label.
+ * d_out_route[batch][max_out]: FA_TDT_ROUTE_* bits per emitted token; d_swap_counts[batch][2]: decisions whose label the script
+ * filter / the blocklist replaced, emitted or not.  INVALID_ARGUMENT (nothing launched, nothing written) for script or top_k out
+ * of range or a NULL d_classes / d_swap_counts. */
+fa_status fa_tdt_greedy_logits_lang_dev(fa_ctx *ctx, const fa_tdt_config *cfg, const void *d_logits, int32_t dtype, int32_t batch,
+                                        int32_t U, int32_t T, int32_t vocab_with_blank, int64_t row_stride, const int32_t *d_enc_len,
+                                        const int32_t *d_audio_frames, const int32_t *d_t0, const int32_t *d_is_last,
+                                        const int32_t *d_global_offset, const int32_t *d_emit_after, int32_t max_out,
+                                        int32_t *d_out_tok, int32_t *d_out_time, int32_t *d_out_dur, float *d_out_conf,
+                                        int32_t *d_out_count, int32_t *d_final_time, int32_t *d_final_u, int32_t *d_status,
+                                        const uint8_t *d_classes, int32_t script, int32_t use_blocklist, int32_t top_k,
+                                        int32_t *d_out_route, int32_t *d_swap_counts);
+
 /* ------------------------------------------------------------------ AHC ------------- */
 /* Exact signature + status contract of the reference FFI
  * (FastClusterWrapper/include/FastClusterWrapper.h:35-41, FastClusterWrapper.cpp:196-244):
