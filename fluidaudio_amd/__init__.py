@@ -31,6 +31,10 @@ from .tdt import (Language, Script, TdtConfig, TdtDurationMapping, TdtFrameNavig
                   token_classes as tdt_token_classes, topk_rows as tdt_topk_rows)
 from .tdt_merge import (MERGE_NO_SEAM, MergedWindows, merge_capacity, merge_route_name, merge_windows, merge_windows_dev,  # noqa: F401
                         splice_safe_table, case_canon_table)
+from .tdt_plan import (TDT_SPAN_DTYPE, TDT_WINDOW_DTYPE, PlannedWindows, TdtWindowPlanner, pack_windows as tdt_pack_windows,  # noqa: F401
+                       pack_windows_dev as tdt_pack_windows_dev, plan_windows as tdt_plan_windows, plan_windows_dev as tdt_plan_windows_dev,
+                       speech_gate as tdt_speech_gate, speech_gate_dev as tdt_speech_gate_dev, window_config as tdt_window_config,
+                       window_count_bound as tdt_window_count_bound, window_layout as tdt_window_layout)
 from .timeline import DiarizerSegment, DiarizerTimeline, DiarizerTimelineConfig, timeline_segments  # noqa: F401
 from .vad import (VAD_SEGMENT_DTYPE, VAD_STREAM_EVENT_DTYPE, VAD_STREAM_STATE_DTYPE, gather_segments, gather_segments_dev, initial_stream_states,  # noqa: F401
                   pack_chunks, pack_chunks_dev, segment_speech_batch, segment_speech_batch_dev, stream_advance, stream_advance_dev, vad_config)

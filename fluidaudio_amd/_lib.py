@@ -65,6 +65,8 @@ EXPORTED_SYMBOLS = [
     "fa_tdt_merge_default_config", "fa_tdt_merge_windows_dev", "fa_tdt_merge_windows",
     "fa_vad_default_config", "fa_vad_chunk_count", "fa_vad_segments_dev", "fa_vad_segments", "fa_vad_pack_chunks_dev", "fa_vad_pack_chunks",
     "fa_vad_gather_segments_dev", "fa_vad_gather_segments", "fa_vad_stream_advance_dev", "fa_vad_stream_advance",
+    "fa_tdt_window_default_config", "fa_tdt_window_layout", "fa_tdt_window_count_bound", "fa_tdt_plan_windows_dev", "fa_tdt_plan_windows",
+    "fa_tdt_pack_windows_dev", "fa_tdt_pack_windows", "fa_tdt_speech_gate_dev", "fa_tdt_speech_gate",
 ]
 
 
@@ -213,6 +215,21 @@ class VadStreamStateRecord(C.Structure):
 
 class VadStreamEventRecord(C.Structure):
     _fields_ = [("stream", C.c_int32), ("chunk", C.c_int32), ("kind", C.c_int32), ("reserved", C.c_int32), ("sample_index", C.c_int64), ("time", C.c_double)]
+
+
+class TdtWindowConfig(C.Structure):
+    _fields_ = [("sample_rate", C.c_int32), ("frame_samples", C.c_int32), ("mel_hop", C.c_int32), ("max_model_samples", C.c_int32), ("overlap_seconds", C.c_double),
+                ("mel_chunk_context", C.c_int32), ("silence_aligned", C.c_int32), ("warmup_prefix_frames", C.c_int32), ("end_aligned", C.c_int32)]
+
+
+class TdtWindowRecord(C.Structure):
+    _fields_ = [("recording", C.c_int32), ("use_warmup_prefix", C.c_int32), ("is_last", C.c_int32), ("emit_after_frame", C.c_int32),
+                ("global_frame_offset", C.c_int32), ("context_frames", C.c_int32), ("actual_audio_frames", C.c_int32), ("reserved", C.c_int32),
+                ("chunk_start", C.c_int64), ("warmup_samples", C.c_int64), ("context_samples", C.c_int64), ("context_start", C.c_int64), ("length", C.c_int64)]
+
+
+class TdtSpanRecord(C.Structure):
+    _fields_ = [("recording", C.c_int32), ("reserved", C.c_int32), ("from_sample", C.c_int64), ("to_sample", C.c_int64)]
 
 
 RESAMPLE_ROUTE_KINDS = ("DECIM", "INTERP", "ROWS", "LDS", "SIMPLE")    # FA_RESAMPLE_ROUTE_*
@@ -476,6 +493,17 @@ def lib() -> C.CDLL:
     L.fa_vad_gather_segments.argtypes = L.fa_vad_gather_segments_dev.argtypes
     L.fa_vad_stream_advance_dev.argtypes = [vp, C.POINTER(VadSegmentationConfig), vp, vp, vp, i32, i32, vp, i32, i32, vp, i64, C.POINTER(i64)]
     L.fa_vad_stream_advance.argtypes = L.fa_vad_stream_advance_dev.argtypes
+    L.fa_tdt_window_default_config.argtypes = [C.POINTER(TdtWindowConfig)]
+    L.fa_tdt_window_default_config.restype = None
+    L.fa_tdt_window_layout.argtypes = [C.POINTER(TdtWindowConfig)] + [C.POINTER(i64)] * 4
+    L.fa_tdt_window_count_bound.argtypes = [C.POINTER(TdtWindowConfig), i64]
+    L.fa_tdt_window_count_bound.restype = i64
+    L.fa_tdt_plan_windows_dev.argtypes = [vp, C.POINTER(TdtWindowConfig), vp, vp, i32, vp, i64, vp] + [vp] * 5 + [vp, vp]
+    L.fa_tdt_plan_windows.argtypes = L.fa_tdt_plan_windows_dev.argtypes
+    L.fa_tdt_pack_windows_dev.argtypes = [vp, C.POINTER(TdtWindowConfig), vp, vp, i32, vp, i64, vp, i64, vp]
+    L.fa_tdt_pack_windows.argtypes = L.fa_tdt_pack_windows_dev.argtypes
+    L.fa_tdt_speech_gate_dev.argtypes = [vp, C.POINTER(TdtWindowConfig), vp, vp, i32, vp, vp, vp, i64, vp, vp, vp]
+    L.fa_tdt_speech_gate.argtypes = L.fa_tdt_speech_gate_dev.argtypes
     _lib = L
     return L
 

@@ -1411,4 +1411,90 @@ struct VadManager {
     }
 };
 
+// ---- TDT long-form: planning the windows (ChunkProcessor.swift; the C entries are batched over recordings, this is ONE recording)
+struct ChunkLayout {                         // chunkLayout's tuple (:140-161)
+    int64_t chunkSamples = 0, strideSamples = 0, melContextSamples = 0, warmupPrefixSamples = 0;
+};
+
+struct ChunkStartDecision {                  // :20-23
+    int64_t start = 0;
+    bool useWarmupPrefix = false;
+};
+
+struct TdtWindowPlanner {
+    bool melChunkContext = true;             // ASRConfig.melChunkContext
+    bool silenceAligned = false;             // preferSilenceAlignment: !melChunkContext && modelVersion == .v3
+    int warmupPrefixFrames = 0;              // path B of the arbitration: 7
+    bool endAligned = true;                  // supportsSuppressedPrefix(modelVersion)
+    double overlapSeconds = 2.0;
+
+    fa_tdt_window_config abi() const {
+        fa_tdt_window_config c;
+        fa_tdt_window_default_config(&c);
+        c.overlap_seconds = overlapSeconds;
+        c.mel_chunk_context = melChunkContext ? 1 : 0; c.silence_aligned = silenceAligned ? 1 : 0;
+        c.warmup_prefix_frames = warmupPrefixFrames; c.end_aligned = endAligned ? 1 : 0;
+        return c;
+    }
+    ChunkLayout chunkLayout() const {
+        const fa_tdt_window_config c = abi();
+        ChunkLayout l;
+        const fa_status st = fa_tdt_window_layout(&c, &l.chunkSamples, &l.strideSamples, &l.melContextSamples, &l.warmupPrefixSamples);
+        if (st != FA_SUCCESS) throw Error(st, "fa_tdt_window_layout");
+        return l;
+    }
+    // the windows process decodes, in order; speechEnd (nullable): speechEndSamples
+    std::vector<fa_tdt_window> plan(Context &ctx, const std::vector<float> &samples, int64_t *speechEnd = nullptr) const {
+        const fa_tdt_window_config c = abi();
+        const int64_t offsets[2] = {0, static_cast<int64_t>(samples.size())};
+        const int64_t bound = fa_tdt_window_count_bound(&c, offsets[1]);
+        if (bound < 0) throw Error(FA_INVALID_ARGUMENT, "fa_tdt_window_count_bound");
+        std::vector<fa_tdt_window> windows(static_cast<size_t>(bound));
+        int64_t range[2] = {0, 0}, end = 0;
+        int32_t status = FA_SUCCESS;
+        ctx.check(fa_tdt_plan_windows(ctx.handle(), &c, samples.data(), offsets, 1, windows.data(), bound, range, nullptr, nullptr, nullptr, nullptr, nullptr, &end, &status),
+                  "fa_tdt_plan_windows");
+        if (status != FA_SUCCESS) throw Error(static_cast<fa_status>(status), "fa_tdt_plan_windows", "the recording holds a non-finite energy");
+        windows.resize(static_cast<size_t>(range[1]));
+        if (speechEnd) *speechEnd = end;
+        return windows;
+    }
+    std::vector<ChunkStartDecision> chunkStartDecisions(Context &ctx, const std::vector<float> &samples) const {
+        std::vector<ChunkStartDecision> out;
+        for (const fa_tdt_window &w : plan(ctx, samples)) out.push_back(ChunkStartDecision{w.chunk_start, w.use_warmup_prefix != 0});
+        return out;
+    }
+    int64_t speechEndSamples(Context &ctx, const std::vector<float> &samples) const {
+        int64_t end = 0;
+        (void)plan(ctx, samples, &end);
+        return end;
+    }
+    // padAudioIfNeeded of every window: [windows][maxModelSamples]
+    std::vector<float> packWindows(Context &ctx, const std::vector<float> &samples, const std::vector<fa_tdt_window> &windows) const {
+        const fa_tdt_window_config c = abi();
+        const int64_t offsets[2] = {0, static_cast<int64_t>(samples.size())};
+        std::vector<float> rows(windows.size() * static_cast<size_t>(c.max_model_samples));
+        ctx.check(fa_tdt_pack_windows(ctx.handle(), &c, samples.data(), offsets, 1, windows.data(), static_cast<int64_t>(windows.size()), rows.data(),
+                                      static_cast<int64_t>(windows.size()), nullptr), "fa_tdt_pack_windows");
+        return rows;
+    }
+    float adaptiveSpeechRmsThreshold(Context &ctx, const std::vector<float> &samples) const {
+        const fa_tdt_window_config c = abi();
+        const int64_t offsets[2] = {0, static_cast<int64_t>(samples.size())};
+        float threshold = 0.0f;
+        ctx.check(fa_tdt_speech_gate(ctx.handle(), &c, samples.data(), offsets, 1, nullptr, &threshold, nullptr, 0, nullptr, nullptr, nullptr), "fa_tdt_speech_gate");
+        return threshold;
+    }
+    // threshold: the recording's adaptive one when not given
+    double speechLikeSeconds(Context &ctx, const std::vector<float> &samples, int64_t startSample, int64_t endSample, std::optional<float> threshold = std::nullopt) const {
+        const fa_tdt_window_config c = abi();
+        const int64_t offsets[2] = {0, static_cast<int64_t>(samples.size())};
+        const fa_tdt_span span{0, 0, startSample, endSample};
+        const float over = threshold.value_or(0.0f);
+        double seconds = 0.0;
+        ctx.check(fa_tdt_speech_gate(ctx.handle(), &c, samples.data(), offsets, 1, threshold ? &over : nullptr, nullptr, &span, 1, nullptr, &seconds, nullptr), "fa_tdt_speech_gate");
+        return seconds;
+    }
+};
+
 }  // namespace fluidaudio

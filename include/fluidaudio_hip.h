@@ -1182,6 +1182,116 @@ fa_status fa_vad_stream_advance(fa_ctx *ctx, const fa_vad_segmentation_config *c
                                 int32_t return_seconds, int32_t time_resolution, fa_vad_stream_event *events, int64_t capacity,
                                 int64_t *count);
 
+/* ------------------------------------------------------------------ TDT long-form: planning the windows ------ */
+/* What ChunkProcessor decides from the audio before any network runs (FluidAudio/ASR/Parakeet/SlidingWindow/TDT/
+ * ChunkProcessor.swift), batched over recordings: speechEndSamples :112-128, the chunk starts (chunkStarts :163-177, regularChunkStarts
+ * :179-187, silenceAlignedChunkStarts :189-268 with bestBoundaryCandidate, the two threshold tests, wouldCompressSpeechTail,
+ * shouldUseWarmupPrefix and boundaryEnergyScore :270-396), the window loop of process (:501-507, 520-565, 577, 626-636;
+ * DualDecodeArbitration.decodeOneChunk :359-402 is the same arithmetic with mel context 0) with lastChunkWarmupSamples :85-102, the
+ * preprocessor's rows (padAudioIfNeeded, AsrManager+Pipeline.swift:153-156), and the half of the seam-gap repair that reads audio
+ * (adaptiveSpeechRmsThreshold :1245-1276, speechLikeSeconds :1518-1534).  Every energy is the reference's `sum += sample * sample` in
+ * fp32, in order, one rounded product and one rounded addition per sample; integers, fp32 and fp64 results are the reference's bit for
+ * bit (pinned by its ChunkProcessorTests, EndAlignedFinalWindowTests and SeamGapRepairTests through tests/tdt_plan_restatement.py).
+ * OUT OF SCOPE: the networks, the arbitration between the decodes (it compares confidences), finding the seam gaps from the tokens,
+ * the re-decoding and collapseSeamWordDuplicates.
+ * The four combinations in use: the default path (mel_chunk_context 1, regular starts, end_aligned = supportsSuppressedPrefix); v3
+ * no-mel and arbitration path A (mel_chunk_context 0, silence_aligned 1, warmup_prefix_frames 0, end_aligned 1); path B (as A with
+ * warmup_prefix_frames 7); path C (mel_chunk_context 0, regular starts, end_aligned 1).  The reference's literals (the ratios 0.05,
+ * 0.35 and 0.8, the quiet threshold 0.003, the spans of 4.0 s, 0.5 s and 0.2 s, the window of sampleRate / 50 samples, the six-frame
+ * minimal overlap, the gate's 0.0005, 0.008, 0.3 and 0.75) stay literals, derived from the geometry as the reference derives them.
+ * Conventions: cfg nullable = the defaults; every refusal below is decided before any device work and writes nothing unless stated;
+ * batch == 0: SUCCESS.  INVALID_ARGUMENT for: a NULL audio_offsets or output range, offsets that start below 0 or descend, a missing
+ * array that would be read or written, a negative size; a geometry with sample_rate, frame_samples, mel_hop or max_model_samples
+ * below 1, warmup_prefix_frames below 0, an overlap that is not finite, negative, or whose sample count does not fit int32; a chunk
+ * that does not exceed the six-frame minimal overlap, or a chunk with its mel context longer than max_model_samples (a row could not
+ * hold a window), or a warm-up prefix as long as a chunk; a search radius above 63 frames (4 s hold 64 frames or more) or a look-ahead
+ * of more than 64 windows (the kernels' limits).  INDEX_OVERFLOW for a recording of 2^31 - 2 frames or more, or a call whose window
+ * bound exceeds INT32_MAX. */
+typedef struct {
+    int32_t sample_rate;             /* ASRConstants.sampleRate 16000 */
+    int32_t frame_samples;           /* ASRConstants.samplesPerEncoderFrame 1280 */
+    int32_t mel_hop;                 /* ASRConstants.melHopSize 160 */
+    int32_t max_model_samples;       /* ASRConstants.maxModelSamples 240000 */
+    double overlap_seconds;          /* ChunkProcessor.overlapSeconds 2.0 */
+    int32_t mel_chunk_context;       /* 1 */
+    int32_t silence_aligned;         /* 0; preferSilenceAlignment */
+    int32_t warmup_prefix_frames;    /* 0; a value above 0 selects the aligned starts too (:169) and lets a boundary ask for the prefix */
+    int32_t end_aligned;             /* 1; supportsSuppressedPrefix(modelVersion) */
+} fa_tdt_window_config;
+void fa_tdt_window_default_config(fa_tdt_window_config *cfg);
+/* chunkLayout (:48-75, :140-161) with cfg->warmup_prefix_frames as the prefix; every output is nullable.  Host only.  With the
+ * defaults 238 080 / 206 080 / 1 280 / 0; with the mel context off 239 360 / 207 360 / 0 / 0. */
+fa_status fa_tdt_window_layout(const fa_tdt_window_config *cfg, int64_t *chunk_samples, int64_t *stride_samples,
+                               int64_t *mel_context_samples, int64_t *warmup_prefix_samples);
+/* The most windows a recording of `samples` samples can get; 0 for samples <= 0, -1 for a refused geometry.  The list of starts holds
+ * 1 + (samples - 1) / stride entries, ascending and below `samples`.  Regular starts are every multiple of the stride below `samples`:
+ * a step beyond the list ends the loop.  Aligned starts can lie in front of their targets, so the loop may step on beyond the list,
+ * by the stride each time and below `samples`: at most (samples - 1) / stride further windows. */
+int64_t fa_tdt_window_count_bound(const fa_tdt_window_config *cfg, int64_t samples);
+typedef struct {
+    int32_t recording;
+    int32_t use_warmup_prefix;       /* the start's ChunkStartDecision.useWarmupPrefix */
+    int32_t is_last;
+    int32_t emit_after_frame;        /* emitTokensAfterFrame; -1: nil */
+    int32_t global_frame_offset;     /* (warmup > 0 ? contextStart : chunkStart) / frame_samples */
+    int32_t context_frames;          /* contextSamples / frame_samples: contextFrameAdjustment */
+    int32_t actual_audio_frames;     /* calculateEncoderFrames(length - contextSamples) */
+    int32_t reserved;
+    int64_t chunk_start, warmup_samples, context_samples, context_start;
+    int64_t length;                  /* audioEnd - contextStart: the preprocessor's originalLength */
+} fa_tdt_window;
+/* audio: the recordings' samples one after the other, recording b at audio_offsets[b] ... audio_offsets[b + 1] (HOST int64[batch + 1];
+ * no alignment of a recording's first sample is assumed).  windows HOST [capacity] (nullable with capacity 0: the count alone), by
+ * recording and in a recording's order; window_range HOST int64[batch + 1]: recording b owns [window_range[b], window_range[b + 1]) —
+ * the array fa_tdt_merge_windows takes.  The same windows as the five int32 arrays fa_tdt_greedy_tables_dev, fa_tdt_greedy_logits_dev
+ * and fa_tdt_greedy_logits_lang_dev read, each [capacity] and nullable: audio_frames (actual_audio_frames), t0
+ * (fa_tdt_initial_time_index(0, 0, context_frames); a window with a suppressed prefix has no context and starts at 0, its
+ * initialTimeIndexOverride), is_last, global_offset, emit_after.  speech_end HOST int64[batch] (nullable): speechEndSamples, or the
+ * recording's length where end_aligned is 0.  statuses HOST int32[batch] (nullable): FA_INVALID_ARGUMENT for a recording in which
+ * the in-order sum of squares over a window [f F - F, f F + F) (F = frame_samples, clipped to the recording) is not finite for some
+ * frame f — a NaN or an infinity among the samples, or squares that overflow; Swift's sorted() has no answer for such scores — which
+ * gets zero windows and leaves the other recordings untouched.  Rounded addition of non-negative terms is monotone, so with every
+ * such sum finite every energy the reference takes is finite.  A recording of 0 samples gets zero windows.
+ * OUTPUT_TOO_SMALL when capacity is below window_range[batch]: window_range, speech_end and statuses are written, no window is.
+ * _dev: audio and the five arrays are DEVICE pointers, read and written in stream order; otherwise HOST pointers.  One host
+ * synchronisation per call. */
+fa_status fa_tdt_plan_windows_dev(fa_ctx *ctx, const fa_tdt_window_config *cfg, const float *d_audio, const int64_t *audio_offsets,
+                                  int32_t batch, fa_tdt_window *windows, int64_t capacity, int64_t *window_range,
+                                  int32_t *d_audio_frames, int32_t *d_t0, int32_t *d_is_last, int32_t *d_global_offset,
+                                  int32_t *d_emit_after, int64_t *speech_end, int32_t *statuses);
+fa_status fa_tdt_plan_windows(fa_ctx *ctx, const fa_tdt_window_config *cfg, const float *audio, const int64_t *audio_offsets,
+                              int32_t batch, fa_tdt_window *windows, int64_t capacity, int64_t *window_range, int32_t *audio_frames,
+                              int32_t *t0, int32_t *is_last, int32_t *global_offset, int32_t *emit_after, int64_t *speech_end,
+                              int32_t *statuses);
+/* The preprocessor's rows: rows float[row_capacity][max_model_samples], row i the `length` samples of windows[i] from context_start
+ * of its recording, copied as bits, zeros behind them; lengths int32[n_windows] (nullable): the lengths, what fa_mel_plan_create /
+ * fa_mel_execute_dev take beside the rows.  windows HOST [n_windows], the records of fa_tdt_plan_windows or hand-made ones:
+ * INVALID_ARGUMENT for a recording outside the batch, a window outside its recording or longer than a row; OUTPUT_TOO_SMALL when
+ * row_capacity is below n_windows (nothing is packed).  _dev: audio, rows and lengths are DEVICE pointers and the entry does NOT
+ * synchronise (the windows travel in the launches' arguments); otherwise HOST pointers and one synchronisation. */
+fa_status fa_tdt_pack_windows_dev(fa_ctx *ctx, const fa_tdt_window_config *cfg, const float *d_audio, const int64_t *audio_offsets,
+                                  int32_t batch, const fa_tdt_window *windows, int64_t n_windows, float *d_rows, int64_t row_capacity,
+                                  int32_t *d_lengths);
+fa_status fa_tdt_pack_windows(fa_ctx *ctx, const fa_tdt_window_config *cfg, const float *audio, const int64_t *audio_offsets,
+                              int32_t batch, const fa_tdt_window *windows, int64_t n_windows, float *rows, int64_t row_capacity,
+                              int32_t *lengths);
+typedef struct { int32_t recording, reserved; int64_t from_sample, to_sample; } fa_tdt_span;
+/* The speech-energy gate of the seam-gap repair.  thresholds HOST float[batch] (nullable): adaptiveSpeechRmsThreshold of every
+ * recording — the frames from offset 0 on, those whose sum is exactly 0 left out, the element at min(count - 1, Int(Double(count) *
+ * 0.75)) of the ascending RMS values by exact selection, times 0.3, clamped to [0.0005, 0.008]; 0.008 when no frame is left.
+ * spans HOST [n_spans]: for span i span_frames[i] (HOST int64, nullable) counts the frames from_sample + k F, whole ones below
+ * to_sample, whose RMS is above (strictly) the threshold of the span's recording — override_thresholds[recording] (HOST
+ * float[batch]) when that array is given, the computed one otherwise — and span_seconds[i] (HOST double, nullable) is Double(frames)
+ * * (Double(frame_samples) / Double(sample_rate)).  statuses as in fa_tdt_plan_windows: a refused recording has threshold NaN, its
+ * spans 0 frames.  INVALID_ARGUMENT for a span whose recording is outside the batch or whose from_sample is below 0 or to_sample
+ * beyond the recording (the reference would read past the audio).  _dev: audio is a DEVICE pointer.  One synchronisation. */
+fa_status fa_tdt_speech_gate_dev(fa_ctx *ctx, const fa_tdt_window_config *cfg, const float *d_audio, const int64_t *audio_offsets,
+                                 int32_t batch, const float *override_thresholds, float *thresholds, const fa_tdt_span *spans,
+                                 int64_t n_spans, int64_t *span_frames, double *span_seconds, int32_t *statuses);
+fa_status fa_tdt_speech_gate(fa_ctx *ctx, const fa_tdt_window_config *cfg, const float *audio, const int64_t *audio_offsets,
+                             int32_t batch, const float *override_thresholds, float *thresholds, const fa_tdt_span *spans,
+                             int64_t n_spans, int64_t *span_frames, double *span_seconds, int32_t *statuses);
+
 /* ------------------------------------------------------------------ resampling ------ */
 /* AudioConverter.linearResample (FluidAudio/Shared/AudioConverter.swift:388-442): planar float[channels][frames] ->
  * mono mix (weight 1/channels) -> linear interpolation to out_rate.  HOST pointers.  Bit-exact restatement. */
