@@ -26,6 +26,9 @@ from .post import (ConstrainedClusterAssignment, HungarianAssignment, assign_emb
 from .resample import linear_resample, poly_taps, resample_poly  # noqa: F401
 from .sharding import gather_ragged_int32, shard_offsets, shard_range  # noqa: F401
 from .sortformer import OfflineSortformerConfig, OfflineSortformerDiarizer, offline_windows, pack_windows, stitch, stitcher_alignment  # noqa: F401
+from .rnnt import (RNNT_BIAS_DEFAULT_BOOST, RNNT_BIAS_MAX_BOOST, RNNT_BIAS_MAX_FORM, RnntBias, RnntConfig, VocabularyTerm,  # noqa: F401
+                   bias_build as rnnt_bias_build, bias_candidates as rnnt_bias_candidates, bias_effective_boost as rnnt_bias_effective_boost,
+                   decode_logits as rnnt_decode_logits, fold as rnnt_fold)
 from .tdt import (Language, Script, TdtConfig, TdtDurationMapping, TdtFrameNavigation, decode_logits as tdt_decode_logits,  # noqa: F401
                   decode_logits_lang as tdt_decode_logits_lang, decode_tables as tdt_decode_tables, matches as tdt_matches,
                   token_classes as tdt_token_classes, topk_rows as tdt_topk_rows)

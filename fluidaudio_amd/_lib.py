@@ -67,6 +67,7 @@ EXPORTED_SYMBOLS = [
     "fa_vad_gather_segments_dev", "fa_vad_gather_segments", "fa_vad_stream_advance_dev", "fa_vad_stream_advance",
     "fa_tdt_window_default_config", "fa_tdt_window_layout", "fa_tdt_window_count_bound", "fa_tdt_plan_windows_dev", "fa_tdt_plan_windows",
     "fa_tdt_pack_windows_dev", "fa_tdt_pack_windows", "fa_tdt_speech_gate_dev", "fa_tdt_speech_gate",
+    "fa_rnnt_bias_effective_boost", "fa_rnnt_bias_build", "fa_rnnt_bias_candidates", "fa_rnnt_default_config", "fa_rnnt_greedy_logits_dev",
 ]
 
 
@@ -233,6 +234,10 @@ class TdtSpanRecord(C.Structure):
 
 
 RESAMPLE_ROUTE_KINDS = ("DECIM", "INTERP", "ROWS", "LDS", "SIMPLE")    # FA_RESAMPLE_ROUTE_*
+
+
+class RnntConfig(C.Structure):                                         # fa_rnnt_config
+    _fields_ = [("blank_id", C.c_int32), ("eou_id", C.c_int32), ("max_symbols_per_step", C.c_int32)]
 
 
 class ResampleRoute(C.Structure):                                      # fa_resample_route (fa_debug_resample_route: tests)
@@ -504,6 +509,13 @@ def lib() -> C.CDLL:
     L.fa_tdt_pack_windows.argtypes = L.fa_tdt_pack_windows_dev.argtypes
     L.fa_tdt_speech_gate_dev.argtypes = [vp, C.POINTER(TdtWindowConfig), vp, vp, i32, vp, vp, vp, i64, vp, vp, vp]
     L.fa_tdt_speech_gate.argtypes = L.fa_tdt_speech_gate_dev.argtypes
+    L.fa_rnnt_bias_effective_boost.argtypes = [i32, f32, f32]
+    L.fa_rnnt_bias_effective_boost.restype = f32
+    L.fa_rnnt_bias_build.argtypes = [vp, i32, vp, vp, i32, vp, i64, C.POINTER(i64), C.POINTER(i32)]
+    L.fa_rnnt_bias_candidates.argtypes = [vp, i64, vp, i32, vp, vp, i32, C.POINTER(i32)]
+    L.fa_rnnt_default_config.argtypes = [C.POINTER(RnntConfig)]
+    L.fa_rnnt_default_config.restype = None
+    L.fa_rnnt_greedy_logits_dev.argtypes = [vp, C.POINTER(RnntConfig), vp, i32, i32, i32, i32, i32, i64, vp, vp, vp, i64, i32, vp, vp, i32] + [vp] * 7
     _lib = L
     return L
 

@@ -973,6 +973,94 @@ struct TdtDecoderV3 {
     }
 };
 
+// ------------------------------------------------------------------------------------------------------------------ streaming RNN-T
+// RnntDecoder.decodeWithEOU (Sources/FluidAudio/ASR/Parakeet/Streaming/RnntDecoder.swift:73-127) and NemotronVocabularyBias
+// (Streaming/Nemotron/NemotronVocabularyBias.swift:55-340) over fa_rnnt_greedy_logits_dev and fa_rnnt_bias_build / _candidates.
+// Texts arrive FOLDED (lowercased().precomposedStringWithCanonicalMapping) and past the caller's letter-count guard (usableSurfaces,
+// :203-212): both need Unicode tables this header does not carry.
+struct RnntConfig {
+    int32_t blankId = 1024, eouId = -1, maxSymbolsPerStep = 10;
+    RnntConfig() { fa_rnnt_config c; fa_rnnt_default_config(&c); blankId = c.blank_id; eouId = c.eou_id; maxSymbolsPerStep = c.max_symbols_per_step; }
+    fa_rnnt_config c() const { return fa_rnnt_config{blankId, eouId, maxSymbolsPerStep}; }
+};
+struct CustomVocabularyTerm {      // the fields the bias reads
+    std::string text;
+    std::optional<float> weight;
+    std::vector<std::string> aliases;
+};
+class NemotronVocabularyBias {
+public:
+    static constexpr float defaultBoost = FA_RNNT_BIAS_DEFAULT_BOOST, maxBoost = FA_RNNT_BIAS_MAX_BOOST;
+    struct Candidate {
+        int tokenId;
+        float boost;
+    };
+    static float effectiveBoost(const CustomVocabularyTerm &term, float fallback = defaultBoost) {   // :196-199
+        return fa_rnnt_bias_effective_boost(term.weight ? 1 : 0, term.weight.value_or(0.0f), fallback);
+    }
+    // init?(terms:pieces:defaultBoost:) (:126-182): nullopt when no usable term remains.  pieces[id]: the folded piece, empty optional = no piece.
+    static std::optional<NemotronVocabularyBias> make(const std::vector<CustomVocabularyTerm> &terms, const std::vector<std::optional<std::string>> &pieces,
+                                                      float fallback = defaultBoost) {
+        std::vector<const char *> surfaces, texts(pieces.size());
+        std::vector<float> boosts;
+        auto checked = [](const std::string &s) -> const char * {
+            if (s.find('\0') != std::string::npos) throw Error(FA_INVALID_ARGUMENT, "fa_rnnt_bias_build", "a text holds a NUL");
+            return s.c_str();
+        };
+        for (const CustomVocabularyTerm &t : terms) {
+            const float boost = effectiveBoost(t, fallback);
+            if (!(boost > 0.0f)) continue;                                                            // :206
+            surfaces.push_back(checked(t.text)); boosts.push_back(boost);
+            for (const std::string &a : t.aliases) { surfaces.push_back(checked(a)); boosts.push_back(boost); }
+        }
+        NemotronVocabularyBias b;
+        b.advances_.resize(pieces.size());
+        for (size_t i = 0; i < pieces.size(); ++i) {
+            texts[i] = pieces[i] ? checked(*pieces[i]) : nullptr;
+            b.advances_[i] = pieces[i] && !pieces[i]->empty() && !(pieces[i]->front() == '<' && pieces[i]->back() == '>');   // :152
+        }
+        int64_t words = 0;
+        const int32_t n = static_cast<int32_t>(surfaces.size()), vocab = static_cast<int32_t>(pieces.size());
+        fa_status st = fa_rnnt_bias_build(texts.data(), vocab, surfaces.data(), boosts.data(), n, nullptr, 0, &words, &b.tailCap_);
+        if (st != FA_SUCCESS) throw Error(st, "fa_rnnt_bias_build", "text that is not UTF-8, or a term longer than FA_RNNT_BIAS_MAX_FORM scalars");
+        if (words == 0) return std::nullopt;
+        b.blob_.resize(static_cast<size_t>(words));
+        st = fa_rnnt_bias_build(texts.data(), vocab, surfaces.data(), boosts.data(), n, b.blob_.data(), words, &words, &b.tailCap_);
+        if (st != FA_SUCCESS) throw Error(st, "fa_rnnt_bias_build");
+        return b;
+    }
+    // observe(_:) (:254-261).  The device entry carries the tail's scalars; this mirror keeps the ids that put them there: a token with
+    // a piece adds at least one scalar, so the last tailCap of them hold the whole tail.
+    void observe(int tokenId) {
+        if (tokenId < 0 || static_cast<size_t>(tokenId) >= advances_.size() || !advances_[static_cast<size_t>(tokenId)]) return;
+        observed_.push_back(tokenId);
+        if (observed_.size() > static_cast<size_t>(tailCap_)) observed_.erase(observed_.begin());
+    }
+    void resetMatchState() { observed_.clear(); }                                                    // :265-268
+    std::vector<Candidate> candidates() const {                                                       // :280-306; ascending token id
+        int32_t count = 0;
+        const int32_t n = static_cast<int32_t>(observed_.size());
+        fa_status st = fa_rnnt_bias_candidates(blob_.data(), static_cast<int64_t>(blob_.size()), observed_.data(), n, nullptr, nullptr, 0, &count);
+        if (st != FA_SUCCESS && st != FA_OUTPUT_TOO_SMALL) throw Error(st, "fa_rnnt_bias_candidates");
+        std::vector<int32_t> ids(static_cast<size_t>(count));
+        std::vector<float> boosts(static_cast<size_t>(count));
+        if (count > 0) {
+            st = fa_rnnt_bias_candidates(blob_.data(), static_cast<int64_t>(blob_.size()), observed_.data(), n, ids.data(), boosts.data(), count, &count);
+            if (st != FA_SUCCESS) throw Error(st, "fa_rnnt_bias_candidates");
+        }
+        std::vector<Candidate> out(ids.size());
+        for (size_t i = 0; i < ids.size(); ++i) out[i] = Candidate{ids[i], boosts[i]};
+        return out;
+    }
+    const std::vector<int32_t> &blob() const { return blob_; }   // upload as it is: d_bias / bias_words of fa_rnnt_greedy_logits_dev
+    int32_t tailCap() const { return tailCap_; }
+
+private:
+    std::vector<int32_t> blob_, observed_;
+    std::vector<char> advances_;
+    int32_t tailCap_ = 0;
+};
+
 // ------------------------------------------------------------------------------------------------------------------ TDT long-form merging
 // ChunkProcessor's fold of mergeChunks over a recording's windows and enforceMonotonicTimestamps (Sources/FluidAudio/ASR/Parakeet/
 // SlidingWindow/TDT/ChunkProcessor.swift:843-855, 952-1219) over fa_tdt_merge_windows: the windows of one or more recordings in one

@@ -408,6 +408,77 @@ fa_status fa_tdt_greedy_logits_lang_dev(fa_ctx *ctx, const fa_tdt_config *cfg, c
                                         const uint8_t *d_classes, int32_t script, int32_t use_blocklist, int32_t top_k,
                                         int32_t *d_out_route, int32_t *d_swap_counts);
 
+/* ------------------------------------------------------------------ streaming RNN-T ------------- */
+/* The streaming ASR path: the greedy loop of RnntDecoder.decodeWithEOU (ASR/Parakeet/Streaming/RnntDecoder.swift:73-127; the
+ * Nemotron managers run the same loop behind a speculative scan, StreamingNemotronMultilingualAsrManager+Decode.swift:189-251,
+ * 278-440) and the decode-time hotword biasing of Streaming/Nemotron/NemotronVocabularyBias.swift:55-340, 465-498.
+ *
+ * ---- the bias tables (HOST pointers, no context, no GPU).  Lower-casing + NFC and the letter-count guard of usableSurfaces
+ * (:203-212, it counts grapheme clusters) are the CALLER's; everything below works on Unicode scalars. */
+#define FA_RNNT_BIAS_DEFAULT_BOOST 4.5f /* NemotronVocabularyBias.defaultBoost (:90) */
+#define FA_RNNT_BIAS_MAX_BOOST 6.0f     /* NemotronVocabularyBias.maxBoost (:98) */
+#define FA_RNNT_BIAS_MAX_FORM 256       /* the longest piece form, in scalars, a table may hold */
+/* effectiveBoost (:196-199): the weight when one is set and <= FA_RNNT_BIAS_MAX_BOOST, default_boost otherwise. */
+float fa_rnnt_bias_effective_boost(int32_t has_weight, float weight, float default_boost);
+/* init (:126-182) as one position-independent blob of int32 words, to be uploaded as it is (layout: csrc/rnnt_bias_core.h).
+ * folded_pieces[vocab]: the folded piece of every token id as NUL-terminated UTF-8, NULL: the id has no piece; a piece that starts
+ * with '<' and ends with '>' never enters the index or the tail (:147-156).  folded_surfaces[n_surfaces] with boosts[n_surfaces]
+ * > 0: the folded surfaces (texts and aliases) that passed the caller's guards.  The library takes pieceForm (:233-250: split at
+ * White_Space scalars, U+2581 in front of every word unless the first scalar is CJK, :219-228), builds the trie (:160-175) and
+ * stores with every node the list accumulate (:310-339) gives from its depth for every entry under it: every vocabulary piece
+ * equal to a prefix of the rest of the form, never the bare marker, from depth 0 of an anchored form only after two letters, all
+ * ids of one folded piece together; one entry per id with the strongest boost, ascending id.  The root's list is
+ * freshStartCandidates.  *tail_cap: the longest form in scalars.
+ * capacity_words == 0 asks for *words_needed only; a smaller capacity than needed: OUTPUT_TOO_SMALL.  No surface, or none with a
+ * scalar besides white space: SUCCESS with *words_needed = 0 and *tail_cap = 0 — decode without a bias.  INVALID_ARGUMENT: text
+ * that is not UTF-8 (as in fa_tdt_token_classes), a boost <= 0 or NaN, a form above FA_RNNT_BIAS_MAX_FORM scalars, NULL outputs. */
+fa_status fa_rnnt_bias_build(const char *const *folded_pieces, int32_t vocab, const char *const *folded_surfaces, const float *boosts,
+                             int32_t n_surfaces, int32_t *blob, int64_t capacity_words, int64_t *words_needed, int32_t *tail_cap);
+/* candidates() (:280-306) after observe (:254-261) of observed[n_observed] from a reset match state: ids ascending, one entry per
+ * id with the strongest boost; ids without a piece leave the state alone.  Walks blob[words] through the accessors the kernel
+ * uses: the header and every offset are checked, a malformed or truncated blob is INVALID_ARGUMENT and is never read out of
+ * bounds.  *count is the number of candidates; more than capacity: OUTPUT_TOO_SMALL, nothing written but *count. */
+fa_status fa_rnnt_bias_candidates(const int32_t *blob, int64_t words, const int32_t *observed, int32_t n_observed, int32_t *ids,
+                                  float *boosts, int32_t capacity, int32_t *count);
+
+typedef struct {
+    int32_t blank_id;
+    int32_t eou_id;               /* the end-of-utterance token (RnntDecoder.swift:32), -1: none */
+    int32_t max_symbols_per_step; /* 10 */
+} fa_rnnt_config;
+/* blank_id 1024 (NemotronStreamingConfig.swift:45), eou_id -1, max_symbols_per_step 10. */
+void fa_rnnt_default_config(fa_rnnt_config *cfg);
+/* The greedy walk for a batch of streams, one wavefront per stream.  d_logits[batch][U][T][row_stride] (fp32 / fp16): the joint
+ * logits for (u = decoder steps taken so far in this chunk, t = encoder frame), u as in fa_tdt_greedy_logits_dev; only the rows on
+ * the greedy path are read.  d_frames[batch] = validOutLen, d_skip[batch] = skipFrames (NULL: 0): maxT = min(frames, T), start =
+ * min(skip, maxT) (:85-88).  For t in start ..< maxT up to max_symbols_per_step decisions at row (u, t): blank goes to the next
+ * frame, eou_id sets d_eou and ends the stream, any other token is emitted with its chunk-local frame t, observed by the bias,
+ * and followed by ++u (:98-123).  A decision needed at u >= U ends the stream with OUTPUT_TOO_SMALL; a token beyond max_out is
+ * counted, not stored, and leaves OUTPUT_TOO_SMALL — as in the TDT walk.
+ * A decision: plain = the first-index argmax of the vocab_with_blank logits (LogitsArgmax's rule: fp16 widened, NaN never wins,
+ * nothing above -inf gives 0).  With d_bias (the blob on the device, bias_words words, tail_cap as fa_rnnt_bias_build returned
+ * it), pickBiased (:482-498): over the depth-0 candidates and those of every live partial match with id < vocab_with_blank,
+ * score = float32(logit[id] + boost); the best candidate replaces plain — blank included — only where its score is strictly
+ * above logit[plain]; NaN on either side never flips.  TIE ORDER: the reference iterates a Swift Dictionary, whose order is
+ * unspecified; THIS LIBRARY defines: the highest score, then the lowest token id.
+ * d_out_plain[batch][max_out]: the displaced plain argmax where the bias flipped the emitted token, -1 otherwise (the reference's
+ * FLUIDAUDIO_BIAS_LOG trace, :342-349, 500-511).
+ * Match state: d_tail[batch][tail_cap] / d_tail_len[batch], the last folded scalars emitted (:254-261), read at entry and written
+ * back at exit: two calls over a split chunk equal one call, and d_tail_len = 0 is resetMatchState (:265-268).
+ * d_status[b]: INVALID_ARGUMENT (no walk, no token) where the blob's magic, version, vocab or tail_cap do not match the arguments;
+ * RUNTIME_ERROR where an offset or length inside the blob leaves bias_words — the kernel checks each before it forms an address.
+ * INVALID_ARGUMENT with nothing launched: NULL ctx / cfg / d_logits / d_frames / d_out_count / d_final_u / d_eou / d_status (and
+ * the three token outputs where max_out > 0); batch, U, T or vocab_with_blank <= 0; row_stride < vocab_with_blank; max_out < 0;
+ * tail_cap outside [0, FA_RNNT_BIAS_MAX_FORM]; a dtype that is neither; d_bias with a NULL d_tail or d_tail_len.
+ * The decoder / joint networks are not in the reference tree: token parity against the models is UNPINNED; the matcher is pinned
+ * by the reference's NemotronVocabularyBiasTests. */
+fa_status fa_rnnt_greedy_logits_dev(fa_ctx *ctx, const fa_rnnt_config *cfg, const void *d_logits, int32_t dtype, int32_t batch,
+                                    int32_t U, int32_t T, int32_t vocab_with_blank, int64_t row_stride, const int32_t *d_frames,
+                                    const int32_t *d_skip, const int32_t *d_bias, int64_t bias_words, int32_t tail_cap,
+                                    int32_t *d_tail, int32_t *d_tail_len, int32_t max_out, int32_t *d_out_tok,
+                                    int32_t *d_out_frame, int32_t *d_out_plain, int32_t *d_out_count, int32_t *d_final_u,
+                                    int32_t *d_eou, int32_t *d_status);
+
 /* ------------------------------------------------------------------ AHC ------------- */
 /* Exact signature + status contract of the reference FFI
  * (FastClusterWrapper/include/FastClusterWrapper.h:35-41, FastClusterWrapper.cpp:196-244):
