@@ -18,6 +18,9 @@ from .paraformer import (PARAFORMER_SPAN_DTYPE, CifResult, ParaformerConfig, Tim
                          keep_table, segments_from_spans, timestamps_batch, timestamps_batch_dev)
 from .pipeline import (ClusteringResult, OfflineClusteringConfig, cluster_embeddings, cluster_embeddings_batch, cluster_embeddings_stagewise, diarize_segments,  # noqa: F401
                        extract_embeddings, select_training_embeddings, span_embedder)
+from .online import (ONLINE_PACK_REPEAT, ONLINE_PACK_ZERO_TAIL, ONLINE_RUN_DTYPE, ONLINE_SEGMENT_DTYPE, OnlineChunkConfig, chunk_finish as online_chunk_finish,
+                     chunk_plan as online_chunk_plan, pack_waveforms as online_pack_waveforms, EMBEDDING_SIZE, SPEAKER_ASSIGNMENT_DTYPE, SPEAKER_KINDS, SPEAKER_PAIR_DTYPE, Speaker, SpeakerDatabase, SpeakerDbConfig,
+                     cosine_distance as speaker_cosine_distance, l2_normalize as speaker_l2_normalize, validate_embedding as speaker_validate_embedding)  # noqa: F401
 from .pool import Pool, device_count  # noqa: F401
 from .reconstruct import (OfflineReconstruction, ReconstructionConfig, SegmentationOutput, chunk_assignments, finalize_segments,  # noqa: F401
                           powerset_decode)

@@ -68,6 +68,10 @@ EXPORTED_SYMBOLS = [
     "fa_tdt_window_default_config", "fa_tdt_window_layout", "fa_tdt_window_count_bound", "fa_tdt_plan_windows_dev", "fa_tdt_plan_windows",
     "fa_tdt_pack_windows_dev", "fa_tdt_pack_windows", "fa_tdt_speech_gate_dev", "fa_tdt_speech_gate",
     "fa_rnnt_bias_effective_boost", "fa_rnnt_bias_build", "fa_rnnt_bias_candidates", "fa_rnnt_default_config", "fa_rnnt_greedy_logits_dev",
+    "fa_speaker_l2_normalize", "fa_speaker_cosine_distance", "fa_speaker_validate_embedding", "fa_speaker_db_default_config", "fa_speaker_db_create", "fa_speaker_db_destroy", "fa_speaker_db_assign_dev", "fa_speaker_db_distances_dev",
+    "fa_speaker_db_mergeable_pairs_dev", "fa_speaker_db_assign", "fa_speaker_db_distances", "fa_speaker_db_mergeable_pairs", "fa_speaker_db_upsert", "fa_speaker_db_get", "fa_speaker_db_ids", "fa_speaker_db_count", "fa_speaker_db_remove",
+    "fa_speaker_db_remove_inactive", "fa_speaker_db_set_permanent", "fa_speaker_db_reset",
+    "fa_online_chunk_default_config", "fa_online_chunk_plan_dev", "fa_online_chunk_plan", "fa_online_pack_waveforms_dev", "fa_online_chunk_finish_dev",
 ]
 
 
@@ -238,6 +242,21 @@ RESAMPLE_ROUTE_KINDS = ("DECIM", "INTERP", "ROWS", "LDS", "SIMPLE")    # FA_RESA
 
 class RnntConfig(C.Structure):                                         # fa_rnnt_config
     _fields_ = [("blank_id", C.c_int32), ("eou_id", C.c_int32), ("max_symbols_per_step", C.c_int32)]
+
+
+class SpeakerDbConfig(C.Structure):                                    # fa_speaker_db_config
+    _fields_ = [("speaker_threshold", C.c_float), ("embedding_threshold", C.c_float), ("min_speech_duration", C.c_float), ("ema_alpha", C.c_float),
+                ("validate_min_magnitude", C.c_float), ("max_speakers", C.c_int32), ("raw_capacity", C.c_int32)]
+
+
+class OnlineChunkConfig(C.Structure):                                  # fa_online_chunk_config
+    _fields_ = [("frames", C.c_int32), ("chunk_samples", C.c_int32), ("min_active_frames", C.c_float), ("min_speech_duration", C.c_float),
+                ("validate_min_magnitude", C.c_float), ("reserved", C.c_int32), ("frame_step", C.c_double)]
+
+
+class SpeakerInfo(C.Structure):                                        # fa_speaker_info
+    _fields_ = [("id", C.c_int32), ("slot", C.c_int32), ("raw_count", C.c_int32), ("update_count", C.c_int32), ("is_permanent", C.c_int32),
+                ("duration", C.c_float), ("created_tick", C.c_int64), ("updated_tick", C.c_int64)]
 
 
 class ResampleRoute(C.Structure):                                      # fa_resample_route (fa_debug_resample_route: tests)
@@ -516,6 +535,35 @@ def lib() -> C.CDLL:
     L.fa_rnnt_default_config.argtypes = [C.POINTER(RnntConfig)]
     L.fa_rnnt_default_config.restype = None
     L.fa_rnnt_greedy_logits_dev.argtypes = [vp, C.POINTER(RnntConfig), vp, i32, i32, i32, i32, i32, i64, vp, vp, vp, i64, i32, vp, vp, i32] + [vp] * 7
+    L.fa_speaker_l2_normalize.argtypes = [vp, vp]
+    L.fa_speaker_cosine_distance.argtypes = [vp, vp]
+    L.fa_speaker_cosine_distance.restype = f32
+    L.fa_speaker_validate_embedding.argtypes = [vp, f32]
+    L.fa_speaker_db_default_config.argtypes = [C.POINTER(SpeakerDbConfig)]
+    L.fa_speaker_db_default_config.restype = None
+    L.fa_speaker_db_create.argtypes = [vp, C.POINTER(SpeakerDbConfig), i32, C.POINTER(vp)]
+    L.fa_speaker_db_destroy.argtypes = [vp]
+    L.fa_speaker_db_destroy.restype = None
+    L.fa_speaker_db_assign_dev.argtypes = [vp, vp, vp, vp, vp, i32, i64, vp]
+    L.fa_speaker_db_distances_dev.argtypes = [vp, vp, vp, i32, vp, vp]
+    L.fa_speaker_db_mergeable_pairs_dev.argtypes = [vp, vp, f32, i32, vp, i32, vp]
+    L.fa_speaker_db_assign.argtypes = L.fa_speaker_db_assign_dev.argtypes
+    L.fa_speaker_db_distances.argtypes = L.fa_speaker_db_distances_dev.argtypes
+    L.fa_speaker_db_mergeable_pairs.argtypes = L.fa_speaker_db_mergeable_pairs_dev.argtypes
+    L.fa_speaker_db_upsert.argtypes = [vp, vp, i32, C.POINTER(SpeakerInfo), vp, vp]
+    L.fa_speaker_db_get.argtypes = [vp, vp, i32, i32, C.POINTER(SpeakerInfo), vp, vp, i32]
+    L.fa_speaker_db_ids.argtypes = [vp, vp, i32, vp, C.POINTER(i32)]
+    L.fa_speaker_db_count.argtypes = [vp, vp, vp]
+    L.fa_speaker_db_remove.argtypes = [vp, vp, i32, i32, i32]
+    L.fa_speaker_db_remove_inactive.argtypes = [vp, vp, i32, i64, i32]
+    L.fa_speaker_db_set_permanent.argtypes = [vp, vp, i32, i32, i32]
+    L.fa_speaker_db_reset.argtypes = [vp, vp, i32, i32]
+    L.fa_online_chunk_default_config.argtypes = [C.POINTER(OnlineChunkConfig)]
+    L.fa_online_chunk_default_config.restype = None
+    L.fa_online_chunk_plan_dev.argtypes = [vp, C.POINTER(OnlineChunkConfig), vp, vp, i32, i32, vp, vp, i32, vp, vp]
+    L.fa_online_chunk_plan.argtypes = [vp, C.POINTER(OnlineChunkConfig), vp, vp, i32, i32, vp, vp, i32, C.POINTER(i32), vp]
+    L.fa_online_pack_waveforms_dev.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
+    L.fa_online_chunk_finish_dev.argtypes = [vp, C.POINTER(OnlineChunkConfig), vp, vp, vp, vp, vp, i32, i64, vp, i64, C.POINTER(i64), vp, vp]
     _lib = L
     return L
 

@@ -7,8 +7,10 @@
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <cstdlib>
+#include <limits>
 #include <map>
 #include <optional>
 #include <stdexcept>
@@ -1583,6 +1585,173 @@ struct TdtWindowPlanner {
         ctx.check(fa_tdt_speech_gate(ctx.handle(), &c, samples.data(), offsets, 1, threshold ? &over : nullptr, nullptr, &span, 1, nullptr, &seconds, nullptr), "fa_tdt_speech_gate");
         return seconds;
     }
+};
+
+// ---- online diarizer: the speaker database (Diarizer/Clustering/SpeakerManager.swift, SpeakerTypes.swift; the C entries are batched over
+// streams, this is ONE stream).  Ids are ints from 1, dates are caller-supplied ticks, names stay with the caller (fluidaudio_hip.h).
+struct SpeakerUtilities {
+    static std::vector<float> l2Normalize(const std::vector<float> &e) {             // VDSPOperations.l2Normalize with the library's sums
+        if (e.size() != 256) throw Error(FA_INVALID_ARGUMENT, "fa_speaker_l2_normalize", "an embedding has 256 elements");
+        std::vector<float> out(256);
+        (void)fa_speaker_l2_normalize(e.data(), out.data());
+        return out;
+    }
+    static float cosineDistance(const std::vector<float> &a, const std::vector<float> &b) {   // infinity for sizes other than 256, as for a mismatch
+        if (a.size() != 256 || b.size() != 256) return std::numeric_limits<float>::infinity();
+        return fa_speaker_cosine_distance(a.data(), b.data());
+    }
+    static bool validateEmbedding(const std::vector<float> &e, float minMagnitude = 0.1f) {
+        return e.size() == 256 && fa_speaker_validate_embedding(e.data(), minMagnitude) != 0;
+    }
+};
+
+struct RawEmbedding {               // SpeakerTypes.swift:208-218 without the UUID: normalised when it is made
+    std::vector<float> embedding;
+    int64_t timestamp = 0;
+    RawEmbedding() = default;
+    explicit RawEmbedding(const std::vector<float> &e, int64_t timestamp = 0) : embedding(SpeakerUtilities::l2Normalize(e)), timestamp(timestamp) {}
+};
+
+struct Speaker {                    // the fields of Speaker the database keeps; currentEmbedding is normalised by the constructor (Speaker.init)
+    int id = 0;
+    std::vector<float> currentEmbedding;
+    float duration = 0.0f;
+    int64_t createdAt = 0, updatedAt = 0;
+    int updateCount = 1;
+    std::vector<RawEmbedding> rawEmbeddings;   // oldest first
+    bool isPermanent = false;
+    Speaker() = default;
+    Speaker(int id, const std::vector<float> &currentEmbedding, float duration = 0.0f, int64_t createdAt = 0, int64_t updatedAt = 0, bool isPermanent = false)
+        : id(id), currentEmbedding(SpeakerUtilities::l2Normalize(currentEmbedding)), duration(duration), createdAt(createdAt), updatedAt(updatedAt), isPermanent(isPermanent) {}
+};
+
+struct TimedSpeakerSegment {        // SpeakerTypes / DiarizerTypes: a record of fa_online_chunk_finish_dev with the caller's embedding beside it
+    int speakerId = 0;              // the database's id (the reference: a string)
+    std::vector<float> embedding;
+    float startTimeSeconds = 0.0f, endTimeSeconds = 0.0f, qualityScore = 0.0f;
+    float durationSeconds() const { return endTimeSeconds - startTimeSeconds; }
+    static TimedSpeakerSegment from(const fa_online_segment &r, const float *embedding256 = nullptr) {
+        TimedSpeakerSegment t;
+        t.speakerId = r.id; t.startTimeSeconds = r.start; t.endTimeSeconds = r.end; t.qualityScore = r.quality;
+        if (embedding256) t.embedding.assign(embedding256, embedding256 + 256);
+        return t;
+    }
+};
+
+class SpeakerManager {
+  public:
+    static constexpr int embeddingSize = 256;
+    struct Pair { int speakerToMerge, destination; };
+    SpeakerManager(Context &ctx, float speakerThreshold = 0.65f, float embeddingThreshold = 0.45f, float minSpeechDuration = 1.0f, int maxSpeakers = 16, int rawCapacity = 50)
+        : ctx_(ctx) {
+        fa_speaker_db_default_config(&cfg_);
+        cfg_.speaker_threshold = speakerThreshold; cfg_.embedding_threshold = embeddingThreshold; cfg_.min_speech_duration = minSpeechDuration;
+        cfg_.max_speakers = maxSpeakers; cfg_.raw_capacity = rawCapacity;
+        ctx_.check(fa_speaker_db_create(ctx_.handle(), &cfg_, 1, &db_), "fa_speaker_db_create");
+    }
+    ~SpeakerManager() { fa_speaker_db_destroy(db_); }
+    SpeakerManager(const SpeakerManager &) = delete;
+    SpeakerManager &operator=(const SpeakerManager &) = delete;
+
+    fa_speaker_assignment lastAssignment{0, -1, FA_SPEAKER_SKIPPED, 0.0f};   // the path the last assignSpeaker took
+    // assignSpeaker (:135-177): nil for an embedding of another size, too short a duration, a non-finite embedding or a full table
+    std::optional<Speaker> assignSpeaker(const std::vector<float> &embedding, float speechDuration, int64_t tick = 0) {
+        if (embedding.size() != static_cast<size_t>(embeddingSize)) return std::nullopt;
+        ctx_.check(fa_speaker_db_assign(ctx_.handle(), db_, embedding.data(), &speechDuration, nullptr, 1, tick, &lastAssignment), "fa_speaker_db_assign");
+        return lastAssignment.id ? getSpeaker(lastAssignment.id) : std::nullopt;
+    }
+    std::pair<std::optional<int>, float> findSpeaker(const std::vector<float> &embedding, std::optional<float> speakerThreshold = std::nullopt) {   // :184-191
+        const std::vector<float> d = distances(embedding);
+        const std::vector<int> ids = slotIds();
+        int best = -1;
+        for (size_t s = 0; s < d.size(); ++s)
+            if (d[s] < (best < 0 ? std::numeric_limits<float>::infinity() : d[best])) best = static_cast<int>(s);
+        if (best >= 0 && d[best] <= speakerThreshold.value_or(cfg_.speaker_threshold)) return {ids[best], d[best]};
+        return {std::nullopt, std::numeric_limits<float>::infinity()};
+    }
+    std::vector<std::pair<int, float>> findMatchingSpeakers(const std::vector<float> &embedding, std::optional<float> speakerThreshold = std::nullopt) {   // :198-212
+        const std::vector<float> d = distances(embedding);
+        const std::vector<int> ids = slotIds();
+        std::vector<std::pair<int, float>> out;
+        for (size_t s = 0; s < d.size(); ++s)
+            if (ids[s] && d[s] <= speakerThreshold.value_or(cfg_.speaker_threshold)) out.emplace_back(ids[s], d[s]);
+        std::stable_sort(out.begin(), out.end(), [](const auto &a, const auto &b) { return a.second < b.second; });
+        return out;
+    }
+    std::vector<Pair> findMergeablePairs(std::optional<float> speakerThreshold = std::nullopt, bool excludeIfBothPermanent = true) {   // :282-328
+        const int cap = std::max(1, cfg_.max_speakers * (cfg_.max_speakers - 1) / 2);
+        std::vector<fa_speaker_pair> rec(static_cast<size_t>(cap));
+        int32_t n = 0;
+        ctx_.check(fa_speaker_db_mergeable_pairs(ctx_.handle(), db_, speakerThreshold.value_or(cfg_.speaker_threshold), excludeIfBothPermanent ? 1 : 0, rec.data(), cap, &n),
+                   "fa_speaker_db_mergeable_pairs");
+        std::vector<Pair> out;
+        for (int i = 0; i < n; ++i) out.push_back(Pair{rec[static_cast<size_t>(i)].source_id, rec[static_cast<size_t>(i)].destination_id});
+        return out;
+    }
+    void upsertSpeaker(const Speaker &s) {   // :552-606; pass a Speaker's fields as they are: an existing id is overwritten without normalising
+        std::vector<float> raws;
+        for (const RawEmbedding &r : s.rawEmbeddings) raws.insert(raws.end(), r.embedding.begin(), r.embedding.end());
+        if (s.currentEmbedding.size() != static_cast<size_t>(embeddingSize) || raws.size() != s.rawEmbeddings.size() * embeddingSize)
+            throw Error(FA_INVALID_ARGUMENT, "fa_speaker_db_upsert", "an embedding has 256 elements");
+        const fa_speaker_info info{s.id, -1, static_cast<int32_t>(s.rawEmbeddings.size()), s.updateCount, s.isPermanent ? 1 : 0, s.duration, s.createdAt, s.updatedAt};
+        ctx_.check(fa_speaker_db_upsert(ctx_.handle(), db_, 0, &info, s.currentEmbedding.data(), raws.empty() ? nullptr : raws.data()), "fa_speaker_db_upsert");
+    }
+    std::optional<Speaker> getSpeaker(int id) {
+        fa_speaker_info info{};
+        std::vector<float> cur(embeddingSize), raws(static_cast<size_t>(cfg_.raw_capacity) * embeddingSize);
+        ctx_.check(fa_speaker_db_get(ctx_.handle(), db_, 0, id, &info, cur.data(), raws.data(), cfg_.raw_capacity), "fa_speaker_db_get");
+        if (info.id == 0) return std::nullopt;
+        Speaker s;
+        s.id = info.id; s.currentEmbedding = cur; s.duration = info.duration; s.createdAt = info.created_tick; s.updatedAt = info.updated_tick;
+        s.updateCount = info.update_count; s.isPermanent = info.is_permanent != 0;
+        for (int k = 0; k < info.raw_count; ++k) {
+            RawEmbedding r;
+            r.embedding.assign(raws.begin() + static_cast<ptrdiff_t>(k) * embeddingSize, raws.begin() + static_cast<ptrdiff_t>(k + 1) * embeddingSize);
+            s.rawEmbeddings.push_back(std::move(r));
+        }
+        return s;
+    }
+    bool hasSpeaker(int id) { return getSpeaker(id).has_value(); }
+    void makeSpeakerPermanent(int id) { ctx_.check(fa_speaker_db_set_permanent(ctx_.handle(), db_, 0, id, 1), "fa_speaker_db_set_permanent"); }
+    void revokePermanence(int id) { ctx_.check(fa_speaker_db_set_permanent(ctx_.handle(), db_, 0, id, 0), "fa_speaker_db_set_permanent"); }
+    void removeSpeaker(int id, bool keepIfPermanent = true) { ctx_.check(fa_speaker_db_remove(ctx_.handle(), db_, 0, id, keepIfPermanent ? 1 : 0), "fa_speaker_db_remove"); }
+    void removeSpeakersInactive(int64_t sinceTick, bool keepIfPermanent = true) {
+        ctx_.check(fa_speaker_db_remove_inactive(ctx_.handle(), db_, 0, sinceTick, keepIfPermanent ? 1 : 0), "fa_speaker_db_remove_inactive");
+    }
+    void reset(bool keepIfPermanent = false) { ctx_.check(fa_speaker_db_reset(ctx_.handle(), db_, 0, keepIfPermanent ? 1 : 0), "fa_speaker_db_reset"); }
+    int speakerCount() {
+        int32_t n = 0;
+        ctx_.check(fa_speaker_db_count(ctx_.handle(), db_, &n), "fa_speaker_db_count");
+        return n;
+    }
+    std::vector<int> speakerIds() {   // ascending, as the reference sorts them
+        std::vector<int32_t> ids(static_cast<size_t>(cfg_.max_speakers));
+        int32_t n = 0;
+        ctx_.check(fa_speaker_db_ids(ctx_.handle(), db_, 0, ids.data(), &n), "fa_speaker_db_ids");
+        std::vector<int> out(ids.begin(), ids.begin() + n);
+        std::sort(out.begin(), out.end());
+        return out;
+    }
+
+  private:
+    std::vector<float> distances(const std::vector<float> &embedding) {
+        if (embedding.size() != static_cast<size_t>(embeddingSize)) throw Error(FA_INVALID_ARGUMENT, "fa_speaker_db_distances", "an embedding has 256 elements");
+        std::vector<float> d(static_cast<size_t>(cfg_.max_speakers));
+        ctx_.check(fa_speaker_db_distances(ctx_.handle(), db_, embedding.data(), 1, d.data(), nullptr), "fa_speaker_db_distances");
+        return d;
+    }
+    std::vector<int> slotIds() {      // the id in every slot, 0 for a free one
+        std::vector<int> out(static_cast<size_t>(cfg_.max_speakers), 0);
+        for (const int id : speakerIds()) {
+            fa_speaker_info info{};
+            ctx_.check(fa_speaker_db_get(ctx_.handle(), db_, 0, id, &info, nullptr, nullptr, 0), "fa_speaker_db_get");
+            if (info.slot >= 0) out[static_cast<size_t>(info.slot)] = id;
+        }
+        return out;
+    }
+    Context &ctx_;
+    fa_speaker_db_config cfg_{};
+    fa_speaker_db *db_ = nullptr;
 };
 
 }  // namespace fluidaudio

@@ -1363,6 +1363,171 @@ fa_status fa_tdt_speech_gate(fa_ctx *ctx, const fa_tdt_window_config *cfg, const
                              int32_t batch, const float *override_thresholds, float *thresholds, const fa_tdt_span *spans,
                              int64_t n_spans, int64_t *span_frames, double *span_seconds, int32_t *statuses);
 
+/* ------------------------------------------------------------------ online diarizer: the speaker database ------ */
+/* SpeakerManager (FluidAudio/Diarizer/Clustering/SpeakerManager.swift:135-212, 282-328, 411-492, 552-628, SpeakerTypes.swift:36-162,
+ * 213-217, SpeakerOperations.swift:62-126, VDSPOperations.swift:12-23) as device-resident state, batched over independent streams (one
+ * SpeakerManager per stream).  Embeddings are 256 floats (SpeakerManager.embeddingSize); nothing else is accepted.
+ *
+ * The fp32 arithmetic is this library's DEFINITION — vDSP_dotpr / vDSP_svesq specify no summation order, so Accelerate's bits are out of
+ * reach and a decision within an ulp of a threshold may differ from a Mac:
+ *   dot256(a, b)  64 lanes, lane l holding dimensions 4l .. 4l+3 with the partial ((a0 b0 + a1 b1) + a2 b2) + a3 b3, every product and sum
+ *                 rounded on its own (no FMA); then p[l] = p[l] + p[l ^ off] for off = 32, 16, 8, 4, 2, 1
+ *   sumsq(a) = dot256(a, a);  l2Normalize: norm = max(sqrtf(sumsq), 1e-12f), scale = 1 / norm, out = a * scale
+ *   cosineDistance: SpeakerOperations.swift:62-101 on those sums (infinity when a sum of squares is <= 0, the unit shortcut within 1e-3
+ *                 of 1, the clamp, 1 - s)
+ *   the mean of the raw embeddings: per dimension a sequential fp32 sum from the oldest raw to the newest from 0.0f, then / Float(count)
+ * Host and kernels share one statement of it (csrc/speaker_db_core.h).
+ *
+ * Where this library departs from the reference:
+ *   ids            int32 counting from 1 per stream, 0 = none; names and non-numeric ids stay with the caller
+ *   Date()         a caller-supplied int64 tick per call;  UUID segment ids: dropped
+ *   search order   Dictionary iteration is unspecified; here slots in ascending order, a tie on the minimum distance to the lowest slot
+ *   a new speaker  goes to the lowest free slot; with none free the item gets kind FULL, id 0, and the state is unchanged (the reference
+ *                  is unbounded)
+ *   a non-finite embedding  kind INVALID (the reference creates a NaN speaker: NaN never compares below the minimum)
+ *   upsert         takes at most raw_capacity raw embeddings (the reference keeps what it is given until the next update)
+ * Out of scope: mergeSpeaker, mergeWith and initializeKnownSpeakers(mode: .merge) — they order raw embeddings by wall-clock timestamp,
+ * and a caller does them with get + upsert; removeRawEmbedding; names, Codable, SendableSpeaker; the unused
+ * SpeakerUtilities.shouldAssignSpeaker heuristics; `confidence`, which assignSpeaker ignores.
+ *
+ * State per stream and slot (max_speakers slots, 1 .. 64), all in device memory: the current embedding, a ring of raw_capacity raw
+ * embeddings (50 is the reference's), duration, update count, created and updated tick, id, live and permanent flags; per stream next_id. */
+typedef struct fa_speaker_db fa_speaker_db;
+typedef struct {
+    float speaker_threshold;       /* 0.65: below it an embedding belongs to the closest speaker */
+    float embedding_threshold;     /* 0.45: below it the speaker's embedding is updated as well */
+    float min_speech_duration;     /* 1.0 s: shorter speech creates no speaker */
+    float ema_alpha;               /* 0.9 (SpeakerManager.swift:452) */
+    float validate_min_magnitude;  /* negative: off (plain SpeakerManager); 0.1: DiarizerManager's validateEmbedding before every assignment */
+    int32_t max_speakers;          /* slots per stream, 1 .. 64 (default 16) */
+    int32_t raw_capacity;          /* raw embeddings kept per speaker (50) */
+} fa_speaker_db_config;
+/* The path assignSpeaker took for an item. */
+enum { FA_SPEAKER_SKIPPED = 0, FA_SPEAKER_UPDATED = 1, FA_SPEAKER_DURATION_ONLY = 2, FA_SPEAKER_LOW_ENERGY = 3, FA_SPEAKER_CREATED = 4,
+       FA_SPEAKER_TOO_SHORT = 5, FA_SPEAKER_INVALID = 6, FA_SPEAKER_FULL = 7 };
+typedef struct { int32_t id, slot, kind; float distance; } fa_speaker_assignment;   /* id 0 / slot -1: none; distance: to the closest speaker (+inf: none) */
+typedef struct { int32_t source_id, destination_id, source_slot, destination_slot; float distance; } fa_speaker_pair;
+typedef struct {
+    int32_t id, slot, raw_count, update_count, is_permanent;
+    float duration;
+    int64_t created_tick, updated_tick;
+} fa_speaker_info;
+/* The arithmetic on its own, on HOST arrays of 256 floats, without a context or a device: VDSPOperations.l2Normalize,
+ * SpeakerUtilities.cosineDistance (+inf for a NULL pointer) and validateEmbedding (1: the magnitude is above min_magnitude and every
+ * element finite). */
+fa_status fa_speaker_l2_normalize(const float *embedding, float *out);
+float fa_speaker_cosine_distance(const float *a, const float *b);
+int32_t fa_speaker_validate_embedding(const float *embedding, float min_magnitude);
+void fa_speaker_db_default_config(fa_speaker_db_config *cfg);
+/* INVALID_ARGUMENT, with nothing allocated or launched, for NULL pointers, streams < 1, max_speakers outside 1 .. 64, raw_capacity < 1.
+ * The database belongs to the context's device; every later call takes a context of that device and is ordered by that context's stream. */
+fa_status fa_speaker_db_create(fa_ctx *ctx, const fa_speaker_db_config *cfg, int32_t streams, fa_speaker_db **out);
+void fa_speaker_db_destroy(fa_speaker_db *db);
+/* assignSpeaker for `per` items of every stream.  DEVICE pointers: d_embeddings float[streams][per][256] (16-byte aligned), d_durations
+ * float[streams][per], d_skip int32[streams][per] (nullable; non-zero: the item is not looked at, id 0, kind SKIPPED),
+ * d_out fa_speaker_assignment[streams][per].  Within a stream the items are taken in index order, each seeing the database the previous
+ * one left; streams are independent.  Per item:
+ *   1. every element finite, and with validate_min_magnitude >= 0 sqrtf(sumsq(e)) > validate_min_magnitude; else INVALID
+ *   2. n = l2Normalize(e);  3. the strict minimum d of cosineDistance(n, current[slot]) over the live slots (+inf with none)
+ *   4. a slot found and d < speaker_threshold: d < embedding_threshold -> updateMainEmbedding when sumsq(n) > 0.01 (UPDATED), nothing at
+ *      all otherwise (LOW_ENERGY); else duration += and the tick (DURATION_ONLY)
+ *   5. else duration >= min_speech_duration: a new speaker with id next_id++ (CREATED; FULL without a free slot); 6. else TOO_SHORT
+ * updateMainEmbedding: m = l2Normalize(n); raw = l2Normalize(m) (RawEmbedding.init normalises again); raw's own sumsq > 0.01 check; the
+ * oldest raw dropped from a full ring, raw appended; current = l2Normalize(mean of raws); current = alpha current + (1 - alpha) m with
+ * 1 - alpha in fp32; current = l2Normalize(current); the duration added, the tick set, the update count incremented.
+ * One wavefront per stream.  Enqueued on the context's stream; no synchronisation. */
+fa_status fa_speaker_db_assign_dev(fa_ctx *ctx, fa_speaker_db *db, const float *d_embeddings, const float *d_durations, const int32_t *d_skip,
+                                   int32_t per, int64_t tick, fa_speaker_assignment *d_out);
+/* findSpeaker / findMatchingSpeakers: d_dist float[streams][per][max_speakers] the cosine distance of query (stream, i) — NOT normalised,
+ * as in the reference — to every slot, +inf on a dead one; d_best_slot int32[streams][per] (nullable) the strict minimum's slot, -1
+ * with none.  The `<= threshold` filter and the ascending sort (ties by slot) are the caller's.  DEVICE pointers; no synchronisation. */
+fa_status fa_speaker_db_distances_dev(fa_ctx *ctx, fa_speaker_db *db, const float *d_queries, int32_t per, float *d_dist, int32_t *d_best_slot);
+/* findMergeablePairs: per stream the pairs i < j of live slots in slot order with distance < threshold, both-permanent pairs left out
+ * on request; the lower slot is the destination unless the higher one is permanent (:318-323).  d_pairs [streams][capacity], d_counts
+ * int32[streams] the pairs found (records beyond capacity are not written).  DEVICE pointers; no synchronisation. */
+fa_status fa_speaker_db_mergeable_pairs_dev(fa_ctx *ctx, fa_speaker_db *db, float threshold, int32_t exclude_if_both_permanent,
+                                            fa_speaker_pair *d_pairs, int32_t capacity, int32_t *d_counts);
+/* The three above on HOST arrays of the same shapes: copied to the device, run, copied back; one synchronisation.  With fewer than
+ * `capacity` pairs in a stream the records behind its count are unspecified. */
+fa_status fa_speaker_db_assign(fa_ctx *ctx, fa_speaker_db *db, const float *embeddings, const float *durations, const int32_t *skip, int32_t per,
+                               int64_t tick, fa_speaker_assignment *out);
+fa_status fa_speaker_db_distances(fa_ctx *ctx, fa_speaker_db *db, const float *queries, int32_t per, float *dist, int32_t *best_slot);
+fa_status fa_speaker_db_mergeable_pairs(fa_ctx *ctx, fa_speaker_db *db, float threshold, int32_t exclude_if_both_permanent, fa_speaker_pair *pairs,
+                                        int32_t capacity, int32_t *counts);
+/* The management entries take HOST pointers, wait for the context's stream and return with their effect complete.
+ * upsert (upsertSpeaker :552-606): info->id >= 1; an existing id has its current embedding overwritten WITHOUT normalising, duration,
+ * raws, update count and updated tick replaced, permanence only ever set, the created tick kept; a new id goes to the lowest free slot
+ * through Speaker.init's l2Normalize, and next_id is raised above it.  raws float[info->raw_count][256], oldest first, stored as they are
+ * (RawEmbedding.init's normalisation is the caller's).  OUTPUT_TOO_SMALL with no free slot.  info->slot is ignored. */
+fa_status fa_speaker_db_upsert(fa_ctx *ctx, fa_speaker_db *db, int32_t stream, const fa_speaker_info *info, const float *current, const float *raws);
+/* getSpeaker: *info (id 0, slot -1 when there is no such speaker), current float[256] (nullable), raws float[raw_rows][256] (nullable)
+ * the first min(raw_count, raw_rows) raw embeddings, oldest first. */
+fa_status fa_speaker_db_get(fa_ctx *ctx, fa_speaker_db *db, int32_t stream, int32_t id, fa_speaker_info *info, float *current, float *raws,
+                            int32_t raw_rows);
+/* the stream's ids in slot order: ids int32[max_speakers] */
+fa_status fa_speaker_db_ids(fa_ctx *ctx, fa_speaker_db *db, int32_t stream, int32_t *ids, int32_t *count);
+/* speakerCount of every stream: counts int32[streams] */
+fa_status fa_speaker_db_count(fa_ctx *ctx, fa_speaker_db *db, int32_t *counts);
+/* removeSpeaker, removeSpeakersInactive(since:) (updated tick < since_tick), makeSpeakerPermanent / revokePermanence, reset (:610-628:
+ * next_id becomes 1, or one above the largest id kept).  stream -1 in remove_inactive and reset: every stream. */
+fa_status fa_speaker_db_remove(fa_ctx *ctx, fa_speaker_db *db, int32_t stream, int32_t id, int32_t keep_if_permanent);
+fa_status fa_speaker_db_remove_inactive(fa_ctx *ctx, fa_speaker_db *db, int32_t stream, int64_t since_tick, int32_t keep_if_permanent);
+fa_status fa_speaker_db_set_permanent(fa_ctx *ctx, fa_speaker_db *db, int32_t stream, int32_t id, int32_t permanent);
+fa_status fa_speaker_db_reset(fa_ctx *ctx, fa_speaker_db *db, int32_t stream, int32_t keep_if_permanent);
+
+/* ---- online diarizer: around the networks (DiarizerManager.processChunkWithSpeakerTracking, Diarizer/Core/DiarizerManager.swift:255-531;
+ * EmbeddingExtractor.getEmbeddings, Diarizer/Extraction/EmbeddingExtractor.swift:60-199), batched over streams and chunks.  The segmentation
+ * and embedding networks stay the caller's; weights float[streams][chunks][frames][3] is what fa_powerset_decode_dev leaves (or soft weights). */
+typedef struct {
+    int32_t frames;              /* 589 */
+    int32_t chunk_samples;       /* 160 000; the constants 80 000 / 160 000 of numMasksInChunk scale as chunk_samples / 2 and chunk_samples */
+    float min_active_frames;     /* 10.0 (DiarizerConfig.minActiveFramesCount) */
+    float min_speech_duration;   /* 1.0 s (DiarizerConfig.minSpeechDuration): shorter runs give no segment */
+    float validate_min_magnitude;/* 0.1: validateEmbedding before the assignment */
+    int32_t reserved;
+    double frame_step;           /* 0.016875 s (SegmentationProcessor.swift:224-239) */
+} fa_online_chunk_config;
+typedef struct { int32_t stream, chunk, local_speaker; } fa_online_run;
+typedef struct { int32_t stream, chunk, local_speaker, id, start_frame, end_frame; float start, end, quality; } fa_online_segment;
+enum { FA_ONLINE_PACK_ZERO_TAIL = 0, FA_ONLINE_PACK_REPEAT = 1 };
+void fa_online_chunk_default_config(fa_online_chunk_config *cfg);
+/* Before the embedding network.  DEVICE pointers.  d_activities float[streams][chunks][3]: calculateSpeakerActivities, a sequential fp32 sum
+ * over the frames.  The clean mask of a speaker is weight * (row sum < 2.0 ? 1 : 0) (:321-333); it runs the model when its sequential sum is
+ * not below min_active_frames (EmbeddingExtractor :71-77).  d_runs [run_capacity]: the (stream, chunk, speaker) triples that run, in that
+ * order, compacted; d_run_count int32[1] how many there are (beyond run_capacity nothing is written); d_mask_rows float[run_capacity][frames]:
+ * per run row[i] = mask[i % numMasksInChunk] with numMasksInChunk = min((frames * samples + chunk_samples / 2) / chunk_samples, frames) in
+ * integers, an all-zero row when it is 0 (:63-66, 154-199).  d_samples_in_chunk int32[streams][chunks], NULL: chunk_samples everywhere.
+ * _dev does not synchronise; fa_online_chunk_plan is the same with run_count a HOST int32 and one synchronisation.  INVALID_ARGUMENT with
+ * nothing launched for NULL pointers, non-positive counts or frames < 1. */
+fa_status fa_online_chunk_plan_dev(fa_ctx *ctx, const fa_online_chunk_config *cfg, const float *d_weights, const int32_t *d_samples_in_chunk,
+                                   int32_t streams, int32_t chunks, float *d_activities, fa_online_run *d_runs, int32_t run_capacity,
+                                   int32_t *d_run_count, float *d_mask_rows);
+fa_status fa_online_chunk_plan(fa_ctx *ctx, const fa_online_chunk_config *cfg, const float *d_weights, const int32_t *d_samples_in_chunk,
+                               int32_t streams, int32_t chunks, float *d_activities, fa_online_run *d_runs, int32_t run_capacity,
+                               int32_t *run_count, float *d_mask_rows);
+/* Ragged audio -> d_out float[rows][chunk_samples] (16-byte aligned): row r takes min(d_lengths[r], chunk_samples) samples from
+ * d_audio + d_offsets[r]; ZERO_TAIL: zeros behind them (DiarizerManager :266-303); REPEAT: out[i] = in[i % n], what the doubling loop of
+ * fillWaveformBuffer (:118-151) leaves; n = 0 leaves zeros.  DEVICE pointers, no synchronisation. */
+fa_status fa_online_pack_waveforms_dev(fa_ctx *ctx, const float *d_audio, const int64_t *d_offsets, const int32_t *d_lengths, int32_t rows,
+                                       int32_t chunk_samples, int32_t mode, float *d_out);
+/* Behind the embedding network: the gate, the assignment into `db` and the timed segments, for db's streams and `chunks` chunks of each; the
+ * database carries across the chunks of a stream in order.  d_weights, d_activities (of the plan), d_embeddings float[streams][chunks][3][256]
+ * (zeros where no model ran; 16-byte aligned) are DEVICE pointers; chunk_offsets HOST double[streams][chunks] seconds.
+ *   gate (:351-378)  activity > min_active_frames, else SKIPPED; then validateEmbedding (INVALID) and assignSpeaker with
+ *                    duration = Float(activity) * Float(frame_step); db's thresholds, this config's validate_min_magnitude
+ *   segments (:415-531)  speakers with activity < min_active_frames or without an id give none (a speaker exactly at the minimum passes
+ *                    here and not the gate: the reference's); per frame the threshold is 0.15 when another speaker exceeds 0.3, else 0.3;
+ *                    a run is kept when Float(end - start) >= min_speech_duration with times offset + Double(frame) * frame_step in fp64;
+ *                    quality = min(1, sqrtf(sumsq(embedding)) / 10) * (activity / Float(end_frame - start_frame))
+ * segments HOST [capacity]: ordered by stream, then chunk, within a chunk by start time (ties: the lower local speaker, then the earlier
+ * frame; Swift's sort leaves ties open).  *count: all segments; OUTPUT_TOO_SMALL when it exceeds capacity (the database is updated and
+ * count set all the same).  chunk_counts HOST int32[streams][chunks] (nullable).  d_assignments DEVICE fa_speaker_assignment
+ * [streams][chunks][3].  One synchronisation. */
+fa_status fa_online_chunk_finish_dev(fa_ctx *ctx, const fa_online_chunk_config *cfg, fa_speaker_db *db, const float *d_weights,
+                                     const float *d_activities, const float *d_embeddings, const double *chunk_offsets, int32_t chunks,
+                                     int64_t tick, fa_online_segment *segments, int64_t capacity, int64_t *count, int32_t *chunk_counts,
+                                     fa_speaker_assignment *d_assignments);
+
 /* ------------------------------------------------------------------ resampling ------ */
 /* AudioConverter.linearResample (FluidAudio/Shared/AudioConverter.swift:388-442): planar float[channels][frames] ->
  * mono mix (weight 1/channels) -> linear interpolation to out_rate.  HOST pointers.  Bit-exact restatement. */
