@@ -404,7 +404,7 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
     const int Np = w.Np, nblk = w.nblk, d = w.d, N_arg = w.N;
 #ifdef FA_AHC_PROFILE
     const int prof_blk = nblk / 2;
-    unsigned long long t_seg[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long t_seg[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long t_prev = clock64();
 #endif
     // Every load of the round's first memory round trip is requested before anything is waited for or branched on: the block records
@@ -708,18 +708,17 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
     bool cok[kC4];
 #pragma unroll
     for (int j = 0; j < kC4; ++j) { cgw[j] = dinf(); cok[j] = false; }
+    const bool hp_a = sp_a == hP;   // SPEC, chained merge: B's cluster keeps its slot (it is the a of the merge after it)
     if (SPEC && spec && pres_chain) {
-        // B's row is this column's scratch entry and B's size is in the record; its centroid was stored by the previous round
-        const bool hp_a = sp_a == hP;
+        // B's row is this column's scratch entry and B's size is in the record (both of the first round trip); its centroid was stored by the previous round.
+        // Requested here: the partner's size and its entry, kept RAW in sp_ma / sp_da[0] — a select between a loaded value and B's would consume the load in this
+        // branch, i.e. put the wait for the partner's cold row in front of the candidate gathers and of the whole decision.  The merge phase sorts them into
+        // (a, b) order where the one-merge path first uses its operands.
         const int ow = hp_a ? sp_b : sp_a, onw = hp_a ? sp_nb : sp_na;
-        const double mw = w.sizes[onw];
-        sp_ma = hp_a ? sph.den : mw; sp_mb = hp_a ? mw : sph.den;
+        sp_ma = w.sizes[onw];
         cload(w.C + static_cast<size_t>(sp_na) * d, sp_xa); cload(w.C + static_cast<size_t>(sp_nb) * d, sp_xb);
         __builtin_amdgcn_sched_barrier(0);
-        double ew[CPT];
-        pair_entries<CPT, kEntryBranch>(w.M, Np, ow, onw, x0, nx, st.sym_limit, sp_a, sp_b, ew);
-        const double eh = (nx[0] != kDead && x0 != sp_a && x0 != sp_b) ? msx : 0.0;
-        sp_da[0] = hp_a ? eh : ew[0]; sp_db[0] = hp_a ? ew[0] : eh;
+        pair_entries<CPT, kEntryBranch>(w.M, Np, ow, onw, x0, nx, st.sym_limit, sp_a, sp_b, sp_da);
     } else if (kUncond || spec)
     {
         // sizes and centroids first, the two matrix entries (a cold row each) last: loads complete in order, the centroid arithmetic runs under the entries'
@@ -884,31 +883,42 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
     int pslot[kPend], pnd[kPend];
 #pragma unroll
     for (int k = 0; k < kPend; ++k) { pkey[k] = dinf(); pslot[k] = x0; pnd[k] = nx[0]; }
+    // SPEC: the global stores B's commit owes (its row entry of this column, size, node ids; the dendrogram row apart).  They are issued behind the first use of
+    // the executed merge's operands — next to that merge's own stores, or where a launch that executes nothing drops the operands — and not in front of it: the
+    // memory counter is in order and counts stores, and behind the conditions they sit in the compiler waits for the whole counter, so in front of the operands'
+    // first use the wait for the operands was also a wait for the acknowledgement of B's row store.  Program order keeps B's store to M[a][x0] in front of the
+    // executed merge's store to the same address (the same thread writes both); no request of this launch reads what they write (trip 3 asks for row z*, which
+    // is neither B's row nor this column when the column is B's).
+    bool actB = false;
+    auto commit_b_stores = [&]() {
+        const int a = sph.a, b = sph.b, nnew = N + st.step;
+        if (actB) w.M[static_cast<size_t>(a) * Np + x0] = msx;
+        else if (x0 == a) { w.sizes[nnew] = sph.den; w.node[x0] = nnew; }
+        else if (x0 == b) w.node[x0] = kDead;
+    };
+    auto commit_b_z = [&]() {
+        if (blk == 0 && tid == 0) {
+            double *z = w.Z + static_cast<size_t>(st.step) * 4;
+            z[0] = sph.na < sph.nb ? sph.na : sph.nb;
+            z[1] = sph.na < sph.nb ? sph.nb : sph.na;
+            z[2] = 0.0;
+            z[3] = sph.den;
+        }
+    };
     if constexpr (SPEC) {
         if (hit) {   // commit B: what the round of B would have done to this column, from the same values (its entry: the scratch row)
             const int a = sph.a, b = sph.b, nnew = N + st.step;
-            const bool actB = nx[0] != kDead && x0 != a && x0 != b;
+            actB = nx[0] != kDead && x0 != a && x0 != b;
             if (actB) {
-                w.M[static_cast<size_t>(a) * Np + x0] = msx;
                 const int f = row_update1(rs[0], e2x[0], msx, a, b, nnew);
                 dirty[0] = dirty[0] || (f & 1) != 0; e2_dirty[0] = e2_dirty[0] || (f & 2) != 0;
             } else if (x0 == a) {
                 nx[0] = nnew; rs[0].d1 = dinf(); rs[0].nn = -1; rs[0].nnnode = -1; e2x[0] = dinf(); dirty[0] = true; e2_dirty[0] = true; in_flight[0] = true;
-                w.sizes[nnew] = sph.den;
-                w.node[x0] = nnew;
             } else if (x0 == b) {
                 nx[0] = kDead; rs[0].d1 = dinf(); rs[0].nn = -1; rs[0].nnnode = -1; dirty[0] = true;
-                w.node[x0] = kDead;
             }
             if (alone) pkey[0] = actB ? msx : dinf();
             else if (x0 == hP) { rs[0].d1 = hpd; rs[0].nn = hps; rs[0].nnnode = hpn; e2x[0] = hpd; dirty[0] = true; e2_dirty[0] = true; }   // B's row finished
-            if (blk == 0 && tid == 0) {
-                double *z = w.Z + static_cast<size_t>(st.step) * 4;
-                z[0] = sph.na < sph.nb ? sph.na : sph.nb;
-                z[1] = sph.na < sph.nb ? sph.nb : sph.na;
-                z[2] = 0.0;
-                z[3] = sph.den;
-            }
         }
     }
     // SPEC: the merge speculated in this round (D) and the state of this column under it
@@ -927,6 +937,9 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
         for (int j = 0; j < kCk; ++j) asm volatile("" :: "v"(sp_xa[j]), "v"(sp_xb[j]));
 #pragma unroll
         for (int j = 0; j < CPT; ++j) asm volatile("" :: "v"(sp_da[j]), "v"(sp_db[j]));
+        if constexpr (SPEC) {
+            if (hit) { commit_b_stores(); commit_b_z(); }   // B alone: nothing is executed behind it
+        }
     }
     if (D.op == OP_MERGE) {
         const int a = D.a, b = D.b, na = D.na, nb = D.nb, nnew = N + step0;
@@ -952,6 +965,14 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
 #pragma unroll
             for (int j = 0; j < CPT; ++j) asm volatile("" :: "v"(da[j]), "v"(db[j]));
         }
+        if constexpr (SPEC) {
+            // the chained merge's operands into (a, b) order (see the request): B's cluster brings its size and this column's scratch entry from the first round
+            // trip, the partner's size and entry arrived raw in ma / da[0]
+            const bool ch = sp_hit && pres_chain, ch_a = ch && hp_a, ch_b = ch && !hp_a;
+            const double mw = ma, ew = da[0], eh = act[0] ? msx : 0.0;
+            ma = ch_a ? sph.den : mw; mb = ch_a ? mw : (ch_b ? sph.den : mb);
+            da[0] = ch_a ? eh : ew; db[0] = ch_a ? ew : (ch_b ? eh : db[0]);
+        }
         const double den = ma + mb;
         if constexpr (kPend > 1) {
 #pragma unroll
@@ -973,7 +994,7 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
 #pragma unroll
             for (int j = 0; j < kCk; ++j) asm volatile("" :: "v"(xa[j]), "v"(xb[j]));   // (as above)
         }
-        AHC_STAMP(9);
+        AHC_STAMP(9);   // SPEC: the one wait for trip 2 (in front of den) lies in this segment
         const bool keeps_centroid = wave == 0 && (st.mode == FA_AHC_MODE_EXACT || blk == 0);
         double part = 0.0;
 #pragma unroll
@@ -1004,9 +1025,9 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
         AHC_STAMP(2);
         // SPEC: rank the candidates by their Lance-Williams value for the new cluster, hand the best (z*) to every wave, request its row entry, size and centroid
         int zs = -1, nzs = -1;
-        double dz = 0.0, szs = 0.0, xz[kCk];
+        double dz = 0.0, szs = 0.0, xz[kCk], ce[kCk];
 #pragma unroll
-        for (int j = 0; j < kCk; ++j) xz[j] = 0.0;
+        for (int j = 0; j < kCk; ++j) { xz[j] = 0.0; ce[j] = 0.0; }
         if constexpr (SPEC) {
             spec_next = cand_on && sp_hit && (hit ? chain_ok : plain_merge) && step0 + 2 < N;
             if (spec_next) {
@@ -1036,8 +1057,13 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
                     dz = wantD ? pair_entry(w.M, Np, zs, nzs, x0, nx[0], st.sym_limit) : 0.0;
                     szs = w.sizes[nzs];
                     cload(w.C + static_cast<size_t>(nzs) * d, xz);
+                    // the new cluster's centroid elements (the bits workgroup 0 stores) depend on nothing of trip 3: four IEEE divisions per lane, computed
+                    // while it travels (the opaque use keeps them here: left alone they sink to their first use, behind the wait for trip 3)
+#pragma unroll
+                    for (int j = 0; j < kCk; ++j) { ce[j] = centroid_elem(xa[j], ma, xb[j], mb, den); asm volatile("" : "+v"(ce[j])); }
                 }
             }
+            AHC_STAMP(10);   // candidates ranked, z* handed over, trip 3 requested
         }
         double dc[CPT];
 #pragma unroll
@@ -1071,6 +1097,9 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
             __syncthreads();
             if (a / kCols == blk)
                 for (int k = tid; k < d; k += kBlk) w.XT[static_cast<size_t>(k) * Np + a] = s_cvec[k];
+        }
+        if constexpr (SPEC) {
+            if (hit) commit_b_stores();   // in front of this merge's store to the same address when it keeps B's slot
         }
         if constexpr (CPT == 1) {
             const int x = x0;
@@ -1132,6 +1161,9 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
                 w.node[b] = kDead;
             }
         }
+        if constexpr (SPEC) {
+            if (hit) commit_b_z();
+        }
         if (blk == 0 && tid == 0) {
             double *z = w.Z + static_cast<size_t>(step0) * 4;
             z[0] = na < nb ? na : nb;  // LinkageOutput::append (FastClusterWrapper.cpp:150-160)
@@ -1139,6 +1171,7 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
             z[2] = 0.0;                // exact height filled by ahc_heights after the loop
             z[3] = den;
         }
+        if constexpr (SPEC) AHC_STAMP(13);   // Lance-Williams row of the executed merge, row state, stores
         if constexpr (SPEC) {
             if (spec_next) {   // the merge D = (this round's cluster at slot a, z*) as ITS round would compute it: centroid, |.|^2, Lance-Williams row, row state
                 const bool ea_lo = a < zs;
@@ -1147,13 +1180,13 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
                 double part2 = 0.0;
 #pragma unroll
                 for (int j = 0; j < kCk; ++j) {
-                    const double ce = centroid_elem(xa[j], ma, xb[j], mb, den);   // the bits workgroup 0 stores for the new cluster
-                    const double xda = ea_lo ? ce : xz[j], xdb = ea_lo ? xz[j] : ce;
+                    const double xda = ea_lo ? ce[j] : xz[j], xdb = ea_lo ? xz[j] : ce[j];
                     if (blk == 0 && wave == 0 && celem(j) < d) w.C[static_cast<size_t>(nD) * d + celem(j)] = centroid_elem(xda, maD, xdb, mbD, denD);
                     const double diff = xda - xdb;
                     part2 += diff * diff;
                 }
                 const double dabD = wave_sum(part2);
+                AHC_STAMP(11);   // trip 3 arrived (size and centroid of z*), |.|^2 of D summed
                 const double invD = 1.0 / denD, waD = maD * invD, wbD = mbD * invD, wabD = waD * wbD;
                 const bool actD = nx[0] != kDead && x0 != Da && x0 != Db;
                 hrs = rs[0]; hnx = nx[0]; hin = in_flight[0];
@@ -1170,6 +1203,7 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
                 }
                 mspec[static_cast<size_t>(npar) * Np + x0] = dcD;
                 shn.valid = 1; shn.a = Da; shn.b = Db; shn.na = ea_lo ? nnew : nzs; shn.nb = ea_lo ? nzs : nnew; shn.den = denD;
+                AHC_STAMP(12);   // D's row done
             }
         }
     } else if (D.op == OP_RESCAN) {
@@ -1275,7 +1309,7 @@ __device__ __forceinline__ void ahc_round_body(const Ws w_in, const int blk, con
     AHC_STAMP(5);
 #ifdef FA_AHC_PROFILE
     if (blk == prof_blk && tid == 0) {
-        for (int i = 0; i < 12; ++i) atomicAdd(&w.prof[i], t_seg[i]);
+        for (int i = 0; i < 14; ++i) atomicAdd(&w.prof[i], t_seg[i]);
         atomicAdd(&w.prof[15], 1ULL);
     }
 #endif

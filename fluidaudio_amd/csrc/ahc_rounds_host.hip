@@ -162,8 +162,12 @@ void print_profile(const Prob &p) {   // FA_AHC_PROFILE builds: the round's cycl
     (void)hipMemcpy(hp, w.prof, sizeof(hp), hipMemcpyDeviceToHost);
     const double n = hp[15] ? static_cast<double>(hp[15]) : 1.0;
     fprintf(stderr, "ahc profile (cycles/round, block %d of %d, %llu rounds): load+sync %.0f | decide %.0f | merge loads+dab %.0f | row update %.0f | block reduce %.0f | tail %.0f\n",
-            w.nblk / 2, w.nblk, hp[15], hp[0] / n, (hp[1] + hp[6] + hp[7] + hp[8]) / n, (hp[2] + hp[9]) / n, hp[3] / n, hp[4] / n, hp[5] / n);
+            w.nblk / 2, w.nblk, hp[15], hp[0] / n, (hp[1] + hp[6] + hp[7] + hp[8]) / n, (hp[2] + hp[9]) / n, (hp[3] + hp[10] + hp[11] + hp[12] + hp[13]) / n, hp[4] / n, hp[5] / n);
     fprintf(stderr, "  merge loads+dab = operands arrive %.0f | centroid, |ca - cb|^2, wave sum %.0f\n", hp[9] / n, hp[2] / n);
+    if (hp[10] + hp[11] + hp[12] + hp[13])   // the speculative round's stamps (slots 10 .. 13)
+        fprintf(stderr, "  row update (speculative round) = candidates ranked, z* handed over, trip 3 requested %.0f | Lance-Williams row, row state, stores %.0f | "
+                        "trip 3 arrived, |.|^2 of the speculated merge %.0f | the speculated merge's row %.0f | rest %.0f\n",
+                hp[10] / n, hp[13] / n, hp[11] / n, hp[12] / n, hp[3] / n);
     fprintf(stderr, "  decide = wave reduction %.0f | barrier + result read %.0f | finished rows + global minimum %.0f | state machine + piggy choice %.0f\n", hp[6] / n, hp[7] / n, hp[8] / n, hp[1] / n);
 #else
     (void)p;
