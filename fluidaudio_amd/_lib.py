@@ -259,7 +259,29 @@ class SpeakerInfo(C.Structure):                                        # fa_spea
                 ("duration", C.c_float), ("created_tick", C.c_int64), ("updated_tick", C.c_int64)]
 
 
-class ResampleRoute(C.Structure):                                      # fa_resample_route (fa_debug_resample_route: tests)
+class SpeakerAssignment(C.Structure):                                  # fa_speaker_assignment
+    _fields_ = [("id", C.c_int32), ("slot", C.c_int32), ("kind", C.c_int32), ("distance", C.c_float)]
+
+
+class SpeakerPair(C.Structure):                                        # fa_speaker_pair
+    _fields_ = [("source_id", C.c_int32), ("destination_id", C.c_int32), ("source_slot", C.c_int32), ("destination_slot", C.c_int32), ("distance", C.c_float)]
+
+
+class OnlineRun(C.Structure):                                          # fa_online_run
+    _fields_ = [("stream", C.c_int32), ("chunk", C.c_int32), ("local_speaker", C.c_int32)]
+
+
+class OnlineSegment(C.Structure):                                      # fa_online_segment
+    _fields_ = [("stream", C.c_int32), ("chunk", C.c_int32), ("local_speaker", C.c_int32), ("id", C.c_int32), ("start_frame", C.c_int32), ("end_frame", C.c_int32),
+                ("start", C.c_float), ("end", C.c_float), ("quality", C.c_float)]
+
+
+class ExportEmbedding(C.Structure):                                    # fa_export_embedding
+    _fields_ = [("chunk_index", C.c_int32), ("speaker_index", C.c_int32), ("start_frame", C.c_int32), ("end_frame", C.c_int32),
+                ("start_time", C.c_double), ("end_time", C.c_double)]
+
+
+class ResampleRoute(C.Structure):                                     # fa_resample_route (fa_debug_resample_route: tests)
     _fields_ = [("lo", C.c_int64), ("hi", C.c_int64), ("split", C.c_int64), ("count", C.c_int64), ("kind", C.c_int32), ("wide", C.c_int32),
                 ("tile_rows", C.c_int32), ("wide_waves", C.c_int32), ("nv", C.c_int32), ("share", C.c_int32), ("groups", C.c_int32)]
 

@@ -7,16 +7,15 @@ reference's expressions.  A side of a recording holds at most MAX_LABELS speaker
 from __future__ import annotations
 
 import ctypes as C
+import functools
 from dataclasses import dataclass, field
 
 import numpy as np
 
-from . import _lib as L
+from . import _args as A, _lib as L
 
 MAX_LABELS = 64
-DER_SEGMENT_DTYPE = np.dtype([("label", np.int32), ("reserved", np.int32), ("start", np.float64), ("end", np.float64)])
-DER_COUNTS_DTYPE = np.dtype([("frames", np.int64), ("miss", np.int64), ("false_alarm", np.int64), ("confusion", np.int64), ("ref", np.int64),
-                             ("ref_labels", np.int32), ("hyp_labels", np.int32)])
+DER_SEGMENT_DTYPE, DER_COUNTS_DTYPE = np.dtype(L.DerSegment), np.dtype(L.DerCounts)
 
 
 @dataclass(frozen=True)
@@ -80,8 +79,7 @@ def index_labels(segments):
     return labels, arr
 
 
-def _invalid(detail: str):
-    return L.FluidAudioHipError(L.INVALID_ARGUMENT, "compute_der", detail)
+_invalid = functools.partial(A.invalid, "compute_der")
 
 
 def _check(frame_step, collar, sides):
@@ -106,10 +104,8 @@ def compute_der_batch(pairs, frame_step: float = 0.01, collar: float = 0.0, ctx:
     if n == 0:
         return []
     ctx = ctx or L.default_context()
-    ref = np.concatenate([r[1] for r, _ in sides])
-    hyp = np.concatenate([h[1] for _, h in sides])
-    ref_range = np.concatenate([[0], np.cumsum([r[1].size for r, _ in sides])]).astype(np.int64)
-    hyp_range = np.concatenate([[0], np.cumsum([h[1].size for _, h in sides])]).astype(np.int64)
+    ref, ref_range = A.ragged([r[1] for r, _ in sides], None, DER_SEGMENT_DTYPE)
+    hyp, hyp_range = A.ragged([h[1] for _, h in sides], None, DER_SEGMENT_DTYPE)
     map_range = np.concatenate([[0], np.cumsum([len(h[0]) for _, h in sides])]).astype(np.int64)
     ov_range = np.concatenate([[0], np.cumsum([len(h[0]) * len(r[0]) for r, h in sides])]).astype(np.int64)
     counts = np.zeros(n, DER_COUNTS_DTYPE)

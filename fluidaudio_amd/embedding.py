@@ -12,11 +12,10 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import _lib as L
-from .reconstruct import SegmentationOutput, _placed
+from . import _args as A, _lib as L
+from .reconstruct import SegmentationOutput
 
-RECORD_DTYPE = np.dtype([("chunk_index", np.int32), ("speaker_index", np.int32), ("start_frame", np.int32), ("end_frame", np.int32),
-                         ("start_time", np.float64), ("end_time", np.float64)])   # fa_export_embedding
+RECORD_DTYPE = np.dtype(L.ExportEmbedding)
 
 
 @dataclass
@@ -93,12 +92,11 @@ class EmbeddingPlan:
     def windows(self, batch: int, audio):
         """The fbank inputs of one batch: a torch CUDA tensor [windows, samples_per_window] = audio[start : start + S] then zeros.
         audio: a torch CUDA fp32 tensor on the plan's device (the whole recording)."""
-        import torch
         w = self.batch_windows(batch)
-        x, on_device = _placed(audio, self.ctx)
+        x, on_device = A.placed(audio, self.ctx)
         if not on_device:
             raise ValueError("EmbeddingPlan.windows needs the audio as a torch CUDA tensor")
-        out = torch.empty((len(w), self.samples_per_window), dtype=torch.float32, device=x.device)
+        out = A.beside(x, (len(w), self.samples_per_window), "float32", torch_empty=True)
         starts = np.ascontiguousarray(self.window_start[w.start:w.stop], np.int64)
         with self.ctx.torch_ordered():
             self.ctx.check(L.lib().fa_embedding_windows_dev(self.ctx.handle, x.data_ptr(), x.numel(), starts.ctypes.data if starts.size else None,
@@ -113,7 +111,7 @@ def plan_embeddings(segmentation: SegmentationOutput, total_samples: int, config
     on the device, ordered against torch's current stream)."""
     cfg = config or EmbeddingConfig()
     ctx = ctx or L.default_context()
-    w, on_device = _placed(segmentation.speaker_weights, ctx)
+    w, on_device = A.placed(segmentation.speaker_weights, ctx)
     nc, nf, ns = (int(v) for v in w.shape)
     cap = nc * ns
     offs = np.ascontiguousarray([] if segmentation.chunk_offsets is None else segmentation.chunk_offsets, np.float64)
@@ -123,22 +121,13 @@ def plan_embeddings(segmentation: SegmentationOutput, total_samples: int, config
     W = int(cfg.weight_frames)
     info = L.EmbeddingInfo()
     c = cfg.c_config(segmentation.frame_duration)
-    if on_device:
-        import torch
-        rows = torch.empty((max(cap, 1), W), dtype=torch.float32, device=w.device)
-        mrows = torch.empty((max(cap, 1), nf), dtype=torch.float32, device=w.device) if mask_rows else None
-        with ctx.torch_ordered():
-            st = L.lib().fa_embedding_plan_dev(ctx.handle, C.byref(c), w.data_ptr(), nc, nf, ns, offs.ctypes.data if offs.size else None, offs.size,
-                                               int(total_samples), recs.ctypes.data, roj.ctypes.data, wor.ctypes.data, wst.ctypes.data, wch.ctypes.data,
-                                               rows.data_ptr(), mrows.data_ptr() if mrows is not None else None, C.byref(info))
-        ctx.check(st, "fa_embedding_plan_dev")
-    else:
-        rows = np.zeros((max(cap, 1), W), np.float32)
-        mrows = np.zeros((max(cap, 1), nf), np.float32) if mask_rows else None
-        st = L.lib().fa_embedding_plan(ctx.handle, C.byref(c), w.ctypes.data, nc, nf, ns, offs.ctypes.data if offs.size else None, offs.size,
-                                       int(total_samples), recs.ctypes.data, roj.ctypes.data, wor.ctypes.data, wst.ctypes.data, wch.ctypes.data,
-                                       rows.ctypes.data, mrows.ctypes.data if mrows is not None else None, C.byref(info))
-        ctx.check(st, "fa_embedding_plan")
+    rows = A.beside(w, (max(cap, 1), W), "float32", torch_empty=True)
+    mrows = A.beside(w, (max(cap, 1), nf), "float32", torch_empty=True) if mask_rows else None
+    name = "fa_embedding_plan_dev" if on_device else "fa_embedding_plan"
+    with ctx.torch_ordered(on_device):
+        st = getattr(L.lib(), name)(ctx.handle, C.byref(c), A.ptr(w), nc, nf, ns, offs.ctypes.data if offs.size else None, offs.size, int(total_samples),
+                                    recs.ctypes.data, roj.ctypes.data, wor.ctypes.data, wst.ctypes.data, wch.ctypes.data, A.ptr(rows), A.ptr(mrows), C.byref(info))
+    ctx.check(st, name)
     jobs, runs, nw = info.jobs, info.runs, info.planned_chunks
     return EmbeddingPlan(recs[:jobs].copy(), roj[:jobs].copy(), wor[:runs].copy(), wst[:nw].copy(), wch[:nw].copy(), rows[:runs],
                          mrows[:jobs] if mrows is not None else None, info.as_dict(), int(info.samples_per_window), ctx)
@@ -148,19 +137,15 @@ def weight_resample(rows, out_frames: int, ctx: L.Context | None = None):
     """WeightInterpolation.resample2D: rows [n, in_frames] (or one row [in_frames]) -> [n, out_frames]; a torch CUDA tensor stays on the
     device.  An empty input or out_frames 0 gives an empty result (resample's `[]`)."""
     ctx = ctx or L.default_context()
-    x, on_device = _placed(rows, ctx)
+    x, on_device = A.placed(rows, ctx)
     one = x.ndim == 1
     x = x.reshape(1, -1) if one else x
     n, k = int(x.shape[0]), int(x.shape[1])
     m = int(out_frames) if k > 0 else 0
-    if on_device:
-        import torch
-        out = torch.empty((n, max(m, 0)), dtype=torch.float32, device=x.device)
-        with ctx.torch_ordered():
-            ctx.check(L.lib().fa_weight_resample_dev(ctx.handle, x.data_ptr(), n, k, m, out.data_ptr()), "fa_weight_resample_dev")
-    else:
-        out = np.zeros((n, max(m, 0)), np.float32)
-        ctx.check(L.lib().fa_weight_resample(ctx.handle, x.ctypes.data, n, k, m, out.ctypes.data), "fa_weight_resample")
+    out = A.beside(x, (n, max(m, 0)), "float32", torch_empty=True)
+    name = "fa_weight_resample_dev" if on_device else "fa_weight_resample"
+    with ctx.torch_ordered(on_device):
+        ctx.check(getattr(L.lib(), name)(ctx.handle, A.ptr(x), n, k, m, A.ptr(out)), name)
     return out[0] if one else out
 
 
@@ -169,22 +154,15 @@ def span_inputs(audio, spans, config: EmbeddingConfig | None = None, ctx: L.Cont
     audio numpy / CPU tensor -> numpy results; a torch CUDA tensor -> device results.  A span without samples is not ok (zero rows)."""
     cfg = config or EmbeddingConfig()
     ctx = ctx or L.default_context()
-    x, on_device = _placed(audio, ctx)
+    x, on_device = A.placed(audio, ctx)
     sp = np.ascontiguousarray(spans, np.float64).reshape(-1, 2)
     n, spw, W = sp.shape[0], cfg.window_samples, int(cfg.weight_frames)
     stat = np.zeros(max(n, 1), np.int32)
     c = cfg.c_config()
-    if on_device:
-        import torch
-        win = torch.zeros((n, spw), dtype=torch.float32, device=x.device)
-        wts = torch.zeros((n, W), dtype=torch.float32, device=x.device)
-        with ctx.torch_ordered():
-            st = L.lib().fa_embedding_span_inputs_dev(ctx.handle, C.byref(c), x.data_ptr(), x.numel(), sp.ctypes.data if n else None, n,
-                                                      win.data_ptr(), wts.data_ptr(), stat.ctypes.data)
-        ctx.check(st, "fa_embedding_span_inputs_dev")
-    else:
-        win, wts = np.zeros((n, spw), np.float32), np.zeros((n, W), np.float32)
-        st = L.lib().fa_embedding_span_inputs(ctx.handle, C.byref(c), x.ctypes.data, x.size, sp.ctypes.data if n else None, n, win.ctypes.data,
-                                              wts.ctypes.data, stat.ctypes.data)
-        ctx.check(st, "fa_embedding_span_inputs")
+    win, wts = A.beside(x, (n, spw), "float32"), A.beside(x, (n, W), "float32")
+    name = "fa_embedding_span_inputs_dev" if on_device else "fa_embedding_span_inputs"
+    with ctx.torch_ordered(on_device):
+        st = getattr(L.lib(), name)(ctx.handle, C.byref(c), A.ptr(x), x.numel() if on_device else x.size, sp.ctypes.data if n else None, n, A.ptr(win), A.ptr(wts),
+                                    stat.ctypes.data)
+    ctx.check(st, name)
     return win, wts, stat[:n] == L.SUCCESS

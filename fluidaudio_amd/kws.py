@@ -10,13 +10,12 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib as L
+from . import _args as A, _lib as L
 
 WILDCARD = -1
 MAX_TOKENS = 127
 DEFAULT_BLANK_ID = 1024            # ContextBiasingConstants.defaultBlankId
-KWS_DETECTION_DTYPE = np.dtype([("utterance", np.int32), ("keyword", np.int32), ("score", np.float32), ("start_frame", np.int32), ("end_frame", np.int32)])
-KWS_WINDOW_DTYPE = np.dtype([("utterance", np.int32), ("keyword", np.int32), ("start_frame", np.int32), ("end_frame", np.int32)])
+KWS_DETECTION_DTYPE, KWS_WINDOW_DTYPE = np.dtype(L.KwsDetection), np.dtype(L.KwsWindow)
 
 
 def adjusted_threshold(min_score, token_count: int) -> float:
@@ -41,10 +40,9 @@ class _Matrix:
             x = log_probs if log_probs.dim() == 3 else log_probs[None]
             import torch
             assert x.dtype == torch.float32 and x.is_cuda and (x.shape[2] <= 1 or x.stride(2) == 1), "log_probs: float32 device tensor, last dimension contiguous"
-            self.keep, self.ptr = x, C.c_void_p(x.data_ptr())
+            self.keep, self.ptr = x, A.ptr(x)
             self.B, self.T, W = (int(v) for v in x.shape)
-            self.row_stride = int(x.stride(1)) if self.T > 1 else W
-            self.matrix_stride = int(x.stride(0)) if self.B > 1 else self.T * self.row_stride
+            self.matrix_stride, self.row_stride = A.dense_strides(x)
         else:
             x = np.ascontiguousarray(log_probs, np.float32)
             x = x if x.ndim == 3 else x[None]
@@ -78,8 +76,8 @@ def spot_keywords_batch(log_probs, keywords, min_score=None, blank_id: int = DEF
     cap = max(1024, 2 * m.B * K) if capacity is None else int(capacity)
 
     def call(dets):
-        return f(ctx.handle, m.ptr, m.B, m.T, m.V, m.row_stride, m.matrix_stride, None if vf is None else vf.ctypes.data, tok.ctypes.data, off.ctypes.data, K,
-                 None if mins is None else mins.ctypes.data, int(blank_id), 1 if merge_overlap else 0, dets.ctypes.data, dets.size, C.byref(n), counts.ctypes.data)
+        return f(ctx.handle, m.ptr, m.B, m.T, m.V, m.row_stride, m.matrix_stride, A.ptr(vf), tok.ctypes.data, off.ctypes.data, K,
+                 A.ptr(mins), int(blank_id), 1 if merge_overlap else 0, dets.ctypes.data, dets.size, C.byref(n), counts.ctypes.data)
     with ctx.torch_ordered(order and m.device):
         dets = np.zeros(max(cap, 1), KWS_DETECTION_DTYPE)
         st = call(dets[:cap])
@@ -104,6 +102,6 @@ def score_windows(log_probs, keywords, windows, blank_id: int = DEFAULT_BLANK_ID
     out = np.zeros(max(len(windows), 1), KWS_DETECTION_DTYPE)
     f = L.lib().fa_ctc_kws_score_windows_dev if m.device else L.lib().fa_ctc_kws_score_windows
     with ctx.torch_ordered(order and m.device):
-        ctx.check(f(ctx.handle, m.ptr, m.B, m.T, m.V, m.row_stride, m.matrix_stride, None if vf is None else vf.ctypes.data,
+        ctx.check(f(ctx.handle, m.ptr, m.B, m.T, m.V, m.row_stride, m.matrix_stride, A.ptr(vf),
                     tok.ctypes.data, off.ctypes.data, len(keywords), win.ctypes.data, len(windows), int(blank_id), out.ctypes.data), f.__name__)
     return out[:len(windows)].copy()

@@ -14,13 +14,11 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from . import _lib as L
+from . import _args as A, _lib as L
 
 EMBEDDING_SIZE = 256   # SpeakerManager.embeddingSize
 SPEAKER_KINDS = ("SKIPPED", "UPDATED", "DURATION_ONLY", "LOW_ENERGY", "CREATED", "TOO_SHORT", "INVALID", "FULL")   # FA_SPEAKER_*
-SPEAKER_ASSIGNMENT_DTYPE = np.dtype([("id", np.int32), ("slot", np.int32), ("kind", np.int32), ("distance", np.float32)])   # fa_speaker_assignment
-SPEAKER_PAIR_DTYPE = np.dtype([("source_id", np.int32), ("destination_id", np.int32), ("source_slot", np.int32), ("destination_slot", np.int32),
-                               ("distance", np.float32)])   # fa_speaker_pair
+SPEAKER_ASSIGNMENT_DTYPE, SPEAKER_PAIR_DTYPE = np.dtype(L.SpeakerAssignment), np.dtype(L.SpeakerPair)
 
 
 @dataclass
@@ -51,9 +49,7 @@ class Speaker:  # the fields of Speaker the database keeps; raw_embeddings oldes
     slot: int = -1
 
 
-ONLINE_RUN_DTYPE = np.dtype([("stream", np.int32), ("chunk", np.int32), ("local_speaker", np.int32)])   # fa_online_run
-ONLINE_SEGMENT_DTYPE = np.dtype([("stream", np.int32), ("chunk", np.int32), ("local_speaker", np.int32), ("id", np.int32), ("start_frame", np.int32),
-                                 ("end_frame", np.int32), ("start", np.float32), ("end", np.float32), ("quality", np.float32)])   # fa_online_segment
+ONLINE_RUN_DTYPE, ONLINE_SEGMENT_DTYPE = np.dtype(L.OnlineRun), np.dtype(L.OnlineSegment)
 ONLINE_PACK_ZERO_TAIL, ONLINE_PACK_REPEAT = 0, 1
 
 
@@ -94,10 +90,6 @@ def validate_embedding(embedding, min_magnitude: float = 0.1) -> bool:
     return e.shape == (EMBEDDING_SIZE,) and bool(L.lib().fa_speaker_validate_embedding(e.ctypes.data, float(min_magnitude)))
 
 
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 class SpeakerDatabase:
     """fa_speaker_db: `streams` independent speaker tables on the context's device."""
 
@@ -122,11 +114,10 @@ class SpeakerDatabase:
 
     def _rows(self, x, per=None):
         """[streams, per, 256] float32 on the device: a CUDA tensor as it is, anything else copied there."""
-        import torch
-        if not (isinstance(x, torch.Tensor) and x.is_cuda):
-            x = torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(f"cuda:{self.ctx.device}")
+        if not (hasattr(x, "data_ptr") and x.is_cuda):
+            x = A.to_device(x, np.float32, f"cuda:{self.ctx.device}")
         assert x.device.index == self.ctx.device, "speaker database: the embeddings live on another device than the context"
-        assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 3 and x.shape[0] == self.streams and x.shape[2] == EMBEDDING_SIZE, \
+        assert A.is_dev(x, "float32", 3) and x.shape[0] == self.streams and x.shape[2] == EMBEDDING_SIZE, \
             f"speaker database: embeddings must be contiguous float32 [{self.streams}, per, {EMBEDDING_SIZE}], not {tuple(x.shape)}"
         assert per is None or x.shape[1] == per
         return x
@@ -142,23 +133,17 @@ class SpeakerDatabase:
                                                     and tuple(t.shape) == (self.streams, per)), f"speaker database: {what} must be contiguous {dt} [{self.streams}, {per}] beside the embeddings"
         out = torch.zeros((self.streams, per, 4), dtype=torch.int32, device=d_embeddings.device)
         with self.ctx.torch_ordered():
-            self.ctx.check(L.lib().fa_speaker_db_assign_dev(self.ctx.handle, self._h, _ptr(d_embeddings), _ptr(d_durations), _ptr(d_skip), per, int(tick),
-                                                            _ptr(out)), "fa_speaker_db_assign_dev")
+            self.ctx.check(L.lib().fa_speaker_db_assign_dev(self.ctx.handle, self._h, A.ptr(d_embeddings), A.ptr(d_durations), A.ptr(d_skip), per, int(tick),
+                                                            A.ptr(out)), "fa_speaker_db_assign_dev")
         return out
 
     def assign(self, embeddings, durations, skip=None, tick: int = 0) -> np.ndarray:
         """assignSpeaker for [streams, per] items, in index order within a stream: records of SPEAKER_ASSIGNMENT_DTYPE [streams, per]."""
-        import torch
         emb = self._rows(embeddings)
         per = emb.shape[1]
-        dev = emb.device
 
         def vec(v, dt):
-            if v is None:
-                return None
-            if isinstance(v, torch.Tensor) and v.is_cuda:
-                return v
-            return torch.from_numpy(np.ascontiguousarray(v, dt).reshape(self.streams, per)).to(dev)
+            return v if hasattr(v, "data_ptr") and v.is_cuda else A.to_device(v, dt, emb.device, (self.streams, per))
 
         out = self.assign_dev(emb, vec(durations, np.float32), vec(skip, np.int32), tick)
         self.ctx.synchronize()
@@ -167,13 +152,11 @@ class SpeakerDatabase:
     def distances(self, queries):
         """findSpeaker's distances: the queries as they are (not normalised) against every slot -> (float32 [streams, per, max_speakers], +inf
         on a free slot; int32 [streams, per] the closest slot, -1: none)."""
-        import torch
         q = self._rows(queries)
         per = q.shape[1]
-        dist = torch.zeros((self.streams, per, self.config.max_speakers), dtype=torch.float32, device=q.device)
-        best = torch.zeros((self.streams, per), dtype=torch.int32, device=q.device)
+        dist, best = A.beside(q, (self.streams, per, self.config.max_speakers), "float32"), A.beside(q, (self.streams, per), "int32")
         with self.ctx.torch_ordered():
-            self.ctx.check(L.lib().fa_speaker_db_distances_dev(self.ctx.handle, self._h, _ptr(q), per, _ptr(dist), _ptr(best)), "fa_speaker_db_distances_dev")
+            self.ctx.check(L.lib().fa_speaker_db_distances_dev(self.ctx.handle, self._h, A.ptr(q), per, A.ptr(dist), A.ptr(best)), "fa_speaker_db_distances_dev")
         self.ctx.synchronize()
         return dist.cpu().numpy(), best.cpu().numpy()
 
@@ -208,8 +191,8 @@ class SpeakerDatabase:
         counts = torch.zeros(self.streams, dtype=torch.int32, device=dev)
         thr = float(self.config.speaker_threshold if speaker_threshold is None else speaker_threshold)
         with self.ctx.torch_ordered():
-            self.ctx.check(L.lib().fa_speaker_db_mergeable_pairs_dev(self.ctx.handle, self._h, thr, 1 if exclude_if_both_permanent else 0, _ptr(pairs), cap,
-                                                                     _ptr(counts)), "fa_speaker_db_mergeable_pairs_dev")
+            self.ctx.check(L.lib().fa_speaker_db_mergeable_pairs_dev(self.ctx.handle, self._h, thr, 1 if exclude_if_both_permanent else 0, A.ptr(pairs), cap,
+                                                                     A.ptr(counts)), "fa_speaker_db_mergeable_pairs_dev")
         self.ctx.synchronize()
         rec, n = pairs.cpu().numpy().view(SPEAKER_PAIR_DTYPE).reshape(self.streams, cap), counts.cpu().numpy()
         return [rec[b, :n[b]].copy() for b in range(self.streams)]
@@ -272,8 +255,7 @@ class SpeakerDatabase:
 
 
 def _dev_f32(x, shape, what, device):
-    import torch
-    assert isinstance(x, torch.Tensor) and x.is_cuda and x.device.index == device and x.dtype == torch.float32 and x.is_contiguous() and tuple(x.shape) == tuple(shape), \
+    assert A.is_dev(x, "float32") and x.device.index == device and tuple(x.shape) == tuple(shape), \
         f"{what} must be a contiguous float32 CUDA tensor {tuple(shape)} on the context's device"
     return x
 
@@ -281,38 +263,33 @@ def _dev_f32(x, shape, what, device):
 def chunk_plan(d_weights, samples_in_chunk=None, config: OnlineChunkConfig | None = None, ctx: L.Context | None = None):
     """fa_online_chunk_plan on d_weights [streams, chunks, frames, 3] (CUDA): activities [streams, chunks, 3] and the model's mask rows
     [runs, frames] as CUDA tensors, the run list as ONLINE_RUN_DTYPE records.  samples_in_chunk: ints [streams, chunks] or None."""
-    import torch
     ctx = ctx or L.default_context()
     cfg = config or OnlineChunkConfig()
     assert d_weights.dim() == 4, "chunk_plan: weights [streams, chunks, frames, 3]"
     B, Cn = d_weights.shape[:2]
     _dev_f32(d_weights, (B, Cn, cfg.frames, 3), "chunk_plan: weights", ctx.device)
     dev = d_weights.device
-    d_samples = None if samples_in_chunk is None else torch.from_numpy(np.ascontiguousarray(samples_in_chunk, np.int32).reshape(B, Cn)).to(dev)
+    d_samples = A.to_device(samples_in_chunk, np.int32, dev, (B, Cn))
     cap = B * Cn * 3
-    act = torch.zeros((B, Cn, 3), dtype=torch.float32, device=dev)
-    runs = torch.zeros((cap, 3), dtype=torch.int32, device=dev)
-    rows = torch.zeros((cap, cfg.frames), dtype=torch.float32, device=dev)
+    act, runs, rows = A.beside(d_weights, (B, Cn, 3), "float32"), A.beside(d_weights, (cap, 3), "int32"), A.beside(d_weights, (cap, cfg.frames), "float32")
     n, c = C.c_int32(), cfg.c()
     with ctx.torch_ordered():
-        ctx.check(L.lib().fa_online_chunk_plan(ctx.handle, C.byref(c), _ptr(d_weights), _ptr(d_samples), B, Cn, _ptr(act), _ptr(runs), cap, C.byref(n), _ptr(rows)),
+        ctx.check(L.lib().fa_online_chunk_plan(ctx.handle, C.byref(c), A.ptr(d_weights), A.ptr(d_samples), B, Cn, A.ptr(act), A.ptr(runs), cap, C.byref(n), A.ptr(rows)),
                   "fa_online_chunk_plan")
     return act, runs[:n.value].cpu().numpy().view(ONLINE_RUN_DTYPE).reshape(-1), rows[:n.value]
 
 
 def pack_waveforms(d_audio, offsets, lengths, chunk_samples: int = 160000, mode: int = ONLINE_PACK_ZERO_TAIL, ctx: L.Context | None = None):
     """fa_online_pack_waveforms_dev: rows [len(offsets), chunk_samples] (CUDA) from the flat CUDA tensor d_audio."""
-    import torch
     ctx = ctx or L.default_context()
     offsets, lengths = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(lengths, np.int32)
-    assert isinstance(d_audio, torch.Tensor) and d_audio.is_cuda and d_audio.device.index == ctx.device and d_audio.dtype == torch.float32 and d_audio.is_contiguous() \
-        and d_audio.dim() == 1, "pack_waveforms: a flat contiguous float32 CUDA tensor on the context's device"
+    assert A.is_dev(d_audio, "float32", 1) and d_audio.device.index == ctx.device, "pack_waveforms: a flat contiguous float32 CUDA tensor on the context's device"
     assert offsets.shape == lengths.shape and offsets.ndim == 1 and offsets.size >= 1 and bool(np.all(lengths >= 0)) and bool(np.all(offsets >= 0)) and \
         bool(np.all(offsets + np.minimum(lengths, chunk_samples) <= d_audio.numel())), "pack_waveforms: a row reaches outside the audio"
-    out = torch.zeros((offsets.size, int(chunk_samples)), dtype=torch.float32, device=d_audio.device)
-    d_off, d_len = torch.from_numpy(offsets).to(d_audio.device), torch.from_numpy(lengths).to(d_audio.device)
+    out = A.beside(d_audio, (offsets.size, int(chunk_samples)), "float32")
+    d_off, d_len = A.to_device(offsets, np.int64, d_audio.device), A.to_device(lengths, np.int32, d_audio.device)
     with ctx.torch_ordered():
-        ctx.check(L.lib().fa_online_pack_waveforms_dev(ctx.handle, _ptr(d_audio), _ptr(d_off), _ptr(d_len), offsets.size, int(chunk_samples), int(mode), _ptr(out)),
+        ctx.check(L.lib().fa_online_pack_waveforms_dev(ctx.handle, A.ptr(d_audio), A.ptr(d_off), A.ptr(d_len), offsets.size, int(chunk_samples), int(mode), A.ptr(out)),
                   "fa_online_pack_waveforms_dev")
     return out
 
@@ -322,7 +299,6 @@ def chunk_finish(db: SpeakerDatabase, d_weights, d_activities, d_embeddings, chu
     """fa_online_chunk_finish_dev: the gate, the assignment into db and the timed segments of [streams, chunks] chunks.  Returns (segments as
     ONLINE_SEGMENT_DTYPE records, assignments SPEAKER_ASSIGNMENT_DTYPE [streams, chunks, 3], chunk_counts [streams, chunks]).  With a
     capacity below the segments' count FluidAudioHipError(OUTPUT_TOO_SMALL) carries the count as .count."""
-    import torch
     cfg = config or OnlineChunkConfig()
     ctx = db.ctx
     assert d_weights.dim() == 4, "chunk_finish: weights [streams, chunks, frames, 3]"
@@ -335,11 +311,11 @@ def chunk_finish(db: SpeakerDatabase, d_weights, d_activities, d_embeddings, chu
     cap = B * Cn * 3 * ((cfg.frames + 1) // 2) if capacity is None else int(capacity)
     seg = np.zeros(max(cap, 1), ONLINE_SEGMENT_DTYPE)
     counts = np.zeros((B, Cn), np.int32)
-    assign = torch.zeros((B, Cn, 3, 4), dtype=torch.int32, device=d_weights.device)
+    assign = A.beside(d_weights, (B, Cn, 3, 4), "int32")
     n, c = C.c_int64(), cfg.c()
     with ctx.torch_ordered():
-        st = L.lib().fa_online_chunk_finish_dev(ctx.handle, C.byref(c), db._h, _ptr(d_weights), _ptr(d_activities), _ptr(d_embeddings), off.ctypes.data, Cn, int(tick),
-                                                seg.ctypes.data, cap, C.byref(n), counts.ctypes.data, _ptr(assign))
+        st = L.lib().fa_online_chunk_finish_dev(ctx.handle, C.byref(c), db._h, A.ptr(d_weights), A.ptr(d_activities), A.ptr(d_embeddings), off.ctypes.data, Cn, int(tick),
+                                                seg.ctypes.data, cap, C.byref(n), counts.ctypes.data, A.ptr(assign))
     if st != L.SUCCESS:
         err = L.FluidAudioHipError(st, "fa_online_chunk_finish_dev", ctx.last_error())
         err.count = int(n.value)

@@ -11,9 +11,9 @@ from collections import namedtuple
 
 import numpy as np
 
-from . import _lib as L
+from . import _args as A, _lib as L
 
-PARAFORMER_SPAN_DTYPE = np.dtype([("utterance", np.int32), ("token_index", np.int32), ("start", np.float64), ("end", np.float64)])
+PARAFORMER_SPAN_DTYPE = np.dtype(L.ParaformerSpan)
 CifResult = namedtuple("CifResult", "ac token_counts fire_counts fire_frames enc_packed")
 TimestampedSegment = namedtuple("TimestampedSegment", "startTime endTime text")   # ParaformerManager.swift:12-22
 WORD_BOUNDARY = "▁"                                                           # ASRConstants.sentencePieceWordBoundary
@@ -34,10 +34,6 @@ class ParaformerConfig:
         return next((b for b in cls.encoderBuckets if b >= frames), cls.encoderBuckets[-1])
 
 
-def _invalid(where: str, detail: str):
-    return L.FluidAudioHipError(L.INVALID_ARGUMENT, where, detail)
-
-
 def default_config() -> L.ParaformerCifConfig:
     cfg = L.ParaformerCifConfig()
     L.lib().fa_paraformer_cif_default_config(C.byref(cfg))
@@ -49,12 +45,28 @@ def _valid(valid_frames, batch, where):
         return None
     v = np.ascontiguousarray(valid_frames, np.int32)
     if v.shape != (batch,):
-        raise _invalid(where, "valid_frames holds one entry per utterance")
+        raise A.invalid(where, "valid_frames holds one entry per utterance")
     return v
 
 
-def _ptr(a):
-    return None if a is None else a.ctypes.data
+def _rows_on_device(t, dtype_names, ndim):
+    """A torch tensor of one of the dtypes and of that rank on a CUDA device whose rows are contiguous: any row and matrix stride."""
+    return any(A.is_dev(t, name, ndim, contiguous=False) for name in dtype_names) and (t.shape[-1] <= 1 or t.stride(-1) == 1)
+
+
+def _run_cif(where, ctx, cfg, enc, dtype, dim, matrix_stride, row_stride, alphas, alpha_stride, valid, pack_enc, ordered) -> CifResult:
+    """The body of cif_batch and cif_batch_dev: enc and alphas are numpy arrays or device tensors, addressed by the strides; ac and
+    enc_packed come back beside them."""
+    B, T = enc.shape[:2]
+    ac = A.beside(enc, (B, cfg.max_tokens, max(dim, 0)), "float32", torch_empty=True)
+    packed = A.beside(enc, (B, cfg.enc_frames, max(dim, 0)), "float32", torch_empty=True) if pack_enc else None
+    counts, fires, frames = np.zeros(B, np.int32), np.zeros(B, np.int32), np.full((B, T + 1), -1, np.int32)
+    if B:
+        ctx = A.context_beside(ctx, enc)
+        with ctx.torch_ordered(ordered):
+            ctx.check(getattr(L.lib(), where)(ctx.handle, C.byref(cfg), A.ptr(enc), dtype, B, T, dim, row_stride, matrix_stride, A.ptr(alphas), alpha_stride, A.ptr(valid),
+                                              A.ptr(ac), A.ptr(packed), counts.ctypes.data, fires.ctypes.data, frames.ctypes.data), where)
+    return CifResult(ac, counts, fires, frames, packed)
 
 
 def cif_batch(enc, alphas, valid_frames=None, dim: int | None = None, config: L.ParaformerCifConfig | None = None, pack_enc: bool = False,
@@ -66,24 +78,14 @@ def cif_batch(enc, alphas, valid_frames=None, dim: int | None = None, config: L.
     where = "fa_paraformer_cif"
     enc = np.ascontiguousarray(enc)
     if enc.ndim != 3 or enc.dtype not in (np.float32, np.float16):
-        raise _invalid(where, "enc is [B, T, S] float32 or float16")
+        raise A.invalid(where, "enc is [B, T, S] float32 or float16")
     alphas = np.ascontiguousarray(alphas, np.float32)
     B, T, S = enc.shape
-    dim = S if dim is None else int(dim)
     if alphas.ndim != 2 or alphas.shape[0] != B or alphas.shape[1] < T:
-        raise _invalid(where, "alphas is [B, >= T]")
+        raise A.invalid(where, "alphas is [B, >= T]")
     cfg = config or default_config()
-    valid = _valid(valid_frames, B, where)
-    ac = np.zeros((B, cfg.max_tokens, max(dim, 0)), np.float32)
-    packed = np.zeros((B, cfg.enc_frames, max(dim, 0)), np.float32) if pack_enc else None
-    counts, fires, frames = np.zeros(B, np.int32), np.zeros(B, np.int32), np.full((B, T + 1), -1, np.int32)
-    if B == 0:
-        return CifResult(ac, counts, fires, frames, packed)
-    ctx = ctx or L.default_context()
-    ctx.check(L.lib().fa_paraformer_cif(ctx.handle, C.byref(cfg), enc.ctypes.data, L.DTYPE_F16 if enc.dtype == np.float16 else L.DTYPE_F32, B, T, dim, S, T * S,
-                                        alphas.ctypes.data, alphas.shape[1], _ptr(valid), ac.ctypes.data, _ptr(packed), counts.ctypes.data, fires.ctypes.data,
-                                        frames.ctypes.data), where)
-    return CifResult(ac, counts, fires, frames, packed)
+    return _run_cif(where, ctx, cfg, enc, L.DTYPE_F16 if enc.dtype == np.float16 else L.DTYPE_F32, S if dim is None else int(dim), T * S, S, alphas, alphas.shape[1],
+                    _valid(valid_frames, B, where), pack_enc, False)
 
 
 def cif_batch_dev(enc, alphas, valid_frames=None, dim: int | None = None, config: L.ParaformerCifConfig | None = None, pack_enc: bool = False,
@@ -91,32 +93,18 @@ def cif_batch_dev(enc, alphas, valid_frames=None, dim: int | None = None, config
     """fa_paraformer_cif_dev: enc [B, T, S] (float32 or float16, rows contiguous: any row and matrix stride) and alphas [B, A] (float32,
     rows contiguous) are torch tensors on the context's device, as the encoder and the CifAlphas model left them; ac and enc_packed come
     back as torch tensors on that device, the counts and the fire frames as numpy arrays."""
-    import torch
     where = "fa_paraformer_cif_dev"
-    if not (isinstance(enc, torch.Tensor) and enc.is_cuda and enc.dim() == 3 and enc.dtype in (torch.float32, torch.float16) and (enc.shape[2] <= 1 or enc.stride(2) == 1)):
-        raise _invalid(where, "enc is a [B, T, S] float32 or float16 tensor on the device with contiguous rows")
-    if not (isinstance(alphas, torch.Tensor) and alphas.is_cuda and alphas.dim() == 2 and alphas.dtype == torch.float32 and (alphas.shape[1] <= 1 or alphas.stride(1) == 1)):
-        raise _invalid(where, "alphas is a [B, A] float32 tensor on the device with contiguous rows")
+    if not _rows_on_device(enc, ("float32", "float16"), 3):
+        raise A.invalid(where, "enc is a [B, T, S] float32 or float16 tensor on the device with contiguous rows")
+    if not _rows_on_device(alphas, ("float32",), 2):
+        raise A.invalid(where, "alphas is a [B, A] float32 tensor on the device with contiguous rows")
     B, T, S = enc.shape
-    dim = S if dim is None else int(dim)
     if alphas.shape[0] != B or alphas.shape[1] < T:
-        raise _invalid(where, "alphas is [B, >= T]")
+        raise A.invalid(where, "alphas is [B, >= T]")
     cfg = config or default_config()
-    valid = _valid(valid_frames, B, where)
-    ac = torch.empty((B, cfg.max_tokens, max(dim, 0)), dtype=torch.float32, device=enc.device)
-    packed = torch.empty((B, cfg.enc_frames, max(dim, 0)), dtype=torch.float32, device=enc.device) if pack_enc else None
-    counts, fires, frames = np.zeros(B, np.int32), np.zeros(B, np.int32), np.full((B, T + 1), -1, np.int32)
-    if B == 0:
-        return CifResult(ac, counts, fires, frames, packed)
-    ctx = ctx or L.default_context(enc.device.index)
-    row_stride = enc.stride(1) if T > 1 else max(S, 1)
-    matrix_stride = enc.stride(0) if B > 1 else T * row_stride
-    alpha_stride = alphas.stride(0) if B > 1 else alphas.shape[1]
-    with ctx.torch_ordered(ordered):
-        ctx.check(L.lib().fa_paraformer_cif_dev(ctx.handle, C.byref(cfg), enc.data_ptr(), L.DTYPE_F16 if enc.dtype == torch.float16 else L.DTYPE_F32, B, T, dim,
-                                                row_stride, matrix_stride, alphas.data_ptr(), alpha_stride, _ptr(valid), ac.data_ptr(),
-                                                None if packed is None else packed.data_ptr(), counts.ctypes.data, fires.ctypes.data, frames.ctypes.data), where)
-    return CifResult(ac, counts, fires, frames, packed)
+    dtype = L.DTYPE_F16 if A.is_dev(enc, "float16", contiguous=False) else L.DTYPE_F32
+    return _run_cif(where, ctx, cfg, enc, dtype, S if dim is None else int(dim), *A.dense_strides(enc, max(S, 1)), alphas, *A.dense_strides(alphas),
+                    _valid(valid_frames, B, where), pack_enc, ordered)
 
 
 def keep_table(vocabulary: dict, size: int | None = None) -> np.ndarray:
@@ -136,7 +124,7 @@ def _stamp_host_args(valid_frames, token_counts, keep, audio_offsets, B, where):
     keep = np.ascontiguousarray(keep, np.uint8)
     audio_offsets = np.ascontiguousarray(audio_offsets, np.int64)
     if token_counts.shape != (B,) or keep.ndim != 1 or audio_offsets.shape != (B + 1,):
-        raise _invalid(where, "token_counts [B], keep [vocab] and audio_offsets [B + 1] are required")
+        raise A.invalid(where, "token_counts [B], keep [vocab] and audio_offsets [B + 1] are required")
     return valid, token_counts, keep, audio_offsets
 
 
@@ -145,7 +133,7 @@ def _run_stamps(f, where, ctx, cfg, alphas_ptr, alpha_stride, B, T, valid, ids_p
     cap = int(token_counts.sum()) if capacity is None else int(capacity)   # an utterance yields at most one span per token
     spans = np.zeros(cap, PARAFORMER_SPAN_DTYPE)
     count = C.c_int64(0)
-    ctx.check(f(ctx.handle, C.byref(cfg), alphas_ptr, alpha_stride, B, T, _ptr(valid), ids_ptr, token_counts.ctypes.data, keep.ctypes.data, keep.size, audio_ptr,
+    ctx.check(f(ctx.handle, C.byref(cfg), alphas_ptr, alpha_stride, B, T, A.ptr(valid), ids_ptr, token_counts.ctypes.data, keep.ctypes.data, keep.size, audio_ptr,
                 audio_offsets.ctypes.data, spans.ctypes.data, cap, C.byref(count), utt.ctypes.data), where)
     return spans[:count.value], utt
 
@@ -161,16 +149,12 @@ def timestamps_batch(alphas, valid_frames, token_ids, token_counts, keep, audio,
     token_ids = np.ascontiguousarray(token_ids, np.int32)
     cfg = config or default_config()
     if alphas.ndim != 2 or token_ids.ndim != 2 or token_ids.shape != (alphas.shape[0], cfg.max_tokens):
-        raise _invalid(where, "alphas is [B, T] and token_ids [B, max_tokens]")
+        raise A.invalid(where, "alphas is [B, T] and token_ids [B, max_tokens]")
     B, T = alphas.shape
-    if audio_offsets is None:
-        audio = [np.ascontiguousarray(x, np.float32).reshape(-1) for x in audio]
-        audio_offsets = np.concatenate([[0], np.cumsum([x.size for x in audio])]).astype(np.int64)
-        audio = np.concatenate(audio) if audio else np.zeros(0, np.float32)
-    audio = np.ascontiguousarray(audio, np.float32)
+    audio, audio_offsets = A.ragged(audio, audio_offsets, np.float32)      # the offsets' shape is _stamp_host_args' to refuse
     valid, token_counts, keep, audio_offsets = _stamp_host_args(valid_frames, token_counts, keep, audio_offsets, B, where)
     if audio.ndim != 1 or (B > 0 and audio_offsets[-1] > audio.size):
-        raise _invalid(where, "audio_offsets end beyond the samples")
+        raise A.invalid(where, "audio_offsets end beyond the samples")
     if B == 0:
         return np.zeros(0, PARAFORMER_SPAN_DTYPE), np.zeros(0, np.int64)
     ctx = ctx or L.default_context()
@@ -182,26 +166,24 @@ def timestamps_batch_dev(alphas, valid_frames, token_ids, token_counts, keep, au
                          capacity: int | None = None, ctx: L.Context | None = None, ordered: bool = True):
     """fa_paraformer_timestamps_dev: alphas [B, A] float32, token_ids [B, max_tokens] int32 (contiguous) and audio (one-dimensional
     float32, the utterances one after the other) are torch tensors on the context's device; the rest are host arrays."""
-    import torch
     where = "fa_paraformer_timestamps_dev"
     cfg = config or default_config()
-    ok = lambda t, dt, nd: isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.dim() == nd   # noqa: E731
-    if not (ok(alphas, torch.float32, 2) and (alphas.shape[1] <= 1 or alphas.stride(1) == 1)):
-        raise _invalid(where, "alphas is a [B, A] float32 tensor on the device with contiguous rows")
+    if not _rows_on_device(alphas, ("float32",), 2):
+        raise A.invalid(where, "alphas is a [B, A] float32 tensor on the device with contiguous rows")
     B, T = alphas.shape
-    if not (ok(token_ids, torch.int32, 2) and token_ids.is_contiguous() and tuple(token_ids.shape) == (B, cfg.max_tokens)):
-        raise _invalid(where, "token_ids is a contiguous [B, max_tokens] int32 tensor on the device")
-    if not (ok(audio, torch.float32, 1) and audio.is_contiguous()):
-        raise _invalid(where, "audio is a contiguous one-dimensional float32 tensor on the device")
+    if not (A.is_dev(token_ids, "int32", 2) and tuple(token_ids.shape) == (B, cfg.max_tokens)):
+        raise A.invalid(where, "token_ids is a contiguous [B, max_tokens] int32 tensor on the device")
+    if not A.is_dev(audio, "float32", 1):
+        raise A.invalid(where, "audio is a contiguous one-dimensional float32 tensor on the device")
     valid, token_counts, keep, audio_offsets = _stamp_host_args(valid_frames, token_counts, keep, audio_offsets, B, where)
     if B > 0 and audio_offsets[-1] > audio.numel():
-        raise _invalid(where, "audio_offsets end beyond the samples")
+        raise A.invalid(where, "audio_offsets end beyond the samples")
     if B == 0:
         return np.zeros(0, PARAFORMER_SPAN_DTYPE), np.zeros(0, np.int64)
     ctx = ctx or L.default_context(alphas.device.index)
     with ctx.torch_ordered(ordered):
-        return _run_stamps(L.lib().fa_paraformer_timestamps_dev, where, ctx, cfg, alphas.data_ptr(), alphas.stride(0) if B > 1 else alphas.shape[1], B, T, valid,
-                           token_ids.data_ptr(), token_counts, keep, audio.data_ptr(), audio_offsets, capacity)
+        return _run_stamps(L.lib().fa_paraformer_timestamps_dev, where, ctx, cfg, alphas.data_ptr(), *A.dense_strides(alphas), B, T, valid, token_ids.data_ptr(),
+                           token_counts, keep, audio.data_ptr(), audio_offsets, capacity)
 
 
 def segments_from_spans(vocabulary: dict, token_ids, spans) -> list:

@@ -12,7 +12,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import _lib as L
+from . import _args as A, _lib as L
 from .formats import RttmSegment, TimedSpeakerSegment
 
 
@@ -53,40 +53,19 @@ class SegmentationOutput:
         return tuple(int(x) for x in self.speaker_weights.shape)
 
 
-def _placed(x, ctx: L.Context):
-    """Where an input goes: a torch CUDA tensor on the context's device -> (contiguous fp32 tensor, True) for a _dev entry; a CPU tensor
-    or any array -> (contiguous fp32 numpy array, False) for the host entry.  A CUDA tensor on another device is refused: its pointer is
-    not valid on the context's device."""
-    if hasattr(x, "data_ptr"):
-        if x.is_cuda:
-            if x.device.index != ctx.device:
-                raise ValueError(f"tensor on {x.device}, context on cuda:{ctx.device}")
-            return x.contiguous().float(), True
-        x = x.detach().float().numpy()
-    return np.ascontiguousarray(x, np.float32), False
-
-
 def powerset_decode(logits, chunk_offsets=None, frame_duration: float = 0.0, log_probs: bool = False, window_duration: float = 10.0,
                     ctx: L.Context | None = None) -> SegmentationOutput:
     """logits [chunks, frames, classes] fp32 (numpy / CPU tensor, or a torch CUDA tensor on ctx's device: the result stays there) -> SegmentationOutput with
     binary per-speaker weights [chunks, frames, 3] and, if asked, the log-probabilities.  frame_duration 0 = window_duration / frames
     (OfflineSegmentationProcessor.swift:286)."""
     ctx = ctx or L.default_context()
-    x, on_device = _placed(logits, ctx)
-    if on_device:
-        import torch
-        nc, nf, k = (int(v) for v in x.shape)
-        w = torch.empty((nc, nf, 3), dtype=torch.float32, device=x.device)
-        lp = torch.empty_like(x) if log_probs else None
-        with ctx.torch_ordered():
-            ctx.check(L.lib().fa_powerset_decode_dev(ctx.handle, x.data_ptr(), nc, nf, k, w.data_ptr(), lp.data_ptr() if lp is not None else None),
-                      "fa_powerset_decode_dev")
-    else:
-        nc, nf, k = x.shape
-        w = np.zeros((nc, nf, 3), np.float32)
-        lp = np.zeros_like(x) if log_probs else None
-        ctx.check(L.lib().fa_powerset_decode(ctx.handle, x.ctypes.data, nc, nf, k, w.ctypes.data, lp.ctypes.data if lp is not None else None),
-                  "fa_powerset_decode")
+    x, on_device = A.placed(logits, ctx)
+    nc, nf, k = (int(v) for v in x.shape)
+    w = A.beside(x, (nc, nf, 3), "float32", torch_empty=True)
+    lp = A.beside(x, (nc, nf, k), "float32", torch_empty=True) if log_probs else None
+    name = "fa_powerset_decode_dev" if on_device else "fa_powerset_decode"
+    with ctx.torch_ordered(on_device):
+        ctx.check(getattr(L.lib(), name)(ctx.handle, A.ptr(x), nc, nf, k, A.ptr(w), A.ptr(lp)), name)
     fd = float(frame_duration) if frame_duration > 0 else (window_duration / nf if nf else 0.0)
     return SegmentationOutput(w, chunk_offsets, fd, lp)
 
@@ -145,9 +124,9 @@ class OfflineReconstruction:
 
     def _call(self, seg: SegmentationOutput, hard, clusters: int, overrides=None, runs_capacity: int = 0, frame_records: bool = False):
         ctx = self.ctx or L.default_context()
-        w, on_device = _placed(seg.speaker_weights, ctx)
+        w, on_device = A.placed(seg.speaker_weights, ctx)
         nc, nf, ns = (int(v) for v in w.shape)
-        wptr = w.data_ptr() if on_device else w.ctypes.data
+        wptr = A.ptr(w)
         offs = np.ascontiguousarray([] if seg.chunk_offsets is None else seg.chunk_offsets, np.float64)
         hard = np.ascontiguousarray(hard, np.int32).reshape(-1)
         assert hard.size == nc * ns, "hard_clusters must be [chunks, speakers]"

@@ -15,7 +15,7 @@ from typing import NamedTuple
 
 import numpy as np
 
-from . import _lib as L
+from . import _args as A, _lib as L
 
 RNNT_BIAS_DEFAULT_BOOST = 4.5   # NemotronVocabularyBias.defaultBoost
 RNNT_BIAS_MAX_BOOST = 6.0       # NemotronVocabularyBias.maxBoost
@@ -141,23 +141,19 @@ def decode_logits(d_logits, vocab_with_blank: int, frames, skip=None, bias: Rnnt
     dev = d_logits.device
     biased = bias is not None and bias.blob.size > 0
     cap = int(bias.tail_cap) if biased else 0
-
-    def vec(v):
-        return None if v is None else torch.as_tensor(np.ascontiguousarray(v, np.int32)).to(dev)
-
-    v_frames, v_skip = vec(frames), vec(skip)
+    v_frames, v_skip = A.to_device(frames, np.int32, dev), A.to_device(skip, np.int32, dev)
     assert v_frames.numel() == B and (v_skip is None or v_skip.numel() == B), "rnnt.decode_logits: one frame count (and skip) per stream"
     d_blob = d_tail = d_len = None
     if biased:
-        d_blob = torch.from_numpy(np.ascontiguousarray(bias.blob, np.int32)).to(dev)
+        d_blob = A.to_device(bias.blob, np.int32, dev)
         h_tail, h_len = np.zeros((B, cap), np.int32), np.zeros(B, np.int32)
         for b, t in enumerate(tails or ()):
             t = np.asarray([] if t is None else t, np.int64)[-cap:]
             h_tail[b, :t.size], h_len[b] = t, t.size
-        d_tail, d_len = torch.from_numpy(h_tail).to(dev), torch.from_numpy(h_len).to(dev)
-    o_tok, o_frame, o_plain = (torch.zeros((B, max_out), dtype=torch.int32, device=dev) for _ in range(3))
-    o_cnt, o_fu, o_eou, o_st = (torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(4))
-    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        d_tail, d_len = A.to_device(h_tail, np.int32, dev), A.to_device(h_len, np.int32, dev)
+    o_tok, o_frame, o_plain = (A.beside(d_logits, (B, max_out), "int32") for _ in range(3))
+    o_cnt, o_fu, o_eou, o_st = (A.beside(d_logits, B, "int32") for _ in range(4))
+    p = A.ptr
     dt = L.DTYPE_F16 if d_logits.dtype == torch.float16 else L.DTYPE_F32
     with ctx.torch_ordered():
         ctx.check(L.lib().fa_rnnt_greedy_logits_dev(ctx.handle, C.byref(cfg), p(d_logits), dt, B, U, T, int(vocab_with_blank), W, p(v_frames), p(v_skip),

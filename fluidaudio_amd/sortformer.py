@@ -12,12 +12,10 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import _lib as L
-from .timeline import (SEGMENT_DTYPE, DiarizerSegment, DiarizerTimeline, DiarizerTimelineConfig, _device_tensor, _lengths, _segments,  # noqa: F401
-                       timeline_segments)
+from . import _args as A, _lib as L
+from .timeline import SEGMENT_DTYPE, DiarizerSegment, DiarizerTimeline, DiarizerTimelineConfig, _lengths, _segments, timeline_segments  # noqa: F401
 
-WINDOW_DTYPE = np.dtype([("recording", np.int32), ("valid_mel", np.int32), ("valid_out", np.int32), ("first", np.int32),
-                         ("mel_start", np.int64), ("g_start", np.int64)])
+WINDOW_DTYPE = np.dtype(L.SortformerWindow)
 
 
 @dataclass
@@ -67,7 +65,7 @@ def pack_windows(d_mel, n_mel_frames, layout: str = "mel_major", config: Offline
     import torch
     config = config or OfflineSortformerConfig()
     ctx = ctx or L.default_context()
-    d_mel = _device_tensor(d_mel, ctx, torch.float32)
+    d_mel = A.device_tensor(d_mel, ctx, torch.float32)
     if d_mel.dim() == 2:
         d_mel = d_mel.unsqueeze(0)
     n = _lengths(n_mel_frames)
@@ -77,8 +75,7 @@ def pack_windows(d_mel, n_mel_frames, layout: str = "mel_major", config: Offline
     frame_stride = int(d_mel.shape[2 if mel_major else 1])
     assert n.size == 0 or int(n.max()) <= frame_stride, "a recording is longer than the mel buffer"
     w = int(offline_windows(n, config)["window_range"][-1])
-    d_out = torch.empty((w, config.mel_features, config.window_mel_frames), dtype=torch.float32, device=d_mel.device)
-    d_len = torch.empty(w, dtype=torch.int32, device=d_mel.device)
+    d_out, d_len = A.beside(d_mel, (w, config.mel_features, config.window_mel_frames), "float32", torch_empty=True), A.beside(d_mel, w, "int32", torch_empty=True)
     cfg = config.c_config()
     with ctx.torch_ordered():
         ctx.check(L.lib().fa_sortformer_pack_windows_dev(ctx.handle, C.byref(cfg), d_mel.data_ptr(),
@@ -94,13 +91,12 @@ def stitch(d_preds, n_mel_frames, config: OfflineSortformerConfig | None = None,
     import torch
     config = config or OfflineSortformerConfig()
     ctx = ctx or L.default_context()
-    d_preds = _device_tensor(d_preds, ctx, torch.float32)
+    d_preds = A.device_tensor(d_preds, ctx, torch.float32)
     n = _lengths(n_mel_frames)
     geo = offline_windows(n, config)
     w, s = int(geo["window_range"][-1]), config.num_speakers
     assert tuple(d_preds.shape) == (w, config.window_output_frames, s), f"predictions must be [{w}, {config.window_output_frames}, {s}]"
-    d_global = torch.empty((int(geo["total_out"].sum()), s), dtype=torch.float32, device=d_preds.device)
-    d_map = torch.empty((w, s), dtype=torch.int32, device=d_preds.device)
+    d_global, d_map = A.beside(d_preds, (int(geo["total_out"].sum()), s), "float32", torch_empty=True), A.beside(d_preds, (w, s), "int32", torch_empty=True)
     cfg = config.c_config()
     with ctx.torch_ordered():
         ctx.check(L.lib().fa_sortformer_stitch_dev(ctx.handle, C.byref(cfg), d_preds.data_ptr(), n.ctypes.data, n.size, w, d_global.data_ptr(),

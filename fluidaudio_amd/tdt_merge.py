@@ -8,11 +8,12 @@ repairSeamGaps (needs the networks), the planning of chunk starts and the stream
 from __future__ import annotations
 
 import ctypes as C
+import functools
 from collections import namedtuple
 
 import numpy as np
 
-from . import _lib as L
+from . import _args as A, _lib as L
 
 MERGE_EMPTY, MERGE_CONCAT, MERGE_CONTIGUOUS, MERGE_LCS, MERGE_MIDPOINT = range(5)
 MERGE_TAIL_VERBATIM, MERGE_TAIL_ADOPT_RIGHT, MERGE_TAIL_KEEP_LEFT = range(3)
@@ -29,8 +30,7 @@ def merge_route_name(code: int) -> str:
     return "none" if code < 0 else _BASE[code & 15] + _TAIL[code >> 4]
 
 
-def _invalid(detail: str):
-    return L.FluidAudioHipError(L.INVALID_ARGUMENT, "merge_windows", detail)
+_invalid = functools.partial(A.invalid, "merge_windows")
 
 
 def splice_safe_table(safe_ids, vocab: int):
@@ -107,8 +107,22 @@ def _ranges(window_range, n_windows, capacities, counts):
     return window_range, out_range
 
 
-def _ptr(a):
-    return None if a is None else a.ctypes.data
+def _run_merge(where, ctx, arrays, count_bound, window_range, splice_safe, case_canon, vocab, frame_seconds, overlap_seconds, capacities, ordered) -> MergedWindows:
+    """The body of merge_windows and merge_windows_dev: `arrays` are the four window arrays and the counts, checked, as numpy arrays or as
+    device tensors; the merged streams come back beside them.  count_bound: per window, the most tokens it can hold."""
+    windows, max_out = arrays[0].shape
+    s, c, vocab = _tables(splice_safe, case_canon, vocab)
+    window_range, out_range = _ranges(window_range, windows, capacities, count_bound)
+    n, total = window_range.size - 1, int(out_range[-1])
+    merged = [A.beside(arrays[0], total, dtype) for dtype in ("int32", "int32", "int32", "float32")]
+    o_cnt, o_st, routes = np.zeros(n, np.int32), np.zeros(n, np.int32), np.full(windows, MERGE_NO_SEAM, np.int32)
+    if n:
+        cfg = _config(frame_seconds, overlap_seconds)
+        ctx = A.context_beside(ctx, arrays[0])
+        with ctx.torch_ordered(ordered):
+            ctx.check(getattr(L.lib(), where)(ctx.handle, C.byref(cfg), *[A.ptr(a) for a in arrays], max_out, A.ptr(window_range), n, A.ptr(s), A.ptr(c), vocab,
+                                              *[A.ptr(a) for a in merged], A.ptr(out_range), A.ptr(o_cnt), A.ptr(o_st), A.ptr(routes)), where)
+    return MergedWindows(*merged, out_range, o_cnt, o_st, routes)
 
 
 def merge_windows(tokens, timestamps, durations, confidences, counts, window_range, splice_safe=None, case_canon=None, vocab=None,
@@ -119,20 +133,8 @@ def merge_windows(tokens, timestamps, durations, confidences, counts, window_ran
     conf, cnt = np.ascontiguousarray(confidences, np.float32), np.ascontiguousarray(counts, np.int32)
     if tok.ndim != 2 or tim.shape != tok.shape or dur.shape != tok.shape or conf.shape != tok.shape or cnt.shape != (tok.shape[0],):
         raise _invalid("the window arrays are [windows, max_out] and the counts [windows]")
-    windows, max_out = tok.shape
-    s, c, vocab = _tables(splice_safe, case_canon, vocab)
-    window_range, out_range = _ranges(window_range, windows, capacities, np.clip(cnt, 0, max_out))
-    n, total = window_range.size - 1, int(out_range[-1])
-    o_tok, o_time, o_dur, o_conf = np.zeros(total, np.int32), np.zeros(total, np.int32), np.zeros(total, np.int32), np.zeros(total, np.float32)
-    o_cnt, o_st, routes = np.zeros(n, np.int32), np.zeros(n, np.int32), np.full(windows, MERGE_NO_SEAM, np.int32)
-    if n == 0:
-        return MergedWindows(o_tok, o_time, o_dur, o_conf, out_range, o_cnt, o_st, routes)
-    cfg = _config(frame_seconds, overlap_seconds)
-    ctx = ctx or L.default_context()
-    ctx.check(L.lib().fa_tdt_merge_windows(ctx.handle, C.byref(cfg), _ptr(tok), _ptr(tim), _ptr(dur), _ptr(conf), _ptr(cnt), max_out, _ptr(window_range), n,
-                                           _ptr(s), _ptr(c), vocab, _ptr(o_tok), _ptr(o_time), _ptr(o_dur), _ptr(o_conf), _ptr(out_range), _ptr(o_cnt),
-                                           _ptr(o_st), _ptr(routes)), "fa_tdt_merge_windows")
-    return MergedWindows(o_tok, o_time, o_dur, o_conf, out_range, o_cnt, o_st, routes)
+    return _run_merge("fa_tdt_merge_windows", ctx, (tok, tim, dur, conf, cnt), np.clip(cnt, 0, tok.shape[1]), window_range, splice_safe, case_canon, vocab,
+                      frame_seconds, overlap_seconds, capacities, False)
 
 
 def merge_windows_dev(d_tokens, d_timestamps, d_durations, d_confidences, d_counts, window_range, splice_safe=None, case_canon=None, vocab=None,
@@ -141,27 +143,11 @@ def merge_windows_dev(d_tokens, d_timestamps, d_durations, d_confidences, d_coun
     o_time, o_dur [windows, max_out] int32, o_conf float32, o_cnt [windows] int32).  The merged streams stay on the device (flat torch
     tensors); ranges, counts, statuses and routes are host arrays.  Without `capacities` every slice gets the bound that holds for any
     counts, max_out * (2 * windows - 1) tokens: pass merge_capacity of the counts where they are known."""
-    import torch
-    for t, dt in ((d_tokens, torch.int32), (d_timestamps, torch.int32), (d_durations, torch.int32), (d_confidences, torch.float32), (d_counts, torch.int32)):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
+    for t, dt in ((d_tokens, "int32"), (d_timestamps, "int32"), (d_durations, "int32"), (d_confidences, "float32"), (d_counts, "int32")):
+        if not A.is_dev(t, dt):
             raise _invalid("the window arrays must be contiguous int32 / float32 tensors on the device")
     if d_tokens.dim() != 2 or any(t.shape != d_tokens.shape for t in (d_timestamps, d_durations, d_confidences)) or d_counts.shape != (d_tokens.shape[0],):
         raise _invalid("the window arrays are [windows, max_out] and the counts [windows]")
     windows, max_out = d_tokens.shape
-    s, c, vocab = _tables(splice_safe, case_canon, vocab)
-    window_range, out_range = _ranges(window_range, windows, capacities, np.full(windows, max_out, np.int64))
-    n, total = window_range.size - 1, int(out_range[-1])
-    dev = d_tokens.device
-    o_tok, o_time, o_dur = (torch.zeros(total, dtype=torch.int32, device=dev) for _ in range(3))
-    o_conf = torch.zeros(total, dtype=torch.float32, device=dev)
-    o_cnt, o_st, routes = np.zeros(n, np.int32), np.zeros(n, np.int32), np.full(windows, MERGE_NO_SEAM, np.int32)
-    if n == 0:
-        return MergedWindows(o_tok, o_time, o_dur, o_conf, out_range, o_cnt, o_st, routes)
-    cfg = _config(frame_seconds, overlap_seconds)
-    ctx = ctx or L.default_context(dev.index)
-    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-    with ctx.torch_ordered(ordered):
-        ctx.check(L.lib().fa_tdt_merge_windows_dev(ctx.handle, C.byref(cfg), p(d_tokens), p(d_timestamps), p(d_durations), p(d_confidences), p(d_counts), max_out,
-                                                   _ptr(window_range), n, _ptr(s), _ptr(c), vocab, p(o_tok), p(o_time), p(o_dur), p(o_conf), _ptr(out_range),
-                                                   _ptr(o_cnt), _ptr(o_st), _ptr(routes)), "fa_tdt_merge_windows_dev")
-    return MergedWindows(o_tok, o_time, o_dur, o_conf, out_range, o_cnt, o_st, routes)
+    return _run_merge("fa_tdt_merge_windows_dev", ctx, (d_tokens, d_timestamps, d_durations, d_confidences, d_counts), np.full(windows, max_out, np.int64), window_range,
+                      splice_safe, case_canon, vocab, frame_seconds, overlap_seconds, capacities, ordered)

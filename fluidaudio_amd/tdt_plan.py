@@ -12,18 +12,10 @@ import dataclasses
 
 import numpy as np
 
-from . import _lib as L
+from . import _args as A, _lib as L
 
-TDT_WINDOW_DTYPE = np.dtype([("recording", np.int32), ("use_warmup_prefix", np.int32), ("is_last", np.int32), ("emit_after_frame", np.int32),
-                             ("global_frame_offset", np.int32), ("context_frames", np.int32), ("actual_audio_frames", np.int32), ("reserved", np.int32),
-                             ("chunk_start", np.int64), ("warmup_samples", np.int64), ("context_samples", np.int64), ("context_start", np.int64),
-                             ("length", np.int64)])
-TDT_SPAN_DTYPE = np.dtype([("recording", np.int32), ("reserved", np.int32), ("from_sample", np.int64), ("to_sample", np.int64)])
+TDT_WINDOW_DTYPE, TDT_SPAN_DTYPE = np.dtype(L.TdtWindowRecord), np.dtype(L.TdtSpanRecord)
 FIVE = ("audio_frames", "t0", "is_last", "global_offset", "emit_after")   # the walk's per-window operands, in the order the entries take them
-
-
-def _invalid(where: str, detail: str):
-    return L.FluidAudioHipError(L.INVALID_ARGUMENT, where, detail)
 
 
 def window_config(melChunkContext: bool = True, silenceAligned: bool = False, warmupPrefixFrames: int = 0, endAligned: bool = True,
@@ -37,21 +29,17 @@ def window_config(melChunkContext: bool = True, silenceAligned: bool = False, wa
     return cfg
 
 
-def _cfg_arg(cfg):
-    return None if cfg is None else C.byref(cfg)
-
-
 def window_layout(config: L.TdtWindowConfig | None = None):
     """chunkLayout: (chunkSamples, strideSamples, melContextSamples, warmupPrefixSamples)."""
     out = [C.c_int64() for _ in range(4)]
-    st = L.lib().fa_tdt_window_layout(_cfg_arg(config), *[C.byref(x) for x in out])
+    st = L.lib().fa_tdt_window_layout(A.cfg_ref(config), *[C.byref(x) for x in out])
     if st != L.SUCCESS:
         raise L.FluidAudioHipError(st, "fa_tdt_window_layout", "the geometry is refused")
     return tuple(x.value for x in out)
 
 
 def window_count_bound(samples: int, config: L.TdtWindowConfig | None = None) -> int:
-    return int(L.lib().fa_tdt_window_count_bound(_cfg_arg(config), int(samples)))
+    return int(L.lib().fa_tdt_window_count_bound(A.cfg_ref(config), int(samples)))
 
 
 @dataclasses.dataclass
@@ -67,131 +55,103 @@ class PlannedWindows:
     emit_after: object
 
 
-def _offsets(audio, audio_offsets, where):
-    if audio_offsets is None:
-        arrays = [np.ascontiguousarray(x, np.float32).reshape(-1) for x in audio]
-        audio_offsets = np.concatenate([[0], np.cumsum([x.size for x in arrays])]).astype(np.int64)
-        audio = np.concatenate(arrays) if arrays else np.zeros(0, np.float32)
-    offsets = np.ascontiguousarray(audio_offsets, np.int64)
-    if offsets.ndim != 1 or offsets.size < 1:
-        raise _invalid(where, "audio_offsets holds batch + 1 offsets")
-    return audio, offsets
+def _windows_arg(windows, where):
+    w = np.ascontiguousarray(windows, TDT_WINDOW_DTYPE)
+    if w.ndim != 1:
+        raise A.invalid(where, "windows is a one-dimensional array of TDT_WINDOW_DTYPE")
+    return w
 
 
-def _is_dev(t, dtype_name="float32"):
-    import torch
-    return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == getattr(torch, dtype_name) and t.is_contiguous() and t.dim() == 1
+def _host_audio(audio, audio_offsets, where, windows=None):
+    """The audio of a host entry, with the windows where the entry takes some: what the shared bodies below are handed."""
+    audio, offsets = A.ragged(audio, audio_offsets, np.float32, where, "audio_offsets holds batch + 1 offsets")
+    w = None if windows is None else _windows_arg(windows, where)
+    if audio.ndim != 1 or offsets[-1] > audio.size:
+        raise A.invalid(where, "audio is one-dimensional and covers audio_offsets")
+    return audio, offsets, w
 
 
-def _capacity(offsets, config, capacity):
-    if capacity is not None:
-        return int(capacity)
-    return int(sum(max(0, window_count_bound(int(n), config)) for n in np.diff(offsets)))
+def _dev_audio(audio, audio_offsets, where, windows=None):
+    if not A.is_dev(audio, "float32", 1):
+        raise A.invalid(where, "audio is a contiguous one-dimensional float32 tensor on the device")
+    _, offsets = A.ragged(audio, audio_offsets, np.float32, where, "audio_offsets holds batch + 1 offsets")
+    w = None if windows is None else _windows_arg(windows, where)
+    if offsets[-1] > audio.numel():
+        raise A.invalid(where, "audio_offsets end beyond the samples")
+    return audio, offsets, w
+
+
+def _run_plan(where, ctx, audio, offsets, config, capacity, ordered) -> PlannedWindows:
+    """The body of plan_windows and plan_windows_dev: the five operands are numpy arrays beside host audio, torch tensors beside a device tensor."""
+    B = offsets.size - 1
+    cap = int(sum(max(0, window_count_bound(int(n), config)) for n in np.diff(offsets))) if capacity is None else int(capacity)
+    windows, window_range = np.zeros(cap, TDT_WINDOW_DTYPE), np.zeros(B + 1, np.int64)
+    five = [A.beside(audio, cap, "int32") for _ in FIVE]
+    speech_end, statuses = np.zeros(B, np.int64), np.zeros(B, np.int32)
+    if B:
+        ctx = A.context_beside(ctx, audio)
+        with ctx.torch_ordered(ordered):
+            ctx.check(getattr(L.lib(), where)(ctx.handle, A.cfg_ref(config), A.ptr(audio), offsets.ctypes.data, B, windows.ctypes.data if cap else None, cap,
+                                              window_range.ctypes.data, *[A.ptr(x) if cap else None for x in five], speech_end.ctypes.data, statuses.ctypes.data), where)
+    n = int(window_range[-1])
+    return PlannedWindows(windows[:n], window_range, speech_end, statuses, *[x[:n] for x in five])
 
 
 def plan_windows(audio, audio_offsets=None, config: L.TdtWindowConfig | None = None, capacity: int | None = None, ctx: L.Context | None = None) -> PlannedWindows:
     """fa_tdt_plan_windows on host arrays: audio a list of B float32 arrays of 16 kHz samples — or one array with audio_offsets
     int64[B + 1].  capacity defaults to the sum of the recordings' bounds."""
     where = "fa_tdt_plan_windows"
-    audio, offsets = _offsets(audio, audio_offsets, where)
-    audio = np.ascontiguousarray(audio, np.float32)
-    if audio.ndim != 1 or offsets[-1] > audio.size:
-        raise _invalid(where, "audio is one-dimensional and covers audio_offsets")
-    B, cap = offsets.size - 1, _capacity(offsets, config, capacity)
-    windows, window_range = np.zeros(cap, TDT_WINDOW_DTYPE), np.zeros(B + 1, np.int64)
-    five = [np.zeros(cap, np.int32) for _ in FIVE]
-    speech_end, statuses = np.zeros(B, np.int64), np.zeros(B, np.int32)
-    if B:
-        ctx = ctx or L.default_context()
-        ctx.check(L.lib().fa_tdt_plan_windows(ctx.handle, _cfg_arg(config), audio.ctypes.data, offsets.ctypes.data, B, windows.ctypes.data if cap else None, cap,
-                                              window_range.ctypes.data, *[x.ctypes.data if cap else None for x in five], speech_end.ctypes.data, statuses.ctypes.data), where)
-    n = int(window_range[-1])
-    return PlannedWindows(windows[:n], window_range, speech_end, statuses, *[x[:n] for x in five])
+    audio, offsets, _ = _host_audio(audio, audio_offsets, where)
+    return _run_plan(where, ctx, audio, offsets, config, capacity, False)
 
 
 def plan_windows_dev(audio, audio_offsets, config: L.TdtWindowConfig | None = None, capacity: int | None = None, ctx: L.Context | None = None,
                      ordered: bool = True) -> PlannedWindows:
     """fa_tdt_plan_windows_dev: audio is a contiguous one-dimensional float32 torch tensor on the context's device.  The five operands of
     the walk come back as int32 torch tensors on that device, laid out as decode_tables / decode_logits read them."""
-    import torch
     where = "fa_tdt_plan_windows_dev"
-    if not _is_dev(audio):
-        raise _invalid(where, "audio is a contiguous one-dimensional float32 tensor on the device")
-    _, offsets = _offsets(audio, audio_offsets, where)
-    if offsets[-1] > audio.numel():
-        raise _invalid(where, "audio_offsets end beyond the samples")
-    B, cap = offsets.size - 1, _capacity(offsets, config, capacity)
-    windows, window_range = np.zeros(cap, TDT_WINDOW_DTYPE), np.zeros(B + 1, np.int64)
-    five = [torch.zeros(max(cap, 1), dtype=torch.int32, device=audio.device) for _ in FIVE]
-    speech_end, statuses = np.zeros(B, np.int64), np.zeros(B, np.int32)
-    if B:
-        ctx = ctx or L.default_context(audio.device.index)
+    audio, offsets, _ = _dev_audio(audio, audio_offsets, where)
+    return _run_plan(where, ctx, audio, offsets, config, capacity, ordered)
+
+
+def _run_pack(where, ctx, audio, offsets, w, config, ordered):
+    """The body of pack_windows and pack_windows_dev; rows and lengths come back beside the audio, as _run_plan's operands do."""
+    row = config.max_model_samples if config is not None else 240000
+    rows, lengths = A.beside(audio, (w.size, max(row, 0)), "float32", torch_empty=True), A.beside(audio, w.size, "int32", torch_empty=True)
+    if w.size:
+        ctx = A.context_beside(ctx, audio)
         with ctx.torch_ordered(ordered):
-            ctx.check(L.lib().fa_tdt_plan_windows_dev(ctx.handle, _cfg_arg(config), audio.data_ptr(), offsets.ctypes.data, B, windows.ctypes.data if cap else None, cap,
-                                                      window_range.ctypes.data, *[x.data_ptr() if cap else None for x in five], speech_end.ctypes.data,
-                                                      statuses.ctypes.data), where)
-    n = int(window_range[-1])
-    return PlannedWindows(windows[:n], window_range, speech_end, statuses, *[x[:n] for x in five])
-
-
-def _windows_arg(windows, where):
-    w = np.ascontiguousarray(windows, TDT_WINDOW_DTYPE)
-    if w.ndim != 1:
-        raise _invalid(where, "windows is a one-dimensional array of TDT_WINDOW_DTYPE")
-    return w
+            ctx.check(getattr(L.lib(), where)(ctx.handle, A.cfg_ref(config), A.ptr(audio), offsets.ctypes.data, offsets.size - 1, w.ctypes.data, w.size, A.ptr(rows),
+                                              w.size, A.ptr(lengths)), where)
+    return rows, lengths
 
 
 def pack_windows(audio, windows, audio_offsets=None, config: L.TdtWindowConfig | None = None, ctx: L.Context | None = None):
     """fa_tdt_pack_windows on host arrays.  Returns (rows [windows, max_model_samples] float32, lengths int32[windows])."""
     where = "fa_tdt_pack_windows"
-    audio, offsets = _offsets(audio, audio_offsets, where)
-    audio, w = np.ascontiguousarray(audio, np.float32), _windows_arg(windows, where)
-    if audio.ndim != 1 or offsets[-1] > audio.size:
-        raise _invalid(where, "audio is one-dimensional and covers audio_offsets")
-    row = config.max_model_samples if config is not None else 240000
-    rows, lengths = np.zeros((w.size, max(row, 0)), np.float32), np.zeros(w.size, np.int32)
-    if w.size:
-        ctx = ctx or L.default_context()
-        ctx.check(L.lib().fa_tdt_pack_windows(ctx.handle, _cfg_arg(config), audio.ctypes.data, offsets.ctypes.data, offsets.size - 1, w.ctypes.data, w.size, rows.ctypes.data,
-                                              w.size, lengths.ctypes.data), where)
-    return rows, lengths
+    return _run_pack(where, ctx, *_host_audio(audio, audio_offsets, where, windows), config, False)
 
 
 def pack_windows_dev(audio, audio_offsets, windows, config: L.TdtWindowConfig | None = None, ctx: L.Context | None = None, ordered: bool = True):
     """fa_tdt_pack_windows_dev: rows and lengths come back as torch tensors on the audio's device, in stream order — the entry does not
     synchronise.  They are what MelPlan / fa_mel_execute_dev take."""
-    import torch
     where = "fa_tdt_pack_windows_dev"
-    if not _is_dev(audio):
-        raise _invalid(where, "audio is a contiguous one-dimensional float32 tensor on the device")
-    _, offsets = _offsets(audio, audio_offsets, where)
-    w = _windows_arg(windows, where)
-    if offsets[-1] > audio.numel():
-        raise _invalid(where, "audio_offsets end beyond the samples")
-    row = config.max_model_samples if config is not None else 240000
-    rows = torch.empty((w.size, max(row, 0)), dtype=torch.float32, device=audio.device)
-    lengths = torch.empty(w.size, dtype=torch.int32, device=audio.device)
-    if w.size:
-        ctx = ctx or L.default_context(audio.device.index)
-        with ctx.torch_ordered(ordered):
-            ctx.check(L.lib().fa_tdt_pack_windows_dev(ctx.handle, _cfg_arg(config), audio.data_ptr(), offsets.ctypes.data, offsets.size - 1, w.ctypes.data, w.size,
-                                                      rows.data_ptr(), w.size, lengths.data_ptr()), where)
-    return rows, lengths
+    return _run_pack(where, ctx, *_dev_audio(audio, audio_offsets, where, windows), config, ordered)
 
 
-def _run_gate(f, where, ctx, config, audio_ptr, offsets, spans, override):
+def _run_gate(where, ctx, config, audio, offsets, spans, override):
     B = offsets.size - 1
     s = np.ascontiguousarray(np.zeros(0, TDT_SPAN_DTYPE) if spans is None else spans, TDT_SPAN_DTYPE)
     over = None if override is None else np.ascontiguousarray(override, np.float32)
     if s.ndim != 1 or (over is not None and over.shape != (B,)):
-        raise _invalid(where, "spans is a one-dimensional array of TDT_SPAN_DTYPE, override_thresholds holds one value per recording")
+        raise A.invalid(where, "spans is a one-dimensional array of TDT_SPAN_DTYPE, override_thresholds holds one value per recording")
     thresholds, statuses = np.zeros(B, np.float32), np.zeros(B, np.int32)
     frames, seconds = np.zeros(s.size, np.int64), np.zeros(s.size, np.float64)
     if B:
-        ctx.check(f(ctx.handle, _cfg_arg(config), audio_ptr, offsets.ctypes.data, B, None if over is None else over.ctypes.data, thresholds.ctypes.data,
-                    s.ctypes.data if s.size else None, s.size, frames.ctypes.data, seconds.ctypes.data, statuses.ctypes.data), where)
+        ctx.check(getattr(L.lib(), where)(ctx.handle, A.cfg_ref(config), A.ptr(audio), offsets.ctypes.data, B, A.ptr(over), thresholds.ctypes.data,
+                                          s.ctypes.data if s.size else None, s.size, frames.ctypes.data, seconds.ctypes.data, statuses.ctypes.data), where)
     elif s.size:
-        raise _invalid(where, "a span names a recording outside the batch")
+        raise A.invalid(where, "a span names a recording outside the batch")
     return thresholds, frames, seconds, statuses
 
 
@@ -199,24 +159,17 @@ def speech_gate(audio, spans=None, audio_offsets=None, override_thresholds=None,
     """fa_tdt_speech_gate on host arrays: (thresholds float32[B], span_frames int64[n], span_seconds float64[n], statuses int32[B]);
     spans: records of TDT_SPAN_DTYPE (recording, from_sample, to_sample)."""
     where = "fa_tdt_speech_gate"
-    audio, offsets = _offsets(audio, audio_offsets, where)
-    audio = np.ascontiguousarray(audio, np.float32)
-    if audio.ndim != 1 or offsets[-1] > audio.size:
-        raise _invalid(where, "audio is one-dimensional and covers audio_offsets")
-    return _run_gate(L.lib().fa_tdt_speech_gate, where, ctx or L.default_context(), config, audio.ctypes.data, offsets, spans, override_thresholds)
+    audio, offsets, _ = _host_audio(audio, audio_offsets, where)
+    return _run_gate(where, ctx or L.default_context(), config, audio, offsets, spans, override_thresholds)
 
 
 def speech_gate_dev(audio, audio_offsets, spans=None, override_thresholds=None, config: L.TdtWindowConfig | None = None, ctx: L.Context | None = None, ordered: bool = True):
     """fa_tdt_speech_gate_dev: audio is a contiguous one-dimensional float32 torch tensor on the context's device."""
     where = "fa_tdt_speech_gate_dev"
-    if not _is_dev(audio):
-        raise _invalid(where, "audio is a contiguous one-dimensional float32 tensor on the device")
-    _, offsets = _offsets(audio, audio_offsets, where)
-    if offsets[-1] > audio.numel():
-        raise _invalid(where, "audio_offsets end beyond the samples")
+    audio, offsets, _ = _dev_audio(audio, audio_offsets, where)
     ctx = ctx or L.default_context(audio.device.index)
     with ctx.torch_ordered(ordered):
-        return _run_gate(L.lib().fa_tdt_speech_gate_dev, where, ctx, config, audio.data_ptr(), offsets, spans, override_thresholds)
+        return _run_gate(where, ctx, config, audio, offsets, spans, override_thresholds)
 
 
 class TdtWindowPlanner:

@@ -10,10 +10,9 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import _lib as L
+from . import _args as A, _lib as L
 
-SEGMENT_DTYPE = np.dtype([("recording", np.int32), ("speaker", np.int32), ("start_frame", np.int64), ("end_frame", np.int64),
-                          ("activity", np.float32), ("finalized", np.int32)])
+SEGMENT_DTYPE = np.dtype(L.DiarizerSegmentRecord)
 
 
 def _swift_round(x) -> int:
@@ -103,15 +102,6 @@ def _lengths(n_mel_frames) -> np.ndarray:
     return np.ascontiguousarray(np.atleast_1d(n_mel_frames), np.int64)
 
 
-def _device_tensor(x, ctx: L.Context, dtype=None):
-    if not (hasattr(x, "data_ptr") and x.is_cuda):
-        raise TypeError("a torch CUDA tensor is required")
-    if x.device.index != ctx.device:
-        raise ValueError(f"tensor on {x.device}, context on cuda:{ctx.device}")
-    x = x.contiguous()
-    return x if dtype is None or x.dtype == dtype else x.to(dtype)
-
-
 def timeline_segments(finalized, finalized_frames=None, tentative=None, tentative_frames=None, config: DiarizerTimelineConfig | None = None,
                       is_complete: bool = True, ctx: L.Context | None = None, capacity: int | None = None):
     """DiarizerTimeline.rebuild for a batch: finalized [sum finalized_frames, S] (torch CUDA tensor: read on the device; anything else:
@@ -127,7 +117,7 @@ def timeline_segments(finalized, finalized_frames=None, tentative=None, tentativ
             return None, 0, None
         if on_device:
             import torch
-            x = _device_tensor(x, ctx, torch.float32)
+            x = A.device_tensor(x, ctx, torch.float32)
             return x, x.numel() // s, x.data_ptr()
         x = np.ascontiguousarray(x.detach().cpu().numpy() if hasattr(x, "data_ptr") else x, np.float32)
         return x, x.size // s, x.ctypes.data
@@ -144,8 +134,7 @@ def timeline_segments(finalized, finalized_frames=None, tentative=None, tentativ
 
     def call(out, cap):
         with ctx.torch_ordered(on_device):
-            return f(ctx.handle, C.byref(cfg), pfin, ff.ctypes.data, ptent, None if tf is None else tf.ctypes.data, ff.size, int(bool(is_complete)),
-                     None if out is None else out.ctypes.data, cap, C.byref(cnt), per.ctypes.data)
+            return f(ctx.handle, C.byref(cfg), pfin, ff.ctypes.data, ptent, A.ptr(tf), ff.size, int(bool(is_complete)), A.ptr(out), cap, C.byref(cnt), per.ctypes.data)
 
     if capacity is None:
         ctx.check(call(None, 0), name)

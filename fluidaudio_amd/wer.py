@@ -9,15 +9,14 @@ segmentation and Swift's canonical-equivalence `==` — the caller passes NORMAL
 whose characters are compared code point by code point."""
 from __future__ import annotations
 
-import ctypes as C
+import functools
 from collections import namedtuple
 
 import numpy as np
 
-from . import _lib as L
+from . import _args as A, _lib as L
 
-EDIT_COUNTS_DTYPE = np.dtype([("total", np.int32), ("insertions", np.int32), ("deletions", np.int32), ("substitutions", np.int32),
-                              ("hyp_len", np.int32), ("ref_len", np.int32)])
+EDIT_COUNTS_DTYPE = np.dtype(L.EditCounts)
 WERMetrics = namedtuple("WERMetrics", "wer insertions deletions substitutions totalWords")                                  # :10
 WERAndCER = namedtuple("WERAndCER", "wer cer insertions deletions substitutions totalWords totalCharacters")                # :28-31
 # the corpus sums as the benchmarks aggregate them (FluidAudioCLI/Commands/ASR/Parakeet/Unified/UnifiedBenchmark.swift:169-187):
@@ -25,8 +24,7 @@ WERAndCER = namedtuple("WERAndCER", "wer cer insertions deletions substitutions 
 CorpusErrorRate = namedtuple("CorpusErrorRate", "word_errors ref_words wer char_errors ref_chars cer")
 
 
-def _invalid(detail: str):
-    return L.FluidAudioHipError(L.INVALID_ARGUMENT, "edit_distance_batch", detail)
+_invalid = functools.partial(A.invalid, "edit_distance_batch")
 
 
 def _ids(seq) -> np.ndarray:
@@ -42,9 +40,18 @@ def _ids(seq) -> np.ndarray:
 
 
 def _pack(seqs):
-    rng = np.zeros(len(seqs) + 1, np.int64)
-    np.cumsum([s.size for s in seqs], out=rng[1:])
-    return (np.concatenate(seqs) if seqs else np.zeros(0, np.int32)).astype(np.int32, copy=False), rng
+    return A.ragged(seqs, None, np.int32)
+
+
+def _run_edit(where, ctx, hyp, hyp_range, ref, ref_range, ordered) -> np.ndarray:
+    """The body of edit_distance_batch and edit_distance_batch_dev: the symbols are numpy arrays or device tensors, the ranges host arrays."""
+    n = hyp_range.size - 1
+    out = np.zeros(n, EDIT_COUNTS_DTYPE)
+    if n:
+        ctx = A.context_beside(ctx, hyp)
+        with ctx.torch_ordered(ordered):
+            ctx.check(getattr(L.lib(), where)(ctx.handle, A.ptr(hyp), hyp_range.ctypes.data, A.ptr(ref), ref_range.ctypes.data, n, out.ctypes.data), where)
+    return out
 
 
 def edit_distance_batch(pairs, ctx: L.Context | None = None) -> np.ndarray:
@@ -55,39 +62,22 @@ def edit_distance_batch(pairs, ctx: L.Context | None = None) -> np.ndarray:
         if len(p) != 2:
             raise _invalid("a pair is (hypothesis, reference)")
         sides.append((_ids(p[0]), _ids(p[1])))
-    out = np.zeros(len(sides), EDIT_COUNTS_DTYPE)
-    if not sides:
-        return out
-    hyp, hyp_range = _pack([h for h, _ in sides])
-    ref, ref_range = _pack([r for _, r in sides])
-    ctx = ctx or L.default_context()
-    ctx.check(L.lib().fa_edit_distance_batch(ctx.handle, hyp.ctypes.data, hyp_range.ctypes.data, ref.ctypes.data, ref_range.ctypes.data, len(sides),
-                                             out.ctypes.data), "fa_edit_distance_batch")
-    return out
+    return _run_edit("fa_edit_distance_batch", ctx, *_pack([h for h, _ in sides]), *_pack([r for _, r in sides]), False)
 
 
 def edit_distance_batch_dev(hyp, hyp_range, ref, ref_range, ctx: L.Context | None = None, ordered: bool = True) -> np.ndarray:
     """The same on symbols that are already on the device (fa_edit_distance_batch_dev): hyp and ref are contiguous int32 torch tensors on
     the context's device — e.g. the ids a decoder left there —, pair k's symbols are hyp[hyp_range[k]:hyp_range[k + 1]] and
     ref[ref_range[k]:ref_range[k + 1]]; the ranges are host integers."""
-    import torch
     hyp_range, ref_range = np.ascontiguousarray(hyp_range, np.int64), np.ascontiguousarray(ref_range, np.int64)
     if hyp_range.ndim != 1 or hyp_range.shape != ref_range.shape or hyp_range.size < 1:
         raise _invalid("the ranges hold n_pairs + 1 entries each")
     for t, rng in ((hyp, hyp_range), (ref, ref_range)):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous()):
+        if not A.is_dev(t, "int32", 1):
             raise _invalid("the symbols must be contiguous one-dimensional int32 tensors on the device")
         if (np.diff(rng) < 0).any() or rng[0] < 0 or rng[-1] > t.numel():
             raise _invalid("a range does not ascend inside its tensor")
-    n = hyp_range.size - 1
-    out = np.zeros(n, EDIT_COUNTS_DTYPE)
-    if n == 0:
-        return out
-    ctx = ctx or L.default_context(hyp.device.index)
-    with ctx.torch_ordered(ordered):
-        ctx.check(L.lib().fa_edit_distance_batch_dev(ctx.handle, hyp.data_ptr(), hyp_range.ctypes.data, ref.data_ptr(), ref_range.ctypes.data, n,
-                                                     out.ctypes.data), "fa_edit_distance_batch_dev")
-    return out
+    return _run_edit("fa_edit_distance_batch_dev", ctx, hyp, hyp_range, ref, ref_range, ordered)
 
 
 def _number(seqs):
