@@ -4,6 +4,10 @@ reference's own interfaces.  All arithmetic runs in csrc/libfluidaudio_hip.so (h
 for gfx950) through the C ABI of include/fluidaudio_hip.h; there is no CPU fallback.
 """
 from ._lib import (AHC_MODE_AUTO, AHC_MODE_EXACT, AHC_MODE_REFERENCE_ORDER, ALLOCATION_FAILURE, INVALID_ARGUMENT, RUNTIME_ERROR, SUCCESS, Context, FluidAudioHipError, build, default_context, lib)  # noqa: F401
+from .aed import (AED_END_CAP, AED_END_EOS, AED_FEED_SEQUENCE, AED_FEED_TOKEN, AED_MODEL_CANARY, AED_MODEL_COHERE, AED_RUNNING, AedConfig, AedDecodeState,  # noqa: F401
+                  AedResult, AedWindows, MergedTokens, cross_attention_mask as aed_cross_attention_mask, encoder_context as aed_encoder_context,
+                  encoder_valid_frames as aed_encoder_valid_frames, merge_token_streams as aed_merge_token_streams, merge_token_windows as aed_merge_token_windows,
+                  merge_token_windows_dev as aed_merge_token_windows_dev, plan_windows as aed_plan_windows)
 from .ahc import AHCClustering, check_dendrogram, cut, fastcluster_compute_centroid_linkage, linkage, linkage_batch  # noqa: F401
 from .beam import ARPAError, ARPALanguageModel, CtcVocabulary, ctc_beam_search, ctc_beam_search_ids_batch  # noqa: F401
 from .ctc import (LogitsArgmax, ctc_greedy_decode, ctc_greedy_ids_batch, ctc_greedy_rows, ctc_greedy_ids_dev, ctc_log_probs_dev,  # noqa: F401

@@ -72,6 +72,8 @@ EXPORTED_SYMBOLS = [
     "fa_speaker_db_mergeable_pairs_dev", "fa_speaker_db_assign", "fa_speaker_db_distances", "fa_speaker_db_mergeable_pairs", "fa_speaker_db_upsert", "fa_speaker_db_get", "fa_speaker_db_ids", "fa_speaker_db_count", "fa_speaker_db_remove",
     "fa_speaker_db_remove_inactive", "fa_speaker_db_set_permanent", "fa_speaker_db_reset",
     "fa_online_chunk_default_config", "fa_online_chunk_plan_dev", "fa_online_chunk_plan", "fa_online_pack_waveforms_dev", "fa_online_chunk_finish_dev",
+    "fa_aed_default_config", "fa_aed_max_out", "fa_aed_state_bytes", "fa_aed_begin_dev", "fa_aed_step_dev", "fa_aed_finish_dev", "fa_aed_finish", "fa_aed_cross_mask_dev",
+    "fa_aed_encoder_valid_frames", "fa_aed_encoder_context_dev", "fa_aed_gather_hidden_dev", "fa_aed_plan_windows", "fa_aed_merge_windows_dev", "fa_aed_merge_windows",
 ]
 
 
@@ -274,6 +276,12 @@ class OnlineRun(C.Structure):                                          # fa_onli
 class OnlineSegment(C.Structure):                                      # fa_online_segment
     _fields_ = [("stream", C.c_int32), ("chunk", C.c_int32), ("local_speaker", C.c_int32), ("id", C.c_int32), ("start_frame", C.c_int32), ("end_frame", C.c_int32),
                 ("start", C.c_float), ("end", C.c_float), ("quality", C.c_float)]
+
+
+class AedConfig(C.Structure):                                          # fa_aed_config
+    _fields_ = [("mode", C.c_int32), ("vocab", C.c_int32), ("eos_id", C.c_int32), ("max_seq", C.c_int32), ("max_new", C.c_int32), ("no_repeat_ngram", C.c_int32),
+                ("repetition_penalty", C.c_float), ("window_tokens", C.c_int32), ("min_match", C.c_int32), ("reserved", C.c_int32), ("chunk_samples", C.c_int64),
+                ("hop_samples", C.c_int64)]
 
 
 class ExportEmbedding(C.Structure):                                    # fa_export_embedding
@@ -586,6 +594,25 @@ def lib() -> C.CDLL:
     L.fa_online_chunk_plan.argtypes = [vp, C.POINTER(OnlineChunkConfig), vp, vp, i32, i32, vp, vp, i32, C.POINTER(i32), vp]
     L.fa_online_pack_waveforms_dev.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
     L.fa_online_chunk_finish_dev.argtypes = [vp, C.POINTER(OnlineChunkConfig), vp, vp, vp, vp, vp, i32, i64, vp, i64, C.POINTER(i64), vp, vp]
+    ac = C.POINTER(AedConfig)
+    L.fa_aed_default_config.argtypes = [ac, i32]
+    L.fa_aed_default_config.restype = None
+    L.fa_aed_max_out.argtypes = [ac]
+    L.fa_aed_max_out.restype = i32
+    L.fa_aed_state_bytes.argtypes = [ac, i32]
+    L.fa_aed_state_bytes.restype = i64
+    L.fa_aed_begin_dev.argtypes = [vp, ac, i32, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp]
+    L.fa_aed_step_dev.argtypes = [vp, ac, i32, vp, vp, i32, i64, vp, vp, vp, i32, vp, vp]
+    L.fa_aed_finish_dev.argtypes = [vp, ac, i32, vp, i32, vp, vp, vp, vp]
+    L.fa_aed_finish.argtypes = L.fa_aed_finish_dev.argtypes
+    L.fa_aed_cross_mask_dev.argtypes = [vp, vp, i32, i32, i32, vp]
+    L.fa_aed_encoder_valid_frames.argtypes = [i64, i32, i32, i32]
+    L.fa_aed_encoder_valid_frames.restype = i32
+    L.fa_aed_encoder_context_dev.argtypes = [vp, vp, i32, i32, i32, i32, i64, i64, i64, vp, vp, vp]
+    L.fa_aed_gather_hidden_dev.argtypes = [vp, ac, i32, vp, vp, i32, i32, i32, i64, i64, i64, vp]
+    L.fa_aed_plan_windows.argtypes = [ac, vp, i64, vp, vp, vp, i64, C.POINTER(i64)]
+    L.fa_aed_merge_windows_dev.argtypes = [vp, ac, vp, vp, vp, i64, vp, vp, vp, vp, vp]
+    L.fa_aed_merge_windows.argtypes = L.fa_aed_merge_windows_dev.argtypes
     _lib = L
     return L
 

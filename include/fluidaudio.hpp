@@ -1063,6 +1063,136 @@ private:
     int32_t tailCap_ = 0;
 };
 
+// ------------------------------------------------------------------------------------------------------------------ AED greedy decoding
+// The host loops round the attention encoder-decoder models over the fa_aed_* entries: CoherePipeline (Sources/FluidAudio/ASR/Cohere/
+// CoherePipeline.swift:525-959: transcribeLong's windows, mergeTokenStreams, encoderValidFrames, decodeCacheExternal's step, the two masks)
+// and CanaryManager (Sources/FluidAudio/ASR/Canary/CanaryManager.swift:50-275: the same windows and merge, makeDecoderContext,
+// greedyDecode).  The networks and every device buffer are the caller's; pointers named d... are DEVICE pointers.
+struct AedConfig {
+    int32_t mode = FA_AED_FEED_TOKEN, vocab = 16384, eosId = 3, maxSeq = 108, maxNew = 108, noRepeatNgram = 3;
+    float repetitionPenalty = 1.1f;
+    int32_t windowTokens = 32, minMatch = 4;
+    int64_t chunkSamples = 560000, hopSamples = 480000;
+    static AedConfig preset(int32_t model) {
+        fa_aed_config c;
+        fa_aed_default_config(&c, model);
+        AedConfig a;
+        a.mode = c.mode; a.vocab = c.vocab; a.eosId = c.eos_id; a.maxSeq = c.max_seq; a.maxNew = c.max_new; a.noRepeatNgram = c.no_repeat_ngram;
+        a.repetitionPenalty = c.repetition_penalty; a.windowTokens = c.window_tokens; a.minMatch = c.min_match; a.chunkSamples = c.chunk_samples; a.hopSamples = c.hop_samples;
+        return a;
+    }
+    static AedConfig cohere() { return preset(FA_AED_MODEL_COHERE); }   // CohereAsrConfig + transcribe's defaults
+    static AedConfig canary() { return preset(FA_AED_MODEL_CANARY); }   // CanaryConfig
+    fa_aed_config c() const { return fa_aed_config{mode, vocab, eosId, maxSeq, maxNew, noRepeatNgram, repetitionPenalty, windowTokens, minMatch, 0, chunkSamples, hopSamples}; }
+    int32_t maxOut() const { const fa_aed_config k = c(); return fa_aed_max_out(&k); }
+    int64_t stateBytes(int32_t batch) const { const fa_aed_config k = c(); return fa_aed_state_bytes(&k, batch); }
+};
+// The decode state of a batch: dState (stateBytes(batch) bytes) and the arrays of the feed in use are the caller's device buffers.
+struct AedDecodeState {
+    AedConfig config;
+    int32_t batch = 0;
+    void *dState = nullptr;
+    int32_t *dInputId = nullptr, *dPositionId = nullptr;   // token feed [batch]
+    void *dSelfMask = nullptr;                             // token feed, optional [batch][maxSeq]
+    int32_t maskDtype = FA_DTYPE_F32;
+    int32_t *dInputIds = nullptr;                          // sequence feed [batch][maxSeq]
+    float *dDecoderMask = nullptr;
+    struct Result {
+        std::vector<std::vector<int32_t>> tokens;
+        std::vector<int32_t> reasons, steps;               // FA_AED_RUNNING / FA_AED_END_EOS / FA_AED_END_CAP
+    };
+    void begin(Context &ctx, const int32_t *dPrompts, int32_t promptStride, const std::vector<int32_t> &promptLens) const {
+        const fa_aed_config k = config.c();
+        if (static_cast<size_t>(batch) != promptLens.size()) throw Error(FA_INVALID_ARGUMENT, "fa_aed_begin_dev", "one prompt length per utterance");
+        ctx.check(fa_aed_begin_dev(ctx.handle(), &k, batch, dPrompts, promptStride, promptLens.data(), dState, dInputId, dPositionId, dSelfMask, maskDtype, dInputIds, dDecoderMask),
+                  "fa_aed_begin_dev");
+    }
+    // one launch, nothing allocated, nothing waited for
+    void step(Context &ctx, const void *dLogits, int32_t dtype, int64_t rowStride) const {
+        const fa_aed_config k = config.c();
+        ctx.check(fa_aed_step_dev(ctx.handle(), &k, batch, dState, dLogits, dtype, rowStride, dInputId, dPositionId, dSelfMask, maskDtype, dInputIds, dDecoderMask), "fa_aed_step_dev");
+    }
+    Result finish(Context &ctx) const {
+        const fa_aed_config k = config.c();
+        const int32_t m = config.maxOut();
+        std::vector<int32_t> tok(static_cast<size_t>(std::max(batch, 0)) * static_cast<size_t>(std::max(m, 0)) + 1), cnt(static_cast<size_t>(std::max(batch, 0)) + 1);
+        Result r;
+        r.reasons.resize(cnt.size());
+        r.steps.resize(cnt.size());
+        ctx.check(fa_aed_finish(ctx.handle(), &k, batch, dState, m, tok.data(), cnt.data(), r.reasons.data(), r.steps.data()), "fa_aed_finish");
+        r.reasons.resize(static_cast<size_t>(batch));
+        r.steps.resize(static_cast<size_t>(batch));
+        for (int32_t b = 0; b < batch; ++b) r.tokens.emplace_back(tok.begin() + static_cast<ptrdiff_t>(b) * m, tok.begin() + static_cast<ptrdiff_t>(b) * m + cnt[static_cast<size_t>(b)]);
+        return r;
+    }
+    // CanaryManager.greedyDecode's hidden row pos - 1 of every running utterance -> dHidden float[batch][D]
+    void gatherHidden(Context &ctx, const void *dDec, int32_t dtype, int32_t S, int32_t D, int64_t strideB, int64_t strideS, int64_t strideD, float *dHidden) const {
+        const fa_aed_config k = config.c();
+        ctx.check(fa_aed_gather_hidden_dev(ctx.handle(), &k, batch, dState, dDec, dtype, S, D, strideB, strideS, strideD, dHidden), "fa_aed_gather_hidden_dev");
+    }
+};
+struct AedLongForm {   // what CoherePipeline and CanaryManager share: the window loop and mergeTokenStreams
+    struct Window { int64_t start, length; };
+    static std::vector<std::vector<Window>> planWindows(const AedConfig &config, const std::vector<int64_t> &samples) {
+        const fa_aed_config k = config.c();
+        std::vector<int64_t> range(samples.size() + 1);
+        int64_t count = 0;
+        fa_status st = fa_aed_plan_windows(&k, samples.data(), static_cast<int64_t>(samples.size()), range.data(), nullptr, nullptr, 0, &count);
+        if (st != FA_SUCCESS) throw Error(st, "fa_aed_plan_windows");
+        std::vector<int64_t> starts(static_cast<size_t>(count) + 1), lens(static_cast<size_t>(count) + 1);
+        st = fa_aed_plan_windows(&k, samples.data(), static_cast<int64_t>(samples.size()), range.data(), starts.data(), lens.data(), count, &count);
+        if (st != FA_SUCCESS) throw Error(st, "fa_aed_plan_windows");
+        std::vector<std::vector<Window>> out(samples.size());
+        for (size_t r = 0; r < samples.size(); ++r)
+            for (int64_t w = range[r]; w < range[r + 1]; ++w) out[r].push_back(Window{starts[static_cast<size_t>(w)], lens[static_cast<size_t>(w)]});
+        return out;
+    }
+    // the fold of mergeTokenStreams over every recording's windows in one device call; answers in input order
+    static std::vector<std::vector<int32_t>> mergeRecordings(Context &ctx, const std::vector<std::vector<std::vector<int32_t>>> &recordings, int windowTokens = 32,
+                                                             int minMatch = 4) {
+        std::vector<int32_t> flat;
+        std::vector<int64_t> offsets{0}, range{0}, outRange{0};
+        for (const auto &r : recordings) {
+            for (const auto &w : r) { flat.insert(flat.end(), w.begin(), w.end()); offsets.push_back(static_cast<int64_t>(flat.size())); }
+            range.push_back(static_cast<int64_t>(offsets.size()) - 1);
+            outRange.push_back(static_cast<int64_t>(flat.size()));
+        }
+        AedConfig config;
+        config.windowTokens = windowTokens; config.minMatch = minMatch;
+        const fa_aed_config k = config.c();
+        std::vector<int32_t> out(flat.size() + 1), counts(recordings.size() + 1);
+        flat.push_back(0);
+        ctx.check(fa_aed_merge_windows(ctx.handle(), &k, flat.data(), offsets.data(), range.data(), static_cast<int64_t>(recordings.size()), out.data(), outRange.data(),
+                                       counts.data(), nullptr, nullptr), "fa_aed_merge_windows");
+        std::vector<std::vector<int32_t>> merged(recordings.size());
+        for (size_t r = 0; r < recordings.size(); ++r) merged[r].assign(out.begin() + outRange[r], out.begin() + outRange[r] + counts[r]);
+        return merged;
+    }
+    static std::vector<int32_t> mergeTokenStreams(Context &ctx, const std::vector<int32_t> &prefix, const std::vector<int32_t> &suffix, int windowTokens = 32, int minMatch = 4) {
+        return mergeRecordings(ctx, {{prefix, suffix}}, windowTokens, minMatch)[0];
+    }
+};
+struct CoherePipeline : AedLongForm {
+    static int encoderValidFrames(int64_t featureLength, int encoderSeqLen, int melFrames = 3500, int encoderFrames = 438) {
+        return fa_aed_encoder_valid_frames(featureLength, encoderSeqLen, melFrames, encoderFrames);
+    }
+    // buildCrossAttentionMask for a batch: dMask [batch][encoderSeqLen] of dtype (FA_DTYPE_F32 / FA_DTYPE_F16 bits), dValid int32[batch]
+    static void buildCrossAttentionMask(Context &ctx, const int32_t *dValid, int32_t batch, int32_t encoderSeqLen, int32_t dtype, void *dMask) {
+        ctx.check(fa_aed_cross_mask_dev(ctx.handle(), dValid, batch, encoderSeqLen, dtype, dMask), "fa_aed_cross_mask_dev");
+    }
+    // buildSelfAttentionMask: the static row of a step is AedDecodeState's dSelfMask; the dynamic variant is step + 1 zeros
+    static std::vector<float> buildDynamicSelfAttentionMask(int step) { return std::vector<float>(static_cast<size_t>(std::max(step, 0)) + 1, 0.0f); }
+    static std::vector<std::vector<Window>> planWindows(const std::vector<int64_t> &samples) { return AedLongForm::planWindows(AedConfig::cohere(), samples); }
+};
+struct CanaryManager : AedLongForm {
+    // makeDecoderContext for a batch: dEnc [batch][D][T] at element strides -> dEmb float[batch][T][D], dMask float[batch][T]
+    static void makeDecoderContext(Context &ctx, const void *dEnc, int32_t dtype, int32_t batch, int32_t D, int32_t T, int64_t strideB, int64_t strideD, int64_t strideT,
+                                   const int32_t *dLen, float *dEmb, float *dMask) {
+        ctx.check(fa_aed_encoder_context_dev(ctx.handle(), dEnc, dtype, batch, D, T, strideB, strideD, strideT, dLen, dEmb, dMask), "fa_aed_encoder_context_dev");
+    }
+    static std::vector<std::vector<Window>> planWindows(const std::vector<int64_t> &samples) { return AedLongForm::planWindows(AedConfig::canary(), samples); }
+};
+
 // ------------------------------------------------------------------------------------------------------------------ TDT long-form merging
 // ChunkProcessor's fold of mergeChunks over a recording's windows and enforceMonotonicTimestamps (Sources/FluidAudio/ASR/Parakeet/
 // SlidingWindow/TDT/ChunkProcessor.swift:843-855, 952-1219) over fa_tdt_merge_windows: the windows of one or more recordings in one

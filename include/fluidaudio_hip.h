@@ -479,6 +479,110 @@ fa_status fa_rnnt_greedy_logits_dev(fa_ctx *ctx, const fa_rnnt_config *cfg, cons
                                     int32_t *d_out_frame, int32_t *d_out_plain, int32_t *d_out_count, int32_t *d_final_u,
                                     int32_t *d_eou, int32_t *d_status);
 
+/* ------------------------------------------------------------------ AED greedy decoding ------ */
+/* The host loop around the attention encoder-decoder models: Cohere Transcribe (FluidAudio/ASR/Cohere/CoherePipeline.swift:525-959)
+ * and Canary (FluidAudio/ASR/Canary/CanaryManager.swift:50-275).  The networks, the mel front end, tokenizers, detokenisation and
+ * CanaryKeywordBooster stay the caller's.  Every output is an integer or an exactly rounded fp32: the repetition penalty is ONE
+ * IEEE fp32 divide or multiply per penalised id (the unit is built without contraction, denormals kept).
+ * LIBRARY'S OWN DEFINITION: a NaN logit never wins (NaN logits are outside the reference's contract); the argmax is the lowest
+ * index among the largest values, 0 where no value qualifies. */
+enum { FA_AED_MODEL_COHERE = 0, FA_AED_MODEL_CANARY = 1 };
+enum { FA_AED_FEED_TOKEN = 0, FA_AED_FEED_SEQUENCE = 1 };
+enum { FA_AED_RUNNING = 0, FA_AED_END_EOS = 1, FA_AED_END_CAP = 2 };
+/* The limits keep a step's LDS (one bit per id, two words per history position) within 48 KiB. */
+enum { FA_AED_MAX_VOCAB = 1 << 18, FA_AED_MAX_SEQ = 2048, FA_AED_MAX_WINDOW_TOKENS = 64 };
+typedef struct {
+    int32_t mode;                /* FA_AED_FEED_TOKEN (Cohere: one token per step, prompt fed step by step) / FA_AED_FEED_SEQUENCE (Canary) */
+    int32_t vocab;               /* 16384 */
+    int32_t eos_id;              /* 3 */
+    int32_t max_seq;             /* CohereAsrConfig.maxSeqLen 108 / CanaryConfig.maxDecoderSteps 128 (S) */
+    int32_t max_new;             /* maxNewTokens 108; unused by the sequence feed */
+    int32_t no_repeat_ngram;     /* 3; <= 0: off (Canary: 0) */
+    float repetition_penalty;    /* 1.1; 1: off (Canary: 1) */
+    int32_t window_tokens;       /* mergeTokenStreams windowTokens 32, 1 ... FA_AED_MAX_WINDOW_TOKENS */
+    int32_t min_match;           /* minMatch 4 */
+    int32_t reserved;
+    int64_t chunk_samples;       /* 560000 (35 s) / 240000 (15 s) */
+    int64_t hop_samples;         /* 480000 / 192000 */
+} fa_aed_config;
+/* model: FA_AED_MODEL_COHERE or FA_AED_MODEL_CANARY (anything else: Cohere). */
+void fa_aed_default_config(fa_aed_config *cfg, int32_t model);
+/* Output tokens an utterance can emit: token feed min(max_new + 1, max_seq) (the reference's loop emits up to max_new + 1 when
+ * max_seq does not bind), sequence feed max_seq.  0 for a config the step entries refuse. */
+int32_t fa_aed_max_out(const fa_aed_config *cfg);
+/* Bytes of the caller-owned DEVICE buffer holding the state of `batch` utterances (history of consumed tokens, its length, the
+ * step, the current input token, the output tokens and their count, the end reason); 0 for a refused config or batch < 1. */
+int64_t fa_aed_state_bytes(const fa_aed_config *cfg, int32_t batch);
+/* Starts `batch` utterances.  d_prompts DEVICE int32[batch][prompt_stride]; prompt_lens HOST int32[batch], each 1 ... min(prompt_stride,
+ * max_seq) (P < 1 is refused; a sequence-feed prompt of max_seq tokens ends at once with FA_AED_END_CAP).  Token feed writes
+ * d_input_id[b] = prompt[0], d_position_id[b] = 0 and, with d_self_mask, the static self-attention mask row of step 0
+ * ([batch][max_seq], mask_dtype FA_DTYPE_F32 or FA_DTYPE_F16 bits: 0 up to and including the step, -1e4 / 0xF0E2 beyond;
+ * buildSelfAttentionMask :817-849 — the dynamic variant is step + 1 zeros, sized by the caller from d_position_id).  Sequence
+ * feed writes d_input_ids int32[batch][max_seq] (prompt, then 0) and d_decoder_mask float[batch][max_seq] (1 / 0).  The arrays of
+ * the other feed may be NULL.  One synchronisation (the prompt lengths are uploaded). */
+fa_status fa_aed_begin_dev(fa_ctx *ctx, const fa_aed_config *cfg, int32_t batch, const int32_t *d_prompts, int32_t prompt_stride,
+                           const int32_t *prompt_lens, void *d_state, int32_t *d_input_id, int32_t *d_position_id, void *d_self_mask,
+                           int32_t mask_dtype, int32_t *d_input_ids, float *d_decoder_mask);
+/* One decode step for the whole batch: ONE launch, no allocation, no synchronisation.  d_logits [batch] rows of `vocab` logits
+ * (fp32 / fp16, widened exactly), row b at element b * row_stride; the row is read once and never written; padding is never read;
+ * rows of finished utterances are never read and none of their outputs is touched.
+ * Token feed (CoherePipeline.swift:728-803): at step s the history holds the tokens consumed at steps 0 .. s-1 (NOT the current
+ * input), the decision is the first-index argmax after applyRepetitionPenalty (:924-935: each distinct in-range history id once,
+ * v >= 0 ? v / p : v * p; skipped for p == 1 or an empty history) and then applyNoRepeatNgram (:937-959: n = 1 bans every history
+ * id, n >= 2 bans what followed each earlier occurrence of the last n-1 tokens, -1e9 overriding the penalty), the current input
+ * is appended to the history AFTER the decision.  For s < P-1 the decision is discarded (the row is not read).  From s >= P-1 EOS
+ * ends the utterance (nothing appended), any other token is appended to the output and becomes the next input.  The loop ends after
+ * step min(max_new + P, max_seq) - 1 (FA_AED_END_CAP).  An utterance that goes on gets d_input_id, d_position_id and, with
+ * d_self_mask, its mask row for the next step.
+ * Sequence feed (CanaryManager.swift:212-275): plain argmax with strict '>' from -greatestFiniteMagnitude (an all -inf row yields
+ * 0); EOS ends; otherwise the token is appended, d_input_ids[b][pos] = token, d_decoder_mask[b][pos] = 1, ++pos; pos == max_seq
+ * ends with FA_AED_END_CAP. */
+fa_status fa_aed_step_dev(fa_ctx *ctx, const fa_aed_config *cfg, int32_t batch, void *d_state, const void *d_logits, int32_t dtype,
+                          int64_t row_stride, int32_t *d_input_id, int32_t *d_position_id, void *d_self_mask, int32_t mask_dtype,
+                          int32_t *d_input_ids, float *d_decoder_mask);
+/* What the state holds now.  tokens int32[batch][max_out] (max_out >= fa_aed_max_out, else OUTPUT_TOO_SMALL; the tail of a row is
+ * 0), counts, reasons (FA_AED_*), steps (token feed: the next step; sequence feed: pos) int32[batch]; reasons / steps nullable.
+ * _dev: DEVICE outputs, no synchronisation.  Host form: HOST outputs, one synchronisation. */
+fa_status fa_aed_finish_dev(fa_ctx *ctx, const fa_aed_config *cfg, int32_t batch, const void *d_state, int32_t max_out, int32_t *d_tokens,
+                            int32_t *d_counts, int32_t *d_reasons, int32_t *d_steps);
+fa_status fa_aed_finish(fa_ctx *ctx, const fa_aed_config *cfg, int32_t batch, const void *d_state, int32_t max_out, int32_t *tokens,
+                        int32_t *counts, int32_t *reasons, int32_t *steps);
+/* buildCrossAttentionMask (:851-876): d_mask [batch][encoder_seq_len], 0 below valid and -1e4 (fp32) / 0xF0E2 (fp16 bits) from it,
+ * d_valid DEVICE int32[batch] clamped to [0, encoder_seq_len]. */
+fa_status fa_aed_cross_mask_dev(fa_ctx *ctx, const int32_t *d_valid, int32_t batch, int32_t encoder_seq_len, int32_t mask_dtype, void *d_mask);
+/* encoderValidFrames (:670-676): ceil(feature_length * encoder_frames / mel_frames) through fp64, clamped to [1, encoder_seq_len];
+ * the reference's frame counts are 3500 and 438.  0 for mel_frames < 1 or a negative argument. */
+int32_t fa_aed_encoder_valid_frames(int64_t feature_length, int32_t encoder_seq_len, int32_t mel_frames, int32_t encoder_frames);
+/* makeDecoderContext (CanaryManager.swift:187-209): d_enc [batch][D][T] (fp32 / fp16) at element strides (stride_b, stride_d,
+ * stride_t; the time stride of a row may be padded, T = 188 in 192) -> d_emb float[batch][T][D] dense and d_mask float[batch][T]:
+ * 1.0 below min(max(len, 1), T), else 0.0; d_len DEVICE int32[batch]. */
+fa_status fa_aed_encoder_context_dev(fa_ctx *ctx, const void *d_enc, int32_t dtype, int32_t batch, int32_t D, int32_t T, int64_t stride_b,
+                                     int64_t stride_d, int64_t stride_t, const int32_t *d_len, float *d_emb, float *d_mask);
+/* The hidden-row gather of :251-256: row pos - 1 (pos from the sequence-feed state) of d_dec [batch][S][D] at element strides
+ * -> d_hidden float[batch][D]; rows of finished utterances are not touched. */
+fa_status fa_aed_gather_hidden_dev(fa_ctx *ctx, const fa_aed_config *cfg, int32_t batch, const void *d_state, const void *d_dec, int32_t dtype,
+                                   int32_t S, int32_t D, int64_t stride_b, int64_t stride_s, int64_t stride_d, float *d_hidden);
+/* The window loop of transcribeLong (CoherePipeline.swift:525-572, CanaryManager.swift:50-71) for n recordings of `samples` samples:
+ * at most one chunk is one window, otherwise windows start every hop and a tail of at most chunk - hop samples after the first
+ * window is dropped.  window_range int64[n + 1]; starts / lens int64[capacity] (nullable: count only); *count is always set;
+ * OUTPUT_TOO_SMALL when the windows do not fit `capacity`.  No context, no device. */
+fa_status fa_aed_plan_windows(const fa_aed_config *cfg, const int64_t *samples, int64_t n, int64_t *window_range, int64_t *starts, int64_t *lens,
+                              int64_t capacity, int64_t *count);
+/* mergeTokenStreams (CoherePipeline.swift:592-634 = CanaryManager.swift:92-130) folded over each recording's windows, one
+ * wavefront per recording.  tokens: flat int32 ids (DEVICE for _dev), window w = [window_offsets[w], window_offsets[w + 1]);
+ * recording r owns windows [recording_range[r], recording_range[r + 1]) and the output slice [out_range[r], out_range[r + 1]),
+ * which must hold the sum of its windows' tokens (else OUTPUT_TOO_SMALL).  The three offset arrays are HOST int64.  Per seam the
+ * longest common substring of the last / first window_tokens tokens (the reference's strict '>' in row-major order: the longest run,
+ * then the lowest row, then the lowest column); below min_match a plain concatenation; an empty side returns the other.
+ * out_counts HOST int32[n]; seam_best_len / seam_best_send HOST int32[windows] (nullable; 0 where a side was empty).
+ * cfg nullable (32, 4).  One synchronisation. */
+fa_status fa_aed_merge_windows_dev(fa_ctx *ctx, const fa_aed_config *cfg, const int32_t *d_tokens, const int64_t *window_offsets,
+                                   const int64_t *recording_range, int64_t n_recordings, int32_t *d_out, const int64_t *out_range,
+                                   int32_t *out_counts, int32_t *seam_best_len, int32_t *seam_best_send);
+fa_status fa_aed_merge_windows(fa_ctx *ctx, const fa_aed_config *cfg, const int32_t *tokens, const int64_t *window_offsets,
+                               const int64_t *recording_range, int64_t n_recordings, int32_t *out, const int64_t *out_range,
+                               int32_t *out_counts, int32_t *seam_best_len, int32_t *seam_best_send);
+
 /* ------------------------------------------------------------------ AHC ------------- */
 /* Exact signature + status contract of the reference FFI
  * (FastClusterWrapper/include/FastClusterWrapper.h:35-41, FastClusterWrapper.cpp:196-244):
