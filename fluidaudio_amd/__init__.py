@@ -33,6 +33,9 @@ from .post import (ConstrainedClusterAssignment, HungarianAssignment, assign_emb
 from .resample import linear_resample, poly_taps, resample_poly  # noqa: F401
 from .sharding import gather_ragged_int32, shard_offsets, shard_range  # noqa: F401
 from .sortformer import OfflineSortformerConfig, OfflineSortformerDiarizer, offline_windows, pack_windows, stitch, stitcher_alignment  # noqa: F401
+from .sortformer_stream import (SORTFORMER_STREAM_PRESETS, SORTFORMER_STREAM_STATUS, SortformerStreamConfig, SortformerStreamSnapshot,  # noqa: F401
+                                SortformerStreamState, SortformerStreamUpdate, chunk_plan as sortformer_stream_chunk_plan, file_chunks as sortformer_stream_file_chunks,
+                                pack_chunks as sortformer_stream_pack_chunks)
 from .rnnt import (RNNT_BIAS_DEFAULT_BOOST, RNNT_BIAS_MAX_BOOST, RNNT_BIAS_MAX_FORM, RnntBias, RnntConfig, VocabularyTerm,  # noqa: F401
                    bias_build as rnnt_bias_build, bias_candidates as rnnt_bias_candidates, bias_effective_boost as rnnt_bias_effective_boost,
                    decode_logits as rnnt_decode_logits, fold as rnnt_fold)

@@ -74,6 +74,9 @@ EXPORTED_SYMBOLS = [
     "fa_online_chunk_default_config", "fa_online_chunk_plan_dev", "fa_online_chunk_plan", "fa_online_pack_waveforms_dev", "fa_online_chunk_finish_dev",
     "fa_aed_default_config", "fa_aed_max_out", "fa_aed_state_bytes", "fa_aed_begin_dev", "fa_aed_step_dev", "fa_aed_finish_dev", "fa_aed_finish", "fa_aed_cross_mask_dev",
     "fa_aed_encoder_valid_frames", "fa_aed_encoder_context_dev", "fa_aed_gather_hidden_dev", "fa_aed_plan_windows", "fa_aed_merge_windows_dev", "fa_aed_merge_windows",
+    "fa_sortformer_stream_default_config", "fa_sortformer_stream_preset_config", "fa_sortformer_stream_geometry", "fa_sortformer_stream_pop_out_length", "fa_sortformer_stream_create",
+    "fa_sortformer_stream_destroy", "fa_sortformer_stream_inputs", "fa_sortformer_stream_get", "fa_sortformer_stream_set", "fa_sortformer_stream_reset", "fa_sortformer_stream_update_dev",
+    "fa_sortformer_stream_update", "fa_sortformer_stream_chunk_plan", "fa_sortformer_stream_file_chunks", "fa_sortformer_stream_pack_chunks_dev",
 ]
 
 
@@ -282,6 +285,26 @@ class AedConfig(C.Structure):                                          # fa_aed_
     _fields_ = [("mode", C.c_int32), ("vocab", C.c_int32), ("eos_id", C.c_int32), ("max_seq", C.c_int32), ("max_new", C.c_int32), ("no_repeat_ngram", C.c_int32),
                 ("repetition_penalty", C.c_float), ("window_tokens", C.c_int32), ("min_match", C.c_int32), ("reserved", C.c_int32), ("chunk_samples", C.c_int64),
                 ("hop_samples", C.c_int64)]
+
+
+class SortformerStreamConfig(C.Structure):                             # fa_sortformer_stream_config
+    _fields_ = [(n, C.c_int32) for n in ("speakers", "d_model", "chunk_len", "chunk_left_context", "chunk_right_context", "fifo_len", "spkcache_len", "spkcache_update_period",
+                                         "sil_frames_per_spk", "max_index", "max_chunk_frames", "subsampling", "n_mels", "reserved")] + \
+               [(n, C.c_float) for n in ("silence_threshold", "pred_score_threshold", "scores_boost_latest", "strong_boost_rate", "weak_boost_rate", "min_pos_scores_rate")]
+
+
+class SortformerStreamGeometry(C.Structure):                           # fa_sortformer_stream_geometry_info
+    _fields_ = [(n, C.c_int32) for n in ("chunk_len", "spkcache_len", "spkcache_update_period", "max_pop", "score_rows", "out_rows", "chunk_mel_frames", "spkcache_len_per_spk",
+                                         "strong_boost_per_spk", "weak_boost_per_spk", "min_pos_scores_per_spk", "lds_bytes")]
+
+
+class SortformerStreamInfo(C.Structure):                               # fa_sortformer_stream_info
+    _fields_ = [(n, C.c_int32) for n in ("spkcache_length", "fifo_length", "spkcache_preds_present", "fifo_preds_present", "silence_frame_count", "reserved")]
+
+
+class SortformerChunk(C.Structure):                                    # fa_sortformer_chunk
+    _fields_ = [("ready", C.c_int32), ("chunk_length", C.c_int32), ("left_offset", C.c_int32), ("right_offset", C.c_int32), ("start_frame", C.c_int64), ("rows", C.c_int64),
+                ("new_start_feat", C.c_int64), ("frames_to_drop", C.c_int64)]
 
 
 class ExportEmbedding(C.Structure):                                    # fa_export_embedding
@@ -613,6 +636,25 @@ def lib() -> C.CDLL:
     L.fa_aed_plan_windows.argtypes = [ac, vp, i64, vp, vp, vp, i64, C.POINTER(i64)]
     L.fa_aed_merge_windows_dev.argtypes = [vp, ac, vp, vp, vp, i64, vp, vp, vp, vp, vp]
     L.fa_aed_merge_windows.argtypes = L.fa_aed_merge_windows_dev.argtypes
+    sc = C.POINTER(SortformerStreamConfig)
+    L.fa_sortformer_stream_default_config.argtypes = [sc]
+    L.fa_sortformer_stream_default_config.restype = None
+    L.fa_sortformer_stream_preset_config.argtypes = [i32, sc]
+    L.fa_sortformer_stream_geometry.argtypes = [sc, C.POINTER(SortformerStreamGeometry)]
+    L.fa_sortformer_stream_pop_out_length.argtypes = [sc, i32]
+    L.fa_sortformer_stream_pop_out_length.restype = i32
+    L.fa_sortformer_stream_create.argtypes = [vp, sc, i32, C.POINTER(vp)]
+    L.fa_sortformer_stream_destroy.argtypes = [vp]
+    L.fa_sortformer_stream_destroy.restype = None
+    L.fa_sortformer_stream_inputs.argtypes = [vp, vp] + [C.POINTER(vp)] * 4
+    L.fa_sortformer_stream_get.argtypes = [vp, vp, i32, C.POINTER(SortformerStreamInfo), vp, vp, vp, vp, vp]
+    L.fa_sortformer_stream_set.argtypes = L.fa_sortformer_stream_get.argtypes
+    L.fa_sortformer_stream_reset.argtypes = [vp, vp, i32]
+    L.fa_sortformer_stream_update_dev.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.fa_sortformer_stream_update.argtypes = L.fa_sortformer_stream_update_dev.argtypes
+    L.fa_sortformer_stream_chunk_plan.argtypes = [sc, vp, vp, i32, vp]
+    L.fa_sortformer_stream_file_chunks.argtypes = [sc, i64, i64, vp, i64, C.POINTER(i64), C.POINTER(i64)]
+    L.fa_sortformer_stream_pack_chunks_dev.argtypes = [vp, sc, vp, vp, vp, i32, vp]
     _lib = L
     return L
 

@@ -1884,4 +1884,102 @@ class SpeakerManager {
     fa_speaker_db *db_ = nullptr;
 };
 
+// ---- streaming Sortformer: the state between chunks (Diarizer/Sortformer/SortformerTypes.swift, SortformerStateUpdater.swift; the C
+// entries are batched over streams, this is ONE stream on host arrays).
+struct SortformerConfig {           // SortformerConfig with its presets; the clamps are the library's (fa_sortformer_stream_geometry)
+    fa_sortformer_stream_config c{};
+    SortformerConfig() { fa_sortformer_stream_default_config(&c); }
+    explicit SortformerConfig(int preset) {
+        if (fa_sortformer_stream_preset_config(preset, &c) != FA_SUCCESS) throw Error(FA_INVALID_ARGUMENT, "fa_sortformer_stream_preset_config", "no such preset");
+    }
+    static SortformerConfig balanced() { return SortformerConfig(FA_SORTFORMER_STREAM_PRESET_BALANCED); }
+    static SortformerConfig highContext() { return SortformerConfig(FA_SORTFORMER_STREAM_PRESET_HIGH_CONTEXT); }
+    static SortformerConfig efficient() { return SortformerConfig(FA_SORTFORMER_STREAM_PRESET_EFFICIENT); }
+    fa_sortformer_stream_geometry_info geometry() const {
+        fa_sortformer_stream_geometry_info g{};
+        if (fa_sortformer_stream_geometry(&c, &g) != FA_SUCCESS) throw Error(FA_INVALID_ARGUMENT, "fa_sortformer_stream_geometry", "the config is refused");
+        return g;
+    }
+    int chunkMelFrames() const { return geometry().chunk_mel_frames; }
+    // getNextChunkFeaturesLocked on a buffer of featLength frames
+    fa_sortformer_chunk nextChunk(int64_t featLength, int64_t startFeat) const {
+        fa_sortformer_chunk k{};
+        if (fa_sortformer_stream_chunk_plan(&c, &featLength, &startFeat, 1, &k) != FA_SUCCESS) throw Error(FA_INVALID_ARGUMENT, "fa_sortformer_stream_chunk_plan", "refused");
+        return k;
+    }
+    // SortformerFeatureLoader: every chunk of a file; numChunks (nullable) as the loader computes it
+    std::vector<fa_sortformer_chunk> fileChunks(int64_t featLength, int64_t featSeqLength, int64_t *numChunks = nullptr) const {
+        int64_t n = 0;
+        const fa_status st = fa_sortformer_stream_file_chunks(&c, featLength, featSeqLength, nullptr, 0, &n, numChunks);
+        if (st != FA_SUCCESS && st != FA_OUTPUT_TOO_SMALL) throw Error(st, "fa_sortformer_stream_file_chunks", "refused");
+        std::vector<fa_sortformer_chunk> out(static_cast<size_t>(n));
+        if (n > 0 && fa_sortformer_stream_file_chunks(&c, featLength, featSeqLength, out.data(), n, &n, numChunks) != FA_SUCCESS)
+            throw Error(FA_RUNTIME_ERROR, "fa_sortformer_stream_file_chunks", "the count changed");
+        return out;
+    }
+};
+
+struct StreamingUpdateResult {      // SortformerTypes.swift:398-420
+    std::vector<float> confirmed, tentative;
+    int numSpeakers = 0;
+    int status = FA_SORTFORMER_STREAM_OK;   // the reference throws; here the update's per-stream status
+    int confirmedFrameCount() const { return numSpeakers ? static_cast<int>(confirmed.size()) / numSpeakers : 0; }
+    int tentativeFrameCount() const { return numSpeakers ? static_cast<int>(tentative.size()) / numSpeakers : 0; }
+};
+
+class SortformerStreamingState {    // SortformerStreamingState + SortformerStateUpdater.streamingUpdate for one stream
+  public:
+    SortformerStreamingState(Context &ctx, const SortformerConfig &config = SortformerConfig()) : ctx_(ctx), cfg_(config), geo_(config.geometry()) {
+        ctx_.check(fa_sortformer_stream_create(ctx_.handle(), &cfg_.c, 1, &st_), "fa_sortformer_stream_create");
+    }
+    ~SortformerStreamingState() { fa_sortformer_stream_destroy(st_); }
+    SortformerStreamingState(const SortformerStreamingState &) = delete;
+    SortformerStreamingState &operator=(const SortformerStreamingState &) = delete;
+
+    // chunk: [rows][d_model] flattened, preds: [rows][speakers] flattened, as the reference takes them
+    StreamingUpdateResult streamingUpdate(const std::vector<float> &chunk, const std::vector<float> &preds, int leftContext, int rightContext) {
+        const size_t D = static_cast<size_t>(cfg_.c.d_model), S = static_cast<size_t>(cfg_.c.speakers), M = static_cast<size_t>(geo_.out_rows);
+        if (chunk.size() % D != 0 || chunk.size() / D > M) throw Error(FA_INVALID_ARGUMENT, "fa_sortformer_stream_update", "a chunk of at most max_chunk_frames rows of d_model");
+        std::vector<float> embs(M * D, 0.0f), conf(M * S), tent(M * S);
+        std::copy(chunk.begin(), chunk.end(), embs.begin());
+        const int32_t embLen = static_cast<int32_t>(chunk.size() / D), predRows = static_cast<int32_t>(preds.size() / S), lc = leftContext, rc = rightContext;
+        int32_t counts[2] = {0, 0}, status = 0;
+        const float none = 0.0f;
+        ctx_.check(fa_sortformer_stream_update(ctx_.handle(), st_, embs.data(), FA_DTYPE_F32, &embLen, preds.empty() ? &none : preds.data(), predRows > 0 ? predRows : 1, &predRows,
+                                               &lc, &rc, nullptr, conf.data(), tent.data(), counts, &status, nullptr), "fa_sortformer_stream_update");
+        StreamingUpdateResult r;
+        r.numSpeakers = cfg_.c.speakers; r.status = status;
+        r.confirmed.assign(conf.begin(), conf.begin() + static_cast<ptrdiff_t>(counts[0] * S));
+        r.tentative.assign(tent.begin(), tent.begin() + static_cast<ptrdiff_t>(counts[1] * S));
+        return r;
+    }
+    fa_sortformer_stream_info info() {
+        fa_sortformer_stream_info i{};
+        ctx_.check(fa_sortformer_stream_get(ctx_.handle(), st_, 0, &i, nullptr, nullptr, nullptr, nullptr, nullptr), "fa_sortformer_stream_get");
+        return i;
+    }
+    int spkcacheLength() { return info().spkcache_length; }
+    int fifoLength() { return info().fifo_length; }
+    int silenceFrameCount() { return info().silence_frame_count; }
+    std::vector<float> spkcache() { return rows(0, geo_.spkcache_len, cfg_.c.d_model, info().spkcache_length); }
+    std::vector<float> fifo() { return rows(2, cfg_.c.fifo_len, cfg_.c.d_model, info().fifo_length); }
+    std::vector<float> meanSilenceEmbedding() { return rows(4, 1, cfg_.c.d_model, 1); }
+    void cleanup() { ctx_.check(fa_sortformer_stream_reset(ctx_.handle(), st_, 0), "fa_sortformer_stream_reset"); }
+
+  private:
+    std::vector<float> rows(int which, int capacity, int width, int length) {   // the first `length` rows of one of get's arrays
+        std::vector<float> all(static_cast<size_t>(capacity) * width);
+        float *p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        p[which] = all.data();
+        fa_sortformer_stream_info i{};
+        ctx_.check(fa_sortformer_stream_get(ctx_.handle(), st_, 0, &i, p[0], p[1], p[2], p[3], p[4]), "fa_sortformer_stream_get");
+        all.resize(static_cast<size_t>(length) * width);
+        return all;
+    }
+    Context &ctx_;
+    SortformerConfig cfg_;
+    fa_sortformer_stream_geometry_info geo_{};
+    fa_sortformer_stream *st_ = nullptr;
+};
+
 }  // namespace fluidaudio

@@ -1632,6 +1632,136 @@ fa_status fa_online_chunk_finish_dev(fa_ctx *ctx, const fa_online_chunk_config *
                                      int64_t tick, fa_online_segment *segments, int64_t capacity, int64_t *count, int32_t *chunk_counts,
                                      fa_speaker_assignment *d_assignments);
 
+/* ------------------------------------------------------------------ streaming Sortformer: FIFO and speaker cache ------ */
+/* The state streaming Sortformer carries between chunks (Sources/FluidAudio/Diarizer/Sortformer/SortformerStateUpdater.swift:31-578,
+ * driven by SortformerDiarizer.swift:514-578, 933-979 and SortformerTypes.swift:264-385) as device-resident state, batched over streams:
+ * the FIFO of recent embeddings, the speaker cache with its compression, the silence profile.  One stream is one
+ * SortformerStreamingState; the network stays the caller's and reads the state's slabs in place.
+ *
+ * Everything behind the base scores is IEEE fp32 add / multiply / divide (unfused) and comparisons, in the reference's order, and equals
+ * the reference bit for bit given the same base scores.  The base scores themselves go through logf / log1pf, which no two libraries
+ * round alike (the reference's are vForce's): they are the library's own, and fa_sortformer_stream_update_dev hands them out.
+ * The library's own definitions beside the reference:
+ *   refusals     the reference throws for short preds or a short chunk; here a per-stream status, the stream's state unchanged, the
+ *                other streams advanced.  A negative core count, an operand outside its array, and a pred that is NaN or outside
+ *                [0, 1] among the rows the update reads are refused as well (the reference traps or carries the NaN into the cache)
+ *   max_index    a config whose live permuted indices could reach the sentinel is refused at creation
+ *   d_model      a multiple of 4 (16-byte accesses) */
+typedef struct fa_sortformer_stream fa_sortformer_stream;
+typedef struct {
+    int32_t speakers;                 /* 1 .. 4 (4) */
+    int32_t d_model;                  /* preEncoderDims (512); a multiple of 4 */
+    int32_t chunk_len;                /* 6; clamped to >= 1 */
+    int32_t chunk_left_context;       /* 1 */
+    int32_t chunk_right_context;      /* 7 */
+    int32_t fifo_len;                 /* 40 */
+    int32_t spkcache_len;             /* 188; clamped to >= (1 + sil_frames_per_spk) * speakers */
+    int32_t spkcache_update_period;   /* 31; clamped to chunk_len .. fifo_len + chunk_len */
+    int32_t sil_frames_per_spk;       /* 3 */
+    int32_t max_index;                /* 99999: the sentinel of a disabled slot */
+    int32_t max_chunk_frames;         /* rows of one chunk's embeddings: chunk_len + both contexts (14) */
+    int32_t subsampling;              /* 8 mel frames per model frame */
+    int32_t n_mels;                   /* 128 */
+    int32_t reserved;
+    float silence_threshold;          /* 0.2 */
+    float pred_score_threshold;       /* 0.25 */
+    float scores_boost_latest;        /* 0.05 */
+    float strong_boost_rate;          /* 0.75 */
+    float weak_boost_rate;            /* 1.5 */
+    float min_pos_scores_rate;        /* 0.5 */
+} fa_sortformer_stream_config;
+/* SortformerConfig.default (= fastV2 = fastV2_1), balancedV2(_1), highContextV2(_1), efficientV2_1 (SortformerTypes.swift:121-216) */
+enum { FA_SORTFORMER_STREAM_PRESET_DEFAULT = 0, FA_SORTFORMER_STREAM_PRESET_BALANCED = 1, FA_SORTFORMER_STREAM_PRESET_HIGH_CONTEXT = 2,
+       FA_SORTFORMER_STREAM_PRESET_EFFICIENT = 3 };
+/* Per-stream status of an update.  OK: advanced.  INACTIVE: d_active was 0, nothing looked at.  Every other one: refused, state unchanged. */
+enum { FA_SORTFORMER_STREAM_OK = 0, FA_SORTFORMER_STREAM_INACTIVE = 1, FA_SORTFORMER_STREAM_SHORT_PREDS_FIFO = 2, FA_SORTFORMER_STREAM_SHORT_CHUNK = 3,
+       FA_SORTFORMER_STREAM_SHORT_PREDS_CHUNK = 4, FA_SORTFORMER_STREAM_SHORT_PREDS_TENTATIVE = 5, FA_SORTFORMER_STREAM_NEGATIVE_CORE = 6,
+       FA_SORTFORMER_STREAM_BAD_PRED = 7, FA_SORTFORMER_STREAM_BAD_OPERAND = 8 };
+typedef struct {   /* what the clamped config comes to */
+    int32_t chunk_len, spkcache_len, spkcache_update_period;   /* after the clamps */
+    int32_t max_pop;            /* rows one pop can take */
+    int32_t score_rows;         /* spkcache_len + max_pop: the row stride of d_log_scores */
+    int32_t out_rows;           /* = max_chunk_frames: the row stride of d_confirmed and d_tentative */
+    int32_t chunk_mel_frames;   /* (chunk_len + both contexts) * subsampling: the rows of one packed chunk */
+    int32_t spkcache_len_per_spk, strong_boost_per_spk, weak_boost_per_spk, min_pos_scores_per_spk;   /* :229-232, Int(Float(x) * rate) */
+    int32_t lds_bytes;          /* of the control kernel */
+} fa_sortformer_stream_geometry_info;
+typedef struct { int32_t spkcache_length, fifo_length, spkcache_preds_present, fifo_preds_present, silence_frame_count, reserved; } fa_sortformer_stream_info;
+typedef struct {   /* one chunk of mel frames for the network */
+    int32_t ready;              /* 0: not enough frames yet (the other fields 0, new_start_feat = start_feat) */
+    int32_t chunk_length;       /* the network's length input */
+    int32_t left_offset, right_offset;   /* mel frames of context in the chunk */
+    int64_t start_frame;        /* the chunk's first frame in the buffer */
+    int64_t rows;               /* frames copied (= chunk_length while streaming) */
+    int64_t new_start_feat;     /* startFeat afterwards */
+    int64_t frames_to_drop;     /* frames to remove from the buffer's front afterwards */
+} fa_sortformer_chunk;
+void fa_sortformer_stream_default_config(fa_sortformer_stream_config *cfg);
+fa_status fa_sortformer_stream_preset_config(int32_t preset, fa_sortformer_stream_config *cfg);
+/* The clamps applied and the derived integers; INVALID_ARGUMENT for a config fa_sortformer_stream_create refuses.  Pure host functions.
+ * pop_out_length: min(max(period, context - fifo_len), context) for a context above fifo_len, 0 otherwise, -1 for an unsound config. */
+fa_status fa_sortformer_stream_geometry(const fa_sortformer_stream_config *cfg, fa_sortformer_stream_geometry_info *out);
+int32_t fa_sortformer_stream_pop_out_length(const fa_sortformer_stream_config *cfg, int32_t context_length);
+/* INVALID_ARGUMENT, with nothing allocated or launched, for NULL pointers, streams outside 1 .. 65535, speakers outside 1 .. 4, a d_model
+ * that is no multiple of 4, negative lengths, rates outside [0, 1024], a pred_score_threshold outside (0, 1), a config where
+ * speakers * (spkcache_len + max_pop + sil_frames_per_spk) reaches max_index, or one whose scored rows exceed the control kernel's LDS.
+ * Every stream starts empty (SortformerStreamingState.init).  The state belongs to the context's device. */
+fa_status fa_sortformer_stream_create(fa_ctx *ctx, const fa_sortformer_stream_config *cfg, int32_t streams, fa_sortformer_stream **out);
+void fa_sortformer_stream_destroy(fa_sortformer_stream *st);
+/* What the batched network reads in place: float[streams][spkcache_len][d_model], int32[streams], float[streams][fifo_len][d_model],
+ * int32[streams]; rows past a length are zero.  The four DEVICE pointers are fixed for the state's lifetime (a caller may capture its
+ * model call in a graph).  Any of the four may be NULL. */
+fa_status fa_sortformer_stream_inputs(fa_ctx *ctx, fa_sortformer_stream *st, float **d_spkcache, int32_t **d_spkcache_lengths, float **d_fifo,
+                                      int32_t **d_fifo_lengths);
+/* One stream's whole state to and from HOST arrays (session restore): spkcache float[spkcache_len][d_model], spkcache_preds
+ * float[spkcache_len][speakers], fifo float[fifo_len][d_model], fifo_preds float[fifo_len][speakers], mean_silence float[d_model]; rows past a
+ * length are zero, preds that are absent read as zeros.  get: any array may be NULL; waits for the context's stream.  set: takes the rows
+ * of the lengths; INVALID_ARGUMENT for lengths outside the slabs, a FIFO with rows but no preds, preds outside [0, 1].  reset =
+ * cleanup() for one stream, or for all with stream -1; enqueued on the context's stream. */
+fa_status fa_sortformer_stream_get(fa_ctx *ctx, fa_sortformer_stream *st, int32_t stream, fa_sortformer_stream_info *info, float *spkcache,
+                                   float *spkcache_preds, float *fifo, float *fifo_preds, float *mean_silence);
+fa_status fa_sortformer_stream_set(fa_ctx *ctx, fa_sortformer_stream *st, int32_t stream, const fa_sortformer_stream_info *info, const float *spkcache,
+                                   const float *spkcache_preds, const float *fifo, const float *fifo_preds, const float *mean_silence);
+fa_status fa_sortformer_stream_reset(fa_ctx *ctx, fa_sortformer_stream *st, int32_t stream);
+/* streamingUpdate (:31-165) for every stream in one call.  DEVICE pointers: d_chunk_embs [streams][max_chunk_frames][d_model] (16-byte
+ * aligned; emb_dtype FA_DTYPE_F32 or FA_DTYPE_F16, widened on load), d_emb_len int32[streams] the rows of each chunk, d_preds
+ * float[streams][pred_stride][speakers] with d_pred_rows int32[streams] valid rows, d_left / d_right int32[streams] the context rows of
+ * this chunk, d_active int32[streams] (nullable; 0: the stream is not looked at).  Out: d_confirmed and d_tentative
+ * float[streams][max_chunk_frames][speakers], d_counts int32[streams][2] their rows, d_status int32[streams], d_log_scores (nullable)
+ * float[streams][score_rows][speakers]: the base scores (getLogPredScores) of the rows a compression scored, the cache's rows first;
+ * rows of a stream that did not compress are left untouched.
+ *   per stream: validate (FIFO rows, rc >= 0, core = emb_len - lc - rc >= 0, chunk and tentative rows at spkcacheLength + fifoLength + lc,
+ *   every pred read in [0, 1]) before the first write; the FIFO's preds replaced from this call's; the core rows appended; if
+ *   core + fifoLength > fifo_len: pop min(max(period, context - fifo_len), context) rows, the silence profile over them in frame order
+ *   ((mean * n + x) / (n + 1), unfused), the rows appended to the speaker cache, and beyond spkcache_len the first-overflow
+ *   initialisation and compressSpkcache (:220-305): base scores, disableLowScores, the latest rows' boost, the strong and the weak boost as
+ *   "the first min(k, frames) in the order (score descending, frame ascending)", the +inf placeholder rows, the global selection as "the
+ *   first spkcache_len in the order (score descending, permuted index ascending)", then the gather through scratch.
+ * Four launches whatever the streams do, nothing allocated, nothing waited for. */
+fa_status fa_sortformer_stream_update_dev(fa_ctx *ctx, fa_sortformer_stream *st, const void *d_chunk_embs, int32_t emb_dtype, const int32_t *d_emb_len,
+                                          const float *d_preds, int32_t pred_stride, const int32_t *d_pred_rows, const int32_t *d_left, const int32_t *d_right,
+                                          const int32_t *d_active, float *d_confirmed, float *d_tentative, int32_t *d_counts, int32_t *d_status,
+                                          float *d_log_scores);
+/* the same on HOST arrays: staged, run, copied back, one synchronisation; rows past a stream's counts are left untouched */
+fa_status fa_sortformer_stream_update(fa_ctx *ctx, fa_sortformer_stream *st, const void *chunk_embs, int32_t emb_dtype, const int32_t *emb_len,
+                                      const float *preds, int32_t pred_stride, const int32_t *pred_rows, const int32_t *left, const int32_t *right,
+                                      const int32_t *active, float *confirmed, float *tentative, int32_t *counts, int32_t *status, float *log_scores);
+/* getNextChunkFeaturesLocked (SortformerDiarizer.swift:933-979) for `streams` buffers of feat_frames[b] mel frames whose next core starts
+ * at start_feat[b]: out[streams].  Pure host function. */
+fa_status fa_sortformer_stream_chunk_plan(const fa_sortformer_stream_config *cfg, const int64_t *feat_frames, const int64_t *start_feat, int32_t streams,
+                                          fa_sortformer_chunk *out);
+/* SortformerFeatureLoader (SortformerTypes.swift:347-383) for a file of feat_length frames whose mel is valid up to feat_seq_length: every
+ * chunk next() returns, chunk_length clamped by feat_seq_length; *num_chunks (nullable) = max(0, (feat_length - rc) / chunk).  *count is
+ * set even when chunks is too small (OUTPUT_TOO_SMALL).  Pure host function. */
+fa_status fa_sortformer_stream_file_chunks(const fa_sortformer_stream_config *cfg, int64_t feat_length, int64_t feat_seq_length, fa_sortformer_chunk *chunks,
+                                           int64_t capacity, int64_t *count, int64_t *num_chunks);
+/* The network's chunk rows: d_rows float[streams][chunk_mel_frames * n_mels], row b the chunk's `rows` frames from start_frame of stream
+ * b's frame-major buffer (d_mel + stream_offsets[b] * n_mels floats; stream_offsets and chunks HOST [streams]), copied as bits, zeros
+ * behind them; a stream that is not ready gets a row of zeros.  The row copy is the TDT planner's (the records travel in the launches'
+ * arguments): no synchronisation. */
+fa_status fa_sortformer_stream_pack_chunks_dev(fa_ctx *ctx, const fa_sortformer_stream_config *cfg, const float *d_mel, const int64_t *stream_offsets,
+                                               const fa_sortformer_chunk *chunks, int32_t streams, float *d_rows);
+
 /* ------------------------------------------------------------------ resampling ------ */
 /* AudioConverter.linearResample (FluidAudio/Shared/AudioConverter.swift:388-442): planar float[channels][frames] ->
  * mono mix (weight 1/channels) -> linear interpolation to out_rate.  HOST pointers.  Bit-exact restatement. */
