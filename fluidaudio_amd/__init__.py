@@ -16,6 +16,9 @@ from .der import DERResult, DERSpeakerSegment, compute_der, compute_der_batch, s
 from .kws import KWS_DETECTION_DTYPE, KWS_WINDOW_DTYPE, adjusted_threshold, score_windows, spot_keywords_batch  # noqa: F401
 from .embedding import EmbeddingConfig, EmbeddingPlan, plan_embeddings, span_inputs, weight_resample  # noqa: F401
 from .formats import AudioWAV, RTTMParser, RTTMParserError, TimedSpeakerSegment, export_embeddings_json  # noqa: F401
+from .fsmn_vad import (fsmn_vad_config, fsmn_vad_frame_count, fsmn_vad_gather_silence_dev,  # noqa: F401
+                       fsmn_vad_pack_feats_dev, fsmn_vad_pack_waveforms, fsmn_vad_pack_waveforms_dev, fsmn_vad_plan_chunks, fsmn_vad_segments,
+                       fsmn_vad_segments_dev)
 from .kmeans import KMeansClustering, SeededRNG, SpeakerCountConstraints  # noqa: F401
 from .mel import AudioMelSpectrogram, LuxTtsMelExtractor, MelPlan, UnifiedMelExtractor  # noqa: F401
 from .paraformer import (PARAFORMER_SPAN_DTYPE, CifResult, ParaformerConfig, TimestampedSegment, cif_batch, cif_batch_dev, decode_tokens,  # noqa: F401

@@ -65,6 +65,8 @@ EXPORTED_SYMBOLS = [
     "fa_tdt_merge_default_config", "fa_tdt_merge_windows_dev", "fa_tdt_merge_windows",
     "fa_vad_default_config", "fa_vad_chunk_count", "fa_vad_segments_dev", "fa_vad_segments", "fa_vad_pack_chunks_dev", "fa_vad_pack_chunks",
     "fa_vad_gather_segments_dev", "fa_vad_gather_segments", "fa_vad_stream_advance_dev", "fa_vad_stream_advance",
+    "fa_fsmn_vad_default_config", "fa_fsmn_vad_frame_count", "fa_fsmn_vad_plan_chunks", "fa_fsmn_vad_pack_waveforms_dev", "fa_fsmn_vad_pack_waveforms",
+    "fa_fsmn_vad_pack_feats_dev", "fa_fsmn_vad_gather_silence_dev", "fa_fsmn_vad_segments_dev", "fa_fsmn_vad_segments",
     "fa_tdt_window_default_config", "fa_tdt_window_layout", "fa_tdt_window_count_bound", "fa_tdt_plan_windows_dev", "fa_tdt_plan_windows",
     "fa_tdt_pack_windows_dev", "fa_tdt_pack_windows", "fa_tdt_speech_gate_dev", "fa_tdt_speech_gate",
     "fa_rnnt_bias_effective_boost", "fa_rnnt_bias_build", "fa_rnnt_bias_candidates", "fa_rnnt_default_config", "fa_rnnt_greedy_logits_dev",
@@ -225,6 +227,20 @@ class VadStreamStateRecord(C.Structure):
 
 class VadStreamEventRecord(C.Structure):
     _fields_ = [("stream", C.c_int32), ("chunk", C.c_int32), ("kind", C.c_int32), ("reserved", C.c_int32), ("sample_index", C.c_int64), ("time", C.c_double)]
+
+
+class FsmnVadConfig(C.Structure):                                      # fa_fsmn_vad_config
+    _fields_ = [("silence_threshold", C.c_float)] + [(n, C.c_int32) for n in ("window_frames", "sil_to_speech_frames", "speech_to_sil_frames", "max_end_silence_frames",
+                                                                                "lookback_frames", "lookahead_frames", "max_segment_frames", "frame_ms")]
+
+
+class FsmnVadChunkRecord(C.Structure):                                 # fa_fsmn_vad_chunk
+    _fields_ = [("recording", C.c_int32), ("bucket", C.c_int32), ("start_sample", C.c_int64), ("end_sample", C.c_int64), ("frames", C.c_int32), ("keep_from", C.c_int32),
+                ("first_frame", C.c_int64)]
+
+
+class FsmnVadSegmentRecord(C.Structure):                               # fa_fsmn_vad_segment
+    _fields_ = [("recording", C.c_int32), ("reason", C.c_int32), ("start_frame", C.c_int32), ("end_frame", C.c_int32), ("start_ms", C.c_int64), ("end_ms", C.c_int64)]
 
 
 class TdtWindowConfig(C.Structure):
@@ -570,6 +586,18 @@ def lib() -> C.CDLL:
     L.fa_vad_gather_segments.argtypes = L.fa_vad_gather_segments_dev.argtypes
     L.fa_vad_stream_advance_dev.argtypes = [vp, C.POINTER(VadSegmentationConfig), vp, vp, vp, i32, i32, vp, i32, i32, vp, i64, C.POINTER(i64)]
     L.fa_vad_stream_advance.argtypes = L.fa_vad_stream_advance_dev.argtypes
+    fc = C.POINTER(FsmnVadConfig)
+    L.fa_fsmn_vad_default_config.argtypes = [fc]
+    L.fa_fsmn_vad_default_config.restype = None
+    L.fa_fsmn_vad_frame_count.argtypes = [i64]
+    L.fa_fsmn_vad_frame_count.restype = i64
+    L.fa_fsmn_vad_plan_chunks.argtypes = [vp, i32, vp, i64, C.POINTER(i64), vp, vp]
+    L.fa_fsmn_vad_pack_waveforms_dev.argtypes = [vp, vp, vp, i32, vp, i64, vp, i64, i64]
+    L.fa_fsmn_vad_pack_waveforms.argtypes = L.fa_fsmn_vad_pack_waveforms_dev.argtypes
+    L.fa_fsmn_vad_pack_feats_dev.argtypes = [vp, vp, i32, i64, vp, i64, i32, vp]
+    L.fa_fsmn_vad_gather_silence_dev.argtypes = [vp, vp, i32, i32, i32, vp, i64, vp, i32, vp, i64]
+    L.fa_fsmn_vad_segments_dev.argtypes = [vp, fc, vp, vp, i32, vp, i64, C.POINTER(i64), vp]
+    L.fa_fsmn_vad_segments.argtypes = L.fa_fsmn_vad_segments_dev.argtypes
     L.fa_tdt_window_default_config.argtypes = [C.POINTER(TdtWindowConfig)]
     L.fa_tdt_window_default_config.restype = None
     L.fa_tdt_window_layout.argtypes = [C.POINTER(TdtWindowConfig)] + [C.POINTER(i64)] * 4

@@ -7,7 +7,7 @@
 // 71-234), the model rows of processAudioSamples / processChunk (VadManager.swift:162-206, 352-376), the bounds of segmentSpeechAudio
 // (:55-67) and streamingStateMachine (VadManager+Streaming.swift:31-107).
 // OUT OF SCOPE: the Silero network and its LSTM state (the caller's: they run the model on the packed rows), isSilentAudio
-// (VadManager.swift:157-160), and FSMN-VAD (VAD/Fsmn/: its decide and its chunk schedule).
+// (VadManager.swift:157-160).  FSMN-VAD (VAD/Fsmn/: its decide and its chunk schedule) is fsmn_vad_launch.h.
 //
 // The raw speeches of one recording (before the padding) start on frame boundaries, each on a frame of its own: a speech that follows a
 // cut starts where the chosen silence ended, behind the end of the one before it.  The frame of a cut that resumes does go on to the

@@ -3,7 +3,7 @@ config:) with detectSpeechSampleRanges (reference: Sources/FluidAudio/VAD/VadMan
 input rows of processAudioSamples / processChunk (VadManager.swift:162-206, 352-376), the audio of segmentSpeechAudio (:55-67) and
 streamingStateMachine (VadManager+Streaming.swift:31-107).  Integers, fp32 comparisons and fp64 divisions: the outputs are the reference's
 bit for bit.  OUT OF SCOPE: the Silero network and its LSTM state (the caller runs the model on the packed rows and hands the
-probabilities back), isSilentAudio, and FSMN-VAD (VAD/Fsmn/)."""
+probabilities back) and isSilentAudio.  FSMN-VAD (VAD/Fsmn/) is fsmn_vad.py."""
 from __future__ import annotations
 
 import ctypes as C

@@ -1631,6 +1631,48 @@ struct VadManager {
     }
 };
 
+// ---- FSMN-VAD (Sources/FluidAudio/VAD/Fsmn/FsmnVadManager.swift) for ONE recording; the batched forms are the C entries
+struct FsmnVadSegment {                      // :5-8
+    int64_t startMs = 0, endMs = 0;
+    bool operator==(const FsmnVadSegment &o) const { return startMs == o.startMs && endMs == o.endMs; }
+};
+
+// The decision constants the reference keeps private (:37-45); their bounds are the refusals of the entries they are handed to.
+struct FsmnVadConfig {
+    float silenceThreshold = 0.2f;
+    int windowFrames = 20, silToSpeech = 15, speechToSil = 15, maxEndSilenceFrames = 80, lookbackFrames = 20, lookaheadFrames = 10, maxSegmentFrames = 6000, frameMs = 10;
+    fa_fsmn_vad_config abi() const {
+        return fa_fsmn_vad_config{silenceThreshold, windowFrames, silToSpeech, speechToSil, maxEndSilenceFrames, lookbackFrames, lookaheadFrames, maxSegmentFrames, frameMs};
+    }
+};
+
+struct FsmnVadManager {
+    static constexpr int hopSamples = 160, fbankWindowSamples = 400, lfrPadFrames = 2, featureDim = 400;
+    FsmnVadConfig config;
+    static int64_t lfrFrameCount(int64_t samples) { return fa_fsmn_vad_frame_count(samples); }
+    // the chunks concatenateChunks scores, with the frame each one's first kept frame lands at
+    static std::vector<fa_fsmn_vad_chunk> chunks(int64_t sampleCount, int64_t *frames = nullptr) {
+        int64_t count = 0, chunkRange[2] = {0, 0}, frameRange[2] = {0, 0};
+        fa_status st = fa_fsmn_vad_plan_chunks(&sampleCount, 1, nullptr, 0, &count, chunkRange, frameRange);
+        std::vector<fa_fsmn_vad_chunk> out(static_cast<size_t>(count));
+        if (st == FA_SUCCESS) st = fa_fsmn_vad_plan_chunks(&sampleCount, 1, out.data(), count, &count, chunkRange, frameRange);
+        if (st != FA_SUCCESS) throw Error(st, "fa_fsmn_vad_plan_chunks");
+        if (frames) *frames = frameRange[1];
+        return out;
+    }
+    // decide on the silence probabilities the scorer gave, one per 10 ms frame
+    std::vector<FsmnVadSegment> decide(Context &ctx, const std::vector<float> &silence) const {
+        const fa_fsmn_vad_config c = config.abi();
+        const int64_t range[2] = {0, static_cast<int64_t>(silence.size())};
+        std::vector<fa_fsmn_vad_segment> segs(silence.size());                   // at most one segment per frame
+        int64_t count = 0;
+        ctx.check(fa_fsmn_vad_segments(ctx.handle(), &c, silence.data(), range, 1, segs.data(), static_cast<int64_t>(segs.size()), &count, nullptr), "fa_fsmn_vad_segments");
+        std::vector<FsmnVadSegment> out;
+        for (int64_t i = 0; i < count; ++i) out.push_back(FsmnVadSegment{segs[static_cast<size_t>(i)].start_ms, segs[static_cast<size_t>(i)].end_ms});
+        return out;
+    }
+};
+
 // ---- TDT long-form: planning the windows (ChunkProcessor.swift; the C entries are batched over recordings, this is ONE recording)
 struct ChunkLayout {                         // chunkLayout's tuple (:140-161)
     int64_t chunkSamples = 0, strideSamples = 0, melContextSamples = 0, warmupPrefixSamples = 0;

@@ -1287,7 +1287,7 @@ fa_status fa_tdt_merge_windows(fa_ctx *ctx, const fa_tdt_merge_config *cfg, cons
  * (VadManager+Streaming.swift:31-107).  Integers, fp32 comparisons and fp64 divisions in the reference's order: the outputs are the
  * reference's bit for bit (pinned by its VadSegmentationTests / VadStreamingTests through tests/vad_restatement.py).  Frames are
  * chunks of 4096 samples at 16 kHz; a model row is 64 context samples and 4096 chunk samples.  OUT OF SCOPE: the Silero network and its
- * LSTM state (the caller's), isSilentAudio, FSMN-VAD (VAD/Fsmn/).
+ * LSTM state (the caller's), isSilentAudio.  FSMN-VAD (VAD/Fsmn/) has the section after this one.
  * Conventions of the four entries: cfg nullable = the defaults; _dev takes DEVICE pointers where it says so and reads them in stream
  * order; *count is set even when the output is NULL (SUCCESS) or too small (OUTPUT_TOO_SMALL, the first `capacity` records written);
  * every refusal is decided before any device work; batch == 0: SUCCESS; one host synchronisation unless stated otherwise. */
@@ -1356,6 +1356,72 @@ fa_status fa_vad_stream_advance(fa_ctx *ctx, const fa_vad_segmentation_config *c
                                 const int32_t *chunk_samples, int32_t streams, int32_t max_chunks, fa_vad_stream_state *states,
                                 int32_t return_seconds, int32_t time_resolution, fa_vad_stream_event *events, int64_t capacity,
                                 int64_t *count);
+
+/* ------------------------------------------------------------------ FSMN-VAD: chunk schedule, model rows, segments ------ */
+/* The host arithmetic round the two networks of FsmnVadManager (FluidAudio/VAD/Fsmn/FsmnVadManager.swift), batched over recordings:
+ * the chunk schedule of concatenateChunks (:91-109) with lfrFrameCount (:113-117), the rows of chunkSilence (:119-155: the scaled
+ * waveform, the zero-padded bucket of features, column 0 of the scores onto the recording's frame grid) and decide (:159-201).
+ * Integers and one fp32 comparison per frame: the outputs are the reference's, quirks included (tests/fsmn_vad_restatement.py restates
+ * the lines; with equal thresholds a window count of exactly that value flips preSpeech on every frame, and the segment behind a
+ * maximal-length close starts inside the one before it).  Frames are 10 ms of 16 kHz audio.  OUT OF SCOPE: the preprocessor and the
+ * scorer (the caller's), detect(audioURL:)'s file reading and resampling (fa_resample_poly), isSilentAudio.
+ * The conventions are those stated above fa_vad_segmentation_config. */
+typedef struct {
+    float silence_threshold;                          /* a frame is speech when p <= threshold: a NaN is not speech */
+    int32_t window_frames;                            /* 1 ... 64 */
+    int32_t sil_to_speech_frames, speech_to_sil_frames;   /* window counts, each 0 ... window_frames */
+    int32_t max_end_silence_frames;                   /* >= 1 */
+    int32_t lookback_frames, lookahead_frames;        /* >= 0 */
+    int32_t max_segment_frames;                       /* >= 1 */
+    int32_t frame_ms;                                 /* >= 1 */
+} fa_fsmn_vad_config;
+void fa_fsmn_vad_default_config(fa_fsmn_vad_config *cfg);     /* 0.2; 20, 15, 15; 80; 20, 10; 6000; 10 */
+/* bucket: the first of 512 / 1024 / 2048 / 3072 that holds `frames`.  keep_from: 0 for a recording's first chunk, else 2 (the frames
+ * computed against replicate padding).  first_frame: the frame of the recording at which the chunk's first kept frame lands. */
+typedef struct { int32_t recording, bucket; int64_t start_sample, end_sample; int32_t frames, keep_from; int64_t first_frame; } fa_fsmn_vad_chunk;
+#define FA_FSMN_VAD_END_SILENCE 0
+#define FA_FSMN_VAD_MAX_LENGTH 1
+#define FA_FSMN_VAD_END_OF_AUDIO 2
+typedef struct { int32_t recording, reason; int32_t start_frame, end_frame; int64_t start_ms, end_ms; } fa_fsmn_vad_segment;
+int64_t fa_fsmn_vad_frame_count(int64_t samples);     /* lfrFrameCount: 0 below 400 samples, else max(0, (samples - 400) / 160 - 1) */
+/* The chunks of every recording (no context, no device).  total_samples HOST int64[batch]; chunks HOST [capacity] (nullable), by
+ * recording and time; chunk_range and frame_range HOST int64[batch + 1], written before the capacity is judged: recording b's chunks
+ * and the frames of its concatenated probabilities.  A chunk whose frames do not exceed keep_from is dropped and ends its recording,
+ * as the reference's loop ends; samples <= 0 plan nothing.  INVALID_ARGUMENT for a negative count or a missing array. */
+fa_status fa_fsmn_vad_plan_chunks(const int64_t *total_samples, int32_t batch, fa_fsmn_vad_chunk *chunks, int64_t capacity, int64_t *count,
+                                  int64_t *chunk_range, int64_t *frame_range);
+/* rows float[row_capacity][row_stride]: row c is audio[start_sample ... end_sample) of chunk c's recording times 32768.0f (one fp32
+ * multiply), zeros up to row_stride.  audio_offsets HOST int64[batch + 1] as for fa_vad_pack_chunks; chunks HOST [n_chunks].
+ * INVALID_ARGUMENT for a chunk outside its recording or longer than row_stride; OUTPUT_TOO_SMALL when row_capacity is below n_chunks:
+ * nothing is written.  _dev: audio and rows are DEVICE pointers and the entry does NOT synchronise. */
+fa_status fa_fsmn_vad_pack_waveforms_dev(fa_ctx *ctx, const float *d_audio, const int64_t *audio_offsets, int32_t batch,
+                                         const fa_fsmn_vad_chunk *chunks, int64_t n_chunks, float *d_rows, int64_t row_stride,
+                                         int64_t row_capacity);
+fa_status fa_fsmn_vad_pack_waveforms(fa_ctx *ctx, const float *audio, const int64_t *audio_offsets, int32_t batch,
+                                     const fa_fsmn_vad_chunk *chunks, int64_t n_chunks, float *rows, int64_t row_stride,
+                                     int64_t row_capacity);
+/* The scorer's input: d_feats [n_chunks][feat_stride][400] (dtype FA_DTYPE_F32 or FA_DTYPE_F16, widened exactly) -> d_out
+ * float[n_chunks][bucket][400]; a chunk's first `frames` rows are copied, the others are zero.  INVALID_ARGUMENT for a chunk with more
+ * frames than bucket or feat_stride.  DEVICE pointers; the entry does NOT synchronise. */
+fa_status fa_fsmn_vad_pack_feats_dev(fa_ctx *ctx, const void *d_feats, int32_t dtype, int64_t feat_stride, const fa_fsmn_vad_chunk *chunks,
+                                     int64_t n_chunks, int32_t bucket, float *d_out);
+/* Column 0 of d_scores [n_chunks][bucket][vocab] (fp32 or fp16) for frames keep_from ..< frames of every chunk ->
+ * d_silence[frame_range[recording] + first_frame + (i - keep_from)]: the strided gather and the concatenation in one pass.
+ * frame_range HOST int64[batch + 1] (fa_fsmn_vad_plan_chunks'); INVALID_ARGUMENT for a chunk that ends beyond its recording's frames,
+ * OUTPUT_TOO_SMALL when silence_capacity is below frame_range[batch].  DEVICE pointers; the entry does NOT synchronise. */
+fa_status fa_fsmn_vad_gather_silence_dev(fa_ctx *ctx, const void *d_scores, int32_t dtype, int32_t bucket, int32_t vocab,
+                                         const fa_fsmn_vad_chunk *chunks, int64_t n_chunks, const int64_t *frame_range, int32_t batch,
+                                         float *d_silence, int64_t silence_capacity);
+/* decide.  probs float[sum frames]: the silence probabilities, recording b's at frame_range[b] ... frame_range[b + 1] (HOST
+ * int64[batch + 1]).  segs HOST [capacity], by recording and time; reason: FA_FSMN_VAD_END_SILENCE (the end is the closing frame -
+ * max_end_silence_frames + lookahead_frames, not clamped), _MAX_LENGTH, _END_OF_AUDIO (the end is the frame count); the milliseconds
+ * are frames * frame_ms.  recording_counts HOST int64[batch] (nullable).  INVALID_ARGUMENT for a config outside the bounds stated at
+ * its fields, a NaN threshold, a NULL, descending or negative range; INDEX_OVERFLOW for a recording of 2^31 frames or more (or whose
+ * frames plus the look-ahead reach 2^31).  _dev: probs is a DEVICE pointer. */
+fa_status fa_fsmn_vad_segments_dev(fa_ctx *ctx, const fa_fsmn_vad_config *cfg, const float *d_probs, const int64_t *frame_range,
+                                   int32_t batch, fa_fsmn_vad_segment *segs, int64_t capacity, int64_t *count, int64_t *recording_counts);
+fa_status fa_fsmn_vad_segments(fa_ctx *ctx, const fa_fsmn_vad_config *cfg, const float *probs, const int64_t *frame_range, int32_t batch,
+                               fa_fsmn_vad_segment *segs, int64_t capacity, int64_t *count, int64_t *recording_counts);
 
 /* ------------------------------------------------------------------ TDT long-form: planning the windows ------ */
 /* What ChunkProcessor decides from the audio before any network runs (FluidAudio/ASR/Parakeet/SlidingWindow/TDT/
