@@ -35,9 +35,7 @@ namespace {
 
 using namespace fa::embedding;
 using fa::grid_for;
-using fa::scan::block_exclusive;
 constexpr int kThreads = fa::scan::kThreads;
-constexpr int kScanPer = 8;             // items per thread of a compaction
 constexpr int kLdsFloats = 8192;        // chunks of up to this many weights are staged in LDS (32 KiB); larger ones are read in place
 
 // WeightInterpolation.InterpolationCoefficients (:19-52) for output index i
@@ -185,8 +183,7 @@ __global__ __launch_bounds__(64) void emb_stats(StatsArgs a) {
     }
 }
 
-// ---------------------------------------------------------------- compaction (block_scan.h: per-block counts, scan_totals, a write pass)
-
+// ---------------------------------------------------------------- compaction: the predicates and the sink of block_scan.h's compact
 
 struct ValidPred {   // item i is a job
     const ItemRec *rec;
@@ -198,32 +195,12 @@ struct RunPred {     // job j runs the model (j < jobs)
     __device__ int operator()(int64_t j) const { return j < *jobs && is_run[j] != 0; }
 };
 
-template <class P>
-__global__ __launch_bounds__(kThreads) void flag_count(P p, int64_t n, int32_t *__restrict__ bsum) {
-    const int64_t e0 = (static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x) * kScanPer;
-    int c = 0;
-    for (int i = 0; i < kScanPer; ++i) if (e0 + i < n) c += p(e0 + i);
-    int tot;
-    (void)block_exclusive(c, &tot);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-
-
 // idx_of[i] = compacted index or -1; item_of[k] = i
-template <class P>
-__global__ __launch_bounds__(kThreads) void flag_write(P p, int64_t n, const int32_t *__restrict__ boff, int32_t *__restrict__ idx_of,
-                                                       int32_t *__restrict__ item_of) {
-    const int64_t e0 = (static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x) * kScanPer;
-    int flags = 0, c = 0;
-    for (int i = 0; i < kScanPer; ++i) if (e0 + i < n && p(e0 + i)) { flags |= 1 << i; ++c; }
-    int tot;
-    int pos = boff[blockIdx.x] + block_exclusive(c, &tot);
-    for (int i = 0; i < kScanPer; ++i) {
-        if (e0 + i >= n) break;
-        if (flags & (1 << i)) { idx_of[e0 + i] = pos; item_of[pos] = static_cast<int32_t>(e0 + i); ++pos; }
-        else idx_of[e0 + i] = -1;
-    }
-}
+struct IndexSink {
+    int32_t *idx_of, *item_of;
+    __device__ void kept(int64_t i, int pos) const { idx_of[i] = pos; item_of[pos] = static_cast<int32_t>(i); }
+    __device__ void dropped(int64_t i) const { idx_of[i] = -1; }
+};
 
 // every job runs the model (skipping off, or before the skip chain decides)
 __global__ __launch_bounds__(kThreads) void runs_init(const int32_t *__restrict__ jobs, int64_t cap, int32_t *__restrict__ is_run, int32_t *__restrict__ src) {
@@ -349,29 +326,19 @@ __global__ __launch_bounds__(kThreads) void resample_rows(const float *__restric
 namespace fa {
 namespace embedding {
 
-int64_t select_blocks(int64_t items) { return (items + kThreads * kScanPer - 1) / (kThreads * kScanPer); }
-
-// per-block counts of the items p selects, their scan (the total to *total), the write pass
-template <class P>
-static void launch_compact(hipStream_t st, P p, int64_t items, int32_t *bsum, int32_t *total, int32_t *idx_of, int32_t *item_of) {
-    const int64_t nb = select_blocks(items);
-    const unsigned nbu = static_cast<unsigned>(nb);
-    hipLaunchKernelGGL(flag_count<P>, dim3(nbu), dim3(kThreads), 0, st, p, items, bsum);
-    hipLaunchKernelGGL(fa::scan::scan_totals<>, dim3(1), dim3(kThreads), 0, st, bsum, nb, total);
-    hipLaunchKernelGGL(flag_write<P>, dim3(nbu), dim3(kThreads), 0, st, p, items, bsum, idx_of, item_of);
-}
+int64_t select_blocks(int64_t items) { return fa::scan::compact_blocks(items); }
 
 void launch_select(hipStream_t st, const StatsArgs &a, const SelectArgs &s) {
     const int64_t nw = a.nw, items = nw * a.S;
     const int32_t n_fs = a.F * a.S;
     const size_t lds = n_fs <= kLdsFloats ? sizeof(float) * n_fs : 0;
     hipLaunchKernelGGL(emb_stats, dim3(static_cast<unsigned>(nw)), dim3(64), lds, st, a);
-    launch_compact(st, ValidPred{a.rec}, items, s.bsum, s.flags + 1, s.job_of_item, s.item_of_job);
+    fa::scan::compact(st, ValidPred{a.rec}, IndexSink{s.job_of_item, s.item_of_job}, items, s.bsum, s.flags + 1);
     hipLaunchKernelGGL(runs_init, dim3(grid_for(items, kThreads)), dim3(kThreads), 0, st, s.flags + 1, items, s.is_run, s.src);
     if (s.skip)
         hipLaunchKernelGGL(skip_chain, dim3(static_cast<unsigned>(((nw + s.B - 1) / s.B) * a.S)), dim3(64), 0, st, s.job_of_item, a.masks, a.nw, a.S, a.F, s.B,
                            s.skip_threshold, s.is_run, s.src);
-    launch_compact(st, RunPred{s.is_run, s.flags + 1}, items, s.bsum, s.flags + 2, s.run_of_src, s.job_of_run);
+    fa::scan::compact(st, RunPred{s.is_run, s.flags + 1}, IndexSink{s.run_of_src, s.job_of_run}, items, s.bsum, s.flags + 2);
     hipLaunchKernelGGL(runs_finish, dim3(grid_for(items, kThreads)), dim3(kThreads), 0, st, s.flags + 1, items, s.src, s.run_of_src, s.job_of_run, s.item_of_job,
                        a.S, s.run_of_job, s.window_of_run);
 }

@@ -7,9 +7,8 @@
 //                   state in closed form (state_at: a find-last-set and a masked population count) and its ballot, and then walk_step:
 //                   wave-uniform code that jumps from a segment's opening to its close on that word.  The chain over the steps is
 //                   serial, so the probabilities of the next four steps are in flight while one is walked.
-// fsmn_vad_write    the records of every recording's slice, compacted to the call's output behind scan_totals (block_scan.h) of the
-//                   slices' fill.
-// fsmn_vad_pack     the scorer-side rows: the scaled waveform of a chunk; fsmn_vad_feats the zero-padded bucket of features;
+// fsmn_vad_write    the records of every recording's slice, placed in the call's output by scan_totals (block_scan.h) of the slices' fill.
+// rows::pack        the scorer-side rows: the scaled waveform of a chunk (row_pack.h, with its scale); fsmn_vad_feats the zero-padded bucket of features;
 //                   fsmn_vad_gather column 0 of the scores, onto the recording's frame grid.
 // No kernel reads a frame or a sample of another recording than its own, and there are no atomics.
 #include <hip/hip_fp16.h>
@@ -17,6 +16,7 @@
 #include "fa_common.h"
 #include "block_scan.h"
 #include "fsmn_vad_launch.h"
+#include "row_pack.h"
 
 namespace fa {
 namespace fsmnvad {
@@ -76,22 +76,6 @@ __global__ __launch_bounds__(scan::kThreads) void fsmn_vad_write(const SegArgs a
     }
 }
 
-// One workgroup per row: groups of four elements.  audio[src ... src + len) * 32768.0f, zeros up to row_stride.
-template <bool kWide>
-__global__ __launch_bounds__(256) void fsmn_vad_pack(const float *__restrict__ audio, const PackGroup g, float *__restrict__ rows, const int64_t row_stride) {
-    const int row = blockIdx.x;
-    const float *__restrict__ src = audio + g.src[row];
-    const int64_t n = g.len[row];
-    float *__restrict__ out = rows + row * row_stride;
-    const auto element = [&](const int64_t e) { return e < n ? src[e] * 32768.0f : 0.0f; };   // :123: one fp32 multiply
-    if (kWide) {
-        for (int64_t j = threadIdx.x; j < row_stride / 4; j += 256)
-            reinterpret_cast<float4 *>(out)[j] = make_float4(element(4 * j), element(4 * j + 1), element(4 * j + 2), element(4 * j + 3));
-    } else {
-        for (int64_t j = threadIdx.x; j < row_stride; j += 256) out[j] = element(j);
-    }
-}
-
 // blockIdx.y: the chunk; a thread per group of four elements of its [bucket][400] output
 template <bool kHalf, bool kWide>
 __global__ __launch_bounds__(256) void fsmn_vad_feats(const void *__restrict__ feats, const int64_t feat_stride, const FeatGroup g, const int32_t bucket, float *__restrict__ out) {
@@ -142,10 +126,8 @@ void launch_segments(hipStream_t stream, const SegArgs &a) {
     if (a.out_slots > 0) fsmn_vad_write<<<a.batch, scan::kThreads, 0, stream>>>(a);
 }
 
-void launch_pack(hipStream_t stream, const float *audio, const PackGroup &g, float *rows, const int64_t row_stride, const bool wide) {
-    if (g.count == 0 || row_stride == 0) return;
-    if (wide) fsmn_vad_pack<true><<<g.count, 256, 0, stream>>>(audio, g, rows, row_stride);
-    else fsmn_vad_pack<false><<<g.count, 256, 0, stream>>>(audio, g, rows, row_stride);
+void launch_pack(hipStream_t stream, const float *audio, const rows::Group &g, float *out, const int64_t row_stride, const bool wide) {
+    rows::launch_pack<true>(stream, audio, g, row_stride, out, nullptr, wide, 32768.0f);   // :123: one fp32 multiply
 }
 
 void launch_feats(hipStream_t stream, const void *feats, const int32_t dtype, const int64_t feat_stride, const FeatGroup &g, const int32_t bucket, float *out, const bool wide) {

@@ -77,16 +77,11 @@ fa_status pack(fa_ctx *ctx, const float *audio, const int64_t *audio_offsets, co
     const float *d_audio = device ? audio : b_audio.as<float>();
     float *d_rows = device ? rows : b_rows.as<float>();
     const bool wide = reinterpret_cast<uintptr_t>(d_rows) % 16 == 0 && row_stride % 4 == 0;   // then every row is aligned
-    for (int64_t g0 = 0; g0 < n; g0 += fv::kGroup) {
-        fv::PackGroup g{};
-        g.count = static_cast<int32_t>(std::min<int64_t>(fv::kGroup, n - g0));
-        for (int32_t i = 0; i < g.count; ++i) {
-            const fa_fsmn_vad_chunk &c = chunks[g0 + i];
-            g.src[i] = audio_offsets[c.recording] - a0 + c.start_sample;
-            g.len[i] = static_cast<int32_t>(c.end_sample - c.start_sample);
-        }
-        fv::launch_pack(st, d_audio, g, d_rows + g0 * row_stride, row_stride, wide);
-    }
+    const auto fill = [&](fa::rows::Group &g, const int64_t i, const int32_t k) {
+        g.src[k] = audio_offsets[chunks[i].recording] - a0 + chunks[i].start_sample;
+        g.len[k] = static_cast<int32_t>(chunks[i].end_sample - chunks[i].start_sample);
+    };
+    fa::rows::for_each_group(n, fill, [&](const fa::rows::Group &g, const int64_t g0) { fv::launch_pack(st, d_audio, g, d_rows + g0 * row_stride, row_stride, wide); });
     FA_HIP_TRY(ctx, hipGetLastError());
     if (!device) {
         FA_HIP_TRY(ctx, hipMemcpyAsync(rows, b_rows.p, row_bytes, hipMemcpyDeviceToHost, st));
@@ -131,13 +126,11 @@ fa_status fa_fsmn_vad_pack_feats_dev(fa_ctx *ctx, const void *d_feats, int32_t d
     fa::DeviceGuard guard(ctx->device);
     const size_t element = dtype == FA_DTYPE_F16 ? 2 : 4;
     const bool wide = reinterpret_cast<uintptr_t>(d_out) % 16 == 0 && reinterpret_cast<uintptr_t>(d_feats) % (4 * element) == 0;   // a feature row is whole groups of four
-    for (int64_t g0 = 0; g0 < n_chunks; g0 += fv::kGroup) {
-        fv::FeatGroup g{};
-        g.count = static_cast<int32_t>(std::min<int64_t>(fv::kGroup, n_chunks - g0));
-        for (int32_t i = 0; i < g.count; ++i) g.frames[i] = chunks[g0 + i].frames;
+    const auto fill = [&](fv::FeatGroup &g, const int64_t i, const int32_t k) { g.frames[k] = chunks[i].frames; };
+    fa::rows::for_each_group<fv::FeatGroup>(n_chunks, fill, [&](const fv::FeatGroup &g, const int64_t g0) {
         fv::launch_feats(ctx->stream, static_cast<const char *>(d_feats) + static_cast<size_t>(g0) * static_cast<size_t>(feat_stride) * fv::kFeatureDim * element, dtype, feat_stride, g,
                          bucket, d_out + static_cast<size_t>(g0) * static_cast<size_t>(bucket) * fv::kFeatureDim, wide);
-    }
+    });
     FA_HIP_TRY(ctx, hipGetLastError());
     return FA_SUCCESS;
     });
@@ -152,18 +145,15 @@ fa_status fa_fsmn_vad_gather_silence_dev(fa_ctx *ctx, const void *d_scores, int3
     if (n_chunks == 0 || bucket == 0) return FA_SUCCESS;
     fa::DeviceGuard guard(ctx->device);
     const size_t element = dtype == FA_DTYPE_F16 ? 2 : 4;
-    for (int64_t g0 = 0; g0 < n_chunks; g0 += fv::kGroup) {
-        fv::GatherGroup g{};
-        g.count = static_cast<int32_t>(std::min<int64_t>(fv::kGroup, n_chunks - g0));
-        for (int32_t i = 0; i < g.count; ++i) {
-            const fa_fsmn_vad_chunk &c = chunks[g0 + i];
-            g.dst[i] = frame_range[c.recording] + c.first_frame;
-            g.keep_from[i] = c.keep_from;
-            g.frames[i] = c.frames;
-        }
+    const auto fill = [&](fv::GatherGroup &g, const int64_t i, const int32_t k) {
+        g.dst[k] = frame_range[chunks[i].recording] + chunks[i].first_frame;
+        g.keep_from[k] = chunks[i].keep_from;
+        g.frames[k] = chunks[i].frames;
+    };
+    fa::rows::for_each_group<fv::GatherGroup>(n_chunks, fill, [&](const fv::GatherGroup &g, const int64_t g0) {
         fv::launch_gather(ctx->stream, static_cast<const char *>(d_scores) + static_cast<size_t>(g0) * static_cast<size_t>(bucket) * static_cast<size_t>(vocab) * element, dtype, bucket,
                           vocab, g, d_silence);
-    }
+    });
     FA_HIP_TRY(ctx, hipGetLastError());
     return FA_SUCCESS;
     });

@@ -18,11 +18,12 @@
 
 #include "fa_verdict.h"
 #include "fsmn_vad_core.h"
+#include "row_pack_launch.h"
 
 namespace fa {
 namespace fsmnvad {
 
-constexpr int kGroup = 64;                   // chunks whose operands travel in one launch's arguments: nothing is staged, no entry waits
+constexpr int kGroup = rows::kGroup;          // chunks whose operands travel in one launch's arguments: nothing is staged, no entry waits
 
 inline fa_fsmn_vad_config config_or_default(const fa_fsmn_vad_config *cfg) {
     if (cfg) return *cfg;
@@ -181,12 +182,6 @@ inline Verdict plan_pack(const void *audio, const int64_t *audio_offsets, const 
     return Verdict{};
 }
 
-struct PackGroup {                           // up to kGroup chunks, by value in the launch's arguments
-    int64_t src[kGroup];                     // the chunk's first sample in the array the kernel is given
-    int32_t len[kGroup];
-    int32_t count;
-};
-
 inline Verdict plan_feats(const void *feats, const int32_t dtype, const int64_t feat_stride, const fa_fsmn_vad_chunk *chunks, const int64_t n, const int32_t bucket,
                           const void *out) {
     const char *who = "fsmn_vad_pack_feats_dev";
@@ -242,8 +237,9 @@ struct GatherGroup {
 };
 
 #if defined(__HIPCC__)
+// a chunk is a row of a rows::Group (row_pack_launch.h): src its first sample in the array the kernel is given, len its samples.
 // rows: the group's first row.  wide: 16-byte stores (rows is 16-byte aligned and row_stride a multiple of 4)
-void launch_pack(hipStream_t stream, const float *audio, const PackGroup &g, float *rows, int64_t row_stride, bool wide);
+void launch_pack(hipStream_t stream, const float *audio, const rows::Group &g, float *rows, int64_t row_stride, bool wide);
 // feats / out: the group's first chunk.  wide: feats and out are 16-byte aligned (8-byte for fp16 feats)
 void launch_feats(hipStream_t stream, const void *feats, int32_t dtype, int64_t feat_stride, const FeatGroup &g, int32_t bucket, float *out, bool wide);
 void launch_gather(hipStream_t stream, const void *scores, int32_t dtype, int32_t bucket, int32_t vocab, const GatherGroup &g, float *silence);

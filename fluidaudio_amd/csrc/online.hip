@@ -144,23 +144,14 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void plan_sums_kernel(const
     }
 }
 
-// One workgroup: the exclusive prefix of the flags in triple order (block_scan.h), the run list and its count.
+// One workgroup: block_scan.h's workgroup_exclusive over the flags in triple order, the run list and its count.
 __global__ __launch_bounds__(fa::scan::kThreads) void plan_scan_kernel(const PlanArgs a) {
     const int64_t n = static_cast<int64_t>(a.streams) * a.chunks * 3;
-    int base = 0;
-    for (int64_t i0 = 0; i0 < n; i0 += fa::scan::kThreads) {
-        const int64_t i = i0 + threadIdx.x;
-        const int keep = i < n ? a.flags[i] : 0;
-        int total = 0;
-        const int at = base + fa::scan::block_exclusive(keep, &total);
-        if (i < n) {
-            a.flags[i] = keep ? at : -1;
-            if (keep && at < a.run_capacity) a.runs[at] = fa_online_run{static_cast<int32_t>(i / 3 / a.chunks), static_cast<int32_t>(i / 3 % a.chunks), static_cast<int32_t>(i % 3)};
-        }
-        base += total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *a.run_count = base;
+    const int count = fa::scan::workgroup_exclusive(n, [&](const int64_t i) { return a.flags[i]; }, [&](const int64_t i, const int keep, const int at) {
+        a.flags[i] = keep ? at : -1;
+        if (keep && at < a.run_capacity) a.runs[at] = fa_online_run{static_cast<int32_t>(i / 3 / a.chunks), static_cast<int32_t>(i / 3 % a.chunks), static_cast<int32_t>(i % 3)};
+    });
+    if (threadIdx.x == 0) *a.run_count = count;
 }
 
 // One workgroup per (stream, chunk, speaker) that runs: its model mask row with the repeat padding of fillMaskBufferOptimized (:154-199)
@@ -268,20 +259,6 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void finish_count_kernel(co
     if ((threadIdx.x & (kWave - 1)) == 0) a.counts[sc] = n;
 }
 
-__global__ __launch_bounds__(fa::scan::kThreads) void finish_scan_kernel(const FinishArgs a) {
-    const int64_t n = static_cast<int64_t>(a.db.streams) * a.chunks;
-    int base = 0;
-    for (int64_t i0 = 0; i0 < n; i0 += fa::scan::kThreads) {
-        const int64_t i = i0 + threadIdx.x;
-        int total = 0;
-        const int at = base + fa::scan::block_exclusive(i < n ? a.counts[i] : 0, &total);
-        if (i < n) a.counts[i] = at;
-        base += total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) a.counts[n] = base;
-}
-
 __global__ __launch_bounds__(kWave * kWavesPerBlock) void finish_write_kernel(const FinishArgs a) {
     const int64_t sc = wave_index();
     const int lane = threadIdx.x & (kWave - 1);
@@ -324,15 +301,13 @@ void launch_pack(hipStream_t stream, const PackArgs &a) {
     hipLaunchKernelGGL(pack_kernel, dim3(grid_for((a.chunk_samples + 3) / 4, 256), static_cast<unsigned>(a.rows)), dim3(256), 0, stream, a);
 }
 void launch_finish(hipStream_t stream, const FinishArgs &a) {
-    const Plan per_stream = plan_of(a.db.streams), per_chunk = plan_of(static_cast<int64_t>(a.db.streams) * a.chunks);
+    const int64_t n = static_cast<int64_t>(a.db.streams) * a.chunks;
+    const Plan per_stream = plan_of(a.db.streams), per_chunk = plan_of(n);
     hipLaunchKernelGGL(finish_assign_kernel, dim3(per_stream.grid), dim3(per_stream.block), 0, stream, a);
     hipLaunchKernelGGL(finish_count_kernel, dim3(per_chunk.grid), dim3(per_chunk.block), 0, stream, a);
-    hipLaunchKernelGGL(finish_scan_kernel, dim3(1), dim3(fa::scan::kThreads), 0, stream, a);
+    hipLaunchKernelGGL(fa::scan::scan_totals<>, dim3(1), dim3(fa::scan::kThreads), 0, stream, a.counts, n, a.counts + n);   // the chunks' counts -> offsets, counts[n] the total
     hipLaunchKernelGGL(finish_write_kernel, dim3(per_chunk.grid), dim3(per_chunk.block), 0, stream, a);
 }
-
-namespace {
-}  // namespace
 
 void launch_assign(hipStream_t stream, const AssignArgs &a) {
     const Plan pl = plan_of(a.db.streams);

@@ -36,9 +36,7 @@ namespace {
 
 using namespace fa::reconstruct;
 using fa::grid_for;
-using fa::scan::block_exclusive;
 constexpr int kThreads = fa::scan::kThreads;
-constexpr int kScanPer = 8;       // items per thread of the run compaction
 
 // ---------------------------------------------------------------- powerset decode
 
@@ -277,33 +275,21 @@ __device__ inline int active_slot(const int32_t *word, const int32_t *sel, int s
     return -1;
 }
 
-// item e = g * smax + j starts a run: slot j is active at g and its cluster was not active at g - 1
-__device__ inline int run_start(const int32_t *word, const int32_t *sel, int smax, int64_t items, int64_t e) {
-    if (e >= items) return 0;
-    const int g = static_cast<int>(e / smax), j = static_cast<int>(e - static_cast<int64_t>(g) * smax);
-    if (j >= (word[g] & kSelMask)) return 0;
-    return g == 0 || active_slot(word, sel, smax, g - 1, sel[e]) < 0;
-}
-
-__global__ __launch_bounds__(kThreads) void run_count(const int32_t *__restrict__ word, const int32_t *__restrict__ sel, int smax, int64_t items,
-                                                      int32_t *__restrict__ bsum) {
-    const int64_t e0 = (static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x) * kScanPer;
-    int n = 0;
-    for (int i = 0; i < kScanPer; ++i) n += run_start(word, sel, smax, items, e0 + i);
-    int tot;
-    (void)block_exclusive(n, &tot);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(kThreads) void run_write(const int32_t *__restrict__ word, const int32_t *__restrict__ sel, int smax, int64_t items,
-                                                      const int32_t *__restrict__ boff, int64_t *__restrict__ starts) {
-    const int64_t e0 = (static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x) * kScanPer;
-    int flags = 0, n = 0;
-    for (int i = 0; i < kScanPer; ++i) if (run_start(word, sel, smax, items, e0 + i)) { flags |= 1 << i; ++n; }
-    int tot;
-    int pos = boff[blockIdx.x] + block_exclusive(n, &tot);
-    for (int i = 0; i < kScanPer; ++i) if (flags & (1 << i)) starts[pos++] = e0 + i;
-}
+// item e = g * smax + j starts a run: slot j is active at g and its cluster was not active at g - 1 (the predicate of block_scan.h's compact)
+struct RunStart {
+    const int32_t *word, *sel;
+    int smax;
+    __device__ int operator()(int64_t e) const {
+        const int g = static_cast<int>(e / smax), j = static_cast<int>(e - static_cast<int64_t>(g) * smax);
+        if (j >= (word[g] & kSelMask)) return 0;
+        return g == 0 || active_slot(word, sel, smax, g - 1, sel[e]) < 0;
+    }
+};
+struct StartSink {   // starts[k] = the item of run k
+    int64_t *starts;
+    __device__ void kept(int64_t e, int pos) const { starts[pos] = e; }
+    __device__ void dropped(int64_t) const {}
+};
 
 // one lane per run: walk forward while the cluster stays active
 __global__ __launch_bounds__(kThreads) void run_walk(const int64_t *__restrict__ starts, const int32_t *__restrict__ total, const int32_t *__restrict__ word,
@@ -343,16 +329,13 @@ void launch_powerset(hipStream_t st, const float *x, int64_t rows, int32_t class
     if (row0 < rows) hipLaunchKernelGGL(powerset_decode_rows, dim3(grid_for(rows - row0, kThreads)), dim3(kThreads), 0, st, x, row0, rows, classes, w, lp);
 }
 
-int64_t run_blocks(int64_t items) { return (items + kThreads * kScanPer - 1) / (kThreads * kScanPer); }
+int64_t run_blocks(int64_t items) { return fa::scan::compact_blocks(items); }
 
 void launch_frames(hipStream_t st, const FrameArgs &a, int32_t *bsum, int32_t *total, int64_t *starts) {
     const unsigned fgrid = grid_for(a.T, kTileG);
     if (a.K <= 64) hipLaunchKernelGGL(recon_frames<1>, dim3(fgrid), dim3(kThreads), 0, st, a);
     else hipLaunchKernelGGL(recon_frames<4>, dim3(fgrid), dim3(kThreads), 0, st, a);
-    const int64_t items = static_cast<int64_t>(a.T) * a.smax, nb = run_blocks(items);
-    hipLaunchKernelGGL(run_count, dim3(static_cast<unsigned>(nb)), dim3(kThreads), 0, st, a.word, a.sel, a.smax, items, bsum);
-    hipLaunchKernelGGL(fa::scan::scan_totals<>, dim3(1), dim3(kThreads), 0, st, bsum, nb, total);
-    hipLaunchKernelGGL(run_write, dim3(static_cast<unsigned>(nb)), dim3(kThreads), 0, st, a.word, a.sel, a.smax, items, bsum, starts);
+    fa::scan::compact(st, RunStart{a.word, a.sel, a.smax}, StartSink{starts}, static_cast<int64_t>(a.T) * a.smax, bsum, total);
 }
 
 void launch_walk(hipStream_t st, const FrameArgs &a, const int64_t *starts, const int32_t *total, int64_t n_raw, RawRun *out) {

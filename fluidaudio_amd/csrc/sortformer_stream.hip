@@ -14,9 +14,10 @@
 //   sfs_gather   (stream, row tile): the compressed cache into scratch — its source rows are neither monotone nor distinct, so nothing
 //                reads the slab that is being written;  sfs_replace: scratch into the model-facing slab.
 // The unit is built with -ffp-contract=off: (mean * n + x) / newN and every add of the scores stay unfused, as in the reference.
-// Every store is a plain C++ assignment.
+// Every store is a plain C++ assignment.  The chunk rows the model reads are row_pack.h's copy, instantiated here (launch_pack).
 #include <hip/hip_fp16.h>
 
+#include "row_pack.h"
 #include "sortformer_stream_launch.h"
 
 namespace fa {
@@ -335,6 +336,10 @@ void launch_update(hipStream_t stream, const UpdateArgs &a) {
     else hipLaunchKernelGGL(sfs_move<false>, dim3(lp.move_grid_x, B), dim3(kMoveBlock), 0, stream, a);
     hipLaunchKernelGGL(sfs_gather, dim3(lp.gather_grid_x, B), dim3(128), 0, stream, a);
     hipLaunchKernelGGL(sfs_replace, dim3(lp.gather_grid_x, B), dim3(128), 0, stream, a);
+}
+
+void launch_pack(hipStream_t stream, const float *mel, const rows::Group &g, const int64_t row_samples, float *out, const bool wide) {
+    rows::launch_pack<false>(stream, mel, g, row_samples, out, nullptr, wide);
 }
 
 }  // namespace sfs

@@ -2,9 +2,8 @@
 // sortformer_stream_launch.h): the handle and its device arrays, the defaults and presets (SortformerTypes.swift:26-97, 121-216), the argument
 // checks and the C ABI of the update, the whole-state get / set / reset (session restore; SortformerStreamingState.cleanup), and the pure
 // host restatements of the chunk geometry (SortformerDiarizer.swift:933-979, SortformerTypes.swift:347-383) with the thin packer over
-// the TDT planner's row copy.
+// the shared row copy (row_pack_launch.h; the kernel is instantiated in sortformer_stream.hip).
 #include "sortformer_stream_launch.h"
-#include "tdt_plan_launch.h"
 
 struct fa_sortformer_stream {
     int device = 0;
@@ -325,19 +324,12 @@ fa_status fa_sortformer_stream_pack_chunks_dev(fa_ctx *ctx, const fa_sortformer_
         if (stream_offsets[b] < 0 || (chunks[b].ready && (chunks[b].start_frame < 0 || chunks[b].rows < 0 || chunks[b].rows > T)) || row > INT32_MAX)
             return fa::set_error(ctx, FA_INVALID_ARGUMENT, "sortformer_stream pack: stream %d: a chunk outside its buffer or longer than a row", b);
     fa::DeviceGuard guard(ctx->device);
-    namespace tp = fa::tdt_plan;
     const bool wide = aligned16(d_rows) && row % 4 == 0;
-    // the TDT planner's row copy (rows copied as bits, zeros behind them); the sources of up to kPackGroup rows travel in a launch's arguments
-    for (int32_t b0 = 0; b0 < streams; b0 += tp::kPackGroup) {
-        tp::PackGroup g{};
-        g.count = std::min<int32_t>(tp::kPackGroup, streams - b0);
-        for (int32_t i = 0; i < g.count; ++i) {
-            const fa_sortformer_chunk &k = chunks[b0 + i];
-            g.src[i] = k.ready ? (stream_offsets[b0 + i] + k.start_frame) * c.n_mels : 0;
-            g.length[i] = k.ready ? static_cast<int32_t>(k.rows * c.n_mels) : 0;
-        }
-        tp::launch_pack(ctx->stream, d_mel, g, row, d_rows + static_cast<int64_t>(b0) * row, nullptr, wide);
-    }
+    const auto fill = [&](fa::rows::Group &g, const int64_t b, const int32_t k) {   // a stream without a chunk: a row of zeros
+        g.src[k] = chunks[b].ready ? (stream_offsets[b] + chunks[b].start_frame) * c.n_mels : 0;
+        g.len[k] = chunks[b].ready ? static_cast<int32_t>(chunks[b].rows * c.n_mels) : 0;
+    };
+    fa::rows::for_each_group(streams, fill, [&](const fa::rows::Group &g, const int64_t b0) { sfs::launch_pack(ctx->stream, d_mel, g, row, d_rows + b0 * row, wide); });
     FA_HIP_TRY(ctx, hipGetLastError());
     return FA_SUCCESS;
 }

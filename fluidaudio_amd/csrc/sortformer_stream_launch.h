@@ -4,6 +4,7 @@
 // hipGetLastError().
 #pragma once
 #include "fa_common.h"
+#include "row_pack_launch.h"
 #include "sortformer_stream_core.h"
 
 namespace fa {
@@ -66,6 +67,9 @@ inline LaunchPlan launch_plan_of(const Config &c, const Slabs &s) {
 
 // control, move, gather, replace: four launches whatever the streams do
 void launch_update(hipStream_t stream, const UpdateArgs &a);
+
+// the model's chunk rows: a group of streams' mel rows copied as bits, zeros behind them (row_pack.h).  rows: the group's first row
+void launch_pack(hipStream_t stream, const float *mel, const rows::Group &g, int64_t row_samples, float *rows, bool wide);
 
 }  // namespace sfs
 }  // namespace fa

@@ -18,12 +18,13 @@
 //                negative, so their bits order as unsigned; the median is the exact rank count / 2 among the keys kept in LDS.  The quiet
 //                probe has lane = 20 ms window, and the loop's exits are read off three ballots.
 // tp_count /     the window loop: lane = window, each turn of the loop is independent given the start (tdt_plan_core.h: turn), the first
-// tp_write       terminating window comes from a ballot.  The windows of the recordings are placed by block_scan.h's scan_totals.
-// tp_pack        the preprocessor's rows; tp_threshold the gate's percentile by exact rank selection over the bits of the kept frames'
+// tp_write       terminating window comes from a ballot.  The windows of the recordings are placed by scan_totals (block_scan.h).
+// rows::pack     the preprocessor's rows (row_pack.h); tp_threshold the gate's percentile by exact rank selection over the bits of the kept frames'
 //                sums (sqrt and the division are monotone, and the selected element alone is converted); tp_spans the speech-like frames.
 // No kernel reads a sample of another recording than its own, and there are no float atomics.
 #include "fa_common.h"
 #include "block_scan.h"
+#include "row_pack.h"
 #include "tdt_plan_launch.h"
 
 namespace fa {
@@ -286,26 +287,6 @@ __global__ __launch_bounds__(kWave) void tp_write(const PlanArgs a) {
     });
 }
 
-// One workgroup per slice of kPackSlice samples of a row.
-template <bool kWide>
-__global__ __launch_bounds__(256) void tp_pack(const uint32_t *__restrict__ audio, const PackGroup g, const int64_t row_samples, uint32_t *__restrict__ rows,
-                                               int32_t *__restrict__ lengths) {
-    const int w = blockIdx.y;
-    const int64_t s0 = static_cast<int64_t>(blockIdx.x) * kPackSlice, s1 = lesser(row_samples, s0 + kPackSlice);
-    const int64_t length = g.length[w];
-    const uint32_t *__restrict__ src = audio + g.src[w];
-    uint32_t *__restrict__ out = rows + static_cast<int64_t>(w) * row_samples;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && lengths) lengths[w] = g.length[w];
-    const auto element = [&](const int64_t s) -> uint32_t { return s < length ? src[s] : 0u; };
-    if (kWide) {
-        for (int64_t s = s0 + 4 * threadIdx.x; s < s1; s += 4 * 256)                             // row_samples and kPackSlice are multiples of 4
-            *reinterpret_cast<uint4 *>(out + s) = make_uint4(element(s), element(s + 1), element(s + 2), element(s + 3));
-    } else {
-        for (int64_t s = s0 + threadIdx.x; s < s1; s += 256) out[s] = element(s);
-    }
-}
-static_assert(kPackSlice % 4 == 0, "a slice is whole groups of four");
-
 // adaptiveSpeechRmsThreshold (:1252-1276).  sqrt(sum / F) ascends with sum, and equal sums give equal values, so the element of rank k
 // among the RMS values is the RMS of the sum of rank k: the selection runs over the bits of the kept sums (positive floats order as
 // unsigned), four passes of one byte each, most significant first, and the chosen sum alone goes through the division and the root.
@@ -386,11 +367,8 @@ void launch_plan(hipStream_t stream, const PlanArgs &a) {
     tp_write<<<a.batch, kWave, 0, stream>>>(a);
 }
 
-void launch_pack(hipStream_t stream, const float *audio, const PackGroup &g, const int64_t row_samples, float *rows, int32_t *lengths, const bool wide) {
-    if (g.count == 0) return;
-    const dim3 grid(grid_for(row_samples, kPackSlice), static_cast<unsigned>(g.count));
-    if (wide) tp_pack<true><<<grid, 256, 0, stream>>>(reinterpret_cast<const uint32_t *>(audio), g, row_samples, reinterpret_cast<uint32_t *>(rows), lengths);
-    else tp_pack<false><<<grid, 256, 0, stream>>>(reinterpret_cast<const uint32_t *>(audio), g, row_samples, reinterpret_cast<uint32_t *>(rows), lengths);
+void launch_pack(hipStream_t stream, const float *audio, const rows::Group &g, const int64_t row_samples, float *out, int32_t *lengths, const bool wide) {
+    rows::launch_pack<false>(stream, audio, g, row_samples, out, lengths, wide);
 }
 
 void launch_gate(hipStream_t stream, const GateArgs &a) {

@@ -108,17 +108,13 @@ fa_status pack(fa_ctx *ctx, const fa_tdt_window_config *cfg, const float *audio,
     float *d_rows = device ? rows : b_rows.as<float>();
     int32_t *d_lengths = device ? lengths : (lengths ? b_lengths.as<int32_t>() : nullptr);
     const bool wide = reinterpret_cast<uintptr_t>(d_rows) % 16 == 0 && g.max_model % 4 == 0;   // then every row is aligned
-    // the sources of up to kPackGroup windows travel in a launch's arguments: nothing is staged, so the device entry need not wait
-    for (int64_t w0 = 0; w0 < n_windows; w0 += tp::kPackGroup) {
-        tp::PackGroup group{};
-        group.count = static_cast<int32_t>(std::min<int64_t>(tp::kPackGroup, n_windows - w0));
-        for (int32_t i = 0; i < group.count; ++i) {
-            const fa_tdt_window &w = windows[w0 + i];
-            group.src[i] = audio_offsets[w.recording] - a0 + w.context_start;
-            group.length[i] = static_cast<int32_t>(w.length);
-        }
+    const auto fill = [&](fa::rows::Group &group, const int64_t i, const int32_t k) {
+        group.src[k] = audio_offsets[windows[i].recording] - a0 + windows[i].context_start;
+        group.len[k] = static_cast<int32_t>(windows[i].length);
+    };
+    fa::rows::for_each_group(n_windows, fill, [&](const fa::rows::Group &group, const int64_t w0) {
         tp::launch_pack(st, d_audio, group, g.max_model, d_rows + w0 * g.max_model, d_lengths ? d_lengths + w0 : nullptr, wide);
-    }
+    });
     FA_HIP_TRY(ctx, hipGetLastError());
     if (!device) {
         FA_HIP_TRY(ctx, hipMemcpyAsync(rows, b_rows.p, row_bytes, hipMemcpyDeviceToHost, st));

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "fa_verdict.h"
+#include "row_pack_launch.h"
 #include "tdt_plan_core.h"
 
 namespace fa {
@@ -19,8 +20,6 @@ constexpr int kWave = 64;
 constexpr int kEnergyBlock = 128;            // frames of a workgroup of the energy kernel
 constexpr int kStage = 32;                   // samples of a lane's run that pass through LDS at a time
 constexpr int kMaxRadius = 63;               // candidates of a search: 2 * 63 + 1 <= 128 slots
-constexpr int kPackGroup = 64;               // windows whose sources travel in one launch's arguments
-constexpr int kPackSlice = 4096;             // samples of a row one workgroup writes
 
 inline fa_tdt_window_config config_or_default(const fa_tdt_window_config *cfg) {
     if (cfg) return *cfg;
@@ -149,13 +148,7 @@ struct PlanArgs {
 void launch_plan(hipStream_t stream, const PlanArgs &a);
 #endif
 
-// ---- the rows
-struct PackGroup {                           // up to kPackGroup windows, by value in the launch's arguments: no table to upload
-    int64_t src[kPackGroup];                 // first sample, from the array the kernel is given
-    int32_t length[kPackGroup];
-    int32_t count;
-};
-
+// ---- the rows (row_pack_launch.h: a window is a row of a rows::Group)
 inline Verdict plan_pack(const fa_tdt_window_config &c, const void *audio, const int64_t *audio_offsets, const int32_t batch, const fa_tdt_window *windows,
                          const int64_t n_windows, const void *rows, const int64_t row_capacity, Geometry *g) {
     const Verdict v = derive(c, g);
@@ -181,7 +174,7 @@ inline Verdict plan_pack(const fa_tdt_window_config &c, const void *audio, const
 
 #if defined(__HIPCC__)
 // rows / lengths: the group's first row.  wide: 16-byte stores (the rows are 16-byte aligned)
-void launch_pack(hipStream_t stream, const float *audio, const PackGroup &g, int64_t row_samples, float *rows, int32_t *lengths, bool wide);
+void launch_pack(hipStream_t stream, const float *audio, const rows::Group &g, int64_t row_samples, float *rows, int32_t *lengths, bool wide);
 #endif
 
 // ---- the gate

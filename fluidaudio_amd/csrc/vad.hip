@@ -17,7 +17,8 @@
 //               the next four steps are in flight while one is walked.
 // vad_count /   the padding pass (:205-224: iteration i writes end[i] and start[i + 1], neither written before, so every gap is
 // vad_write     independent), the clamps (:228-233, :43-50), the end > start filter and the times, lane = raw speech; the kept records
-//               of a recording are compacted by block_scan.h (count, scan_totals, write).
+//               are placed by block_scan.h: block_exclusive counts a recording's, scan_totals places the recordings and
+//               workgroup_exclusive the records within one.
 // vad_pack      the model rows; vad_gather the ragged copy of the segments' audio; vad_stream the streaming machine, lane = stream.
 // No kernel reads a frame or a sample of another recording than its own, and there are no float atomics.
 #include "fa_common.h"
@@ -202,17 +203,13 @@ __global__ __launch_bounds__(scan::kThreads) void vad_write(const SegArgs a) {
     const int b = blockIdx.x;
     const SegRecording r = a.rec[b];
     const int32_t n = least(a.raw_counts[b], r.frames);
-    int64_t at = a.kept[b];                  // the records of the recordings before this one
-    for (int32_t i0 = 0; i0 < n; i0 += scan::kThreads) {
-        const int32_t i = i0 + threadIdx.x;
-        Finished f{0, 0, false};
-        if (i < n) f = finish(a.raw + r.raw0, i, n, r.total, a.o.pad);
-        int total;
-        const int64_t slot = at + scan::block_exclusive(f.keep ? 1 : 0, &total);
-        if (f.keep && slot < a.out_slots)
-            a.out[slot] = fa_vad_segment{b, 0, f.start, f.end, static_cast<double>(f.start) / kRate, static_cast<double>(f.end) / kRate};
-        at += total;
-    }
+    const int64_t first = a.kept[b];         // the records of the recordings before this one
+    Finished f{0, 0, false};                 // raw speech i of this thread, from value_of(i) to place(i, ...)
+    const auto keep_of = [&](const int32_t i) { f = finish(a.raw + r.raw0, i, n, r.total, a.o.pad); return f.keep ? 1 : 0; };
+    (void)scan::workgroup_exclusive(n, keep_of, [&](int32_t, const int keep, const int at) {
+        if (keep && first + at < a.out_slots)
+            a.out[first + at] = fa_vad_segment{b, 0, f.start, f.end, static_cast<double>(f.start) / kRate, static_cast<double>(f.end) / kRate};
+    });
 }
 
 // One workgroup per row: 1040 groups of four elements.

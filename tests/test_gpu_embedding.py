@@ -347,6 +347,19 @@ def test_compaction_block_boundary(fa, gpu_ctx, C, skip):
         assert 0 < want["skipped"] < len(want["records"])
 
 
+@pytest.mark.parametrize("C", [2047, 2048, 2049, 4095, 4096, 4097])
+def test_compaction_kept_none_all_and_the_last_item(fa, gpu_ctx, C):
+    """One speaker: an item per planned chunk, so C items end one short of, at, and one past the first and the second compaction workgroup
+    (256 x 8 items each).  No item kept, every item kept, and the last item alone."""
+    for kind in ("none", "all", "last"):
+        w = np.zeros((C, 8, 1), f32)
+        if kind != "none":
+            w[0 if kind == "all" else C - 1:] = 1
+        _, want = check(fa, gpu_ctx, w, np.arange(C) * 1.0, 16000 * (C + 20), weight_frames=5)
+        assert want["evaluated"] == C and len(want["records"]) == {"none": 0, "all": C, "last": 1}[kind]
+        assert kind == "none" or want["records"][-1][0] == C - 1
+
+
 def test_plan_early_exits(fa, gpu_ctx):
     """The status, the error text and the fa_embedding_info fields at every exit fa_embedding_plan takes before it touches the device, in the
     order it checks: a call that is wrong in two ways reports the earlier one."""

@@ -152,6 +152,36 @@ def test_packed_waveforms_are_the_scaled_samples(fa, gpu_ctx, chain):
     assert e.value.status == fa.INVALID_ARGUMENT
 
 
+PACK_SLICE = 4096                                 # samples of a row one workgroup writes (csrc/row_pack_launch.h: kPackSlice)
+
+
+@pytest.mark.parametrize("stride", (PACK_SLICE - 4, PACK_SLICE, PACK_SLICE + 4, PACK_SLICE + 3))
+def test_packed_rows_round_a_slice_and_across_groups(fa, gpu_ctx, stride):
+    """Rows one group of four short of a slice, a slice, one group into a second slice, and a stride that is no multiple of four (the
+    dword path); 64, 65 and 129 chunks (a launch carries 64) of 0, 1, stride - 1 and stride samples, from sources that are not 16-byte
+    aligned.  Every row is float32(x) * float32(32768) bit for bit, then zeros."""
+    import torch
+    rng = np.random.default_rng(stride)
+    audio = rng.uniform(-1, 1, stride + 300).astype(np.float32)
+    audio[:6] = (np.inf, -np.inf, 1e-40, -0.0, 3e38, 2.0 ** -15)                                 # the product overflows, leaves the denormals, is exact
+    lead = 3
+    dev = torch.from_numpy(np.concatenate([np.full(lead, np.nan, np.float32), audio, np.full(5, np.nan, np.float32)])).cuda()
+    offsets = np.array([lead, lead + audio.size], np.int64)
+    for count in (64, 65, 129):
+        chunks = np.zeros(count, fa.fsmn_vad.FSMN_VAD_CHUNK_DTYPE)
+        chunks["start_sample"] = rng.integers(0, 300, count)
+        chunks["start_sample"][:4] = (0, 1, 2, 3)
+        chunks["end_sample"] = chunks["start_sample"] + np.resize(np.array([0, 1, stride - 1, stride]), count)
+        chunks["end_sample"][-1] = chunks["start_sample"][-1] + stride                           # the last row of the last group is a full one
+        want = np.zeros((count, stride), np.float32)
+        for i, c in enumerate(chunks):
+            n = int(c["end_sample"] - c["start_sample"])
+            with np.errstate(over="ignore"):
+                want[i, :n] = audio[c["start_sample"]:c["end_sample"]] * np.float32(32768)
+        rows = fa.fsmn_vad_pack_waveforms_dev(dev, offsets, chunks, row_stride=stride, ctx=gpu_ctx)
+        assert rows.shape == (count, stride) and rows.cpu().numpy().tobytes() == want.tobytes()
+
+
 @pytest.mark.parametrize("dtype", ["float32", "float16"])
 def test_gathered_silence_is_the_frame_grid(fa, gpu_ctx, chain, dtype):
     """The reference test's own stand-in scorer: column 0 of a chunk's frame i is its absolute frame start / 160 + i, so the gathered

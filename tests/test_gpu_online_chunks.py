@@ -118,13 +118,12 @@ def test_pack_both_modes_at_ragged_lengths(fa, gpu_ctx, chunk_samples):
         assert R.bits(got).tolist() == R.bits(want).tolist()
 
 
-def finish_case(frames, chunks, seed):
-    """Three streams: weights (soft, hard, crafted first chunk), embeddings (voices with noise, a zero row, a row under the magnitude),
+def finish_case(frames, chunks, seed, B=3):
+    """B streams: weights (soft, hard, crafted first chunk), embeddings (voices with noise, a zero row, a row under the magnitude),
     offsets (0 for the first chunk), and the restatement's records, assignments and state."""
     rng = np.random.default_rng(seed)
     kw = cfg_for(frames)
     rcfg = R.ChunkConfig(**kw)
-    B = 3
     ar = R.Arith(R.dot256)
     mgrs = [R.SpeakerManager(ar, max_speakers=4, raw_capacity=3, min_speech_duration=0.1) for _ in range(B)]
     voices = [unit(rng) for _ in range(4)]
@@ -200,6 +199,73 @@ def test_finish_equals_the_restatement(fa, gpu_ctx, finish_cases, frames, chunks
                 assert device_state(db, b) == restated_state(mgrs[b])
         finally:
             db.close()
+
+
+@pytest.mark.parametrize("streams,chunks", ((85, 1), (43, 2), (171, 1), (128, 2)))
+def test_plan_scans_more_triples_than_one_pass_holds(fa, gpu_ctx, streams, chunks):
+    """255, 258, 513 and 768 (stream, chunk, speaker) triples — a triple count is a multiple of 3, so these are the counts next to one
+    pass of the 256-thread scan, one past two passes, and three whole passes.  One frame per chunk: a speaker runs when it alone is
+    active.  Triples 254 and 256 (round the end of the first pass) are made to run where they exist, and so is one of the last chunk."""
+    import torch
+    frames = FRAMES[0]
+    rng = np.random.default_rng(streams * 10 + chunks)
+    kw = cfg_for(frames)
+    cfg, rcfg = fa.OnlineChunkConfig(**kw), R.ChunkConfig(**kw)
+    full, n = kw["chunk_samples"], streams * chunks
+    hw = (rng.random((n, frames, 3)) < 0.4).astype(F)
+    for chunk, speaker in ((n - 1, 2), (84, 2), (85, 1)):
+        if chunk < n:
+            hw[chunk] = 0
+            hw[chunk, :, speaker] = 1
+    hw = hw.reshape(streams, chunks, frames, 3)
+    samples = rng.choice(np.array([1, full // 2, full - 1, full], np.int32), (streams, chunks))
+    want_act, want_runs, want_rows = np.zeros((streams, chunks, 3), F), [], []
+    for b in range(streams):
+        for c in range(chunks):
+            want_act[b, c], rows = R.plan_chunk(hw[b, c], int(samples[b, c]), rcfg)
+            for s, row in enumerate(rows):
+                if row is not None:
+                    want_runs.append((b, c, s))
+                    want_rows.append(row)
+    flat = [(b * chunks + c) * 3 + s for b, c, s in want_runs]
+    assert 20 < len(flat) < n * 3 and all(t in flat for t in (254, 256) if t < n * 3) and flat[-1] >= n * 3 - 3   # the inputs
+    act, runs, rows = fa.online_chunk_plan(torch.from_numpy(hw).cuda(), samples, config=cfg, ctx=gpu_ctx)
+    assert R.bits(act.cpu().numpy()).tolist() == R.bits(want_act).tolist()
+    assert [tuple(int(x) for x in r) for r in runs.tolist()] == want_runs
+    assert R.bits(rows.cpu().numpy()).tolist() == R.bits(np.array(want_rows, F).reshape(-1, frames)).tolist()
+
+
+@pytest.mark.parametrize("streams,chunks", ((128, 2), (257, 1), (129, 2)))
+def test_finish_scans_more_chunks_than_one_pass_holds(fa, gpu_ctx, streams, chunks):
+    """256, 257 and 258 (stream, chunk) pairs: the scan of the chunks' segment counts fills one pass of its 256 threads exactly, and runs
+    one and two pairs into a second.  17 frames a chunk, the smallest size class whose chunks keep segments."""
+    import torch
+    frames, n = 17, streams * chunks
+    kw, w, emb, off, want_seg, want_assign, want_counts, mgrs = finish_case(frames, chunks, 77 + n, B=streams)
+    flat_counts = want_counts.reshape(-1)
+    assert len(want_seg) > 256 and flat_counts[:256].sum() > 0 and (n == 256 or flat_counts[256:].sum() > 0)   # the inputs
+    cfg = fa.OnlineChunkConfig(**kw)
+    dw, de = torch.from_numpy(w).cuda(), torch.from_numpy(emb).cuda()
+    act, _, _ = fa.online_chunk_plan(dw, None, config=cfg, ctx=gpu_ctx)
+    config = fa.SpeakerDbConfig(max_speakers=4, raw_capacity=3, min_speech_duration=0.1)
+    short = fa.SpeakerDatabase(streams, config, ctx=gpu_ctx)
+    try:
+        with pytest.raises(fa.FluidAudioHipError) as err:                               # one record short: the count is still the full one
+            fa.online_chunk_finish(short, dw, act, de, off, config=cfg, tick=7, capacity=len(want_seg) - 1)
+        assert err.value.status == fa._lib.OUTPUT_TOO_SMALL and err.value.count == len(want_seg)
+    finally:
+        short.close()
+    db = fa.SpeakerDatabase(streams, config, ctx=gpu_ctx)
+    try:
+        seg, assign, counts = fa.online_chunk_finish(db, dw, act, de, off, config=cfg, tick=7)
+        assert assign["id"].tolist() == want_assign["id"].tolist() and assign["slot"].tolist() == want_assign["slot"].tolist()
+        assert assign["kind"].tolist() == want_assign["kind"].tolist() and assign["distance"].view(np.uint32).tolist() == want_assign["distance"].tolist()
+        assert counts.tolist() == want_counts.tolist()
+        assert seg_tuples(seg) == want_seg
+        for b in (0, 2, streams - 1):
+            assert device_state(db, b) == restated_state(mgrs[b])
+    finally:
+        db.close()
 
 
 def test_end_to_end_eight_streams_of_five_chunks(fa, gpu_ctx):

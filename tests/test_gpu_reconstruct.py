@@ -272,6 +272,22 @@ def test_run_compaction_block_boundary(fa, gpu_ctx, F):
     assert st["T"] == F
 
 
+@pytest.mark.parametrize("F", [2047, 2048, 2049, 4095, 4096, 4097])
+def test_run_compaction_kept_none_densest_and_the_last_item(fa, gpu_ctx, F):
+    """One cluster, one slot per frame: F items end one short of, at, and one past the first and the second compaction workgroup (256 x 8
+    items each).  No run; a run on every other frame, the most a cluster can start (a start needs the frame before it inactive); and one
+    run that starts on the last item."""
+    hard = np.array([[0, -2, 0]], np.int32)
+    for kind, runs in (("none", 0), ("densest", (F + 1) // 2), ("last", 1)):
+        w = np.zeros((1, F, 3), np.float32)
+        if kind == "densest":
+            w[0, ::2, 0] = 1
+        elif kind == "last":
+            w[0, -1, 2] = 1
+        _, st = check(fa, gpu_ctx, w, hard, 1, [0.0], 0.0625, min_segment_duration=0.0, min_gap_duration=0.0)
+        assert st["T"] == F and len(st["raw"]) == runs
+
+
 def test_powerset_decode_of_misaligned_logits(fa, gpu_ctx):
     """7 classes whose logits start one float past a 16-byte boundary take the row kernel and give what the aligned tensor gives; fewer
     rows than one group of four run as the tail alone."""

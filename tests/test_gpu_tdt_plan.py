@@ -147,6 +147,33 @@ def test_rows_and_lengths_bit_for_bit(fa, gpu_ctx, cases):
         assert d_rows.cpu().numpy().view(np.uint32).tobytes() == rows.tobytes()
 
 
+@pytest.mark.parametrize("row", (10400, 10402))
+def test_rows_across_launch_groups(fa, gpu_ctx, row):
+    """64, 65 and 129 windows (a launch carries 64) into rows of two slices and a part, with 16-byte stores (10400) and without (10402);
+    lengths 0, 1, row - 1 and row from odd source offsets; the samples are arbitrary bit patterns, NaNs with payloads among them."""
+    import torch
+    cfg = fa.tdt_window_config(maxModelSamples=row)
+    rng = np.random.default_rng(row)
+    bits = rng.integers(0, 1 << 32, row + 300, dtype=np.uint64).astype(np.uint32)
+    bits[:3] = (0x7FC00001, 0xFF800001, 0x7F800000)                              # a quiet NaN with a payload, a signalling one, +inf
+    lead = 3
+    dev = torch.from_numpy(np.concatenate([np.full(lead, POISON), bits, np.full(5, POISON)]).view(np.float32)).cuda()
+    offsets = np.array([lead, lead + bits.size], np.int64)
+    for count in (64, 65, 129):
+        windows = np.zeros(count, fa.TDT_WINDOW_DTYPE)
+        windows["context_start"] = rng.integers(0, 300, count)
+        windows["context_start"][:4] = (0, 1, 2, 3)
+        windows["length"] = np.resize(np.array([0, 1, row - 1, row]), count)
+        windows["length"][-1] = row                                              # the last row of the last group is a full one
+        want = np.zeros((count, row), np.uint32)
+        for i, w in enumerate(windows):
+            want[i, :w["length"]] = bits[w["context_start"]:w["context_start"] + w["length"]]
+        rows, lengths = fa.tdt_pack_windows_dev(dev, offsets, windows, config=cfg, ctx=gpu_ctx)
+        torch.cuda.synchronize()
+        assert lengths.cpu().numpy().tolist() == windows["length"].tolist()
+        assert rows.shape == (count, row) and rows.cpu().numpy().view(np.uint32).tobytes() == want.tobytes()
+
+
 def tone(n, amplitude, lo=0, hi=None):
     x = np.zeros(n, np.float32)
     i = np.arange(lo, n if hi is None else hi)
