@@ -1,4 +1,5 @@
-// fa_verdict.h — how a plain-C++ argument pass (der_geom.h, timeline_launch.h, paraformer_launch.h, tdt_merge_launch.h, vad_launch.h) reports a refusal
+// fa_verdict.h — how a plain-C++ argument pass or plan (der_geom.h, timeline_launch.h, paraformer_launch.h, tdt_merge_launch.h, vad_launch.h,
+// kws_plan.h, speaker_db_core.h) reports a refusal
 // without a context: the status and the text, which the host unit hands to fa::set_error — unchanged, or behind the entry's name.  No HIP
 // call; the stand-alone programs under tests/cpu include it too.
 #pragma once

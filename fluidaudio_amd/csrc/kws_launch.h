@@ -1,32 +1,16 @@
-// kws_launch.h — what the CTC word spotter's host code (kws_host.hip: the argument pass, the job lists, the arena passes, sort-and-merge,
-// the C ABI) and its kernel translation unit (kws.hip) share: the limits, a job, a candidate record, the kernel's operands and its one
-// launcher.  Internal; not part of the C ABI.
+// kws_launch.h — what the CTC word spotter's host unit (kws_host.hip: staging, launches, synchronisations, the C ABI) and its kernel
+// unit (kws.hip) share beyond the plan (kws_plan.h: the limits, a job, a candidate record, everything the host decides): the kernel's
+// tiling constants, its operands and its one launcher.  Internal; not part of the C ABI.
 #pragma once
 #include "fa_common.h"
+#include "kws_plan.h"
 
 namespace fa {
 namespace kws {
 
-constexpr int kWave = 64;
 constexpr int kWavesPerGroup = 4;   // jobs of one workgroup: consecutive in the job list, which is ordered by utterance
-constexpr int kChunk = 8;           // arena records a job reserves with one atomic
 constexpr int kAhead = 8;           // frames whose emissions a wavefront has in flight ahead of the DP step that needs them
 constexpr int kXcds = 8;            // workgroups with equal blockIdx % 8 share an L2
-
-// the widest keyword of a launch with R states per lane: 2N + 1 <= 64 R
-constexpr int max_tokens(const int states_per_lane) { return (kWave * states_per_lane - 1) / 2; }
-static_assert(max_tokens(4) == FA_KWS_MAX_TOKENS, "four states per lane serve the longest keyword the ABI admits");
-
-struct Job {
-    int32_t utterance, keyword;
-    int32_t t0, t1;                 // the frames [t0, t1) the DP walks: 1 <= tokens <= t1 - t0
-};
-
-struct Record {                     // a candidate before sort-and-merge (spotting), or a window's answer (constrained)
-    int32_t job;                    // index into the launch's job list; -1: the unused tail of a reserved chunk
-    float score;
-    int32_t start, end;
-};
 
 struct WalkArgs {
     const float *lp;                // matrix u at u * matrix_stride, row t at t * row_stride, `vocab` columns read

@@ -1,7 +1,8 @@
-// online_launch.h — what the host side of the online diarizer's speaker database (online_host.hip: the handle, the argument checks, the C
-// ABI, the management entries) and its kernel unit (online.hip) share: the database's device arrays, the operands of each kernel, the
-// launch plans and the launchers.  The arithmetic and the per-slot layout: speaker_db_core.h.  Internal; not part of the C ABI.
-// Launch errors surface through hipGetLastError().
+// online_launch.h — what the online diarizer's two host units (speaker_db_host.hip: the speaker database's handle and entries;
+// online_host.hip: the entries around the networks) and its kernel unit (online.hip) share: the database's device arrays, the operands
+// of each kernel, the launch plans and the launchers, and at the end the handle itself with the two checks both host units make.  The
+// arithmetic, the per-slot layout and the management edits: speaker_db_core.h.  Internal; not part of the C ABI.  Launch errors
+// surface through hipGetLastError().
 #pragma once
 #include "fa_common.h"
 #include "speaker_db_core.h"
@@ -96,6 +97,30 @@ void launch_finish(hipStream_t stream, const FinishArgs &a);
 void launch_assign(hipStream_t stream, const AssignArgs &a);
 void launch_distances(hipStream_t stream, const DistanceArgs &a);
 void launch_pairs(hipStream_t stream, const PairArgs &a);
+
+inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+}  // namespace online
+}  // namespace fa
+
+struct fa_speaker_db {
+    int device = 0;
+    fa::spk::Params p{};
+    int32_t streams = 0;
+    fa::DevBuf current, raws, meta, next_id;
+    fa::online::DbArrays arrays() const {
+        return fa::online::DbArrays{current.as<float>(), raws.as<float>(), meta.as<fa::spk::SlotMeta>(), next_id.as<int32_t>(), streams, p.max_speakers, p.raw_capacity};
+    }
+};
+
+namespace fa {
+namespace online {
+
+inline fa_status check_db(fa_ctx *ctx, const fa_speaker_db *db, const char *what) {
+    if (!ctx || !db) return FA_INVALID_ARGUMENT;
+    if (db->device != ctx->device) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "%s: the database lives on another device than the context", what);
+    return FA_SUCCESS;
+}
 
 }  // namespace online
 }  // namespace fa

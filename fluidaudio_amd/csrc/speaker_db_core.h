@@ -1,6 +1,9 @@
 // speaker_db_core.h — the arithmetic and the state layout of the online speaker database (SpeakerManager.swift:135-212, 411-492,
 // SpeakerTypes.swift:36-162, 213-217, SpeakerOperations.swift:62-126, VDSPOperations.swift:12-23) that the host and the kernels of
-// online.hip share.  Plain C++ in its host half: no HIP type is named unless hipcc compiles it.
+// online.hip share, and at the end the management edits of one stream's slot scalars (upsertSpeaker, getSpeaker, removeSpeaker,
+// removeSpeakersInactive, makeSpeakerPermanent / revokePermanence, reset, speakerCount: SpeakerManager.swift:223-242, 334-367, 500-628),
+// which speaker_db_host.hip runs between a fetch and a write-back.  Plain C++ in its host half: no HIP type is named unless hipcc
+// compiles it; tests/cpu/speaker_db_core_main.cpp walks it under the sanitizers.
 //
 // The fp32 arithmetic is THIS library's definition.  vDSP_dotpr / vDSP_svesq specify no summation order, so Accelerate's bits are out of
 // reach and a decision within an ulp of a threshold may differ from a Mac.  Defined here, and used by everything of this feature:
@@ -16,6 +19,10 @@
 #pragma once
 #include <cmath>
 #include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "fa_verdict.h"
 
 #if defined(__HIPCC__)
 #define FA_SPK_HD __host__ __device__
@@ -264,6 +271,107 @@ template <class V> FA_SPK_HD inline Record assign_one(View &db, const Params &p,
     db.live |= 1ull << slot;
     out.id = id; out.slot = slot; out.kind = kCreated;
     return out;
+}
+
+// ---- the management edits: one stream's slot scalars on the host.  Each returns whether it changed them; the embeddings' rows stay
+// where they are (the host unit copies them once an edit has accepted).
+struct HostStream {
+    std::vector<SlotMeta> meta;   // [max_speakers]
+    int32_t next_id = 1;
+    int find(const int32_t id) const {
+        for (size_t s = 0; s < meta.size(); ++s)
+            if ((meta[s].flags & kLive) && meta[s].id == id) return static_cast<int>(s);
+        return -1;
+    }
+    int lowest_free() const {
+        for (size_t s = 0; s < meta.size(); ++s)
+            if (!(meta[s].flags & kLive)) return static_cast<int>(s);
+        return -1;
+    }
+};
+
+struct Upsert {
+    Verdict verdict;          // refused: nothing was edited
+    int slot = -1;            // where the current embedding and the raws go
+    bool normalise = false;   // a new speaker: Speaker.init normalises the current embedding
+};
+
+// upsertSpeaker (:552-606) of info->id >= 1 with 0 <= info->raw_count raws.
+inline Upsert upsert_edit(HostStream &h, const fa_speaker_info &info, const int32_t raw_capacity, const int32_t stream) {
+    Upsert u;
+    if (info.raw_count > raw_capacity) { u.verdict = refuse(FA_INVALID_ARGUMENT, "speaker_db upsert: more raw embeddings than raw_capacity"); return u; }
+    u.slot = h.find(info.id);
+    if (u.slot >= 0) {   // :565-580: the fields as given, createdAt kept, permanence only ever set
+        SlotMeta &m = h.meta[u.slot];
+        m.duration = info.duration; m.updates = info.update_count; m.updated = info.updated_tick;
+        if (info.is_permanent) m.flags |= kPermanent;
+    } else {             // :582-602
+        u.slot = h.lowest_free();
+        if (u.slot < 0) { u.verdict = refuse(FA_OUTPUT_TOO_SMALL, "speaker_db upsert: no free slot in stream %d", stream); return u; }
+        u.normalise = true;
+        h.meta[u.slot] = fresh_meta(info.id, info.duration, info.created_tick, info.updated_tick, info.is_permanent != 0);
+        h.meta[u.slot].updates = info.update_count;
+        h.next_id = h.next_id > info.id + 1 ? h.next_id : info.id + 1;
+    }
+    h.meta[u.slot].head = 0; h.meta[u.slot].count = info.raw_count;
+    return u;
+}
+
+// getSpeaker: *info (id 0, slot -1 without such a speaker); the slot, whose meta tells the caller where the rows are.
+inline int get_edit(const HostStream &h, const int32_t id, fa_speaker_info *info) {
+    std::memset(info, 0, sizeof(*info));
+    info->slot = -1;
+    const int slot = h.find(id);
+    if (slot < 0) return slot;
+    const SlotMeta &m = h.meta[slot];
+    info->id = m.id; info->slot = slot; info->raw_count = m.count; info->update_count = m.updates; info->is_permanent = (m.flags & kPermanent) ? 1 : 0;
+    info->duration = m.duration; info->created_tick = m.created; info->updated_tick = m.updated;
+    return slot;
+}
+
+// the live ids in slot order into ids[max_speakers]; their number
+inline int32_t ids(const HostStream &h, int32_t *out) {
+    int32_t n = 0;
+    for (const SlotMeta &m : h.meta)
+        if (m.flags & kLive) out[n++] = m.id;
+    return n;
+}
+
+inline int32_t count(const HostStream &h) {
+    int32_t n = 0;
+    for (const SlotMeta &m : h.meta) n += (m.flags & kLive) ? 1 : 0;
+    return n;
+}
+
+inline bool remove(HostStream &h, const int32_t id, const bool keep_if_permanent) {   // :334-347
+    const int slot = h.find(id);
+    if (slot < 0 || (keep_if_permanent && (h.meta[slot].flags & kPermanent))) return false;
+    h.meta[slot] = SlotMeta{};
+    return true;
+}
+
+inline bool remove_inactive(HostStream &h, const int64_t since_tick, const bool keep_if_permanent) {   // :353-367
+    bool changed = false;
+    for (SlotMeta &m : h.meta)
+        if ((m.flags & kLive) && m.updated < since_tick && !(keep_if_permanent && (m.flags & kPermanent))) { m = SlotMeta{}; changed = true; }
+    return changed;
+}
+
+inline bool set_permanent(HostStream &h, const int32_t id, const bool permanent) {
+    const int slot = h.find(id);
+    if (slot < 0) return false;
+    h.meta[slot].flags = kLive | (permanent ? kPermanent : 0);
+    return true;
+}
+
+inline bool reset(HostStream &h, const bool keep_if_permanent) {   // :610-628
+    int32_t max_id = 0;
+    for (SlotMeta &m : h.meta) {
+        if (keep_if_permanent && (m.flags & kLive) && (m.flags & kPermanent)) max_id = m.id > max_id ? m.id : max_id;
+        else m = SlotMeta{};
+    }
+    h.next_id = max_id + 1;
+    return true;
 }
 
 }  // namespace spk

@@ -1,7 +1,8 @@
 """fluidaudio_amd/csrc/speaker_db_core.h — the arithmetic and the state layout of the online speaker database that host and kernels share —
 under the address and undefined-behaviour sanitizers: tests/cpu/speaker_db_core_main.cpp, a stand-alone program, assigns into databases
 whose arrays have exactly their size (raw_capacity 1, 3 and 50), fills every slot, overflows the table and wraps the ring; it runs as a
-child process and must end clean.  Every record and every current embedding it prints equals the restatement's, as bits.  No GPU."""
+child process and must end clean.  Every record and every current embedding it prints equals the restatement's, as bits.  It then runs
+a script of management edits on tables of 1, 3 and 64 slots; the state after every step equals SpeakerManager's.  No GPU."""
 import os
 import subprocess
 import sys
@@ -65,6 +66,14 @@ def out(tmp_path_factory):
             runs[-1]["recs"].append((int(l[1]), int(l[2]), int(l[3]), int(l[4], 16)))
         elif l[0] == "SLOT":
             runs[-1]["slots"].append((int(l[1]), int(l[2]), int(l[3]), int(l[4]), int(l[5], 16), int(l[6]), int(l[7]), [int(x, 16) for x in l[8:]]))
+        elif l[0] == "MANAGE":
+            runs.append(dict(manage=(int(l[1]), int(l[2])), steps=[]))
+        elif l[0] == "STEP":
+            assert l[5] == "|" and "COUNT-MISMATCH" not in l
+            slots = [tuple(int(x, 16) if i % 8 == 5 else int(x) for i, x in enumerate(l[6 + 8 * j: 14 + 8 * j])) for j in range((len(l) - 6) // 8)]
+            runs[-1]["steps"].append([l[1], int(l[2]), int(l[3]), int(l[4]), slots, None])
+        elif l[0] == "TEXT":
+            runs[-1]["steps"][-1][5] = " ".join(l[1:])
         elif l[0] == "COS":
             runs.append(dict(cos=[int(x, 16) for x in l[1:]]))
     return runs
@@ -84,6 +93,77 @@ def test_the_program_ends_clean_and_equals_the_restatement(out):
     assert all(taken.get(k, 0) > 0 for k in ("UPDATED", "DURATION_ONLY", "CREATED", "TOO_SHORT", "FULL", "ring_wrap")), taken
     assert any(len(r["slots"]) == r["cfg"][0] for r in configs[:3])
     assert max(s[2] for s in configs[2]["slots"]) == 50
+
+
+def script(S, Rcap):
+    """The program's manage(S, R) on the restatement: [step, status, next_id, count, [(slot, id, raws, updates, permanent, duration bits,
+    created, updated)], text] after every step."""
+    m = R.SpeakerManager(R.Arith(R.dot256), max_speakers=S, raw_capacity=Rcap)
+    steps = []
+    one = np.ones(256, F)
+
+    def state(step, status=0, text=""):
+        live = [(s, sp.id, len(sp.raws), sp.update_count, int(sp.permanent), R.bits1(sp.duration), sp.created, sp.updated) for s, sp in m.speakers()]
+        assert [x[1] for x in live] == m.speaker_ids and sorted(x[1] for x in live) == sorted(m.state())
+        steps.append([step, status, m.next_id, m.speaker_count, live, text])
+
+    def upsert(id, raws, updates, permanent, duration, created, updated):
+        if raws > Rcap:   # the C ABI's own refusal: the reference's ring has no such bound
+            return 1, "speaker_db upsert: more raw embeddings than raw_capacity"
+        ok = m.upsert_speaker(id, one, duration, [R.RawEmbedding(m.ar, one, 0)] * raws, updates, created, updated, permanent)
+        return (0, "") if ok else (3, "speaker_db upsert: no free slot in stream 0")
+
+    state("empty")
+    state("upsert_new", *upsert(5, 0, 2, False, 1.5, 10, 11))
+    state("upsert_existing", *upsert(5, Rcap, 7, True, 2.5, 99, 20))
+    state("upsert_too_many_raws", *upsert(9, Rcap + 1, 1, False, 1.0, 0, 0))
+    for i in range(S - 1):
+        upsert(100 + i, i % (Rcap + 1), 1, i % 3 == 0, 0.25 * i, i, i)
+    state("filled")
+    state("upsert_full", *upsert(999, 0, 1, False, 1.0, 0, 0))
+    m.remove_speaker(4242, True)
+    state("remove_missing")
+    m.remove_speaker(5, True)
+    state("remove_permanent_kept")
+    m.revoke_permanence(5)
+    m.make_speaker_permanent(4242)
+    state("revoked")
+    m.remove_speaker(5, True)
+    state("removed")
+    state("upsert_low_id", *upsert(3, 1, 1, False, 3.0, 7, 8))
+    m.make_speaker_permanent(3)
+    state("made_permanent")
+    m.remove_speaker(3, False)
+    state("remove_permanent_forced")
+    m.remove_speakers_inactive(S // 2, True)
+    state("remove_inactive")
+    m.reset(True)
+    state("reset_keep")
+    state("upsert_after_reset", *upsert(2, 0, 1, False, 1.0, 1, 1))
+    m.reset(False)
+    state("reset_all")
+    return steps
+
+
+def test_the_management_edits_equal_the_restatement(out):
+    runs = [r for r in out if "manage" in r]
+    assert [r["manage"] for r in runs] == [(1, 3), (3, 3), (64, 3)]
+    for run in runs:
+        want = script(*run["manage"])
+        assert [s[0] for s in run["steps"]] == [s[0] for s in want]
+        for got, exp in zip(run["steps"], want):
+            assert got == exp, (run["manage"], got[0])
+        by = {s[0]: s for s in run["steps"]}
+        S = run["manage"][0]
+        # the edges the script is for: each refusal, a table filled and emptied, speakers kept by their permanence and removed without it
+        assert (by["upsert_too_many_raws"][1], by["upsert_full"][1], by["upsert_existing"][1]) == (1, 3, 0)
+        assert by["filled"][3] == S and by["reset_all"][2:5] == [1, 0, []]
+        assert by["remove_permanent_kept"][3] == S and by["removed"][3] == S - 1 and by["remove_permanent_forced"][3] == S - 1
+        if S > 3:
+            assert 0 < by["remove_inactive"][3] < by["remove_permanent_forced"][3]
+            assert 0 < by["reset_keep"][3] < by["remove_inactive"][3] and by["reset_keep"][2] == max(x[1] for x in by["reset_keep"][4]) + 1
+        else:
+            assert by["reset_keep"][3] == (1 if S == 3 else 0) and by["reset_keep"][2] == (101 if S == 3 else 1)
 
 
 def test_the_cosine_branches(out):
