@@ -42,6 +42,9 @@ from .sortformer_stream import (SORTFORMER_STREAM_PRESETS, SORTFORMER_STREAM_STA
 from .rnnt import (RNNT_BIAS_DEFAULT_BOOST, RNNT_BIAS_MAX_BOOST, RNNT_BIAS_MAX_FORM, RnntBias, RnntConfig, VocabularyTerm,  # noqa: F401
                    bias_build as rnnt_bias_build, bias_candidates as rnnt_bias_candidates, bias_effective_boost as rnnt_bias_effective_boost,
                    decode_logits as rnnt_decode_logits, fold as rnnt_fold)
+from .rnnt_stream import (RNNT_STREAM_CLASS_LANG_TAG, RNNT_STREAM_CLASS_LEXICAL, RNNT_STREAM_STATUS, SECONDS_PER_ENCODER_FRAME,  # noqa: F401
+                          RnntStreamConfig, RnntStreamSnapshot, RnntStreamState, RnntStreamTracked, rms as rnnt_stream_rms, seconds as rnnt_stream_seconds,
+                          token_classes as rnnt_stream_token_classes)
 from .tdt import (Language, Script, TdtConfig, TdtDurationMapping, TdtFrameNavigation, decode_logits as tdt_decode_logits,  # noqa: F401
                   decode_logits_lang as tdt_decode_logits_lang, decode_tables as tdt_decode_tables, matches as tdt_matches,
                   token_classes as tdt_token_classes, topk_rows as tdt_topk_rows)

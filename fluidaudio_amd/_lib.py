@@ -79,6 +79,9 @@ EXPORTED_SYMBOLS = [
     "fa_sortformer_stream_default_config", "fa_sortformer_stream_preset_config", "fa_sortformer_stream_geometry", "fa_sortformer_stream_pop_out_length", "fa_sortformer_stream_create",
     "fa_sortformer_stream_destroy", "fa_sortformer_stream_inputs", "fa_sortformer_stream_get", "fa_sortformer_stream_set", "fa_sortformer_stream_reset", "fa_sortformer_stream_update_dev",
     "fa_sortformer_stream_update", "fa_sortformer_stream_chunk_plan", "fa_sortformer_stream_file_chunks", "fa_sortformer_stream_pack_chunks_dev",
+    "fa_rnnt_stream_default_config", "fa_rnnt_stream_geometry", "fa_rnnt_stream_rms", "fa_rnnt_stream_create", "fa_rnnt_stream_destroy", "fa_rnnt_stream_reset", "fa_rnnt_stream_get",
+    "fa_rnnt_stream_set", "fa_rnnt_stream_gate_dev", "fa_rnnt_stream_mel_inputs_dev", "fa_rnnt_stream_advance_dev", "fa_rnnt_stream_track_dev", "fa_rnnt_stream_finalize_dev",
+    "fa_rnnt_stream_merge_rescued_dev", "fa_rnnt_stream_gate", "fa_rnnt_stream_track", "fa_rnnt_stream_merge_rescued",
 ]
 
 
@@ -321,6 +324,27 @@ class SortformerStreamInfo(C.Structure):                               # fa_sort
 class SortformerChunk(C.Structure):                                    # fa_sortformer_chunk
     _fields_ = [("ready", C.c_int32), ("chunk_length", C.c_int32), ("left_offset", C.c_int32), ("right_offset", C.c_int32), ("start_frame", C.c_int64), ("rows", C.c_int64),
                 ("new_start_feat", C.c_int64), ("frames_to_drop", C.c_int64)]
+
+
+class RnntStreamConfig(C.Structure):                                   # fa_rnnt_stream_config
+    _fields_ = [(n, C.c_int32) for n in ("window_samples", "close_silent_windows", "pre_roll_windows", "min_speech_windows", "max_span_samples", "open_slack_frames",
+                                         "close_slack_frames", "vad_hangover_chunks", "mel_features", "pre_encode_cache", "total_mel_frames", "reserved")] + \
+               [(n, C.c_float) for n in ("rescue_rms_threshold", "vad_rms_threshold")]
+
+
+class RnntStreamInfo(C.Structure):                                     # fa_rnnt_stream_info
+    _fields_ = [(n, C.c_int32) for n in ("frame_cursor", "span_open", "span_start_frame", "span_last_speech_frame", "span_speech_windows", "span_pre_roll_frames",
+                                         "silent_window_run", "span_overflowed", "span_samples", "pre_roll_samples", "vad_consecutive_low_chunks", "vad_skip_count",
+                                         "absolute_frame_base", "detected_blank_spans", "blank_rescues", "mel_cache_frames")]
+
+
+class RnntStreamRequest(C.Structure):                                  # fa_rnnt_stream_request
+    _fields_ = [(n, C.c_int32) for n in ("stream", "span_start_frame", "span_end_frame", "speech_windows", "audio_samples", "decode_chunks", "status", "reserved")] + \
+               [("audio_offset", C.c_int64)]
+
+
+class RnntStreamGeometry(C.Structure):                                 # fa_rnnt_stream_geometry_info
+    _fields_ = [(n, C.c_int32) for n in ("span_capacity", "pre_roll_capacity", "mel_cache_capacity", "reserved")]
 
 
 class ExportEmbedding(C.Structure):                                    # fa_export_embedding
@@ -683,6 +707,26 @@ def lib() -> C.CDLL:
     L.fa_sortformer_stream_chunk_plan.argtypes = [sc, vp, vp, i32, vp]
     L.fa_sortformer_stream_file_chunks.argtypes = [sc, i64, i64, vp, i64, C.POINTER(i64), C.POINTER(i64)]
     L.fa_sortformer_stream_pack_chunks_dev.argtypes = [vp, sc, vp, vp, vp, i32, vp]
+    rc = C.POINTER(RnntStreamConfig)
+    L.fa_rnnt_stream_default_config.argtypes = [rc]
+    L.fa_rnnt_stream_default_config.restype = None
+    L.fa_rnnt_stream_geometry.argtypes = [rc, C.POINTER(RnntStreamGeometry)]
+    L.fa_rnnt_stream_rms.argtypes = [vp, i64, i32, C.POINTER(f32)]
+    L.fa_rnnt_stream_create.argtypes = [vp, rc, i32, C.POINTER(vp)]
+    L.fa_rnnt_stream_destroy.argtypes = [vp]
+    L.fa_rnnt_stream_destroy.restype = None
+    L.fa_rnnt_stream_reset.argtypes = [vp, vp, i32]
+    L.fa_rnnt_stream_get.argtypes = [vp, vp, i32, C.POINTER(RnntStreamInfo), vp, vp, vp]
+    L.fa_rnnt_stream_set.argtypes = L.fa_rnnt_stream_get.argtypes
+    L.fa_rnnt_stream_gate_dev.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.fa_rnnt_stream_gate.argtypes = L.fa_rnnt_stream_gate_dev.argtypes
+    L.fa_rnnt_stream_mel_inputs_dev.argtypes = [vp, vp, vp, i32, i64, i64, i64, vp, vp, i32, vp, vp]
+    L.fa_rnnt_stream_advance_dev.argtypes = [vp, vp, vp, vp, i32, vp, i32]
+    L.fa_rnnt_stream_track_dev.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, i32, i32, vp, i32, vp, i64, vp, vp]
+    L.fa_rnnt_stream_track.argtypes = L.fa_rnnt_stream_track_dev.argtypes
+    L.fa_rnnt_stream_finalize_dev.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, i32, i32, vp, i32, vp, i64, vp, vp]
+    L.fa_rnnt_stream_merge_rescued_dev.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, i32, vp]
+    L.fa_rnnt_stream_merge_rescued.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, i32, vp]
     _lib = L
     return L
 

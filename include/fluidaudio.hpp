@@ -2024,4 +2024,111 @@ class SortformerStreamingState {    // SortformerStreamingState + SortformerStat
     fa_sortformer_stream *st_ = nullptr;
 };
 
+// ---- the Nemotron streaming session around its networks (ASR/Parakeet/Streaming/Nemotron/StreamingNemotronMultilingualAsrManager+Pipeline.swift,
+// +Buffers.swift, +BlankRescue.swift; the C entries are batched over streams, this is ONE stream on host arrays).
+struct NemotronStreamConfig {       // the knobs of the gate, the mel cache and the blank-span rescue; totalMelFrames is the caller's
+    fa_rnnt_stream_config c{};
+    explicit NemotronStreamConfig(int totalMelFrames) { fa_rnnt_stream_default_config(&c); c.total_mel_frames = totalMelFrames; }
+    fa_rnnt_stream_geometry_info geometry() const {
+        fa_rnnt_stream_geometry_info g{};
+        if (fa_rnnt_stream_geometry(&c, &g) != FA_SUCCESS) throw Error(FA_INVALID_ARGUMENT, "fa_rnnt_stream_geometry", "the config is refused");
+        return g;
+    }
+};
+
+struct RescueRequest {              // what closeSpanAndMaybeRescue hands to rescueDecode, the audio padded as :243-251
+    fa_rnnt_stream_request record{};
+    std::vector<float> audio;       // decode_chunks * rescueChunkSamples
+};
+
+struct NemotronTokenTiming {        // the fields of TokenTiming this path reads; startTime = frame * 0.08
+    int tokenId = 0;
+    int frame = 0;
+    double startTime() const { return static_cast<double>(frame) * 0.08; }
+};
+
+class NemotronStreamSession {       // the gate, the span tracker and mergeRescuedTokens of one stream
+  public:
+    NemotronStreamSession(Context &ctx, const NemotronStreamConfig &config, std::vector<uint8_t> tokenClasses)
+        : ctx_(ctx), cfg_(config), classes_(std::move(tokenClasses)) {
+        ctx_.check(fa_rnnt_stream_create(ctx_.handle(), &cfg_.c, 1, &st_), "fa_rnnt_stream_create");
+    }
+    ~NemotronStreamSession() { fa_rnnt_stream_destroy(st_); }
+    NemotronStreamSession(const NemotronStreamSession &) = delete;
+    NemotronStreamSession &operator=(const NemotronStreamSession &) = delete;
+
+    static float rms(const std::vector<float> &x, bool gate = false) {
+        float r = 0.0f;
+        if (fa_rnnt_stream_rms(x.empty() ? nullptr : x.data(), static_cast<int64_t>(x.size()), gate ? 1 : 0, &r) != FA_SUCCESS) throw Error(FA_INVALID_ARGUMENT, "fa_rnnt_stream_rms");
+        return r;
+    }
+    // Pipeline.swift:86-104: true when the chunk skips the encoder
+    bool gate(const std::vector<float> &samples, float *rmsOut = nullptr) {
+        float r = 0.0f;
+        int32_t skip = 0, run = 0, count = 0, status = 0;
+        ctx_.check(fa_rnnt_stream_gate(ctx_.handle(), st_, samples.empty() ? nullptr : samples.data(), static_cast<int32_t>(samples.size()), nullptr, &r, &skip, &run, &count, &status),
+                   "fa_rnnt_stream_gate");
+        if (rmsOut) *rmsOut = r;
+        return skip != 0;
+    }
+    // updateRescueSpans over one chunk against the live timings: the spans that ask for a rescue decode
+    std::vector<RescueRequest> track(const std::vector<float> &samples, const std::vector<NemotronTokenTiming> &timings, int rescueChunkSamples) {
+        const int32_t windows = static_cast<int32_t>(samples.size()) / cfg_.c.window_samples, capacity = windows / (cfg_.c.close_silent_windows + 1) + 1;
+        const fa_rnnt_stream_geometry_info g = cfg_.geometry();
+        const int64_t room = static_cast<int64_t>(capacity) * (static_cast<int64_t>(g.span_capacity) + 2 * static_cast<int64_t>(rescueChunkSamples));
+        std::vector<int32_t> frames(timings.size() + 1), ids(timings.size() + 1);
+        for (size_t i = 0; i < timings.size(); ++i) { frames[i] = timings[i].frame; ids[i] = timings[i].tokenId; }
+        const int32_t count = static_cast<int32_t>(timings.size());
+        std::vector<fa_rnnt_stream_request> records(static_cast<size_t>(capacity));
+        std::vector<float> arena(static_cast<size_t>(room));
+        int32_t found = 0, status = 0;
+        ctx_.check(fa_rnnt_stream_track(ctx_.handle(), st_, samples.empty() ? nullptr : samples.data(), static_cast<int32_t>(samples.size()), nullptr, frames.data(), ids.data(), &count,
+                                        count, classes_.empty() ? nullptr : classes_.data(), static_cast<int32_t>(classes_.size()), rescueChunkSamples, records.data(), capacity,
+                                        arena.data(), room, &found, &status), "fa_rnnt_stream_track");
+        if (status != FA_RNNT_STREAM_OK || found > capacity) throw Error(FA_RUNTIME_ERROR, "fa_rnnt_stream_track", "a request did not fit");
+        std::vector<RescueRequest> out(static_cast<size_t>(found));
+        for (int32_t i = 0; i < found; ++i) {
+            out[static_cast<size_t>(i)].record = records[static_cast<size_t>(i)];
+            const float *p = arena.data() + records[static_cast<size_t>(i)].audio_offset;
+            out[static_cast<size_t>(i)].audio.assign(p, p + static_cast<int64_t>(records[static_cast<size_t>(i)].decode_chunks) * rescueChunkSamples);
+        }
+        return out;
+    }
+    // rescueDecode's staging and mergeRescuedTokens: true when the rescue was committed.  stagedIds with language tags, one frame per id that is none.
+    bool mergeRescued(const RescueRequest &request, const std::vector<int> &stagedIds, const std::vector<int> &stagedFrames, std::vector<int> &liveIds,
+                      std::vector<NemotronTokenTiming> &liveTimings) {
+        const int32_t scap = static_cast<int32_t>(stagedIds.size()) + 1, lcap = static_cast<int32_t>(liveIds.size() + stagedIds.size()) + 1;
+        std::vector<int32_t> sid(static_cast<size_t>(scap)), sfr(static_cast<size_t>(scap)), ids(static_cast<size_t>(lcap)), frames(static_cast<size_t>(lcap)), timed(static_cast<size_t>(lcap));
+        std::copy(stagedIds.begin(), stagedIds.end(), sid.begin());
+        std::copy(stagedFrames.begin(), stagedFrames.end(), sfr.begin());
+        std::copy(liveIds.begin(), liveIds.end(), ids.begin());
+        for (size_t i = 0; i < liveTimings.size(); ++i) { frames[i] = liveTimings[i].frame; timed[i] = liveTimings[i].tokenId; }
+        int32_t nid = static_cast<int32_t>(stagedIds.size()), nfr = static_cast<int32_t>(stagedFrames.size()), idc = static_cast<int32_t>(liveIds.size()),
+                tc = static_cast<int32_t>(liveTimings.size()), status = 0;
+        fa_rnnt_stream_request r = request.record;
+        r.stream = 0;
+        ctx_.check(fa_rnnt_stream_merge_rescued(ctx_.handle(), st_, &r, 1, sid.data(), sfr.data(), &nid, &nfr, scap, ids.data(), frames.data(), timed.data(), &idc, &tc, lcap,
+                                                classes_.empty() ? nullptr : classes_.data(), static_cast<int32_t>(classes_.size()), &status), "fa_rnnt_stream_merge_rescued");
+        if (status != FA_RNNT_STREAM_OK && status != FA_RNNT_STREAM_NO_LEXICAL) throw Error(FA_INVALID_ARGUMENT, "fa_rnnt_stream_merge_rescued", "the staged tokens are refused");
+        liveIds.assign(ids.begin(), ids.begin() + idc);
+        liveTimings.resize(static_cast<size_t>(tc));
+        for (int32_t i = 0; i < tc; ++i) liveTimings[static_cast<size_t>(i)] = NemotronTokenTiming{timed[static_cast<size_t>(i)], frames[static_cast<size_t>(i)]};
+        return status == FA_RNNT_STREAM_OK;
+    }
+    fa_rnnt_stream_info info() {
+        fa_rnnt_stream_info i{};
+        ctx_.check(fa_rnnt_stream_get(ctx_.handle(), st_, 0, &i, nullptr, nullptr, nullptr), "fa_rnnt_stream_get");
+        return i;
+    }
+    int detectedBlankSpanCount() { return info().detected_blank_spans; }
+    int blankRescueCount() { return info().blank_rescues; }
+    void reset() { ctx_.check(fa_rnnt_stream_reset(ctx_.handle(), st_, 0), "fa_rnnt_stream_reset"); }
+
+  private:
+    Context &ctx_;
+    NemotronStreamConfig cfg_;
+    std::vector<uint8_t> classes_;
+    fa_rnnt_stream *st_ = nullptr;
+};
+
 }  // namespace fluidaudio

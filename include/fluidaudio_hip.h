@@ -1828,6 +1828,147 @@ fa_status fa_sortformer_stream_file_chunks(const fa_sortformer_stream_config *cf
 fa_status fa_sortformer_stream_pack_chunks_dev(fa_ctx *ctx, const fa_sortformer_stream_config *cfg, const float *d_mel, const int64_t *stream_offsets,
                                                const fa_sortformer_chunk *chunks, int32_t streams, float *d_rows);
 
+/* ------------------------------------------------------------------ Nemotron streaming session: gate, mel cache, blank-span rescue ------ */
+/* What a Nemotron streaming session does around its networks and its decode walk (fa_rnnt_greedy_logits_dev), as device-resident state
+ * batched over streams: the VAD-gated skip with hangover (StreamingNemotronMultilingualAsrManager+Pipeline.swift:78-104, +Buffers.swift:35-63),
+ * the mel cache in front of the encoder's input (+Buffers.swift:140-210) and the blank-span rescue's bookkeeping (+BlankRescue.swift:
+ * the span machine :70-119, the closing test :123-164, the padded span audio :243-251, the staged tokens' filter, clamp and merge :264-354).
+ * The networks, the rescue decode itself and the tokenizer stay the caller's.  Call order per chunk: gate, mel_inputs, the encoder,
+ * fa_rnnt_greedy_logits_dev, advance, track, the rescue decode of the requests, merge_rescued.
+ * The library's own definitions beside the reference:
+ *   times     every startTime of this path is Double(frame) * 0.08, so the reference's comparisons on seconds are comparisons on the
+ *             int32 frames kept here: f >= start - 1 && f <= last + 5, and > for the insert index
+ *   RMS       vDSP_rmsqv's summation order is unspecified; the order here is rnnt_stream_core.h's: element i belongs to lane (i / 4) % 64
+ *             (of wavefront (i / 256) % 4 for the gate's chunk), a lane adds its squares in ascending i with a fused multiply-add, six
+ *             butterfly steps (xor 32, 16, 8, 4, 2, 1), the gate's four wavefront sums added in ascending order, one IEEE divide by n,
+ *             one correctly rounded square root; silent = rms < threshold
+ *   closures  the closures of one chunk are judged against the live timings of that chunk and merged afterwards (the reference rescues
+ *             inside the window loop); equal, because rescued frames are clamped to last + 1 and the next span's test starts at
+ *             start' - 1 >= last + 2.  merge_rescued runs before the next chunk's track. */
+typedef struct fa_rnnt_stream fa_rnnt_stream;
+typedef struct {
+    int32_t window_samples;           /* 1280 = one encoder frame; a multiple of 4 in 4 .. 8192 */
+    int32_t close_silent_windows;     /* 2; 1 .. 1024 */
+    int32_t pre_roll_windows;         /* 3; 0 .. 64 */
+    int32_t min_speech_windows;       /* 2; 0 .. 2^20 */
+    int32_t max_span_samples;         /* 240000 = 15 s; 1 .. 2^24 */
+    int32_t open_slack_frames;        /* 1; 0 .. close_silent_windows - 1 (see closures above) */
+    int32_t close_slack_frames;       /* 5; 0 .. 2^20 */
+    int32_t vad_hangover_chunks;      /* 2; 1 .. 2^20 */
+    int32_t mel_features;             /* 128; 1 .. 4096 */
+    int32_t pre_encode_cache;         /* 9; 0 .. 64 */
+    int32_t total_mel_frames;         /* the encoder's frame axis: required, pre_encode_cache (at least 1) .. 65536 */
+    int32_t reserved;
+    float rescue_rms_threshold;       /* 0.0025; 0 disables span tracking; finite, >= 0 */
+    float vad_rms_threshold;          /* 0 = the gate is off (the reference's default); in [0, 1) */
+} fa_rnnt_stream_config;
+/* Per-stream (and per-request) status.  OK: done.  INACTIVE: d_active was 0, nothing looked at.  BAD_OPERAND: a count outside its array
+ * or a stream outside the state, nothing written.  OUTPUT_TOO_SMALL: a request without a record or without room in the arena, or a
+ * merge beyond the live capacity.  NO_LEXICAL (requests of merge_rescued): the staged tokens held no lexical one, nothing committed. */
+enum { FA_RNNT_STREAM_OK = 0, FA_RNNT_STREAM_INACTIVE = 1, FA_RNNT_STREAM_BAD_OPERAND = 2, FA_RNNT_STREAM_OUTPUT_TOO_SMALL = 3, FA_RNNT_STREAM_NO_LEXICAL = 4 };
+/* the class byte of a vocabulary id */
+enum { FA_RNNT_STREAM_CLASS_LEXICAL = 1, FA_RNNT_STREAM_CLASS_LANG_TAG = 2 };
+typedef struct {   /* one stream's scalars (get / set) */
+    int32_t frame_cursor;                    /* rescueFrameCursor */
+    int32_t span_open, span_start_frame, span_last_speech_frame, span_speech_windows, span_pre_roll_frames, silent_window_run, span_overflowed;
+    int32_t span_samples;                    /* rescueSpanAudio.count */
+    int32_t pre_roll_samples;                /* rescuePreRollTail.count */
+    int32_t vad_consecutive_low_chunks, vad_skip_count, absolute_frame_base;
+    int32_t detected_blank_spans, blank_rescues;
+    int32_t mel_cache_frames;                /* 0: no cache yet */
+} fa_rnnt_stream_info;
+typedef struct {   /* one rescue request */
+    int32_t stream;
+    int32_t span_start_frame;                /* start - preRoll */
+    int32_t span_end_frame;                  /* lastSpeech + 1 */
+    int32_t speech_windows;
+    int32_t audio_samples;                   /* the span's samples */
+    int32_t decode_chunks;                   /* ceil(audio_samples / rescue_chunk_samples) + 1 */
+    int32_t status;                          /* OK, or OUTPUT_TOO_SMALL: no room in the arena (audio_offset -1) */
+    int32_t reserved;
+    int64_t audio_offset;                    /* floats into the arena: decode_chunks * rescue_chunk_samples floats, zeros behind the span */
+} fa_rnnt_stream_request;
+typedef struct {   /* what the config comes to */
+    int32_t span_capacity;                   /* floats of one stream's span slab: max_span_samples rounded up to whole windows, plus one window */
+    int32_t pre_roll_capacity;               /* floats of one stream's pre-roll ring */
+    int32_t mel_cache_capacity;              /* floats of one stream's mel cache: mel_features * pre_encode_cache */
+    int32_t reserved;
+} fa_rnnt_stream_geometry_info;
+void fa_rnnt_stream_default_config(fa_rnnt_stream_config *cfg);   /* the table above; total_mel_frames 0: the caller's */
+fa_status fa_rnnt_stream_geometry(const fa_rnnt_stream_config *cfg, fa_rnnt_stream_geometry_info *out);   /* pure host function */
+/* The host's emulation of the kernels' RMS order over x[n]: a window's (gate 0: one wavefront) or the gate's chunk (gate 1: four).  Bit-equal
+ * to d_rms and to the windows' decisions.  Pure host function. */
+fa_status fa_rnnt_stream_rms(const float *x, int64_t n, int32_t gate, float *rms);
+/* INVALID_ARGUMENT, with a text that names the bound and nothing allocated, for NULL pointers, streams outside 1 .. 65535 and every
+ * field outside the limits above.  Every stream starts as resetStates() leaves it. */
+fa_status fa_rnnt_stream_create(fa_ctx *ctx, const fa_rnnt_stream_config *cfg, int32_t streams, fa_rnnt_stream **out);
+void fa_rnnt_stream_destroy(fa_rnnt_stream *st);
+/* resetRescueState plus the gate's counters, the frame base and the mel cache, for one stream or (stream -1) all; enqueued. */
+fa_status fa_rnnt_stream_reset(fa_ctx *ctx, fa_rnnt_stream *st, int32_t stream);
+/* One stream's whole state to and from HOST arrays (session restore): span_audio float[span_capacity], pre_roll float[pre_roll_capacity]
+ * oldest window first, mel_cache float[mel_features][pre_encode_cache]; the floats past a count are zero.  get: any array may be NULL;
+ * waits for the context's stream.  set: INVALID_ARGUMENT for counts outside their slabs or no whole windows, or a missing array. */
+fa_status fa_rnnt_stream_get(fa_ctx *ctx, fa_rnnt_stream *st, int32_t stream, fa_rnnt_stream_info *info, float *span_audio, float *pre_roll, float *mel_cache);
+fa_status fa_rnnt_stream_set(fa_ctx *ctx, fa_rnnt_stream *st, int32_t stream, const fa_rnnt_stream_info *info, const float *span_audio, const float *pre_roll,
+                             const float *mel_cache);
+/* The device steps.  DEVICE pointers; every stream in a fixed number of launches, nothing allocated, nothing waited for.  d_active
+ * int32[streams] is nullable (0: the stream is not touched, its status INACTIVE).
+ * gate (Pipeline.swift:86-104): d_chunks float[streams][chunk_samples] (chunk_samples >= 0; an empty chunk is silent).  Out: d_rms
+ * float[streams] (0 while the gate is off), d_skip int32[streams] (1: the chunk skips the encoder; the stream's skip count and frame base
+ * have advanced), d_run_list int32[streams] the active streams that run, ascending, with *d_run_count, d_status int32[streams].  2 launches. */
+fa_status fa_rnnt_stream_gate_dev(fa_ctx *ctx, fa_rnnt_stream *st, const float *d_chunks, int32_t chunk_samples, const int32_t *d_active, float *d_rms,
+                                  int32_t *d_skip, int32_t *d_run_list, int32_t *d_run_count, int32_t *d_status);
+/* mel_inputs (prependMelCachePure / extractMelCachePure) for the *d_count (at most max_count) distinct streams of d_streams: d_mel holds
+ * element (b, f, t) of the chunk's mel at b * stream_stride + f * row_stride + t * frame_stride floats; d_rows
+ * float[max_count][mel_features][total_mel_frames], row k of stream d_streams[k]: its cache, the chunk's first min(chunk_frames,
+ * total - pre) frames from column pre on, zeros elsewhere; then the cache becomes the chunk's last min(pre, chunk_frames) frames.
+ * d_status int32[max_count] per listed slot.  2 launches. */
+fa_status fa_rnnt_stream_mel_inputs_dev(fa_ctx *ctx, fa_rnnt_stream *st, const float *d_mel, int32_t chunk_frames, int64_t stream_stride, int64_t row_stride,
+                                        int64_t frame_stride, const int32_t *d_streams, const int32_t *d_count, int32_t max_count, float *d_rows, int32_t *d_status);
+/* absoluteFrameBase += the encoder's frames for the listed streams (Pipeline.swift:347, 575): d_frames int32[max_count] per slot, or
+ * NULL for `frames` everywhere.  1 launch. */
+fa_status fa_rnnt_stream_advance_dev(fa_ctx *ctx, fa_rnnt_stream *st, const int32_t *d_streams, const int32_t *d_count, int32_t max_count, const int32_t *d_frames,
+                                     int32_t frames);
+/* track (updateRescueSpans + closeSpanAndMaybeRescue's test): the chunk rows of gate, and the live timed tokens d_tok_frame / d_tok_id
+ * int32[streams][token_capacity] with d_tok_count int32[streams]; d_class uint8[vocab] (ids outside it have no class).  Walks
+ * chunk_samples / window_samples windows, advances the cursor, and leaves one request per closed span that emitted no lexical token:
+ * d_requests[request_capacity] in stream order, the span's audio in d_arena float[arena_capacity] (16-byte aligned) padded with zeros to
+ * decode_chunks chunks of rescue_chunk_samples (a multiple of 4), *d_request_count = the requests found, whatever fitted.  A request
+ * past request_capacity has no record; one whose padded audio ends past arena_capacity has status OUTPUT_TOO_SMALL and no audio; the
+ * stream's status is OUTPUT_TOO_SMALL then.  3 launches.  finalize (finalizeRescueSpanIfNeeded) closes the open span of the listed
+ * streams the same way, requests in list order, d_status per listed slot. */
+fa_status fa_rnnt_stream_track_dev(fa_ctx *ctx, fa_rnnt_stream *st, const float *d_chunks, int32_t chunk_samples, const int32_t *d_active, const int32_t *d_tok_frame,
+                                   const int32_t *d_tok_id, const int32_t *d_tok_count, int32_t token_capacity, const uint8_t *d_class, int32_t vocab,
+                                   int32_t rescue_chunk_samples, fa_rnnt_stream_request *d_requests, int32_t request_capacity, float *d_arena, int64_t arena_capacity,
+                                   int32_t *d_request_count, int32_t *d_status);
+fa_status fa_rnnt_stream_finalize_dev(fa_ctx *ctx, fa_rnnt_stream *st, const int32_t *d_streams, const int32_t *d_count, int32_t max_count, const int32_t *d_tok_frame,
+                                      const int32_t *d_tok_id, const int32_t *d_tok_count, int32_t token_capacity, const uint8_t *d_class, int32_t vocab,
+                                      int32_t rescue_chunk_samples, fa_rnnt_stream_request *d_requests, int32_t request_capacity, float *d_arena, int64_t arena_capacity,
+                                      int32_t *d_request_count, int32_t *d_status);
+/* merge_rescued (:264-354) for the first min(*d_request_count, request_capacity) requests, in request order within a stream: request r's
+ * staged ids d_staged_ids int32[request_capacity][staged_capacity] (d_staged_id_count[r] of them, language tags included) and absolute
+ * frames d_staged_frames (d_staged_frame_count[r], one per id that is no tag); the live d_live_ids int32[streams][live_capacity] with
+ * d_live_id_count, and the timed d_live_frames / d_live_timed_ids (nullable) int32[streams][live_capacity] with d_live_timed_count.
+ * Tags dropped, frames above span_end_frame clamped to it, committed only with a lexical id, inserted in place; the stream's rescued
+ * count bumped.  d_request_status int32[request_capacity].  2 launches. */
+fa_status fa_rnnt_stream_merge_rescued_dev(fa_ctx *ctx, fa_rnnt_stream *st, const fa_rnnt_stream_request *d_requests, const int32_t *d_request_count,
+                                           int32_t request_capacity, const int32_t *d_staged_ids, const int32_t *d_staged_frames, const int32_t *d_staged_id_count,
+                                           const int32_t *d_staged_frame_count, int32_t staged_capacity, int32_t *d_live_ids, int32_t *d_live_frames,
+                                           int32_t *d_live_timed_ids, int32_t *d_live_id_count, int32_t *d_live_timed_count, int32_t live_capacity,
+                                           const uint8_t *d_class, int32_t vocab, int32_t *d_request_status);
+/* The same on HOST arrays: staged, run, copied back, one synchronisation.  track: *request_count is what was found; the records and the
+ * arena come back whole. */
+fa_status fa_rnnt_stream_gate(fa_ctx *ctx, fa_rnnt_stream *st, const float *chunks, int32_t chunk_samples, const int32_t *active, float *rms, int32_t *skip,
+                              int32_t *run_list, int32_t *run_count, int32_t *status);
+fa_status fa_rnnt_stream_track(fa_ctx *ctx, fa_rnnt_stream *st, const float *chunks, int32_t chunk_samples, const int32_t *active, const int32_t *tok_frame,
+                               const int32_t *tok_id, const int32_t *tok_count, int32_t token_capacity, const uint8_t *class_of, int32_t vocab,
+                               int32_t rescue_chunk_samples, fa_rnnt_stream_request *requests, int32_t request_capacity, float *arena, int64_t arena_capacity,
+                               int32_t *request_count, int32_t *status);
+fa_status fa_rnnt_stream_merge_rescued(fa_ctx *ctx, fa_rnnt_stream *st, const fa_rnnt_stream_request *requests, int32_t request_count, const int32_t *staged_ids,
+                                       const int32_t *staged_frames, const int32_t *staged_id_count, const int32_t *staged_frame_count, int32_t staged_capacity,
+                                       int32_t *live_ids, int32_t *live_frames, int32_t *live_timed_ids, int32_t *live_id_count, int32_t *live_timed_count,
+                                       int32_t live_capacity, const uint8_t *class_of, int32_t vocab, int32_t *request_status);
+
 /* ------------------------------------------------------------------ resampling ------ */
 /* AudioConverter.linearResample (FluidAudio/Shared/AudioConverter.swift:388-442): planar float[channels][frames] ->
  * mono mix (weight 1/channels) -> linear interpolation to out_rate.  HOST pointers.  Bit-exact restatement. */
