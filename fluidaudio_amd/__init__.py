@@ -14,6 +14,7 @@ from .ctc import (LogitsArgmax, ctc_greedy_decode, ctc_greedy_ids_batch, ctc_gre
                   decode_ctc_token_ids)
 from .der import DERResult, DERSpeakerSegment, compute_der, compute_der_batch, segments_from_timed, segments_from_timeline  # noqa: F401
 from .kws import KWS_DETECTION_DTYPE, KWS_WINDOW_DTYPE, adjusted_threshold, score_windows, spot_keywords_batch  # noqa: F401
+from . import vocab_rescore  # noqa: F401
 from .embedding import EmbeddingConfig, EmbeddingPlan, plan_embeddings, span_inputs, weight_resample  # noqa: F401
 from .formats import AudioWAV, RTTMParser, RTTMParserError, TimedSpeakerSegment, export_embeddings_json  # noqa: F401
 from .fsmn_vad import (fsmn_vad_config, fsmn_vad_frame_count, fsmn_vad_gather_silence_dev,  # noqa: F401

@@ -82,6 +82,8 @@ EXPORTED_SYMBOLS = [
     "fa_rnnt_stream_default_config", "fa_rnnt_stream_geometry", "fa_rnnt_stream_rms", "fa_rnnt_stream_create", "fa_rnnt_stream_destroy", "fa_rnnt_stream_reset", "fa_rnnt_stream_get",
     "fa_rnnt_stream_set", "fa_rnnt_stream_gate_dev", "fa_rnnt_stream_mel_inputs_dev", "fa_rnnt_stream_advance_dev", "fa_rnnt_stream_track_dev", "fa_rnnt_stream_finalize_dev",
     "fa_rnnt_stream_merge_rescued_dev", "fa_rnnt_stream_gate", "fa_rnnt_stream_track", "fa_rnnt_stream_merge_rescued",
+    "fa_vocab_rescore_default_config", "fa_vocab_rescore_boost", "fa_vocab_rescore_build", "fa_vocab_rescore_candidates", "fa_vocab_rescore_decide_dev",
+    "fa_vocab_rescore_decide",
 ]
 
 
@@ -198,6 +200,24 @@ class KwsDetection(C.Structure):
 
 class KwsWindow(C.Structure):
     _fields_ = [("utterance", C.c_int32), ("keyword", C.c_int32), ("start_frame", C.c_int32), ("end_frame", C.c_int32)]
+
+
+class VrCandidate(C.Structure):                                        # fa_vr_candidate
+    _fields_ = [(n, C.c_int32) for n in ("utterance", "term", "first_word", "span_len", "origin", "form")] + [("similarity", C.c_float)]
+
+
+class VrBoostConfig(C.Structure):                                      # fa_vr_boost_config
+    _fields_ = [("use_adaptive_thresholds", C.c_int32), ("reference_token_count", C.c_int32), ("short_term_taper_pivot", C.c_int32),
+                ("short_term_taper_exponent", C.c_float)]
+
+
+class VrDecideConfig(C.Structure):                                     # fa_vr_decide_config
+    _fields_ = [("frame_duration", C.c_double), ("margin_seconds", C.c_double), ("cbw", C.c_float), ("blank_id", C.c_int32), ("boost", VrBoostConfig)]
+
+
+class VrVerdict(C.Structure):                                          # fa_vr_verdict
+    _fields_ = [(n, C.c_float) for n in ("term_score", "original_score", "boost", "boosted_score")] + \
+               [(n, C.c_int32) for n in ("alt_won", "compared", "should_replace", "outcome", "start_frame", "end_frame")]
 
 
 class ParaformerCifConfig(C.Structure):
@@ -633,6 +653,14 @@ def lib() -> C.CDLL:
     L.fa_tdt_pack_windows.argtypes = L.fa_tdt_pack_windows_dev.argtypes
     L.fa_tdt_speech_gate_dev.argtypes = [vp, C.POINTER(TdtWindowConfig), vp, vp, i32, vp, vp, vp, i64, vp, vp, vp]
     L.fa_tdt_speech_gate.argtypes = L.fa_tdt_speech_gate_dev.argtypes
+    L.fa_vocab_rescore_default_config.argtypes = [vp]
+    L.fa_vocab_rescore_default_config.restype = None
+    L.fa_vocab_rescore_boost.argtypes = [f32, i32, vp]
+    L.fa_vocab_rescore_boost.restype = f32
+    L.fa_vocab_rescore_build.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, i64, C.POINTER(i64), vp, i64]
+    L.fa_vocab_rescore_candidates.argtypes = [vp, vp, i64, vp, i32, vp, vp, vp, f32, vp, i64, C.POINTER(i64), vp]
+    L.fa_vocab_rescore_decide_dev.argtypes = [vp, vp, i32, i32, i32, i64, i64, vp, vp, vp, i64, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.fa_vocab_rescore_decide.argtypes = L.fa_vocab_rescore_decide_dev.argtypes
     L.fa_rnnt_bias_effective_boost.argtypes = [i32, f32, f32]
     L.fa_rnnt_bias_effective_boost.restype = f32
     L.fa_rnnt_bias_build.argtypes = [vp, i32, vp, vp, i32, vp, i64, C.POINTER(i64), C.POINTER(i32)]

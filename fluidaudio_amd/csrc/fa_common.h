@@ -140,7 +140,7 @@ bool fault_hit(int site);
     ROUTE(RESAMPLE_SIMPLE, "FA_RESAMPLE_SIMPLE") ROUTE(RESAMPLE_NO_DECIM, "FA_RESAMPLE_NO_DECIM")                                     \
     ROUTE(RESAMPLE_NO_DECIM_TILES, "FA_RESAMPLE_NO_DECIM_TILES") ROUTE(RESAMPLE_NO_ROWS, "FA_RESAMPLE_NO_ROWS")                       \
     ROUTE(RESAMPLE_NO_WIDE, "FA_RESAMPLE_NO_WIDE") ROUTE(RESAMPLE_WIDE, "FA_RESAMPLE_WIDE")                                            \
-    ROUTE(KWS_ARENA, "FA_KWS_ARENA") ROUTE(TDT_MERGE_LDS_SIDE, "FA_TDT_MERGE_LDS_SIDE")
+    ROUTE(KWS_ARENA, "FA_KWS_ARENA") ROUTE(TDT_MERGE_LDS_SIDE, "FA_TDT_MERGE_LDS_SIDE") ROUTE(VR_ARENA, "FA_VR_ARENA")
 enum class Sw : int {
 #define FA_SW_ENUM(id, name) id,
     FA_SWITCHES(FA_SW_ENUM)

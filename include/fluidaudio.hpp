@@ -1368,6 +1368,155 @@ private:
     }
 };
 
+// VocabularyRescorer's term-centric path (…/Rescorer/VocabularyRescorer+TokenRescoring.swift:693-1034, :272-307, +TokenEvaluation.swift:29-173)
+// for one utterance, over fa_vocab_rescore_build / _candidates / _decide.  A word or a form is a row of symbols, one per Character of the
+// normalized string (any injective numbering, `space` for the space): normalizeForSimilarity, both tokenizers, the word timings and the
+// stopword lists are the caller's, as are preserveCapitalization and the rebuilt text.  The spotter-anchored rescue is not part of it.
+struct VocabularyRescorer {
+    static constexpr int32_t space = FA_VR_SPACE;
+    static constexpr float minSimilarityFloor = 0.50f;   // ContextBiasingConstants
+    using Symbols = std::vector<int32_t>;
+    using LogProbs = CtcKeywordSpotter::LogProbs;
+    struct Term {
+        int32_t charCount = 0;                       // vocabTerm.count
+        std::optional<float> minSimilarity;
+        std::vector<Symbols> forms;                  // buildNormalizedForms' order, the canonical form first (it may be empty)
+        std::vector<int32_t> ctcTokenIds, altTokenIds;   // encode(text); encodeWithoutBoundary(text), empty: none
+    };
+    struct Word {
+        Symbols symbols;                             // normalizeForSimilarity(word), possibly empty
+        bool stopword = false, multiWordStopword = false;
+        double startTime = 0.0, endTime = 0.0;
+    };
+    struct Decision {
+        std::vector<fa_vr_candidate> candidates;
+        std::vector<fa_vr_verdict> verdicts;         // one per candidate
+        std::vector<int32_t> applied;                // indices into candidates, in application order
+    };
+
+    std::vector<Term> terms;
+    std::vector<int32_t> blob;
+    fa_vr_decide_config config;
+
+    explicit VocabularyRescorer(std::vector<Term> vocabulary, int32_t minTermLength = 3) : terms(std::move(vocabulary)) {
+        fa_vocab_rescore_default_config(&config);
+        std::vector<int32_t> counts, symbols;
+        std::vector<float> mins;
+        std::vector<int64_t> termRows{0}, rowOffsets{0};
+        for (const Term &t : terms) {
+            counts.push_back(t.charCount);
+            mins.push_back(t.minSimilarity.value_or(-1.0f));
+            for (const Symbols &f : t.forms) {
+                symbols.insert(symbols.end(), f.begin(), f.end());
+                rowOffsets.push_back(static_cast<int64_t>(symbols.size()));
+            }
+            termRows.push_back(static_cast<int64_t>(rowOffsets.size()) - 1);
+        }
+        symbols.push_back(0);   // never an empty array
+        counts.push_back(0);
+        mins.push_back(0.0f);
+        char text[192] = "";
+        int64_t need = 0;
+        for (int pass = 0; pass < 2; ++pass) {   // the size, then the blob
+            const fa_status st = fa_vocab_rescore_build(counts.data(), mins.data(), termRows.data(), rowOffsets.data(), symbols.data(), static_cast<int32_t>(terms.size()),
+                                                        minTermLength, pass ? blob.data() : nullptr, pass ? need : 0, &need, text, static_cast<int64_t>(sizeof(text)));
+            if (st != FA_SUCCESS) throw Error(st, "fa_vocab_rescore_build", text);
+            if (need == 0) break;
+            blob.resize(static_cast<size_t>(need));
+        }
+    }
+
+    // the candidate records of one utterance in the reference's append order
+    std::vector<fa_vr_candidate> candidates(fa_ctx *ctx, const std::vector<Word> &words, float minSimilarity = minSimilarityFloor) const {
+        std::vector<int32_t> symbols;
+        std::vector<int64_t> wordOffsets{0};
+        std::vector<uint8_t> flags;
+        for (const Word &w : words) {
+            symbols.insert(symbols.end(), w.symbols.begin(), w.symbols.end());
+            wordOffsets.push_back(static_cast<int64_t>(symbols.size()));
+            flags.push_back(static_cast<uint8_t>((w.stopword ? FA_VR_WORD_STOPWORD : 0) | (w.multiWordStopword ? FA_VR_WORD_MULTI_WORD_STOPWORD : 0)));
+        }
+        symbols.push_back(0);
+        flags.push_back(0);
+        const int64_t utterance[2] = {0, static_cast<int64_t>(words.size())};
+        std::vector<fa_vr_candidate> out(64);
+        int64_t count = 0;
+        for (int attempt = 0; attempt < 2; ++attempt) {   // the second call has room for the count the first one reported
+            const fa_status st = fa_vocab_rescore_candidates(ctx, blob.data(), static_cast<int64_t>(blob.size()), utterance, 1, wordOffsets.data(), symbols.data(), flags.data(),
+                                                             minSimilarity, out.data(), static_cast<int64_t>(out.size()), &count, nullptr);
+            if (st == FA_OUTPUT_TOO_SMALL && attempt == 0) { out.resize(static_cast<size_t>(count)); continue; }
+            if (st != FA_SUCCESS) throw Error(st, "fa_vocab_rescore_candidates", ctx ? fa_ctx_last_error(ctx) : nullptr);
+            break;
+        }
+        out.resize(static_cast<size_t>(count));
+        return out;
+    }
+
+    // evaluateCTCMatch for each candidate and arbitratePendingReplacements; phraseTokens[c]: encode(originalPhrase) of candidate c
+    Decision decide(fa_ctx *ctx, const LogProbs &logProbs, const std::vector<Word> &words, std::vector<fa_vr_candidate> found,
+                    const std::vector<std::vector<int32_t>> &phraseTokens, const std::vector<uint8_t> &occupied = {}) const {
+        if (phraseTokens.size() != found.size() || (!occupied.empty() && occupied.size() != words.size()))
+            throw Error(FA_INVALID_ARGUMENT, "VocabularyRescorer: a token row per candidate and an occupied byte per word are required");
+        const int32_t T = static_cast<int32_t>(logProbs.size());
+        int32_t V = T > 0 ? static_cast<int32_t>(logProbs[0].size()) : 1;
+        std::vector<float> flat;
+        for (const auto &row : logProbs) {
+            if (static_cast<int32_t>(row.size()) != V) throw Error(FA_INVALID_ARGUMENT, "VocabularyRescorer: frames of different lengths");
+            flat.insert(flat.end(), row.begin(), row.end());
+        }
+        if (V < 1) V = 1;
+        flat.push_back(0.0f);
+        std::vector<double> starts, ends;
+        for (const Word &w : words) { starts.push_back(w.startTime); ends.push_back(w.endTime); }
+        starts.push_back(0.0);
+        ends.push_back(0.0);
+        const auto pack = [](const auto &rows, auto row_of, std::vector<int32_t> &tokens, std::vector<int64_t> &off) {
+            off.assign(1, 0);
+            for (const auto &r : rows) {
+                const std::vector<int32_t> &t = row_of(r);
+                tokens.insert(tokens.end(), t.begin(), t.end());
+                off.push_back(static_cast<int64_t>(tokens.size()));
+            }
+            tokens.push_back(0);
+        };
+        std::vector<int32_t> termTokens, altTokens, phrases;
+        std::vector<int64_t> termOff, altOff, phraseOff;
+        pack(terms, [](const Term &t) -> const std::vector<int32_t> & { return t.ctcTokenIds; }, termTokens, termOff);
+        pack(terms, [](const Term &t) -> const std::vector<int32_t> & { return t.altTokenIds; }, altTokens, altOff);
+        pack(phraseTokens, [](const std::vector<int32_t> &t) -> const std::vector<int32_t> & { return t; }, phrases, phraseOff);
+        const int64_t utterance[2] = {0, static_cast<int64_t>(words.size())};
+        Decision d;
+        d.candidates = std::move(found);
+        d.verdicts.resize(d.candidates.size() + 1);
+        d.applied.resize(d.candidates.size() + 1);
+        int64_t applied = 0;
+        const fa_status st = fa_vocab_rescore_decide(ctx, flat.data(), 1, T, V, V, static_cast<int64_t>(T) * V, nullptr, &config, d.candidates.data(),
+                                                     static_cast<int64_t>(d.candidates.size()), utterance, starts.data(), ends.data(), static_cast<int32_t>(terms.size()),
+                                                     termTokens.data(), termOff.data(), altTokens.data(), altOff.data(), phrases.data(), phraseOff.data(),
+                                                     occupied.empty() ? nullptr : occupied.data(), d.verdicts.data(), d.applied.data(), &applied);
+        if (st != FA_SUCCESS) throw Error(st, "fa_vocab_rescore_decide", ctx ? fa_ctx_last_error(ctx) : nullptr);
+        d.verdicts.resize(d.candidates.size());
+        d.applied.resize(static_cast<size_t>(applied));
+        return d;
+    }
+
+    // The term-centric path of ctcTokenRescore round the caller's tokenizer: encode(first word, span length) gives the tokens of the
+    // original phrase — the raw words of the span joined by a space — and is asked once per distinct span.
+    template <class Encode>
+    Decision ctcTokenRescore(fa_ctx *ctx, const LogProbs &logProbs, const std::vector<Word> &words, Encode &&encode, float minSimilarity = minSimilarityFloor) const {
+        std::vector<fa_vr_candidate> found = candidates(ctx, words, minSimilarity);
+        std::map<std::pair<int32_t, int32_t>, std::vector<int32_t>> cache;
+        std::vector<std::vector<int32_t>> phraseTokens;
+        for (const fa_vr_candidate &c : found) {
+            const auto key = std::make_pair(c.first_word, c.span_len);
+            auto at = cache.find(key);
+            if (at == cache.end()) at = cache.emplace(key, encode(c.first_word, c.span_len)).first;
+            phraseTokens.push_back(at->second);
+        }
+        return decide(ctx, logProbs, words, std::move(found), phraseTokens);
+    }
+};
+
 // ------------------------------------------------------------------------------------------------------------------ Paraformer
 // ParaformerConfig (Sources/FluidAudio/ASR/Paraformer/ParaformerConfig.swift:8-39)
 struct ParaformerConfig {

@@ -101,6 +101,7 @@ const char *fa_version(void);
  *                                            passes that walk overflowed jobs again
  *   FA_TDT_MERGE_LDS_SIDE=tokens             the longest overlap side a seam of fa_tdt_merge_windows keeps in LDS (at most 128, the default): a
  *                                            small one sends short sides through the workspace route
+ *   FA_VR_ARENA=records                      the survivor arena of fa_vocab_rescore_candidates: a small one forces the second walk
  * fa_debug_set_switch(name, value): value NULL = unset.  Changes what the NEXT calls see (process-wide; not for use while calls are in flight
  * on other threads).  RUNTIME_ERROR without FLUIDAUDIO_HIP_DEBUG_HOOKS=1, INVALID_ARGUMENT for an unknown name. */
 fa_status fa_debug_set_switch(const char *name, const char *value);
@@ -311,6 +312,88 @@ fa_status fa_ctc_kws_score_windows(fa_ctx *ctx, const float *log_probs, int32_t 
                                    int64_t row_stride, int64_t matrix_stride, const int32_t *valid_frames,
                                    const int32_t *keyword_tokens, const int64_t *keyword_offsets, int32_t keywords,
                                    const fa_kws_window *windows, int64_t n_windows, int32_t blank_id, fa_kws_detection *out);
+
+/* The vocabulary rescorer's term-centric path (…/CustomVocabulary/Rescorer/VocabularyRescorer+TokenRescoring.swift:693-1034, :272-307,
+ * +TokenEvaluation.swift:29-173, :319-377, +Utilities.swift:8-17, :43-62, :87-96, :321-339, VocabularyRescorer.swift:111-129): candidate
+ * discovery by string similarity on the device, the CTC verdicts through the window kernels above, the arbitration on the host.
+ * Similarities are the reference's fp32 values bit for bit.  The caller's: normalizeForSimilarity and the split into Characters (a word
+ * or a form is a row of int32 symbols, any injective numbering of the Characters with FA_VR_SPACE for the space), both tokenizers,
+ * buildWordTimings, the stopword lists (two flag bits per word), preserveCapitalization and the rebuilt text, the evidence records' UTF-8
+ * ranges and reason strings.  Not covered: the word-centric path, collectSpotterAnchoredCandidates (this library behaves as
+ * spotterRescueEnabled = false does; fa_vocab_rescore_decide takes candidate records from anywhere), the "No tokenizer" branch. */
+enum { FA_VR_SPACE = 32, FA_VR_MAX_FORM = 64, FA_VR_MAX_ALPHABET = 1024 };
+enum { FA_VR_ORIGIN_MULTI_WORD = 1, FA_VR_ORIGIN_SINGLE_WORD = 2 };
+enum { FA_VR_WORD_STOPWORD = 1, FA_VR_WORD_MULTI_WORD_STOPWORD = 2 };
+enum { FA_VR_APPLIED = 1, FA_VR_SUPERSEDED = 2, FA_VR_REJECTED = 3, FA_VR_UNAVAILABLE = 4 };
+/* term: the term's index in the build's input; form: the index among the term's kept forms (the matched alias; 0 is the canonical form
+ * where that is kept), -1 where no form was better than similarity 0 */
+typedef struct { int32_t utterance, term, first_word, span_len, origin, form; float similarity; } fa_vr_candidate;
+typedef struct {
+    int32_t use_adaptive_thresholds;     /* 1 */
+    int32_t reference_token_count;       /* 3 */
+    int32_t short_term_taper_pivot;      /* 1: no taper */
+    float short_term_taper_exponent;     /* 2.0 */
+} fa_vr_boost_config;
+typedef struct {
+    double frame_duration;               /* seconds per CTC frame; > 0 (0.08) */
+    double margin_seconds;               /* 0.10 */
+    float cbw;                           /* 3.0 */
+    int32_t blank_id;                    /* 1024 */
+    fa_vr_boost_config boost;
+} fa_vr_decide_config;
+/* term_score: the better of the term's tokens and its alternative tokens (alt_won) in the window [start_frame, end_frame); compared = 0:
+ * the phrase has no tokens (or the term none), nothing is replaced, original_score = -inf, boost = 0, boosted_score = term_score.
+ * Non-finite scores are reported as they are. */
+typedef struct {
+    float term_score, original_score, boost, boosted_score;
+    int32_t alt_won, compared, should_replace, outcome, start_frame, end_frame;
+} fa_vr_verdict;
+void fa_vocab_rescore_default_config(fa_vr_decide_config *cfg);
+/* adaptiveCbw; log2 and pow are evaluated in fp64 and rounded once to fp32, the arithmetic round them is the reference's fp32.  cfg NULL: the defaults. */
+float fa_vocab_rescore_boost(float cbw, int32_t token_count, const fa_vr_boost_config *cfg);
+/* The vocabulary as a position-independent blob of int32 words.  HOST memory only.  Term t: char_counts[t] = vocabTerm.count,
+ * min_similarities[t] (below 0: none; the array NULL: none at all), and the rows [term_rows[t], term_rows[t + 1]) of the ragged table
+ * symbols / row_offsets as its forms in buildNormalizedForms' order, the canonical one first (it may be empty).  Empty forms and later
+ * duplicates are dropped; a term with char_count < min_term_length or without a form left is skipped.  A form of more than
+ * FA_VR_MAX_FORM symbols, or FA_VR_MAX_ALPHABET - 1 or more distinct symbols, is INVALID_ARGUMENT.  *words_needed is set;
+ * capacity_words 0 only asks for it, a smaller buffer than needed is OUTPUT_TOO_SMALL.  text (nullable) [text_capacity] receives the
+ * reason of a refusal. */
+fa_status fa_vocab_rescore_build(const int32_t *char_counts, const float *min_similarities, const int64_t *term_rows, const int64_t *row_offsets,
+                                 const int32_t *symbols, int32_t terms, int32_t min_term_length, int32_t *blob, int64_t capacity_words,
+                                 int64_t *words_needed, char *text, int64_t text_capacity);
+/* The two loops of :755-1033 for every (utterance, term).  Everything is HOST memory; the blob is checked whole before it is uploaded.
+ * Utterance u has the words [utterance_offsets[u], utterance_offsets[u + 1]); word w the symbols [word_offsets[w], word_offsets[w + 1])
+ * of word_symbols (rows back to back in word order; a row may be empty) and the flag byte word_flags[w] (FA_VR_WORD_*).  The records
+ * come in the reference's append order: utterance, term, multi-word before single-word, multi-word by span length then start,
+ * single-word by word.  The capacity contract is fa_ctc_kws_spot_batch's: *count is always set, utterance_counts int64[batch]
+ * (nullable), OUTPUT_TOO_SMALL writes the first `capacity` records.  One host synchronisation, unless the survivors overflow the
+ * device arena (65536 records or `capacity`, whichever is more; FA_VR_ARENA=records for tests): then the walk runs once more with room
+ * for the count it reported. */
+fa_status fa_vocab_rescore_candidates(fa_ctx *ctx, const int32_t *blob, int64_t blob_words, const int64_t *utterance_offsets, int32_t batch,
+                                      const int64_t *word_offsets, const int32_t *word_symbols, const uint8_t *word_flags, float min_similarity,
+                                      fa_vr_candidate *candidates, int64_t capacity, int64_t *count, int64_t *utterance_counts);
+/* evaluateCTCMatch for every candidate, then arbitratePendingReplacements per utterance.  The log-probs are addressed like
+ * fa_ctc_kws_score_windows(_dev)'s; everything else is HOST memory.  candidates [n_candidates] in the order the arbitration takes as
+ * candidate order; word times fp64 per word of the utterance_offsets table; term t has the tokens
+ * term_tokens[term_token_offsets[t] ..) and the alternative tokens alt_tokens[alt_token_offsets[t] ..) (alt_token_offsets NULL or an
+ * empty row: none); candidate c the original phrase's tokens phrase_tokens[phrase_token_offsets[c] ..).  occupied (nullable): a byte per
+ * word, non-zero for an index that is taken before the pass.  verdicts [n_candidates]; applied [n_candidates] receives, utterance after
+ * utterance, the indices of the applied candidates in application order, applied_counts int64[batch] how many each utterance has (both
+ * nullable).  The three scores of every candidate go through one batched call of the window kernels. */
+fa_status fa_vocab_rescore_decide_dev(fa_ctx *ctx, const float *d_log_probs, int32_t batch, int32_t frames, int32_t vocab, int64_t row_stride,
+                                      int64_t matrix_stride, const int32_t *valid_frames, const fa_vr_decide_config *cfg,
+                                      const fa_vr_candidate *candidates, int64_t n_candidates, const int64_t *utterance_offsets,
+                                      const double *word_starts, const double *word_ends, int32_t terms, const int32_t *term_tokens,
+                                      const int64_t *term_token_offsets, const int32_t *alt_tokens, const int64_t *alt_token_offsets,
+                                      const int32_t *phrase_tokens, const int64_t *phrase_token_offsets, const uint8_t *occupied,
+                                      fa_vr_verdict *verdicts, int32_t *applied, int64_t *applied_counts);
+fa_status fa_vocab_rescore_decide(fa_ctx *ctx, const float *log_probs, int32_t batch, int32_t frames, int32_t vocab, int64_t row_stride,
+                                  int64_t matrix_stride, const int32_t *valid_frames, const fa_vr_decide_config *cfg,
+                                  const fa_vr_candidate *candidates, int64_t n_candidates, const int64_t *utterance_offsets,
+                                  const double *word_starts, const double *word_ends, int32_t terms, const int32_t *term_tokens,
+                                  const int64_t *term_token_offsets, const int32_t *alt_tokens, const int64_t *alt_token_offsets,
+                                  const int32_t *phrase_tokens, const int64_t *phrase_token_offsets, const uint8_t *occupied,
+                                  fa_vr_verdict *verdicts, int32_t *applied, int64_t *applied_counts);
 
 /* ------------------------------------------------------------------ TDT ------------- */
 /* Control flow of TdtDecoderV3.decodeWithTimings (FluidAudio/ASR/Parakeet/SlidingWindow/TDT/Decoder/TdtDecoderV3.swift:103-607)
