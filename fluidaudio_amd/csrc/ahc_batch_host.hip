@@ -84,7 +84,7 @@ struct BlockMapRun {
         if (by_args) launch_round_args(ctx->stream, big, ph, grid, args, lds);
         else launch_round_map(ctx->stream, big, ph, grid, d_table, d_map, lds);
     }
-    fa_status before_replay(RoundGraph *&use) {
+    fa_status before_replay(RoundGraph *&use, int /* one length: the capture's */) {
         int n_active = 0;
         for (const Prob &p : probs) n_active += p.active ? 1 : 0;
         if (mapped_active < 0 || n_active * 2 <= mapped_active) {   // (re)build the map and the graph over the running problems
@@ -162,7 +162,9 @@ fa_status ahc_batch_once(fa_ctx *ctx, int count, const double *const *d_data, co
     }
     BlockMapRun run{ctx, probs, reinterpret_cast<const Ws *>(base + o_table), reinterpret_cast<int2 *>(base + o_map), sizeof(double) * d, big};
     FA_HIP_TRY(ctx, hipMemcpyAsync(const_cast<Ws *>(run.d_table), table.data(), sizeof(Ws) * count, hipMemcpyHostToDevice, ctx->stream));
-    FA_TRY(drive_rounds(ctx, probs.data(), count, budget, [&](RoundGraph *&use) { return run.before_replay(use); }, [&](const int ph) { run.launch(ph); }));
+    // each state is read before the next replay: before_replay may capture the graph again, from states the replay in front has just delivered
+    FA_TRY(drive_rounds(ctx, probs.data(), count, route::drive_plan_batch(kRoundsPerGraph, budget), [&](RoundGraph *&use, const int len) { return run.before_replay(use, len); },
+                        [&](const int ph) { run.launch(ph); }));
     return batch_epilogue(ctx, probs, ord, ev, stats, statuses, completed);
 }
 
@@ -188,7 +190,7 @@ struct UniformRun {
     RoundGraph *current = nullptr;
     std::unique_ptr<RoundGraph> own;   // the graph of a shrunken grid
     void launch(const int ph) const { launch_round_uni(ctx->stream, kernel, ph, grid_y, w0, offs, stride_pages, lds); }
-    fa_status before_replay(RoundGraph *&use) {
+    fa_status before_replay(RoundGraph *&use, int /* one length: the capture's */) {
         const int count = static_cast<int>(probs.size());
         int last_active = -1;
         size_t longest = 0;
@@ -252,7 +254,8 @@ fa_status ahc_batch_uniform(fa_ctx *ctx, int count, const double *const *d_data,
     }
     FA_HIP_TRY(ctx, hipEventRecord(ev[1], ctx->stream));
     UniformRun run{ctx, probs, base, Nmax, d, cpt, static_cast<unsigned>(stride >> 12), probs[0].w, round_offsets(probs[0].w), sizeof(double) * d};
-    FA_TRY(drive_rounds(ctx, probs.data(), count, route::replay_budget(Nmax), [&](RoundGraph *&use) { return run.before_replay(use); },
+    FA_TRY(drive_rounds(ctx, probs.data(), count, route::drive_plan_batch(route::rounds_for(Nmax), route::replay_budget(Nmax)),   // no replay queued ahead: see ahc_batch_once
+                        [&](RoundGraph *&use, const int len) { return run.before_replay(use, len); },
                         [&](const int ph) { run.launch(ph); }));
     return batch_epilogue(ctx, probs, ord, ev, stats, statuses, completed);
 }

@@ -64,32 +64,72 @@ struct RoundGraph {   // `rounds` rounds captured once, replayed until every pro
     }
 };
 struct CachedGraph {   // the round launches of one problem shape, kept in the context between calls
-    RoundGraph rg;
+    RoundGraph rg;                // the full length: rounds_for(N)
+    RoundGraph shorter[route::kRungs - 1];   // the single-problem route's shorter replays (route::kLadder[1 ..]), captured with rg when route::rungs_for(N) > 1
     const void *base = nullptr;
     size_t N = 0, d = 0;
     int cpt = 1;
     bool spec = false;            // the speculative round (FA_AHC_SPEC)
     int grid_y = 0, kernel = 0;   // uniform batches: problems in the grid and which build of the round serves them
+    RoundGraph *of_length(const int rounds) {   // the captured replay of `rounds` rounds (a length route::plan_next hands out)
+        if (rounds != rg.rounds) for (RoundGraph &g : shorter) if (g.ok && g.rounds == rounds) return &g;
+        return &rg;
+    }
 };
 CachedGraph *cached_graph_renew(fa_ctx *ctx, void *&slot);   // ahc_rounds_host.hip: an empty one in the context's `slot` (ahc_graph / ahc_uni_graph), the old one freed
 
-// ---- the drive loop: replays until no problem of the set is active or `budget` replays are spent.  Per replay: before_replay(rg) hands out the graph to
-// replay — (re)captured by the caller's own rule; nullptr: launch(0) IS the replay (the single-block form: all its rounds in one launch) —, the replay, one
-// state copy per running problem, ONE synchronisation, prob_after_replay for each (a problem's failure is its p.st; only a failing call ends the loop).
+// ---- the drive loop: replays until no problem of the set is active or the plan's budget is spent.  Per replay: before_replay(rg, rounds) hands out the
+// graph to replay — `rounds` is the length the plan asks for (a batch has one length and (re)captures by the caller's own rule); nullptr: launch(0) IS the
+// replay (the single-block form: all its rounds in one launch) —, the replay, one state copy per running problem, ONE wait, prob_after_replay for each (a
+// problem's failure is its p.st; only a failing call ends the loop).
+// A plan of depth 1 (the batches; FA_AHC_SYNC_DRIVE) waits for the stream, with the states copied to Prob::h.  A deeper plan enqueues the next replay BEFORE
+// that wait while route::plan_next allows it, so the stream is not empty while the host reads a state and launches a graph of hundreds of nodes: each
+// replay's state then goes into its own slot of the context's pinned ring, followed by the slot's event, and the host waits for the OLDEST event.  (The
+// ring is not used at depth 1: a batch of 16 problems pays 16 pinned copies per replay, measurably more than the pageable ones in front of a
+// synchronisation.)  A replay that runs behind a `halt` or a `done` carries the state forward, like the rest of a replay does; whatever is still queued when
+// the loop ends is waited for before it returns.
+inline fa_status drive_ring(fa_ctx *ctx, const int count) {   // the ring holds kQueueDepth slots of `count` states
+    const size_t slot = (sizeof(AhcState) * static_cast<size_t>(count) + 255) & ~static_cast<size_t>(255);
+    if (ctx->ahc_ring_slot_bytes < slot) {
+        if (ctx->ahc_ring) { FA_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipHostFree(ctx->ahc_ring); ctx->ahc_ring = nullptr; ctx->ahc_ring_slot_bytes = 0; }
+        FA_HIP_TRY(ctx, hipHostMalloc(&ctx->ahc_ring, slot * route::kQueueDepth, hipHostMallocDefault));
+        ctx->ahc_ring_slot_bytes = slot;
+    }
+    for (auto &e : ctx->ahc_ring_ev) if (!e) FA_HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return FA_SUCCESS;
+}
 template <class Before, class Launch>
-fa_status drive_rounds(fa_ctx *ctx, Prob *probs, const int count, const long long budget, Before &&before_replay, Launch &&launch) {
-    for (long long it = 0; it < budget; ++it) {
+fa_status drive_rounds(fa_ctx *ctx, Prob *probs, const int count, route::DrivePlan plan, Before &&before_replay, Launch &&launch) {
+    static_assert(route::kQueueDepth == 2, "the context keeps two ring slots and two events");
+    const bool ahead = plan.depth > 1;
+    if (ahead) FA_TRY(drive_ring(ctx, count));
+    struct Drain {   // nothing of this loop is in flight once it has returned, whichever way
+        fa_ctx *ctx; route::DrivePlan &plan;
+        ~Drain() { if (plan.queued > 0) (void)hipStreamSynchronize(ctx->stream); }
+    } drain{ctx, plan};
+    auto slot_of = [&](const int i) { return reinterpret_cast<AhcState *>(static_cast<char *>(ctx->ahc_ring) + ctx->ahc_ring_slot_bytes * static_cast<size_t>(i)); };
+    int head = 0;   // ring slot of the oldest replay in flight
+    for (;;) {
         bool any = false;
         for (int j = 0; j < count; ++j) any = any || probs[j].active;
-        if (!any) break;
-        RoundGraph *rg = nullptr;
-        FA_TRY(before_replay(rg));
-        if (rg) FA_TRY(rg->replay(ctx, launch));
-        else { launch(0); FA_HIP_TRY(ctx, hipGetLastError()); }
-        for (int j = 0; j < count; ++j)
-            if (probs[j].active) FA_HIP_TRY(ctx, hipMemcpyAsync(&probs[j].h, probs[j].w.state, sizeof(AhcState), hipMemcpyDeviceToHost, ctx->stream));
-        FA_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        for (int j = 0; j < count; ++j) if (probs[j].active) (void)prob_after_replay(ctx, probs[j]);
+        while (any) {
+            const int rounds = route::plan_next(plan);
+            if (!rounds) break;
+            const int at = (head + plan.queued - 1) % route::kQueueDepth;
+            RoundGraph *rg = nullptr;
+            FA_TRY(before_replay(rg, rounds));
+            if (rg) FA_TRY(rg->replay(ctx, launch));
+            else { launch(0); FA_HIP_TRY(ctx, hipGetLastError()); }
+            for (int j = 0; j < count; ++j)
+                if (probs[j].active) FA_HIP_TRY(ctx, hipMemcpyAsync(ahead ? slot_of(at) + j : &probs[j].h, probs[j].w.state, sizeof(AhcState), hipMemcpyDeviceToHost, ctx->stream));
+            if (ahead) FA_HIP_TRY(ctx, hipEventRecord(ctx->ahc_ring_ev[at], ctx->stream));
+        }
+        if (!plan.queued) break;   // nothing active, or the budget is spent
+        if (ahead) FA_HIP_TRY(ctx, hipEventSynchronize(ctx->ahc_ring_ev[head]));
+        else FA_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        for (int j = 0; j < count; ++j) if (probs[j].active) { if (ahead) probs[j].h = slot_of(head)[j]; (void)prob_after_replay(ctx, probs[j]); }
+        route::plan_retire(plan, static_cast<long long>(probs[0].N) - 1 - probs[0].h.step);
+        head = (head + 1) % route::kQueueDepth;
     }
     return FA_SUCCESS;
 }

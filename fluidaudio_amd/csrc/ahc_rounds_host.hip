@@ -111,6 +111,7 @@ fa_status prob_adopt(fa_ctx *ctx, Prob &p, const int merges, const double eps, c
     launch_records(ctx->stream, 1, w);   // needs eps (the state) and the rows
     FA_HIP_TRY(ctx, hipGetLastError());
     FA_HIP_TRY(ctx, hipMemsetAsync(spec_of(w.state), 0, sizeof(AhcSpec), ctx->stream));   // no hypothesis survives an adoption
+    p.h.step = merges;   // what the drive plan of prob_run_rounds counts from
     return FA_SUCCESS;
 }
 
@@ -126,19 +127,23 @@ fa_status prob_run_rounds(fa_ctx *ctx, Prob &p) {
         if (single_block) launch_single_block(ctx->stream, p.cpt, w, rounds, lds);   // all rounds of a replay in one launch
         else launch_round_single(ctx->stream, form.kernel, ph, w, offs, lds);
     };
-    // The captured graph only holds launch parameters (workspace pointers, block count): it is reused as long as the workspace sits at
-    // the same address and the shape is the same — repeated calls on recordings of one length skip capture + instantiation.
-    RoundGraph *rg = nullptr;
+    // The captured graphs only hold launch parameters (workspace pointers, block count): they are reused as long as the workspace sits at
+    // the same address and the shape is the same — repeated calls on recordings of one length skip capture + instantiation.  A problem whose replay
+    // has the full length gets the ladder of shorter replays with it (route::kLadder), whichever drive this call uses.
+    CachedGraph *cg = nullptr;
     if (!single_block) {
-        CachedGraph *cg = static_cast<CachedGraph *>(ctx->ahc_graph);
+        cg = static_cast<CachedGraph *>(ctx->ahc_graph);
         if (!cg || cg->base != ctx->ahc_ws || cg->N != N || cg->d != d || cg->cpt != p.cpt || cg->spec != form.spec || !cg->rg.ok) {
             cg = cached_graph_renew(ctx, ctx->ahc_graph);
             cg->base = ctx->ahc_ws; cg->N = N; cg->d = d; cg->cpt = p.cpt; cg->spec = form.spec;
             cg->rg.capture(ctx, launch, rounds);
+            for (int r = 1; r < route::rungs_for(N); ++r) cg->shorter[r - 1].capture(ctx, launch, route::kLadder[r]);
         }
-        rg = &cg->rg;
     }
-    FA_TRY(drive_rounds(ctx, &p, 1, route::replay_budget(N), [&](RoundGraph *&use) { use = rg; return FA_SUCCESS; }, launch));
+    route::DrivePlan plan = route::drive_plan(N, p.h.step, form.spec, fa::sw_on(fa::Sw::AHC_SYNC_DRIVE));
+    if (!cg) plan.ladder = false;   // the single-block form: launch(0) runs rounds_for(N) rounds
+    else for (int r = 1; r < route::rungs_for(N); ++r) if (!cg->shorter[r - 1].ok) plan.ladder = false;   // a rung that could not be captured: one length
+    FA_TRY(drive_rounds(ctx, &p, 1, plan, [&](RoundGraph *&use, const int len) { use = cg ? cg->of_length(len) : nullptr; return FA_SUCCESS; }, launch));
     if (p.st != FA_SUCCESS) return p.st;
     p.spec_hits = 0;
     if (fa::sw_on(fa::Sw::AHC_DEBUG) || fa_debug_hooks_enabled()) {   // the commit counter: only for the debug line and the test hook (one more copy)

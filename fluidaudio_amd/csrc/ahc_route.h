@@ -52,6 +52,75 @@ inline int rounds_for(const size_t n) {
 // replays a problem of N points may take: a bound on its rounds (merges + re-scans + windows)
 inline long long replay_budget(const size_t N) { return 64 + 8 * static_cast<long long>(N) / rounds_for(N); }
 
+// ---- the plan of the drive loop (ahc_launch.h: drive_rounds): how long the next replay is and whether it may be enqueued before the state of the
+// replays in flight has been read.
+// The ladder: a problem whose replay has the full length also keeps shorter ones, so that the last replays do not run hundreds of launches behind `done`
+// (a launch behind `done` still crosses a kernel boundary and reduces every block record: ~4 us each, 352 of them per 8 h recording with one length).
+// Each length is a multiple of 4 (counter rotation and parity).
+constexpr int kRungs = 3;
+constexpr int kLadder[kRungs] = {kRoundsPerGraph, 128, 32};
+constexpr int kQueueDepth = 2;   // replays in flight at most
+static_assert(kRoundsPerGraph % 4 == 0 && kLadder[1] % 4 == 0 && kLadder[2] % 4 == 0 && kLadder[1] < kRoundsPerGraph, "replay lengths: multiples of 4, descending");
+struct DrivePlan {
+    long long left = 0;         // merges still to do by the last state the host has read (N - 1 - step); meaningful for one problem only
+    int per_round = 1;          // merges a round commits at most: 2 with the speculative round, 1 otherwise
+    int full = kRoundsPerGraph; // rounds_for(N): the one length of the synchronous drive
+    int depth = 1;              // replays in flight at most (1: the synchronous drive, every state is read before the next replay is enqueued)
+    bool ladder = false;        // lengths from kLadder; otherwise always `full`
+    long long budget = 0;       // rounds the loop may enqueue: replay_budget(N) replays of `full` rounds
+    long long spent = 0;        // rounds enqueued so far
+    int in_flight[kQueueDepth] = {0, 0};   // rounds of the replays whose state has not been read, oldest first
+    int queued = 0;
+};
+inline int rungs_for(const size_t N) { return rounds_for(N) == kRoundsPerGraph && kLadder[0] == kRoundsPerGraph ? kRungs : 1; }   // small problems keep their single length
+// one problem of N points with `step` merges done; synchronous: FA_AHC_SYNC_DRIVE (one replay of rounds_for(N) at a time, as before the look-ahead)
+inline DrivePlan drive_plan(const size_t N, const long long step, const bool spec, const bool synchronous) {
+    DrivePlan p;
+    p.left = static_cast<long long>(N) - 1 - step;
+    p.per_round = spec ? 2 : 1;
+    p.full = rounds_for(N);
+    p.depth = synchronous ? 1 : kQueueDepth;
+    p.ladder = !synchronous && rungs_for(N) > 1;
+    p.budget = replay_budget(N) * p.full;
+    return p;
+}
+// a batch: `budget` replays of one length, each state read before the next replay (its callers may capture their graph again between two replays)
+inline DrivePlan drive_plan_batch(const int full, const long long budget) {
+    DrivePlan p;
+    p.full = full;
+    p.budget = budget * full;
+    return p;
+}
+// merges that are certainly left when everything in flight has run: a round commits at most per_round merges
+inline long long plan_floor(const DrivePlan &p) {
+    long long rounds = 0;
+    for (int i = 0; i < p.queued; ++i) rounds += p.in_flight[i];
+    return p.left - p.per_round * rounds;
+}
+// Rounds of the replay to enqueue now, 0: none before the oldest state in flight has been read (or the budget is spent).  A replay goes behind others only
+// while those cannot finish the problem (plan_floor > 0): the synchronous drive would have enqueued it as well.  Its length is the longest rung the merges
+// certainly left fill even at per_round merges a round, the shortest rung when none does.
+inline int plan_next(DrivePlan &p) {
+    if (p.queued >= p.depth || p.queued >= kQueueDepth) return 0;
+    const long long floor = plan_floor(p);
+    if (p.queued > 0 && floor <= 0) return 0;
+    int len = p.full;
+    if (p.ladder) {
+        len = kLadder[kRungs - 1];
+        for (int r = 0; r < kRungs; ++r) if (static_cast<long long>(p.per_round) * kLadder[r] <= floor) { len = kLadder[r]; break; }
+    }
+    if (p.spent + len > p.budget) return 0;
+    p.in_flight[p.queued++] = len;
+    p.spent += len;
+    return len;
+}
+// the state of the oldest replay in flight has been read: `left` merges were still to do behind it
+inline void plan_retire(DrivePlan &p, const long long left) {
+    for (int i = 1; i < p.queued; ++i) p.in_flight[i - 1] = p.in_flight[i];
+    if (p.queued > 0) p.in_flight[--p.queued] = 0;
+    p.left = left;
+}
+
 // ---- one problem: which of the 13 builds of ahc_round_t<false, ...> (the table in ahc_rounds.hip is in this order)
 enum SingleKernel { kSpecK1, kSpecK2, kSpecK3, kSpecK4, kC4Big, kC4, kC2Big, kC2, kC1Big, kC1K1, kC1K2, kC1K3, kC1K4, kSingleKernels };
 struct RoundForm {

@@ -290,6 +290,9 @@ void fa_ctx_destroy(fa_ctx *ctx) {
     if (ctx->ahc_uni_graph && ctx->ahc_graph_free) ctx->ahc_graph_free(ctx->ahc_uni_graph);
     if (ctx->mel_cache && ctx->mel_cache_free) ctx->mel_cache_free(ctx->mel_cache);
     for (auto &e : ctx->ahc_ev) if (e) (void)hipEventDestroy(e);
+    for (auto &e : ctx->ahc_ring_ev) if (e) (void)hipEventDestroy(e);
+    if (ctx->ahc_ring) (void)hipHostFree(ctx->ahc_ring);
+    if (ctx->z_host) (void)hipHostFree(ctx->z_host);
     for (auto &e : ctx->tim_ev) if (e) (void)hipEventDestroy(e);
     if (ctx->owns_stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;

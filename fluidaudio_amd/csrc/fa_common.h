@@ -38,6 +38,14 @@ struct fa_ctx {
     void *ahc_graph = nullptr;                 // owned by ahc.hip (ahc_graph_free releases it)
     void (*ahc_graph_free)(void *) = nullptr;
     void *ahc_uni_graph = nullptr;             // the same for the round launches of a uniform batch (ahc_batch_uniform): a batch job repeats one shape
+    // a drive loop that enqueues a replay before it has read the state of the one in front (ahc_launch.h: drive_rounds, one problem) has every replay's
+    // state copied into its own slot of this pinned ring, followed by the slot's event, and waits for the oldest event.  Grow-only.
+    void *ahc_ring = nullptr;
+    size_t ahc_ring_slot_bytes = 0;
+    hipEvent_t ahc_ring_ev[2] = {nullptr, nullptr};
+    // the clustering stage of ONE recording takes its dendrogram on the host, in this pinned buffer (offline_host.hip: link / cut).  Grow-only.
+    void *z_host = nullptr;
+    size_t z_host_bytes = 0;
     // linkage batches of a few LARGE problems run their merge chains concurrently, one per helper context (own stream, own workspace): see
     // ahc_run_device_batch.  Created on first use, trimmed and destroyed with this context.
     fa_ctx *helpers[3] = {nullptr, nullptr, nullptr};
@@ -135,7 +143,7 @@ bool fault_hit(int site);
     ROUTE(AHC_RO_NO_MATRIX, "FA_AHC_RO_NO_MATRIX") ROUTE(AHC_RO_NO_HANDOVER, "FA_AHC_RO_NO_HANDOVER") ROUTE(AHC_UNI_CPT, "FA_AHC_UNI_CPT") ROUTE(AHC_UNI_GROUPS, "FA_AHC_UNI_GROUPS")    \
     ROUTE(AHC_RO_HANDOVER_AT, "FA_AHC_RO_HANDOVER_AT") ROUTE(AHC_RO_REPLAY_PAIRS, "FA_AHC_RO_REPLAY_PAIRS")                           \
     ROUTE(AHC_UNI_WAVES, "FA_AHC_UNI_WAVES") ROUTE(AHC_IN_FLIGHT, "FA_AHC_IN_FLIGHT") ROUTE(AHC_DEBUG, "FA_AHC_DEBUG")                \
-    ROUTE(AHC_SPEC, "FA_AHC_SPEC")                                                                                                   \
+    ROUTE(AHC_SPEC, "FA_AHC_SPEC") ROUTE(AHC_SYNC_DRIVE, "FA_AHC_SYNC_DRIVE")                                                          \
     ROUTE(MEL_GENERIC, "FA_MEL_GENERIC") ROUTE(MEL_SLICE_MB, "FA_MEL_SLICE_MB") ROUTE(VBX_NO_TILED, "FA_VBX_NO_TILED")                \
     ROUTE(RESAMPLE_SIMPLE, "FA_RESAMPLE_SIMPLE") ROUTE(RESAMPLE_NO_DECIM, "FA_RESAMPLE_NO_DECIM")                                     \
     ROUTE(RESAMPLE_NO_DECIM_TILES, "FA_RESAMPLE_NO_DECIM_TILES") ROUTE(RESAMPLE_NO_ROWS, "FA_RESAMPLE_NO_ROWS")                       \

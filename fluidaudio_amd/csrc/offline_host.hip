@@ -54,6 +54,10 @@ struct ClusterJob {
     int32_t *labels; double *centroids; int32_t max_centroids; int32_t *n_centroids; fa_offline_cluster_info *info;
     // optional copies of the intermediates (fa_offline_cluster_ex): AHC labels and VBx hard labels of the training rows, ELBO per iteration
     int32_t *aux_ahc = nullptr; int32_t *aux_hard = nullptr; double *aux_elbos = nullptr;
+    // the recording runs its linkage alone (link()): the dendrogram goes straight to the context's pinned buffer, where cut() reads it — no device copy
+    // of it (b_z), no pageable vector.  A batch (link_batch) leaves its dendrograms on the device, one b_z per recording.
+    bool z_to_host = false;
+    const double *z_host = nullptr;   // set by link(): the dendrogram is there
 
     fa::DevBuf b_emb32, b_rho_in, b_ok, b_emb, b_temb, b_trho, b_train, b_norm, b_z;
     const float *d_emb32 = nullptr;
@@ -68,6 +72,15 @@ struct ClusterJob {
         if (b.alloc(ctx, bytes) == hipSuccess) return FA_SUCCESS;
         (void)hipGetLastError();
         return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "%s", what);
+    }
+    // the context's pinned buffer for the dendrogram, at least `bytes` large (nothing of an earlier call reads it any more: the entries return behind a synchronisation)
+    fa_status z_host_room(const size_t bytes) {
+        if (ctx->z_host_bytes >= bytes) return FA_SUCCESS;
+        if (ctx->z_host) (void)hipHostFree(ctx->z_host);
+        ctx->z_host = nullptr; ctx->z_host_bytes = 0;
+        if (hipHostMalloc(&ctx->z_host, bytes, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); ctx->z_host = nullptr; return fa::set_error(ctx, FA_ALLOCATION_FAILURE, "offline cluster: allocation failed"); }
+        ctx->z_host_bytes = bytes;
+        return FA_SUCCESS;
     }
     // the training rows on the host (the rare paths that take a host-pointer entry or sum on the host)
     fa_status training_rows_to_host(std::vector<double> &temb_host) {
@@ -88,7 +101,7 @@ struct ClusterJob {
     }
 
 
-    // inputs to the device (once), selectTrainingEmbeddings, unit rows for the linkage (b_norm) and room for the dendrogram (b_z) when nt >= 2
+    // inputs to the device (once), selectTrainingEmbeddings, unit rows for the linkage (b_norm) and room for the dendrogram (b_z; not with z_to_host) when nt >= 2
     fa_status prepare() {
         hipStream_t st = ctx->stream;
         t_begin = now_s();
@@ -130,10 +143,11 @@ struct ClusterJob {
             d_trho = b_trho.as<double>();
         }
         FA_HIP_TRY(ctx, hipGetLastError());
-        FA_HIP_TRY(ctx, hipStreamSynchronize(st));   // `train` is a host temporary
+        if (!all_rows) FA_HIP_TRY(ctx, hipStreamSynchronize(st));   // `train` is a host temporary (nothing of it is in flight when every row trains)
         if (nt >= 2) {   // AHC input (:301-306): unit rows
             FA_TRY(room(b_norm, sizeof(double) * nt * d));
-            FA_TRY(room(b_z, sizeof(double) * 4 * (nt - 1)));
+            if (!z_to_host) FA_TRY(room(b_z, sizeof(double) * 4 * (nt - 1)));
+            else FA_TRY(z_host_room(sizeof(double) * 4 * static_cast<size_t>(nt - 1)));
             FA_TRY(fa::ahc_normalize_dev(ctx, d_temb, b_norm.as<double>(), nt, d));
         }
         t_inputs = now_s();
@@ -146,6 +160,8 @@ struct ClusterJob {
         if (nt >= 2) {
             if (ahc_status != FA_SUCCESS) {
                 for (int64_t i = 0; i < nt; ++i) s.initial[i] = static_cast<int32_t>(i);
+            } else if (z_host) {   // delivered by the linkage, behind its own synchronisation
+                FA_TRY(fa_ahc_cut(z_host, static_cast<size_t>(nt), config->clustering_threshold, s.initial.data()));
             } else {
                 std::vector<double> z(static_cast<size_t>(4 * (nt - 1)));
                 FA_HIP_TRY(ctx, hipMemcpyAsync(z.data(), b_z.p, sizeof(double) * z.size(), hipMemcpyDeviceToHost, ctx->stream));
@@ -298,7 +314,11 @@ struct ClusterJob {
     fa_status link() {
         if (nt < 2) return FA_SUCCESS;
         if (fa::fault_hit(FA_FAULT_AHC)) return FA_RUNTIME_ERROR;
-        return fa::ahc_run_device(ctx, b_norm.as<double>(), static_cast<size_t>(nt), static_cast<size_t>(d), b_z.as<double>(), config->ahc_mode, &ahc_stats);
+        if (!z_to_host) return fa::ahc_run_device(ctx, b_norm.as<double>(), static_cast<size_t>(nt), static_cast<size_t>(d), b_z.as<double>(), config->ahc_mode, &ahc_stats);
+        const fa_status st = fa::ahc_run_device(ctx, b_norm.as<double>(), static_cast<size_t>(nt), static_cast<size_t>(d), static_cast<double *>(ctx->z_host), config->ahc_mode, &ahc_stats,
+                                                /* z_on_host = */ true);
+        if (st == FA_SUCCESS) z_host = static_cast<const double *>(ctx->z_host);
+        return st;
     }
 };
 
@@ -427,6 +447,7 @@ fa_status fa_offline_cluster_ex(fa_ctx *ctx, const float *embeddings, int64_t n,
     if (!ctx) return FA_INVALID_ARGUMENT;
     ClusterJob job{ctx, embeddings, n, d, rho, rho_dim, chunk_indices, phi, config, device_pointers, labels, centroids, max_centroids, n_centroids, info,
                    ahc_labels, vbx_hard, elbos};
+    job.z_to_host = true;
     FA_TRY(job.check_args());
     fa::DeviceGuard guard(ctx->device);
     return fa::no_throw(ctx, "offline cluster", [&]() -> fa_status {

@@ -94,6 +94,8 @@ const char *fa_version(void);
  *                                            INVALID_ARGUMENT.  4: a hand-over lands within 4 rows of any chosen row
  *   FA_AHC_DEBUG                             one line of statistics per linkage call on stderr
  *   FA_AHC_SPEC=0                            the one-merge round instead of the speculative one (two merges per launch where the next was foreseen)
+ *   FA_AHC_SYNC_DRIVE                        the round replays of one problem one at a time, each of the full length and each state read before the next is
+ *                                            enqueued (no replay queued ahead, no shorter replays towards the end)
  *   FA_MEL_GENERIC, FA_MEL_SLICE_MB=n        the generic mel kernel; slice size of host-pointer batches
  *   FA_VBX_NO_TILED                          the untiled VBx iteration
  *   FA_RESAMPLE_SIMPLE, _NO_DECIM, _NO_DECIM_TILES, _NO_ROWS, _NO_WIDE, FA_RESAMPLE_WIDE=rows:waves (16:8, 16:10, 32:8, 32:10)   polyphase kernel family
