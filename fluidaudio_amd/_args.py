@@ -82,10 +82,17 @@ def placed(x, ctx: L.Context):
 
 
 def to_device(v, dtype, device, shape=None):
-    """Host values as a torch tensor of the numpy dtype (and of that shape) on the device; None stays None."""
+    """Host values as a torch tensor of the numpy dtype (and of that shape) on the device; None stays None.  A contiguous CUDA tensor of that
+    dtype on the device is handed through: nothing is uploaded, and the host does not wait for torch's stream as an upload from pageable
+    memory makes it."""
     import torch
     if v is None:
         return None
+    if isinstance(v, torch.Tensor) and v.is_cuda:
+        d = torch.device(device)
+        if v.dtype != getattr(torch, np.dtype(dtype).name) or v.device.type != d.type or d.index not in (None, v.device.index) or not v.is_contiguous():
+            raise TypeError(f"a contiguous {np.dtype(dtype).name} tensor on {device} is required, not {v.dtype} on {v.device}")
+        return v if shape is None else v.reshape(shape)
     v = np.ascontiguousarray(v, dtype)
     return torch.from_numpy(v if shape is None else v.reshape(shape)).to(device)
 

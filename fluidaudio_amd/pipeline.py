@@ -72,26 +72,54 @@ def select_training_embeddings(embedding256) -> list:
     return sel if sel else list(range(len(e)))
 
 
+def _resident(t, dtype_name: str, ctx: L.Context, what: str):
+    """A matrix the device-pointer forms read behind its pointer: a contiguous two-dimensional torch CUDA tensor of exactly that dtype
+    (the library reads the bytes as they are: an int32 tensor would be taken for floats) on the context's device.  Refused before any
+    library call: TypeError for what is no such tensor, ValueError for one on another device, as _args.device_tensor does."""
+    import torch
+    if not (isinstance(t, torch.Tensor) and t.is_cuda):
+        raise TypeError(f"{what}: a torch CUDA tensor is required")
+    if t.dtype != getattr(torch, dtype_name) or t.dim() != 2 or not t.is_contiguous():
+        raise TypeError(f"{what}: a contiguous two-dimensional {dtype_name} tensor is required, not {t.dtype} {tuple(t.shape)} with strides {tuple(t.stride())}")
+    if t.device.index != ctx.device:
+        raise ValueError(f"{what} on {t.device}, context on cuda:{ctx.device}")
+    return t
+
+
+def _rho_dim(rho, ctx: L.Context, what: str) -> int:
+    """The PLDA dimension of device-resident rho: 0 — no VBx, nothing is read behind the pointer — for None and for a tensor that is empty or
+    not two-dimensional, as ever; a matrix that is read has to be what _resident asks for."""
+    if rho is None:
+        return 0
+    if not hasattr(rho, "data_ptr"):
+        raise TypeError(f"{what}: a torch CUDA tensor beside device-resident embeddings, or None")
+    if rho.dim() != 2 or rho.numel() == 0:
+        return 0
+    return int(_resident(rho, "float64", ctx, what).shape[1])
+
+
 def cluster_embeddings(embedding256, rho128, chunk_indices, phi, config: OfflineClusteringConfig | None = None,
                        ctx: L.Context | None = None, intermediates: bool = False) -> ClusteringResult:
     """One device-resident call (fa_offline_cluster).  ``initial_clusters`` / ``vbx`` of the result are not populated (they never
     leave the device) unless ``intermediates`` asks for copies (fa_offline_cluster_ex: AHC labels in ``initial_clusters``, VBx hard
     labels and ELBOs in ``info["vbx_hard"]`` / ``info["elbos"]``); ``timings`` carries the library's per-stage wall-clock and
-    ``info`` its counters."""
+    ``info`` its counters.  Embeddings / rho given as torch CUDA tensors (float32 / float64, contiguous, on ctx's device) are read where
+    they are (device_pointers = 1), on ctx's stream, ordered against torch's current stream (Context.torch_ordered): whatever produces
+    them there is complete when the stage reads them."""
     import ctypes as C
     cfg = config or OfflineClusteringConfig()
     cfg.validate()
     ctx = ctx or L.default_context()
     on_device = hasattr(embedding256, "data_ptr")          # torch CUDA tensors: device_pointers = 1, nothing is uploaded
     if on_device:
-        emb, rho = embedding256, rho128
-        assert emb.is_cuda and emb.is_contiguous() and emb.dtype.itemsize == 4 and emb.dim() == 2
+        emb = _resident(embedding256, "float32", ctx, "cluster_embeddings: embeddings")
+        rho = rho128
         if emb.shape[0] == 0:
             raise ValueError("noSpeechDetected")
         n, d = int(emb.shape[0]), int(emb.shape[1])
-        rd = int(rho.shape[1]) if rho is not None and rho.dim() == 2 and rho.numel() else 0
-        if rd:
-            assert rho.is_cuda and rho.is_contiguous() and rho.dtype.itemsize == 8 and int(rho.shape[0]) == n
+        rd = _rho_dim(rho, ctx, "cluster_embeddings: rho")
+        if rd and int(rho.shape[0]) != n:
+            raise ValueError(f"cluster_embeddings: rho has {int(rho.shape[0])} rows, the embeddings {n}")
         emb_ptr, rho_ptr = emb.data_ptr(), (rho.data_ptr() if rd else None)
     else:
         emb = np.ascontiguousarray(embedding256, np.float32)
@@ -119,13 +147,17 @@ def cluster_embeddings(embedding256, rho128, chunk_indices, phi, config: Offline
     k, info = C.c_int32(), L.OfflineClusterInfo()
     if intermediates:
         ahc_lab, hard, elbos = np.full(n, -1, np.int32), np.full(n, -1, np.int32), np.zeros(max(cfg.max_vbx_iterations, 1))
-        ctx.check(L.lib().fa_offline_cluster_ex(ctx.handle, emb_ptr, n, d, rho_ptr, rd, chunks.ctypes.data,
-                                                ph.ctypes.data if rd else None, C.byref(c), int(on_device), labels.ctypes.data, cen.ctypes.data, cap, C.byref(k),
-                                                C.byref(info), ahc_lab.ctypes.data, hard.ctypes.data, elbos.ctypes.data), "fa_offline_cluster_ex")
+        with ctx.torch_ordered(on_device):
+            st = L.lib().fa_offline_cluster_ex(ctx.handle, emb_ptr, n, d, rho_ptr, rd, chunks.ctypes.data,
+                                               ph.ctypes.data if rd else None, C.byref(c), int(on_device), labels.ctypes.data, cen.ctypes.data, cap, C.byref(k),
+                                               C.byref(info), ahc_lab.ctypes.data, hard.ctypes.data, elbos.ctypes.data)
+        ctx.check(st, "fa_offline_cluster_ex")
     else:
-        ctx.check(L.lib().fa_offline_cluster(ctx.handle, emb_ptr, n, d, rho_ptr, rd, chunks.ctypes.data,
-                                             ph.ctypes.data if rd else None, C.byref(c), int(on_device), labels.ctypes.data, cen.ctypes.data, cap, C.byref(k),
-                                             C.byref(info)), "fa_offline_cluster")
+        with ctx.torch_ordered(on_device):
+            st = L.lib().fa_offline_cluster(ctx.handle, emb_ptr, n, d, rho_ptr, rd, chunks.ctypes.data,
+                                            ph.ctypes.data if rd else None, C.byref(c), int(on_device), labels.ctypes.data, cen.ctypes.data, cap, C.byref(k),
+                                            C.byref(info))
+        ctx.check(st, "fa_offline_cluster")
     t = {"inputs_s": info.inputs_s, "ahc_s": info.ahc_s, "vbx_s": info.vbx_s, "assign_s": info.assign_s, "total_s": info.total_s}
     res = ClusteringResult(labels if intermediates else np.asarray(labels).tolist(), cen[:k.value].copy(), [], None, [], t)
     res.info = {f: getattr(info, f) for f, _ in info._fields_ if f != "ahc"}
@@ -169,7 +201,8 @@ def _c_config(cfg: OfflineClusteringConfig):
 def cluster_embeddings_batch(recordings, phi, config: OfflineClusteringConfig | None = None, ctx: L.Context | None = None):
     """Several recordings through the clustering stage in one call (fa_offline_cluster_batch: their merge chains advance together).
     recordings: iterable of (embedding256 [n, d] float32, rho128 [n, rho_dim] float64, chunk_indices [n]) with common d / rho_dim.
-    Embeddings / rho given as torch CUDA tensors (all recordings, or none) go through fa_offline_cluster_batch_dev: nothing is uploaded.
+    Embeddings / rho given as torch CUDA tensors (all recordings, or none; float32 / float64, contiguous, on ctx's device) go through
+    fa_offline_cluster_batch_dev: nothing is uploaded, and the call is ordered against torch's current stream (Context.torch_ordered).
     Returns (statuses, [ClusteringResult | None]) — per recording identical to cluster_embeddings()."""
     import ctypes as C
     cfg = config or OfflineClusteringConfig()
@@ -178,9 +211,9 @@ def cluster_embeddings_batch(recordings, phi, config: OfflineClusteringConfig | 
     recordings = list(recordings)
     on_device = bool(recordings) and all(hasattr(e, "data_ptr") for e, _, _ in recordings)
     if on_device:
-        for e, r, _ in recordings:
-            assert e.is_cuda and e.is_contiguous() and e.dtype.itemsize == 4 and e.dim() == 2
-            assert r is None or (r.is_cuda and r.is_contiguous() and r.dtype.itemsize == 8)
+        for i, (e, r, _) in enumerate(recordings):
+            _resident(e, "float32", ctx, f"cluster_embeddings_batch: embeddings of recording {i}")
+            _rho_dim(r, ctx, f"cluster_embeddings_batch: rho of recording {i}")
         recs = [(_DevArray(e), _DevArray(r), np.ascontiguousarray(c, np.int32)) for e, r, c in recordings]
     else:
         recs = [(np.ascontiguousarray(e, np.float32), np.ascontiguousarray(r, np.float64), np.ascontiguousarray(c, np.int32)) for e, r, c in recordings]
@@ -208,7 +241,8 @@ def cluster_embeddings_batch(recordings, phi, config: OfflineClusteringConfig | 
     st = (C.c_int32 * k)()
     c = _c_config(cfg)
     entry = L.lib().fa_offline_cluster_batch_dev if on_device else L.lib().fa_offline_cluster_batch
-    entry(ctx.handle, k, ep, ns, d, rp if rd else None, rd, cp, ph.ctypes.data if rd else None, C.byref(c), lp, zp, cap, kc, infos, st)
+    with ctx.torch_ordered(on_device):
+        entry(ctx.handle, k, ep, ns, d, rp if rd else None, rd, cp, ph.ctypes.data if rd else None, C.byref(c), lp, zp, cap, kc, infos, st)
     out = []
     for i in range(k):
         if st[i] != L.SUCCESS:

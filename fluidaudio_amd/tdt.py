@@ -14,7 +14,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import _lib as L
+from . import _args as A, _lib as L
 
 STANDARD_OVERLAP_FRAMES = 25  # ASRConstants.standardOverlapFrames
 
@@ -76,7 +76,8 @@ def decode_logits(d_logits, vocab_with_blank: int, enc_len, audio_frames=None, t
     """Batched greedy walk on joint LOGITS.  d_logits: a contiguous torch CUDA tensor [B, U, T, W] of float32 or float16 — any other dtype
     is refused, the entry has no code for it — with W >= vocab_with_blank + len(config.duration_bins): a row holds the token logits, the
     duration logits behind them, and W - that many elements of padding the walk never reads.  Its first element may lie at any address a
-    tensor of its dtype can have (a view into a larger allocation is fine).  Same result structure as decode_tables."""
+    tensor of its dtype can have (a view into a larger allocation is fine).  The per-chunk vectors are int sequences, or contiguous int32
+    tensors on the logits' device (then nothing is uploaded and the host does not wait for torch's stream).  Same result structure as decode_tables."""
     import torch
     ctx = ctx or L.default_context()
     config = config or TdtConfig()
@@ -91,7 +92,7 @@ def decode_logits(d_logits, vocab_with_blank: int, enc_len, audio_frames=None, t
     dev = d_logits.device
 
     def vec(v):
-        return None if v is None else torch.as_tensor(np.asarray(v, np.int32)).to(dev)
+        return A.to_device(v, np.int32, dev)
 
     v_enc, v_af, v_t0, v_last, v_go, v_ea = (vec(enc_len), vec(audio_frames), vec(t0), vec(is_last), vec(global_offset),
                                              vec(None if emit_after is None else [-1 if e is None else e for e in emit_after]))
@@ -251,7 +252,7 @@ def decode_logits_lang(d_logits, vocab_with_blank: int, classes, script, enc_len
     assert d_cls.dtype == torch.uint8 and d_cls.numel() == int(vocab_with_blank), "decode_logits_lang: classes must be vocab_with_blank uint8 bytes"
 
     def vec(v):
-        return None if v is None else torch.as_tensor(np.asarray(v, np.int32)).to(dev)
+        return A.to_device(v, np.int32, dev)
 
     v_enc, v_af, v_t0, v_last, v_go, v_ea = (vec(enc_len), vec(audio_frames), vec(t0), vec(is_last), vec(global_offset),
                                              vec(None if emit_after is None else [-1 if e is None else e for e in emit_after]))
@@ -289,7 +290,7 @@ def decode_tables(d_tok, d_bin, d_prob, enc_len, audio_frames=None, t0=None, is_
     dev = d_tok.device
 
     def vec(v):
-        return None if v is None else torch.as_tensor(np.asarray(v, np.int32)).to(dev)
+        return A.to_device(v, np.int32, dev)
 
     v_enc, v_af, v_t0, v_last, v_go, v_ea = (vec(enc_len), vec(audio_frames), vec(t0), vec(is_last), vec(global_offset),
                                              vec(None if emit_after is None else [-1 if e is None else e for e in emit_after]))

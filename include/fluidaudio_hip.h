@@ -822,7 +822,11 @@ void fa_offline_cluster_default_config(fa_offline_cluster_config *cfg);
  * PLDA features (rho_dim == 0: no VBx, centroids come from the AHC labels); chunk_indices: HOST int32[n] (needed when
  * constrained_assignment != 0); phi: HOST double[rho_dim].  embeddings / rho are HOST pointers unless device_pointers != 0.
  * labels: HOST int32[n] out (-2 = slot dropped by the constrained assignment); centroids: HOST double[max_centroids*d] out or
- * NULL; *n_centroids out; info may be NULL.  n == 0 -> INVALID_ARGUMENT (the reference throws noSpeechDetected, :281-283). */
+ * NULL; *n_centroids out; info may be NULL.  n == 0 -> INVALID_ARGUMENT (the reference throws noSpeechDetected, :281-283).
+ * STREAM CONTRACT of device_pointers != 0: the stage reads embeddings / rho on the context's stream, and all it waits for is that stream.
+ * The inputs must therefore be complete on, or ordered before, the context's stream when the call is made: produced on that stream,
+ * or on another one that the caller has synchronised or made the context's stream wait for (an event recorded behind the producer and
+ * hipStreamWaitEvent on fa_ctx_stream(ctx)).  The context's stream is non-blocking: nothing orders it against another stream by itself. */
 fa_status fa_offline_cluster(fa_ctx *ctx, const float *embeddings, int64_t n, int32_t d, const double *rho, int32_t rho_dim,
                              const int32_t *chunk_indices, const double *phi, const fa_offline_cluster_config *config,
                              int32_t device_pointers, int32_t *labels, double *centroids, int32_t max_centroids,
@@ -830,7 +834,7 @@ fa_status fa_offline_cluster(fa_ctx *ctx, const float *embeddings, int64_t n, in
 /* The same call with copies of the stage's intermediates (verification at full size: bench.py and the 8 h digest test compare them
  * with the CPU side): ahc_labels HOST int32[training rows] = AHCClustering.cluster's labels (AHCClustering.swift:20-67), vbx_hard
  * HOST int32[training rows] = argmax of the VBx posteriors (VBxClustering.swift:144-146), elbos HOST double[max_vbx_iterations]
- * (info->vbx_iterations of them are written).  Each may be NULL. */
+ * (info->vbx_iterations of them are written).  Each may be NULL.  device_pointers != 0: fa_offline_cluster's stream contract. */
 fa_status fa_offline_cluster_ex(fa_ctx *ctx, const float *embeddings, int64_t n, int32_t d, const double *rho, int32_t rho_dim,
                                 const int32_t *chunk_indices, const double *phi, const fa_offline_cluster_config *config,
                                 int32_t device_pointers, int32_t *labels, double *centroids, int32_t max_centroids,
@@ -849,7 +853,8 @@ fa_status fa_offline_cluster_batch(fa_ctx *ctx, int32_t count, const float *cons
                                    int32_t max_centroids, int32_t *n_centroids, fa_offline_cluster_info *infos, int32_t *statuses);
 /* The same with the recordings' inputs RESIDENT on the context's device (what device_pointers = 1 is to fa_offline_cluster): d_embeddings[r] /
  * d_rho[r] are DEVICE pointers (the arrays of pointers themselves, n, chunk_indices[r], phi, labels[r], centroids[r] stay on the host).  The call
- * waits for the context's stream first (the inputs' producer), nothing is uploaded.  Results equal fa_offline_cluster_batch's bit for bit. */
+ * waits for the context's stream first (the inputs' producer), nothing is uploaded.  Results equal fa_offline_cluster_batch's bit for bit.
+ * fa_offline_cluster's stream contract holds for every d_embeddings[r] / d_rho[r]: complete on, or ordered before, the context's stream. */
 fa_status fa_offline_cluster_batch_dev(fa_ctx *ctx, int32_t count, const float *const *d_embeddings, const int64_t *n, int32_t d,
                                        const double *const *d_rho, int32_t rho_dim, const int32_t *const *chunk_indices, const double *phi,
                                        const fa_offline_cluster_config *config, int32_t *const *labels, double *const *centroids,
