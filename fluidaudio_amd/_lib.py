@@ -24,6 +24,8 @@ MEL_LAYOUT_MEL_MAJOR, MEL_LAYOUT_FRAME_MAJOR = 0, 1
 MEL_CENTER_ZERO, MEL_CENTER_REFLECT = 0, 1
 MEL_SCALE_SLANEY, MEL_SCALE_HTK_NONORM = 0, 1
 MEL_TAIL_ZERO, MEL_TAIL_REPLICATE = 0, 1
+FBANK_WINDOW_HAMMING, FBANK_WINDOW_POVEY = 0, 1
+FBANK_TAIL_REPLICATE, FBANK_TAIL_VALID = 0, 1
 DTYPE_F32, DTYPE_F16 = 0, 1
 AHC_MODE_AUTO, AHC_MODE_EXACT, AHC_MODE_REFERENCE_ORDER = 0, 1, 2
 FAULT_VBX, FAULT_THREAD_START, FAULT_DEVBUF_MALLOC, FAULT_WS_MALLOC, FAULT_AHC = 0, 1, 2, 3, 4   # fa_debug_inject_fault sites (tests)
@@ -84,6 +86,8 @@ EXPORTED_SYMBOLS = [
     "fa_rnnt_stream_merge_rescued_dev", "fa_rnnt_stream_gate", "fa_rnnt_stream_track", "fa_rnnt_stream_merge_rescued",
     "fa_vocab_rescore_default_config", "fa_vocab_rescore_boost", "fa_vocab_rescore_build", "fa_vocab_rescore_candidates", "fa_vocab_rescore_decide_dev",
     "fa_vocab_rescore_decide",
+    "fa_fbank_default_config", "fa_fbank_num_frames", "fa_fbank_num_rows", "fa_fbank_plan_create", "fa_fbank_plan_destroy", "fa_fbank_plan_row_stride",
+    "fa_fbank_plan_utt_stride", "fa_fbank_execute_dev", "fa_fbank_batch", "fa_fbank_window", "fa_fbank_filterbank",
 ]
 
 
@@ -99,6 +103,13 @@ class MelConfig(C.Structure):
                 ("floor_mode", C.c_int32), ("window_periodic", C.c_int32), ("padding_mode", C.c_int32),
                 ("layout", C.c_int32), ("power", C.c_float), ("center_pad", C.c_int32), ("mel_scale", C.c_int32),
                 ("tail_mode", C.c_int32), ("filterbank", C.c_void_p)]
+
+
+class FbankConfig(C.Structure):                                        # fa_fbank_config
+    _fields_ = [("sample_rate", C.c_int32), ("n_mels", C.c_int32), ("n_fft", C.c_int32), ("hop", C.c_int32), ("win", C.c_int32),
+                ("waveform_scale", C.c_float), ("preemph", C.c_float), ("low_freq", C.c_float), ("high_freq", C.c_float), ("log_floor", C.c_float),
+                ("window_type", C.c_int32), ("remove_dc", C.c_int32), ("lfr_m", C.c_int32), ("lfr_n", C.c_int32), ("tail_mode", C.c_int32),
+                ("window", C.c_void_p), ("filterbank", C.c_void_p)]
 
 
 class TdtConfig(C.Structure):
@@ -455,6 +466,23 @@ def lib() -> C.CDLL:
     L.fa_mel_hann_window.argtypes = [C.POINTER(MelConfig), vp]
     L.fa_mel_normalize_per_feature_dev.argtypes = [vp, vp, i32, i32, i32, i32, vp]
     L.fa_mel_filterbank.argtypes = [C.POINTER(MelConfig), vp]
+    L.fa_fbank_default_config.argtypes = [C.POINTER(FbankConfig)]
+    L.fa_fbank_default_config.restype = None
+    L.fa_fbank_num_frames.argtypes = [C.POINTER(FbankConfig), i64]
+    L.fa_fbank_num_frames.restype = i32
+    L.fa_fbank_num_rows.argtypes = [C.POINTER(FbankConfig), i32]
+    L.fa_fbank_num_rows.restype = i32
+    L.fa_fbank_plan_create.argtypes = [vp, C.POINTER(FbankConfig), vp, i32, vp, vp, i32, C.POINTER(vp)]
+    L.fa_fbank_plan_destroy.argtypes = [vp]
+    L.fa_fbank_plan_destroy.restype = None
+    L.fa_fbank_plan_row_stride.argtypes = [vp]
+    L.fa_fbank_plan_row_stride.restype = i32
+    L.fa_fbank_plan_utt_stride.argtypes = [vp]
+    L.fa_fbank_plan_utt_stride.restype = i64
+    L.fa_fbank_execute_dev.argtypes = [vp, vp, vp, vp]
+    L.fa_fbank_batch.argtypes = [vp, C.POINTER(FbankConfig), vp, vp, i32, vp, vp, i32, vp, vp]
+    L.fa_fbank_window.argtypes = [C.POINTER(FbankConfig), vp]
+    L.fa_fbank_filterbank.argtypes = [C.POINTER(FbankConfig), vp]
     L.fa_ctc_greedy_batch_dev.argtypes = [vp, vp, i32, i32, i32, i32, i64, i64, vp, i32, vp, vp, vp]
     L.fa_ctc_log_softmax_batch_dev.argtypes = [vp, vp, i32, i32, i32, i32, i64, i64, f32, f32, i32, vp]
     L.fa_ctc_greedy_batch.argtypes = [vp, vp, i32, i32, i32, i32, i64, i64, vp, i32, vp, vp, vp]

@@ -2280,4 +2280,34 @@ class NemotronStreamSession {       // the gate, the span tracker and mergeRescu
     fa_rnnt_stream *st_ = nullptr;
 };
 
+// Kaldi fbank -> LFR -> CMVN (FunASR's WavFrontend; the reference's CoreML replica: Documentation/ASR/SenseVoice.md:27,107-114) for a batch.
+// A plan fixes the utterance offsets, the tables and the CMVN vectors; execute() is one launch on the context's stream.
+class FbankPlan {
+  public:
+    static fa_fbank_config wavFrontendConfig() { fa_fbank_config c; fa_fbank_default_config(&c); return c; }
+    // shift / scale: empty = none, else lfr_m * n_mels values
+    FbankPlan(Context &ctx, const fa_fbank_config &cfg, const std::vector<int64_t> &offsets, const std::vector<float> &shift = {},
+              const std::vector<float> &scale = {}, int32_t rowStride = 0)
+        : ctx_(ctx) {
+        const size_t width = static_cast<size_t>(cfg.lfr_m) * cfg.n_mels;
+        if (offsets.size() < 2 || (!shift.empty() && shift.size() != width) || (!scale.empty() && scale.size() != width))
+            throw Error(FA_INVALID_ARGUMENT, "FbankPlan", "offsets: batch + 1 entries; shift / scale: lfr_m * n_mels values");
+        ctx_.check(fa_fbank_plan_create(ctx_.handle(), &cfg, offsets.data(), static_cast<int32_t>(offsets.size() - 1), shift.empty() ? nullptr : shift.data(),
+                                        scale.empty() ? nullptr : scale.data(), rowStride, &plan_), "fa_fbank_plan_create");
+    }
+    ~FbankPlan() { fa_fbank_plan_destroy(plan_); }
+    FbankPlan(const FbankPlan &) = delete;
+    FbankPlan &operator=(const FbankPlan &) = delete;
+    int32_t rowStride() const { return fa_fbank_plan_row_stride(plan_); }
+    int64_t utteranceStride() const { return fa_fbank_plan_utt_stride(plan_); }
+    static int32_t numFrames(const fa_fbank_config &cfg, int64_t samples) { return fa_fbank_num_frames(&cfg, samples); }
+    static int32_t numRows(const fa_fbank_config &cfg, int32_t frames) { return fa_fbank_num_rows(&cfg, frames); }
+    // device pointers: pcm float[offsets.back()], out float[batch * utteranceStride()], rows int32[batch] or null
+    void execute(const float *dPcm, float *dOut, int32_t *dRows = nullptr) { ctx_.check(fa_fbank_execute_dev(plan_, dPcm, dOut, dRows), "fa_fbank_execute_dev"); }
+
+  private:
+    Context &ctx_;
+    fa_fbank_plan *plan_ = nullptr;
+};
+
 }  // namespace fluidaudio

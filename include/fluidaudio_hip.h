@@ -229,6 +229,71 @@ fa_status fa_mel_normalize_per_feature_dev(fa_ctx *ctx, float *d_mel, int32_t ba
 fa_status fa_mel_hann_window(const fa_mel_config *cfg, float *out /* win */);
 fa_status fa_mel_filterbank(const fa_mel_config *cfg, float *out /* n_mels * (n_fft/2+1) */);
 
+/* ------------------------------------------------------------------ Kaldi fbank ----- */
+/* The front end FunASR's WavFrontend puts before Paraformer, SenseVoice, FSMN-VAD and CAM++ (kaldi fbank -> LFR -> CMVN; the reference
+ * runs a CoreML replica of it, Documentation/ASR/SenseVoice.md:27,107-114, FsmnVadModels.swift:7, ParaformerModels.swift:21,
+ * CampPlusModels.swift:7), for a batch of utterances in one launch.  It restates Kaldi / torchaudio.compliance.kaldi.fbank.  Per
+ * utterance of n samples:
+ *   1. x <- x * waveform_scale.
+ *   2. T = n < win ? 0 : 1 + (n - win) / hop frames, frame t = x[t hop .. t hop + win): snip-edges, no padding, no dither.
+ *   3. per frame: subtract the frame's mean (remove_dc); pre-emphasis inside the frame, y[i] = x[i] - c x[i-1] for i >= 1 and
+ *      y[0] = x[0] - c x[0]; the window (Hamming 0.54 - 0.46 cos(2 pi i / (win - 1)), Povey (0.5 - 0.5 cos(2 pi i / (win - 1)))^0.85);
+ *      zero-pad to n_fft; the power spectrum |X_k|^2.
+ *   4. mel bank: mel(f) = 1127 ln(1 + f / 700); n_mels + 2 points equally spaced in mel from mel(low_freq) to mel(high_freq)
+ *      (high_freq <= 0: Nyquist + high_freq); bin b weighs FFT bin k < n_fft / 2 by max(0, min((m_k - left) / (centre - left),
+ *      (right - m_k) / (right - centre))), m_k = mel(k sample_rate / n_fft); the Nyquist column is 0.
+ *   5. log(max(energy, log_floor)).
+ *   6. LFR(m, n): lpad = (m - 1) / 2; row i, slot k takes frame clamp(i n + k - lpad, 0, T - 1); rows R = ceil(T / n)
+ *      (FA_FBANK_TAIL_REPLICATE, WavFrontend) or max(0, (T + lpad - m) / n + 1) (FA_FBANK_TAIL_VALID, the FSMN-VAD preprocessor as
+ *      converted, FsmnVadManager.swift:111-117); m = n = 1 is plain fbank.
+ *   7. CMVN: out = (v + shift[j]) * scale[j] for stacked feature j = k n_mels + b (FunASR's AddShift / Rescale vectors, the caller's).
+ * The tables are built in double and rounded to fp32.  Out of scope: utterance-mean subtraction, dither, energy features, fp16
+ * output; n_fft other than 512 (win <= 512) is refused by this kernel generation. */
+enum { FA_FBANK_WINDOW_HAMMING = 0, FA_FBANK_WINDOW_POVEY = 1 };
+enum { FA_FBANK_TAIL_REPLICATE = 0, FA_FBANK_TAIL_VALID = 1 };
+typedef struct {
+    int32_t sample_rate;      /* 16000 */
+    int32_t n_mels;           /* 80   (1..256) */
+    int32_t n_fft;            /* 512 */
+    int32_t hop;              /* 160 */
+    int32_t win;              /* 400  (<= n_fft) */
+    float waveform_scale;     /* 32768 */
+    float preemph;            /* 0.97 */
+    float low_freq;           /* 20 */
+    float high_freq;          /* 0: Nyquist; <= 0 is added to Nyquist */
+    float log_floor;          /* 1.1920929e-07 (FLT_EPSILON) */
+    int32_t window_type;      /* FA_FBANK_WINDOW_* */
+    int32_t remove_dc;        /* 1 */
+    int32_t lfr_m, lfr_n;     /* 7, 6 (1..64) */
+    int32_t tail_mode;        /* FA_FBANK_TAIL_* */
+    const float *window;      /* optional HOST table [win] that replaces the built-in window; NULL = window_type */
+    const float *filterbank;  /* optional HOST table [n_mels][n_fft/2 + 1] that replaces the built-in bank; NULL = step 4 */
+} fa_fbank_config;
+void fa_fbank_default_config(fa_fbank_config *cfg);   /* WavFrontend: 80 mels, Hamming, LFR 7 / 6, replicated tail */
+int32_t fa_fbank_num_frames(const fa_fbank_config *cfg, int64_t n_samples);   /* T of step 2 */
+int32_t fa_fbank_num_rows(const fa_fbank_config *cfg, int32_t frames);        /* R of step 6 */
+
+/* A plan fixes the batch geometry, the tables and the CMVN vectors; executing it is one kernel launch: nothing is allocated and
+ * nothing waited for.  offsets: HOST int64[batch + 1] into the packed pcm buffer.  shift, scale: HOST float[lfr_m * n_mels] or NULL
+ * (none).  row_stride: rows allocated per utterance (the encoder's length bucket, SenseVoiceConfig.swift:13), >= R of every
+ * utterance, else OUTPUT_TOO_SMALL; 0 = the largest R of the batch (at least 1).
+ * Output: out[b][row][lfr_m * n_mels], utterance b at out + b * fa_fbank_plan_utt_stride(plan); rows >= R(b) are written as zeros. */
+typedef struct fa_fbank_plan fa_fbank_plan;
+fa_status fa_fbank_plan_create(fa_ctx *ctx, const fa_fbank_config *cfg, const int64_t *offsets, int32_t batch, const float *shift,
+                               const float *scale, int32_t row_stride, fa_fbank_plan **out);
+void fa_fbank_plan_destroy(fa_fbank_plan *plan);
+int32_t fa_fbank_plan_row_stride(const fa_fbank_plan *plan);
+int64_t fa_fbank_plan_utt_stride(const fa_fbank_plan *plan);   /* floats per utterance in the output */
+/* d_pcm: device float[offsets[batch]]; d_out: device float[batch * utt_stride]; d_rows: device int32[batch] (R(b)) or NULL.  Enqueued
+ * on the context's stream. */
+fa_status fa_fbank_execute_dev(fa_fbank_plan *plan, const float *d_pcm, float *d_out, int32_t *d_rows);
+/* Host pointers: plan, copy in, launch, copy out, one synchronisation.  rows: int32[batch] or NULL. */
+fa_status fa_fbank_batch(fa_ctx *ctx, const fa_fbank_config *cfg, const float *pcm, const int64_t *offsets, int32_t batch, const float *shift,
+                         const float *scale, int32_t row_stride, float *out, int32_t *rows);
+/* Host copies of the tables of steps 3 and 4 (or the caller's own, when the configuration carries them). */
+fa_status fa_fbank_window(const fa_fbank_config *cfg, float *out /* win */);
+fa_status fa_fbank_filterbank(const fa_fbank_config *cfg, float *out /* n_mels * (n_fft/2+1) */);
+
 /* ------------------------------------------------------------------ argmax / CTC ---- */
 /* Replaces LogitsArgmax.argmaxPerFrame (FluidAudio/ASR/Shared/LogitsArgmax.swift:16-55) and the
  * greedy collapse of ctcGreedyDecode (FluidAudio/ASR/Parakeet/SlidingWindow/CTC/CtcDecoder.swift:15-36,
