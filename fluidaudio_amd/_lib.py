@@ -88,6 +88,9 @@ EXPORTED_SYMBOLS = [
     "fa_vocab_rescore_decide",
     "fa_fbank_default_config", "fa_fbank_num_frames", "fa_fbank_num_rows", "fa_fbank_plan_create", "fa_fbank_plan_destroy", "fa_fbank_plan_row_stride",
     "fa_fbank_plan_utt_stride", "fa_fbank_execute_dev", "fa_fbank_batch", "fa_fbank_window", "fa_fbank_filterbank",
+    "fa_lseend_default_config", "fa_lseend_mel_frames", "fa_lseend_plan_file", "fa_lseend_plan_push", "fa_lseend_features_dev", "fa_lseend_features",
+    "fa_lseend_stream_create", "fa_lseend_stream_destroy", "fa_lseend_stream_reset", "fa_lseend_stream_push_dev", "fa_lseend_stream_push", "fa_lseend_stream_get",
+    "fa_lseend_stream_set", "fa_lseend_gather_probs_dev", "fa_lseend_gather_probs",
 ]
 
 
@@ -110,6 +113,22 @@ class FbankConfig(C.Structure):                                        # fa_fban
                 ("waveform_scale", C.c_float), ("preemph", C.c_float), ("low_freq", C.c_float), ("high_freq", C.c_float), ("log_floor", C.c_float),
                 ("window_type", C.c_int32), ("remove_dc", C.c_int32), ("lfr_m", C.c_int32), ("lfr_n", C.c_int32), ("tail_mode", C.c_int32),
                 ("window", C.c_void_p), ("filterbank", C.c_void_p)]
+
+
+class LseendConfig(C.Structure):                                       # fa_lseend_config
+    _fields_ = [("sample_rate", C.c_int32), ("n_mels", C.c_int32), ("n_fft", C.c_int32), ("hop", C.c_int32), ("win", C.c_int32), ("context_size", C.c_int32),
+                ("subsampling", C.c_int32), ("conv_delay", C.c_int32), ("chunk_size", C.c_int32), ("log_floor", C.c_float)]
+
+
+class LseendItemPlan(C.Structure):                                     # fa_lseend_item_plan
+    _fields_ = [("frames", C.c_int64), ("frame0", C.c_int64), ("windows", C.c_int64), ("window0", C.c_int64), ("out_rows", C.c_int64), ("out_row0", C.c_int64),
+                ("flush_samples", C.c_int64), ("stream_window0", C.c_int64), ("unread_audio", C.c_int32), ("unread_mel_rows", C.c_int32),
+                ("decoder_mask_end", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LseendStreamInfo(C.Structure):                                   # fa_lseend_stream_info
+    _fields_ = [("audio_samples", C.c_int64), ("frames", C.c_int64), ("windows", C.c_int64), ("unread_audio", C.c_int32), ("unread_mel_rows", C.c_int32),
+                ("decoder_mask_end", C.c_int32), ("reserved", C.c_int32)]
 
 
 class TdtConfig(C.Structure):
@@ -483,6 +502,25 @@ def lib() -> C.CDLL:
     L.fa_fbank_batch.argtypes = [vp, C.POINTER(FbankConfig), vp, vp, i32, vp, vp, i32, vp, vp]
     L.fa_fbank_window.argtypes = [C.POINTER(FbankConfig), vp]
     L.fa_fbank_filterbank.argtypes = [C.POINTER(FbankConfig), vp]
+    lc = C.POINTER(LseendConfig)
+    L.fa_lseend_default_config.argtypes = [lc]
+    L.fa_lseend_default_config.restype = None
+    L.fa_lseend_mel_frames.argtypes = [lc]
+    L.fa_lseend_mel_frames.restype = i32
+    L.fa_lseend_plan_file.argtypes = [lc, vp, i32, vp, vp, vp, i64]
+    L.fa_lseend_plan_push.argtypes = [lc, C.POINTER(LseendStreamInfo), i64, i32, C.POINTER(LseendItemPlan), vp, vp, i64]
+    L.fa_lseend_features_dev.argtypes = [vp, lc, vp, vp, i32, vp, vp, vp, vp, vp]
+    L.fa_lseend_features.argtypes = [vp, lc, vp, vp, i32, vp, vp, vp, vp, vp]
+    L.fa_lseend_stream_create.argtypes = [vp, lc, i32, i64, C.POINTER(vp)]
+    L.fa_lseend_stream_destroy.argtypes = [vp]
+    L.fa_lseend_stream_destroy.restype = None
+    L.fa_lseend_stream_reset.argtypes = [vp, vp, i32]
+    L.fa_lseend_stream_push_dev.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp]
+    L.fa_lseend_stream_push.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp]
+    L.fa_lseend_stream_get.argtypes = [vp, vp, i32, C.POINTER(LseendStreamInfo), vp, vp, vp]
+    L.fa_lseend_stream_set.argtypes = [vp, vp, i32, C.POINTER(LseendStreamInfo), vp, vp, vp]
+    L.fa_lseend_gather_probs_dev.argtypes = [vp, vp, i32, i32, i32, i64, i64, vp, vp, vp, i64]
+    L.fa_lseend_gather_probs.argtypes = [vp, vp, i32, i32, i32, i64, i64, vp, vp, vp, i64]
     L.fa_ctc_greedy_batch_dev.argtypes = [vp, vp, i32, i32, i32, i32, i64, i64, vp, i32, vp, vp, vp]
     L.fa_ctc_log_softmax_batch_dev.argtypes = [vp, vp, i32, i32, i32, i32, i64, i64, f32, f32, i32, vp]
     L.fa_ctc_greedy_batch.argtypes = [vp, vp, i32, i32, i32, i32, i64, i64, vp, i32, vp, vp, vp]

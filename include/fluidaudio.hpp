@@ -2310,4 +2310,74 @@ class FbankPlan {
     fa_fbank_plan *plan_ = nullptr;
 };
 
+// The LS-EEND front end (LSEENDFeatureProvider, LSEENDPreprocessor.swift:158-202,249-384, and predict's copy, LSEENDInference.swift:95-119):
+// log10-mel, cumulative mean, model windows, masks and warm-up counts.  Every pointer named d... is a device pointer; the calls are
+// enqueued on the context's stream.  The header's section "LS-EEND front end" states the arithmetic.
+struct LseendFrontEnd {
+    static fa_lseend_config defaultConfig() { fa_lseend_config c; fa_lseend_default_config(&c); return c; }
+    static int32_t melFrames(const fa_lseend_config &cfg) { return fa_lseend_mel_frames(&cfg); }
+    // what the offline call does to each recording (offsets: batch + 1 entries); host only
+    static std::vector<fa_lseend_item_plan> planFile(const fa_lseend_config &cfg, const std::vector<int64_t> &offsets) {
+        if (offsets.size() < 2) throw Error(FA_INVALID_ARGUMENT, "LseendFrontEnd::planFile", "offsets: batch + 1 entries");
+        std::vector<fa_lseend_item_plan> plans(offsets.size() - 1);
+        const fa_status st = fa_lseend_plan_file(&cfg, offsets.data(), static_cast<int32_t>(plans.size()), plans.data(), nullptr, nullptr, 0);
+        if (st != FA_SUCCESS) throw Error(st, "fa_lseend_plan_file", "");
+        return plans;
+    }
+    // every window of every recording; the arrays are sized by planFile; dMasks, dWarmups, dOutRows, dRaw may be null
+    static void features(Context &ctx, const fa_lseend_config &cfg, const float *dPcm, const std::vector<int64_t> &offsets, float *dWindows, float *dMasks = nullptr,
+                         int32_t *dWarmups = nullptr, int64_t *dOutRows = nullptr, float *dRaw = nullptr) {
+        if (offsets.size() < 2) throw Error(FA_INVALID_ARGUMENT, "LseendFrontEnd::features", "offsets: batch + 1 entries");
+        ctx.check(fa_lseend_features_dev(ctx.handle(), &cfg, dPcm, offsets.data(), static_cast<int32_t>(offsets.size() - 1), dWindows, dMasks, dWarmups, dOutRows, dRaw),
+                  "fa_lseend_features_dev");
+    }
+    // rows [warmup, chunk) x speakers of every window of dProbs [windows][chunk][rowStride] into the dense dOut [outCapacity][speakers]
+    static void gatherProbs(Context &ctx, const float *dProbs, int32_t windows, int32_t chunkSize, int32_t speakers, int64_t windowStride, int64_t rowStride,
+                            const int32_t *dWarmups, const int64_t *dOutRows, float *dOut, int64_t outCapacity) {
+        ctx.check(fa_lseend_gather_probs_dev(ctx.handle(), dProbs, windows, chunkSize, speakers, windowStride, rowStride, dWarmups, dOutRows, dOut, outCapacity),
+                  "fa_lseend_gather_probs_dev");
+    }
+};
+
+class LseendStream {                // `streams` feature streams with their carried state in HBM
+  public:
+    struct Snapshot {               // takeSnapshot / rollback without the network's own state
+        fa_lseend_stream_info info{};
+        std::vector<float> audioTail, melTail;
+        std::vector<double> sums;
+    };
+    LseendStream(Context &ctx, const fa_lseend_config &cfg, int32_t streams, int64_t maxPushSamples) : ctx_(ctx), nMels_(cfg.n_mels) {
+        ctx_.check(fa_lseend_stream_create(ctx_.handle(), &cfg, streams, maxPushSamples, &st_), "fa_lseend_stream_create");
+    }
+    ~LseendStream() { fa_lseend_stream_destroy(st_); }
+    LseendStream(const LseendStream &) = delete;
+    LseendStream &operator=(const LseendStream &) = delete;
+    void reset(int32_t stream = -1) { ctx_.check(fa_lseend_stream_reset(ctx_.handle(), st_, stream), "fa_lseend_stream_reset"); }
+    // offsets: streams + 1 entries into dPcm; flush: empty or one flag per stream; returns what the call did to every stream
+    std::vector<fa_lseend_item_plan> push(const float *dPcm, const std::vector<int64_t> &offsets, const std::vector<int32_t> &flush, int64_t windowCapacity, float *dWindows,
+                                          float *dMasks = nullptr, int32_t *dWarmups = nullptr, int64_t *dOutRows = nullptr, float *dRaw = nullptr) {
+        if (offsets.size() < 2 || (!flush.empty() && flush.size() != offsets.size() - 1))
+            throw Error(FA_INVALID_ARGUMENT, "LseendStream::push", "offsets: streams + 1 entries; flush: empty or one flag per stream");
+        std::vector<fa_lseend_item_plan> plans(offsets.size() - 1);
+        ctx_.check(fa_lseend_stream_push_dev(ctx_.handle(), st_, dPcm, offsets.data(), flush.empty() ? nullptr : flush.data(), windowCapacity, dWindows, dMasks, dWarmups,
+                                             dOutRows, dRaw, plans.data()), "fa_lseend_stream_push_dev");
+        return plans;
+    }
+    Snapshot snapshot(int32_t stream) {
+        Snapshot s;
+        ctx_.check(fa_lseend_stream_get(ctx_.handle(), st_, stream, &s.info, nullptr, nullptr, nullptr), "fa_lseend_stream_get");
+        s.audioTail.resize(s.info.unread_audio); s.melTail.resize(static_cast<size_t>(s.info.unread_mel_rows) * nMels_); s.sums.resize(nMels_);
+        ctx_.check(fa_lseend_stream_get(ctx_.handle(), st_, stream, &s.info, s.audioTail.data(), s.melTail.data(), s.sums.data()), "fa_lseend_stream_get");
+        return s;
+    }
+    void rollback(int32_t stream, const Snapshot &s) {
+        ctx_.check(fa_lseend_stream_set(ctx_.handle(), st_, stream, &s.info, s.audioTail.data(), s.melTail.data(), s.sums.data()), "fa_lseend_stream_set");
+    }
+
+  private:
+    Context &ctx_;
+    int32_t nMels_;
+    fa_lseend_stream *st_ = nullptr;
+};
+
 }  // namespace fluidaudio

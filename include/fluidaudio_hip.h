@@ -294,6 +294,97 @@ fa_status fa_fbank_batch(fa_ctx *ctx, const fa_fbank_config *cfg, const float *p
 fa_status fa_fbank_window(const fa_fbank_config *cfg, float *out /* win */);
 fa_status fa_fbank_filterbank(const fa_fbank_config *cfg, float *out /* n_mels * (n_fft/2+1) */);
 
+/* ------------------------------------------------------------------ LS-EEND front end */
+/* What LSEENDFeatureProvider does between the audio and the network, and LSEENDModel.predict behind it (Diarizer/LS-EEND/
+ * LSEENDPreprocessor.swift:249-279 processAudioQueue, :185-202 emitNextChunk, :158-180 the flush, :284-384 StreamingChunkQueue;
+ * LSEENDInference.swift:87-123; LSEENDTypes.swift:52-57), batched over items.  An item is a whole recording (fa_lseend_features_dev) or
+ * one stream's newly pushed audio (fa_lseend_stream_push_dev); both run the same three launches and differ only in the carried state.
+ *   1. mel: AudioMelSpectrogram in the flavour of :70-82 (preemph 0, periodic Hann of win centred in n_fft, Slaney bank,
+ *      log(max(v, log_floor))) on the audio queue: n_fft / 2 zeros, the samples, and for a flush flush_samples zeros plus the shortfall
+ *      to the next chunk of hop * subsampling * chunk_size samples; frame f covers queue positions [f hop, f hop + n_fft).  Frames come
+ *      in whole chunks only.  n_fft has to be 256 (EEND's 8 kHz, 25 ms / 10 ms front end); any other value is INVALID_ARGUMENT.
+ *   2. times float(1 / ln 10).
+ *   3. cumulative mean normalisation over the whole recording or stream: y_k = x_k - mu_k.  DIFFERS FROM THE REFERENCE in arithmetic:
+ *      the reference runs mu_k = mu_(k-1) + (x_k - mu_(k-1)) / k in fp32, frame after frame; here mu_k = float(S_k / k) with S_k the
+ *      fp64 sum of x_1 .. x_k in the tile order csrc/lseend_core.h defines, then the fp32 subtraction.  Equal in exact arithmetic; a
+ *      stream and the offline call group the sum differently, so both are held to float64, not to each other bit for bit.
+ *   4. windows: the mel queue is context_size literal zero rows, then the rows y; window c is its rows [c chunk_mels, c chunk_mels +
+ *      mel_frames), chunk_mels = subsampling * chunk_size, mel_frames = (chunk_size - 1) subsampling + 2 context_size + 1.
+ *      2 context_size + 1 < subsampling is INVALID_ARGUMENT.
+ *   5. per window: the decoder-mask slice float[chunk_size] (0 below conv_delay, 1 from it on, :65-67,:193-197), the warm-up count
+ *      max(min(conv_delay - frames fed, chunk_size), 0), and the row at which its kept rows [warmup, chunk_size) start in the dense
+ *      probabilities of the call (items one behind another).
+ * Every count is a host integer: the plans below give them without a device. */
+typedef struct {
+    int32_t sample_rate;     /* 8000 */
+    int32_t n_mels;          /* 23   (1..128) */
+    int32_t n_fft;           /* 256 */
+    int32_t hop;             /* 80   (<= n_fft / 2) */
+    int32_t win;             /* 200  (<= n_fft) */
+    int32_t context_size;    /* 7 */
+    int32_t subsampling;     /* 10 */
+    int32_t conv_delay;      /* 9 */
+    int32_t chunk_size;      /* 5    output frames per model call */
+    float log_floor;         /* 1e-10 */
+} fa_lseend_config;
+typedef struct {             /* one item of one call */
+    int64_t frames, frame0;          /* mel rows computed; the first one's index in the call's raw-row array */
+    int64_t windows, window0;        /* windows emitted; the first one's index in the call's arena */
+    int64_t out_rows, out_row0;      /* rows [warmup, chunk_size) of those windows; the first one's row in the dense probabilities */
+    int64_t flush_samples;           /* zeros the flush appended (0 without one) */
+    int64_t stream_window0;          /* index of the first emitted window in its stream or recording */
+    int32_t unread_audio, unread_mel_rows;   /* carried behind the call */
+    int32_t decoder_mask_end, reserved;
+} fa_lseend_item_plan;
+typedef struct {             /* a stream's counters (takeSnapshot / rollback, :206-233, without the network's own state) */
+    int64_t audio_samples;           /* samples pushed so far, flush zeros included */
+    int64_t frames, windows;         /* mel rows computed (the CMN count), windows emitted */
+    int32_t unread_audio, unread_mel_rows;   /* <= chunk samples + n_fft - hop - 1, <= mel_frames - 1 */
+    int32_t decoder_mask_end, reserved;
+} fa_lseend_stream_info;
+void fa_lseend_default_config(fa_lseend_config *cfg);
+int32_t fa_lseend_mel_frames(const fa_lseend_config *cfg);   /* rows of a window; 0 for a configuration that is refused */
+/* Pure host functions.  plan_file: every recording of a batch pushed whole and flushed (processComplete); warmups int32[windows] and
+ * masks float[windows][chunk_size] of all recordings one behind another, either may be NULL, else window_capacity windows of room.
+ * plan_push: one call on one stream; *state all zero is a fresh stream, and is advanced. */
+fa_status fa_lseend_plan_file(const fa_lseend_config *cfg, const int64_t *offsets, int32_t batch, fa_lseend_item_plan *items, int32_t *warmups, float *masks,
+                              int64_t window_capacity);
+fa_status fa_lseend_plan_push(const fa_lseend_config *cfg, fa_lseend_stream_info *state, int64_t samples, int32_t flush, fa_lseend_item_plan *plan, int32_t *warmups,
+                              float *masks, int64_t window_capacity);
+/* Offline.  DEVICE pointers sized by fa_lseend_plan_file: d_pcm float[offsets[batch]], d_windows float[W][mel_frames][n_mels], d_masks
+ * float[W][chunk_size], d_warmups int32[W], d_out_rows int64[W], d_raw float[F][n_mels] the un-normalised log10-mel rows; the last four
+ * may be NULL (not written).  offsets is a HOST array.  Three launches on the context's stream, buffers from the context's cache. */
+fa_status fa_lseend_features_dev(fa_ctx *ctx, const fa_lseend_config *cfg, const float *d_pcm, const int64_t *offsets, int32_t batch, float *d_windows,
+                                 float *d_masks, int32_t *d_warmups, int64_t *d_out_rows, float *d_raw);
+fa_status fa_lseend_features(fa_ctx *ctx, const fa_lseend_config *cfg, const float *pcm, const int64_t *offsets, int32_t batch, float *windows, float *masks,
+                             int32_t *warmups, int64_t *out_rows, float *raw);   /* host pointers, one synchronisation */
+/* Streaming: `streams` independent streams whose unread audio, unread normalised rows and per-mel fp64 sum stay in HBM.  A push takes at
+ * most max_push_samples per stream; the workspace is sized for that at creation and nothing is allocated afterwards. */
+typedef struct fa_lseend_stream fa_lseend_stream;
+fa_status fa_lseend_stream_create(fa_ctx *ctx, const fa_lseend_config *cfg, int32_t streams, int64_t max_push_samples, fa_lseend_stream **out);
+void fa_lseend_stream_destroy(fa_lseend_stream *st);
+fa_status fa_lseend_stream_reset(fa_ctx *ctx, fa_lseend_stream *st, int32_t stream /* -1: all */);
+/* One call for all streams: stream s takes d_pcm[offsets[s] .. offsets[s + 1]) (HOST offsets, may be empty) and, with flush[s] != 0
+ * (HOST array or NULL), the flush.  The windows that became ready go to the caller's arena, streams one behind another, as in the
+ * offline call; more than window_capacity of them is OUTPUT_TOO_SMALL and changes nothing.  plans: HOST fa_lseend_item_plan[streams]
+ * or NULL, what the call did, known before the launches. */
+fa_status fa_lseend_stream_push_dev(fa_ctx *ctx, fa_lseend_stream *st, const float *d_pcm, const int64_t *offsets, const int32_t *flush, int64_t window_capacity,
+                                    float *d_windows, float *d_masks, int32_t *d_warmups, int64_t *d_out_rows, float *d_raw, fa_lseend_item_plan *plans);
+fa_status fa_lseend_stream_push(fa_ctx *ctx, fa_lseend_stream *st, const float *pcm, const int64_t *offsets, const int32_t *flush, int64_t window_capacity, float *windows,
+                                float *masks, int32_t *warmups, int64_t *out_rows, float *raw, int64_t raw_capacity, fa_lseend_item_plan *plans);   /* host pointers */
+/* takeSnapshot / rollback as host data: audio_tail float[unread_audio], mel_tail float[unread_mel_rows][n_mels], sums double[n_mels].
+ * get: any array may be NULL; set: every array of non-zero size is required and info has to be a state the queues reach.  Both synchronise the stream. */
+fa_status fa_lseend_stream_get(fa_ctx *ctx, fa_lseend_stream *st, int32_t stream, fa_lseend_stream_info *info, float *audio_tail, float *mel_tail, double *sums);
+fa_status fa_lseend_stream_set(fa_ctx *ctx, fa_lseend_stream *st, int32_t stream, const fa_lseend_stream_info *info, const float *audio_tail, const float *mel_tail,
+                               const double *sums);
+/* predict's copy (LSEENDInference.swift:95-119): window w's rows [warmups[w], chunk_size) x speakers of the strided d_probs
+ * [windows][chunk_size][row_stride >= speakers] go to d_out[out_rows[w] ..][speakers], the dense layout fa_timeline_segments_dev takes.
+ * d_warmups / d_out_rows are what the calls above wrote; a window whose rows would pass out_capacity rows is left out. */
+fa_status fa_lseend_gather_probs_dev(fa_ctx *ctx, const float *d_probs, int32_t windows, int32_t chunk_size, int32_t speakers, int64_t window_stride, int64_t row_stride,
+                                     const int32_t *d_warmups, const int64_t *d_out_rows, float *d_out, int64_t out_capacity);
+fa_status fa_lseend_gather_probs(fa_ctx *ctx, const float *probs, int32_t windows, int32_t chunk_size, int32_t speakers, int64_t window_stride, int64_t row_stride,
+                                 const int32_t *warmups, const int64_t *out_rows, float *out, int64_t out_capacity);   /* host pointers */
+
 /* ------------------------------------------------------------------ argmax / CTC ---- */
 /* Replaces LogitsArgmax.argmaxPerFrame (FluidAudio/ASR/Shared/LogitsArgmax.swift:16-55) and the
  * greedy collapse of ctcGreedyDecode (FluidAudio/ASR/Parakeet/SlidingWindow/CTC/CtcDecoder.swift:15-36,
