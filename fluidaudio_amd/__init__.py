@@ -19,6 +19,8 @@ from .embedding import EmbeddingConfig, EmbeddingPlan, plan_embeddings, span_inp
 from .fbank import WavFrontend, fbank_batch, fbank_config, fbank_filterbank, fbank_num_frames, fbank_num_rows, fbank_window  # noqa: F401
 from .lseend import (LseendFeatures, LseendStream, lseend_config, lseend_features, lseend_gather_probs, lseend_mel_frames,  # noqa: F401
                      lseend_plan_file, lseend_plan_push)
+from .luxtts import (LuxTtsSession, luxtts_anchor_euler, luxtts_config, luxtts_plan, luxtts_prompt_loudness,  # noqa: F401
+                     luxtts_time_steps)
 from .formats import AudioWAV, RTTMParser, RTTMParserError, TimedSpeakerSegment, export_embeddings_json  # noqa: F401
 from .fsmn_vad import (fsmn_vad_config, fsmn_vad_frame_count, fsmn_vad_gather_silence_dev,  # noqa: F401
                        fsmn_vad_pack_feats_dev, fsmn_vad_pack_waveforms, fsmn_vad_pack_waveforms_dev, fsmn_vad_plan_chunks, fsmn_vad_segments,

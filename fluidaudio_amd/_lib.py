@@ -91,6 +91,10 @@ EXPORTED_SYMBOLS = [
     "fa_lseend_default_config", "fa_lseend_mel_frames", "fa_lseend_plan_file", "fa_lseend_plan_push", "fa_lseend_features_dev", "fa_lseend_features",
     "fa_lseend_stream_create", "fa_lseend_stream_destroy", "fa_lseend_stream_reset", "fa_lseend_stream_push_dev", "fa_lseend_stream_push", "fa_lseend_stream_get",
     "fa_lseend_stream_set", "fa_lseend_gather_probs_dev", "fa_lseend_gather_probs",
+    "fa_luxtts_default_config", "fa_luxtts_plan", "fa_luxtts_time_steps", "fa_luxtts_prompt_loudness", "fa_luxtts_anchor_euler", "fa_luxtts_session_create",
+    "fa_luxtts_session_destroy", "fa_luxtts_session_slabs", "fa_luxtts_session_begin", "fa_luxtts_session_get", "fa_luxtts_prompt_dev", "fa_luxtts_inputs_dev",
+    "fa_luxtts_text_condition_dev", "fa_luxtts_step_dev", "fa_luxtts_vocoder_input_dev", "fa_luxtts_finish_dev", "fa_luxtts_prompt", "fa_luxtts_inputs",
+    "fa_luxtts_text_condition", "fa_luxtts_step", "fa_luxtts_vocoder_input", "fa_luxtts_finish",
 ]
 
 
@@ -129,6 +133,25 @@ class LseendItemPlan(C.Structure):                                     # fa_lsee
 class LseendStreamInfo(C.Structure):                                   # fa_lseend_stream_info
     _fields_ = [("audio_samples", C.c_int64), ("frames", C.c_int64), ("windows", C.c_int64), ("unread_audio", C.c_int32), ("unread_mel_rows", C.c_int32),
                 ("decoder_mask_end", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LuxTtsConfig(C.Structure):                                       # fa_luxtts_config
+    _fields_ = [("t_shift", C.c_double), ("max_prompt_seconds", C.c_double), ("sample_rate", C.c_int32), ("n_fft", C.c_int32), ("hop", C.c_int32), ("n_mels", C.c_int32),
+                ("max_tokens", C.c_int32), ("max_frames", C.c_int32), ("n_buckets", C.c_int32), ("buckets", C.c_int32 * 4), ("out_hop", C.c_int32), ("num_steps", C.c_int32),
+                ("log_floor", C.c_float), ("feat_scale", C.c_float), ("target_rms", C.c_float)]
+
+
+class LuxTtsItemPlan(C.Structure):                                     # fa_luxtts_item_plan
+    _fields_ = [("samples", C.c_int64), ("sample_count", C.c_int64), ("prompt_frames", C.c_int32), ("tokens", C.c_int32), ("features_length", C.c_int32),
+                ("gen_frames", C.c_int32), ("avg", C.c_int32), ("bucket", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LuxTtsRecord(C.Structure):                                       # fa_luxtts_record
+    _fields_ = [("mean_square", C.c_float), ("rms", C.c_float), ("gain", C.c_float), ("status", C.c_int32)]
+
+
+class LuxTtsSlabs(C.Structure):                                        # fa_luxtts_slabs: device addresses
+    _fields_ = [(name, C.c_void_p) for name in ("tokens", "token_mask", "text_condition", "speech_condition", "x", "frame_mask", "records")]
 
 
 class TdtConfig(C.Structure):
@@ -521,6 +544,23 @@ def lib() -> C.CDLL:
     L.fa_lseend_stream_set.argtypes = [vp, vp, i32, C.POINTER(LseendStreamInfo), vp, vp, vp]
     L.fa_lseend_gather_probs_dev.argtypes = [vp, vp, i32, i32, i32, i64, i64, vp, vp, vp, i64]
     L.fa_lseend_gather_probs.argtypes = [vp, vp, i32, i32, i32, i64, i64, vp, vp, vp, i64]
+    xc = C.POINTER(LuxTtsConfig)
+    L.fa_luxtts_default_config.argtypes = [xc]
+    L.fa_luxtts_default_config.restype = None
+    L.fa_luxtts_plan.argtypes = [xc, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.fa_luxtts_time_steps.argtypes = [xc, vp]
+    L.fa_luxtts_prompt_loudness.argtypes = [xc, vp, i64, C.POINTER(LuxTtsRecord)]
+    L.fa_luxtts_anchor_euler.argtypes = [xc, i32, vp, vp, i64]
+    L.fa_luxtts_session_create.argtypes = [vp, xc, i32, C.POINTER(vp)]
+    L.fa_luxtts_session_destroy.argtypes = [vp]
+    L.fa_luxtts_session_destroy.restype = None
+    L.fa_luxtts_session_slabs.argtypes = [vp, C.POINTER(LuxTtsSlabs)]
+    L.fa_luxtts_session_begin.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.fa_luxtts_session_get.argtypes = [vp, vp, i32, vp]
+    for name, args in {"fa_luxtts_prompt": [vp, vp, vp, vp], "fa_luxtts_inputs": [vp, vp, vp, vp, vp], "fa_luxtts_text_condition": [vp, vp, vp, i64, i64],
+                       "fa_luxtts_step": [vp, vp, i32, vp, i64, i64], "fa_luxtts_vocoder_input": [vp, vp, i32, vp, i32, vp],
+                       "fa_luxtts_finish": [vp, vp, vp, i64, vp, vp]}.items():       # the host-pointer form and its device form take the same list
+        getattr(L, name).argtypes = getattr(L, name + "_dev").argtypes = args
     L.fa_ctc_greedy_batch_dev.argtypes = [vp, vp, i32, i32, i32, i32, i64, i64, vp, i32, vp, vp, vp]
     L.fa_ctc_log_softmax_batch_dev.argtypes = [vp, vp, i32, i32, i32, i32, i64, i64, f32, f32, i32, vp]
     L.fa_ctc_greedy_batch.argtypes = [vp, vp, i32, i32, i32, i32, i64, i64, vp, i32, vp, vp, vp]

@@ -2380,4 +2380,68 @@ class LseendStream {                // `streams` feature streams with their carr
     fa_lseend_stream *st_ = nullptr;
 };
 
+// The LuxTTS session (LuxTtsSynthesizer.synthesize, LuxTtsSynthesizer.swift:59-299, between its three networks): `batch` utterances whose
+// tokens, masks, conditions and solver state stay in HBM from the prompt to the waveform.  d* are device pointers, vectors are host data.
+class LuxTtsSession {
+  public:
+    static fa_luxtts_config defaultConfig() { fa_luxtts_config c; fa_luxtts_default_config(&c); return c; }
+    static std::vector<double> timeSteps(const fa_luxtts_config &cfg) {
+        std::vector<double> t(static_cast<size_t>(cfg.num_steps > 0 ? cfg.num_steps : 0) + 1);
+        const fa_status st = fa_luxtts_time_steps(&cfg, t.data());
+        if (st != FA_SUCCESS) throw Error(st, "fa_luxtts_time_steps", "");
+        return t;
+    }
+    LuxTtsSession(Context &ctx, const fa_luxtts_config &cfg, int32_t batch) : ctx_(ctx), batch_(batch) {
+        ctx_.check(fa_luxtts_session_create(ctx_.handle(), &cfg, batch, &s_), "fa_luxtts_session_create");
+    }
+    ~LuxTtsSession() { fa_luxtts_session_destroy(s_); }
+    LuxTtsSession(const LuxTtsSession &) = delete;
+    LuxTtsSession &operator=(const LuxTtsSession &) = delete;
+    fa_luxtts_slabs slabs() const { fa_luxtts_slabs out{}; fa_luxtts_session_slabs(s_, &out); return out; }
+    // one entry per item; the plans say which items were refused and which vocoder bucket the others take
+    std::vector<fa_luxtts_item_plan> begin(const std::vector<int64_t> &promptSamples, const std::vector<int32_t> &promptTokens, const std::vector<int32_t> &textTokens,
+                                           const std::vector<float> &speeds) {
+        const size_t B = static_cast<size_t>(batch_);
+        if (promptSamples.size() != B || promptTokens.size() != B || textTokens.size() != B || speeds.size() != B)
+            throw Error(FA_INVALID_ARGUMENT, "LuxTtsSession::begin", "one entry per item");
+        std::vector<fa_luxtts_item_plan> plans(B);
+        ctx_.check(fa_luxtts_session_begin(ctx_.handle(), s_, promptSamples.data(), promptTokens.data(), textTokens.data(), speeds.data(), plans.data()), "fa_luxtts_session_begin");
+        return plans;
+    }
+    void prompt(const float *dPcm, const std::vector<int64_t> &offsets) {
+        need(offsets.size(), 1, "LuxTtsSession::prompt");
+        ctx_.check(fa_luxtts_prompt_dev(ctx_.handle(), s_, dPcm, offsets.data()), "fa_luxtts_prompt_dev");
+    }
+    void inputs(const int32_t *dTokenIds, const std::vector<int64_t> &tokenOffsets, const std::vector<uint64_t> &seeds) {
+        need(tokenOffsets.size(), 1, "LuxTtsSession::inputs"); need(seeds.size(), 0, "LuxTtsSession::inputs");
+        ctx_.check(fa_luxtts_inputs_dev(ctx_.handle(), s_, dTokenIds, tokenOffsets.data(), seeds.data()), "fa_luxtts_inputs_dev");
+    }
+    void textCondition(const float *dEmbeds, int64_t rowStride, int64_t itemStride) {
+        ctx_.check(fa_luxtts_text_condition_dev(ctx_.handle(), s_, dEmbeds, rowStride, itemStride), "fa_luxtts_text_condition_dev");
+    }
+    void step(int32_t step, const float *dV, int64_t rowStride, int64_t itemStride) {
+        ctx_.check(fa_luxtts_step_dev(ctx_.handle(), s_, step, dV, rowStride, itemStride), "fa_luxtts_step_dev");
+    }
+    void vocoderInput(int32_t bucket, const std::vector<int32_t> &items, float *dMel) {
+        ctx_.check(fa_luxtts_vocoder_input_dev(ctx_.handle(), s_, bucket, items.data(), static_cast<int32_t>(items.size()), dMel), "fa_luxtts_vocoder_input_dev");
+    }
+    void finish(const float *dAudio, int64_t rowStride, const std::vector<int64_t> &sampleOffsets, float *dOut) {
+        need(sampleOffsets.size(), 1, "LuxTtsSession::finish");
+        ctx_.check(fa_luxtts_finish_dev(ctx_.handle(), s_, dAudio, rowStride, sampleOffsets.data(), dOut), "fa_luxtts_finish_dev");
+    }
+    std::vector<fa_luxtts_record> records() {   // synchronises the stream
+        std::vector<fa_luxtts_record> r(static_cast<size_t>(batch_));
+        ctx_.check(fa_luxtts_session_get(ctx_.handle(), s_, FA_LUXTTS_SLAB_RECORDS, r.data()), "fa_luxtts_session_get");
+        return r;
+    }
+
+  private:
+    void need(size_t have, size_t extra, const char *where) const {
+        if (have != static_cast<size_t>(batch_) + extra) throw Error(FA_INVALID_ARGUMENT, where, "one entry per item (offsets: one more)");
+    }
+    Context &ctx_;
+    int32_t batch_;
+    fa_luxtts_session *s_ = nullptr;
+};
+
 }  // namespace fluidaudio

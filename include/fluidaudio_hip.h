@@ -385,6 +385,103 @@ fa_status fa_lseend_gather_probs_dev(fa_ctx *ctx, const float *d_probs, int32_t 
 fa_status fa_lseend_gather_probs(fa_ctx *ctx, const float *probs, int32_t windows, int32_t chunk_size, int32_t speakers, int64_t window_stride, int64_t row_stride,
                                  const int32_t *warmups, const int64_t *out_rows, float *out, int64_t out_capacity);   /* host pointers */
 
+/* ------------------------------------------------------------------ LuxTTS session */
+/* The host arithmetic of LuxTtsSynthesizer.synthesize (FluidAudio/TTS/LuxTts/LuxTtsSynthesizer.swift:59-299, LuxTtsSolver.swift,
+ * LuxTtsMelExtractor.swift:52-132, LuxTtsConstants.swift) between its three networks, batched over utterances on device slabs the
+ * networks read in place.  The text encoder, the flow-matching decoder, the vocoder, the G2P and the tokenizer stay the caller's.  Order
+ * of a batch: fa_luxtts_session_begin (the plan), fa_luxtts_prompt_dev, fa_luxtts_inputs_dev, the text encoder, fa_luxtts_text_condition_dev,
+ * num_steps times (the decoder, fa_luxtts_step_dev), per bucket (fa_luxtts_vocoder_input_dev, the vocoder), fa_luxtts_finish_dev.
+ *   plan     per item, in the reference's order of guards (:59-128, Solver :37): samples = min(n, Int(max_prompt_seconds * sample_rate));
+ *            prompt_frames = (samples + hop / 2) / hop; tokens = prompt + text; features_length = prompt_frames + ceil(prompt_frames /
+ *            prompt_tokens * text_tokens / speed) in double; gen_frames; bucket = the first one >= gen_frames; avg = features_length /
+ *            tokens; sample_count = min((gen_frames - 1) out_hop, (bucket - 1) out_hop).  A refused item has its status and zeros; later
+ *            entries write zeros into its slab rows (1.0 into its masks) and nothing else.
+ *   prompt   mean square of the capped prompt in the fixed fp32 order of csrc/luxtts_core.h (vDSP_measqv leaves it open), rms = sqrt,
+ *            gain = target_rms / rms where rms < target_rms, else 1; rms == 0 is FA_LUXTTS_SILENT_PROMPT in the record and zero rows.
+ *            speech_condition[b, f, :] = log(max(HTK mel of |STFT| of the gained prompt, log_floor)) * feat_scale for f < prompt_frames
+ *            (periodic Hann of n_fft, torch reflect padding, the tables of fa_mel_hann_window / fa_mel_filterbank), zeros behind.
+ *            n_fft has to be 1024 and n_mels a multiple of 4 up to 128; anything else is INVALID_ARGUMENT.
+ *   inputs   tokens with zero tails, token_mask 1.0 from `tokens` on, frame_mask 1.0 from features_length on, x = the first
+ *            features_length * n_mels draws of StyleTTS2NoiseSource(seed) (StyleTTS2DiffusionSchedule.swift:49-73), zeros behind.
+ *   text     text_condition[b, f, :] = embeds[b, f / avg, :] for f < tokens * avg, embeds[b, tokens, :] for the remainder frames, zeros
+ *            from features_length on.
+ *   step     x <- the anchor-Euler update (:236-248) in the fp32 order of csrc/luxtts_core.h, active rows only.
+ *   vocoder  mel[k, m, f] = x[b, prompt_frames + f, m] * (1 / feat_scale) for f < gen_frames, log(log_floor) up to the bucket.
+ *   finish   the first sample_count samples of the item's vocoder row, clipped to [-1, 1], times rms / target_rms where the prompt
+ *            was boosted, at sample_offsets[b]. */
+typedef struct {
+    double t_shift;              /* 0.5 */
+    double max_prompt_seconds;   /* 5 */
+    int32_t sample_rate;         /* 24000 */
+    int32_t n_fft;               /* 1024 */
+    int32_t hop;                 /* 256 */
+    int32_t n_mels;              /* 100 */
+    int32_t max_tokens;          /* 256 */
+    int32_t max_frames;          /* 1024 */
+    int32_t n_buckets;           /* 2 (1..4) */
+    int32_t buckets[4];          /* 282, 555: ascending generated-frame counts of the published vocoders */
+    int32_t out_hop;             /* 512: the vocoder's hop at the output rate */
+    int32_t num_steps;           /* 4 (1..16) */
+    float log_floor;             /* 1e-7 */
+    float feat_scale;            /* 0.1 */
+    float target_rms;            /* 0.1; 0 switches the loudness normalisation off */
+} fa_luxtts_config;
+enum { FA_LUXTTS_OK = 0, FA_LUXTTS_NO_SAMPLES = 1, FA_LUXTTS_BAD_SPEED = 2, FA_LUXTTS_PROMPT_TOO_SHORT = 3, FA_LUXTTS_TOO_MANY_TOKENS = 4,
+       FA_LUXTTS_TOO_MANY_FRAMES = 5, FA_LUXTTS_TEXT_TOO_SHORT = 6, FA_LUXTTS_NO_BUCKET = 7, FA_LUXTTS_DEGENERATE_DURATION = 8,
+       FA_LUXTTS_SILENT_PROMPT = 9 /* in the device record only */ };
+typedef struct {
+    int64_t samples, sample_count;
+    int32_t prompt_frames, tokens, features_length, gen_frames, avg, bucket, status, reserved;
+} fa_luxtts_item_plan;
+typedef struct { float mean_square, rms, gain; int32_t status; } fa_luxtts_record;
+typedef struct {                 /* DEVICE pointers, fixed for the session's lifetime */
+    int32_t *tokens;             /* [batch][max_tokens] */
+    float *token_mask;           /* [batch][max_tokens] */
+    float *text_condition, *speech_condition, *x;   /* [batch][max_frames][n_mels] */
+    float *frame_mask;           /* [batch][max_frames] */
+    fa_luxtts_record *records;   /* [batch] */
+} fa_luxtts_slabs;
+enum { FA_LUXTTS_SLAB_TOKENS = 0, FA_LUXTTS_SLAB_TOKEN_MASK = 1, FA_LUXTTS_SLAB_TEXT_CONDITION = 2, FA_LUXTTS_SLAB_SPEECH_CONDITION = 3,
+       FA_LUXTTS_SLAB_X = 4, FA_LUXTTS_SLAB_FRAME_MASK = 5, FA_LUXTTS_SLAB_RECORDS = 6 };
+void fa_luxtts_default_config(fa_luxtts_config *cfg);
+/* Pure host functions.  plan: token counts below 1 are INVALID_ARGUMENT (:53-58 is the tokenizer's business); bucket_counts
+ * int32[n_buckets] and bucket_items int32[n_buckets][batch] (the accepted items of every bucket, ascending) may be NULL.
+ * time_steps: the num_steps + 1 doubles of LuxTtsSolver.timeSteps.  prompt_loudness / anchor_euler: the two fp32 orders of
+ * csrc/luxtts_core.h run on the host, for one prompt and for n elements of step `step`. */
+fa_status fa_luxtts_plan(const fa_luxtts_config *cfg, int32_t batch, const int64_t *prompt_samples, const int32_t *prompt_tokens, const int32_t *text_tokens,
+                         const float *speeds, fa_luxtts_item_plan *items, int32_t *bucket_counts, int32_t *bucket_items);
+fa_status fa_luxtts_time_steps(const fa_luxtts_config *cfg, double *out);
+fa_status fa_luxtts_prompt_loudness(const fa_luxtts_config *cfg, const float *pcm, int64_t n, fa_luxtts_record *out);
+fa_status fa_luxtts_anchor_euler(const fa_luxtts_config *cfg, int32_t step, float *x, const float *v, int64_t n);
+/* The session owns the slabs; after creation nothing is allocated and no _dev entry waits for the device. */
+typedef struct fa_luxtts_session fa_luxtts_session;
+fa_status fa_luxtts_session_create(fa_ctx *ctx, const fa_luxtts_config *cfg, int32_t batch, fa_luxtts_session **out);
+void fa_luxtts_session_destroy(fa_luxtts_session *s);
+fa_status fa_luxtts_session_slabs(fa_luxtts_session *s, fa_luxtts_slabs *out);
+/* Plans the batch (as fa_luxtts_plan; items may be NULL) and queues the plan's upload.  Every entry below works on this plan. */
+fa_status fa_luxtts_session_begin(fa_ctx *ctx, fa_luxtts_session *s, const int64_t *prompt_samples, const int32_t *prompt_tokens, const int32_t *text_tokens,
+                                  const float *speeds, fa_luxtts_item_plan *items);
+/* One whole slab (FA_LUXTTS_SLAB_*) into host memory; synchronises the stream. */
+fa_status fa_luxtts_session_get(fa_ctx *ctx, fa_luxtts_session *s, int32_t slab, void *out);
+/* d_* are DEVICE pointers, every other array is a HOST array of batch (offsets: batch + 1) entries.  d_pcm: item b's prompt at
+ * offsets[b], at least the planned sample count long.  d_token_ids int32: item b's prompt + text ids at token_offsets[b].  seeds uint64.
+ * d_embeds / d_v: float [batch][rows][row_stride >= n_mels], item_stride floats apart (rows: tokens + 1 / features_length at least).
+ * vocoder_input: `items` lists n items of one bucket, d_mel float[n][n_mels][bucket].  finish: d_audio float[batch][row_stride],
+ * item b's samples go to d_out + sample_offsets[b] (batch + 1 entries, room for sample_count each). */
+fa_status fa_luxtts_prompt_dev(fa_ctx *ctx, fa_luxtts_session *s, const float *d_pcm, const int64_t *offsets);
+fa_status fa_luxtts_inputs_dev(fa_ctx *ctx, fa_luxtts_session *s, const int32_t *d_token_ids, const int64_t *token_offsets, const uint64_t *seeds);
+fa_status fa_luxtts_text_condition_dev(fa_ctx *ctx, fa_luxtts_session *s, const float *d_embeds, int64_t row_stride, int64_t item_stride);
+fa_status fa_luxtts_step_dev(fa_ctx *ctx, fa_luxtts_session *s, int32_t step, const float *d_v, int64_t row_stride, int64_t item_stride);
+fa_status fa_luxtts_vocoder_input_dev(fa_ctx *ctx, fa_luxtts_session *s, int32_t bucket, const int32_t *items, int32_t n, float *d_mel);
+fa_status fa_luxtts_finish_dev(fa_ctx *ctx, fa_luxtts_session *s, const float *d_audio, int64_t row_stride, const int64_t *sample_offsets, float *d_out);
+/* The same with host pointers: upload, run, fetch (mel, out), one synchronisation each. */
+fa_status fa_luxtts_prompt(fa_ctx *ctx, fa_luxtts_session *s, const float *pcm, const int64_t *offsets);
+fa_status fa_luxtts_inputs(fa_ctx *ctx, fa_luxtts_session *s, const int32_t *token_ids, const int64_t *token_offsets, const uint64_t *seeds);
+fa_status fa_luxtts_text_condition(fa_ctx *ctx, fa_luxtts_session *s, const float *embeds, int64_t row_stride, int64_t item_stride);
+fa_status fa_luxtts_step(fa_ctx *ctx, fa_luxtts_session *s, int32_t step, const float *v, int64_t row_stride, int64_t item_stride);
+fa_status fa_luxtts_vocoder_input(fa_ctx *ctx, fa_luxtts_session *s, int32_t bucket, const int32_t *items, int32_t n, float *mel);
+fa_status fa_luxtts_finish(fa_ctx *ctx, fa_luxtts_session *s, const float *audio, int64_t row_stride, const int64_t *sample_offsets, float *out);
+
 /* ------------------------------------------------------------------ argmax / CTC ---- */
 /* Replaces LogitsArgmax.argmaxPerFrame (FluidAudio/ASR/Shared/LogitsArgmax.swift:16-55) and the
  * greedy collapse of ctcGreedyDecode (FluidAudio/ASR/Parakeet/SlidingWindow/CTC/CtcDecoder.swift:15-36,
