@@ -11,6 +11,8 @@ import numpy as np
 
 from . import _lib as L
 
+AHC_STARTUP_INFO_DTYPE = np.dtype(L.AhcStartupInfo)
+
 
 def linkage(data, mode: int = L.AHC_MODE_AUTO, ctx: L.Context | None = None, return_stats: bool = False):
     """Centroid-linkage dendrogram (SciPy format, merge order) of row-major fp64 `data` [N, d].
@@ -46,6 +48,30 @@ def linkage_batch(problems, mode: int = L.AHC_MODE_AUTO, ctx: L.Context | None =
     L.lib().fa_ahc_linkage_batch(ctx.handle, k, dp, ns, d, zp, mode, 0, stats, st)
     out = ([int(v) for v in st], zs)
     return out + ([s.as_dict() for s in stats],) if return_stats else out
+
+
+def debug_startup(data, mode: int = L.AHC_MODE_AUTO, route: int = 0, ctx: L.Context | None = None, capacity: int | None = None) -> dict:
+    """What the start-up of a linkage problem leaves on the device, and no round behind it (fa_debug_ahc_startup, a test hook: the process
+    needs FLUIDAUDIO_HIP_DEBUG_HOOKS=1).  route 0: the start-up of the filter-based rounds in `mode`; route 1: norms and the Gram-form
+    matrix as the matrix-filtered reference-order run builds them.  Returns slots, dmax, nmax, eps, nan_flag and the arrays M [slots, slots],
+    norms, node, d1, nn, nnnode, e2 [slots]; an array the route does not produce comes back None.  capacity: slots the arrays are sized for
+    (default: what the problem needs; a smaller one is refused by the library)."""
+    ctx = ctx or L.default_context()
+    x = np.ascontiguousarray(data, np.float64)
+    n, d = x.shape
+    f, info = L.lib().fa_debug_ahc_startup, L.AhcStartupInfo()
+    if capacity is None:   # the library names the slots in the refusal of an empty capacity
+        st = f(ctx.handle, x.ctypes.data, n, d, mode, route, C.byref(info), 0, *[None] * 7)
+        if st != L.OUTPUT_TOO_SMALL:
+            raise L.FluidAudioHipError(st, "fa_debug_ahc_startup", ctx.last_error())
+        capacity = info.slots
+    a = {"M": np.zeros((capacity, capacity)), "norms": np.zeros(capacity), "node": np.zeros(capacity, np.int32), "d1": np.zeros(capacity),
+         "nn": np.zeros(capacity, np.int32), "nnnode": np.zeros(capacity, np.int32), "e2": np.zeros(capacity)}
+    ctx.check(f(ctx.handle, x.ctypes.data, n, d, mode, route, C.byref(info), capacity, *(v.ctypes.data for v in a.values())), "fa_debug_ahc_startup")
+    s = info.slots
+    has = {"norms": mode == L.AHC_MODE_AUTO, "d1": route == 0, "nn": route == 0, "nnnode": route == 0, "e2": route == 0}
+    out = {k: (v.reshape(-1)[:s * s].reshape(s, s) if k == "M" else v[:s]) if has.get(k, True) else None for k, v in a.items()}
+    return dict(slots=s, dmax=info.dmax, nmax=info.nmax, eps=info.eps, nan_flag=info.nan_flag, **out)
 
 
 def fastcluster_compute_centroid_linkage(data) -> tuple[int, np.ndarray]:

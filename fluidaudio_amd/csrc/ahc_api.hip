@@ -69,6 +69,21 @@ fa_status fa_ahc_linkage(fa_ctx *ctx, const double *data, size_t n, size_t d, do
     }
 }
 
+// Test hook (its siblings live in ctx.hip; this one calls into the linkage's host units, which ctx.hip must not need: it is also linked on its own).
+fa_status fa_debug_ahc_startup(fa_ctx *ctx, const double *data, size_t n, size_t d, int32_t mode, int32_t route, fa_ahc_startup_info *info, size_t capacity,
+                               double *m, double *norms, int32_t *node, double *d1, int32_t *nn, int32_t *nnnode, double *e2) {
+    if (!ctx || !data || !info) return FA_INVALID_ARGUMENT;
+    if (!fa_debug_hooks_enabled()) return FA_RUNTIME_ERROR;
+    *info = fa_ahc_startup_info{};
+    if (n < 2 || d == 0 || n > static_cast<size_t>(INT32_MAX) || d > static_cast<size_t>(INT32_MAX) || (route != 0 && route != 1) ||
+        (mode != FA_AHC_MODE_AUTO && !(mode == FA_AHC_MODE_EXACT && route == 0)))
+        return fa::set_error(ctx, FA_INVALID_ARGUMENT, "fa_debug_ahc_startup: n >= 2, d >= 1, route 0 (AUTO or EXACT) or route 1 (AUTO)");
+    return fa::no_throw(ctx, "fa_debug_ahc_startup", [&]() -> fa_status {
+        fa::DeviceGuard guard(ctx->device);
+        return fa::ahc_debug_startup(ctx, data, n, d, mode, route, info, capacity, m, norms, node, d1, nn, nnnode, e2);
+    });
+}
+
 // `count` independent linkage problems (recordings) of dimension d in one call: their serial merge chains advance together
 // (one launch = one round of every unfinished problem).  data[k]: n[k] x d row-major, dendrograms[k]: (n[k] - 1) x 4 — HOST
 // pointers unless device_pointers != 0 (the two pointer ARRAYS are always host arrays).  statuses[k] (nullable) carries the

@@ -540,6 +540,57 @@ RomLayout rom_layout(size_t N, size_t Np, size_t d) {
 
 size_t rom_total_bytes(size_t N, size_t Np, size_t d) { return rom_layout(N, Np, d).total; }
 
+// The run's views of its workspace at `base`: its own arrays, the one the kernels shared with the matrix-free run see, the one the Gram-form start-up sees.
+struct RomViews { RomWs w; RoWs rw; Ws gw; double *d_norms; };
+static RomViews rom_bind(char *base, const RomLayout &L, const size_t N, const size_t Np, const size_t d) {
+    const size_t nblk = Np / kBlk;
+    RomWs w{};
+    w.dev = reinterpret_cast<RomDev *>(base + L.dev); w.flags = reinterpret_cast<int32_t *>(base + L.flags);
+    w.part = reinterpret_cast<RomPart *>(base + L.part); w.part2 = reinterpret_cast<double *>(base + L.part2);
+    w.prof = reinterpret_cast<unsigned long long *>(base + L.prof);
+    w.node = reinterpret_cast<int32_t *>(base + L.node); w.slot_of = reinterpret_cast<int32_t *>(base + L.slot); w.sizes = reinterpret_cast<double *>(base + L.sizes);
+    w.ent = reinterpret_cast<fa_ro::Ent *>(base + L.ent); w.pos = reinterpret_cast<int32_t *>(base + L.pos);
+    w.nghbr = reinterpret_cast<int32_t *>(base + L.ngh); w.next = reinterpret_cast<int32_t *>(base + L.next); w.prev = reinterpret_cast<int32_t *>(base + L.prev);
+    w.pair_a = reinterpret_cast<double *>(base + L.pa); w.pair_b = reinterpret_cast<double *>(base + L.pb); w.height_sq = reinterpret_cast<double *>(base + L.hs);
+    w.C = reinterpret_cast<double *>(base + L.c); w.XT = reinterpret_cast<double *>(base + L.xt); w.M = reinterpret_cast<double *>(base + L.m);
+    w.N = static_cast<int32_t>(N); w.Np = static_cast<int32_t>(Np); w.d = static_cast<int32_t>(d); w.nblk = static_cast<int32_t>(nblk);
+    RoWs rw{};   // the kernels shared with the matrix-free run (ro_init, ro_finish) see their own view of the same arrays
+    rw.C = w.C; rw.XT = w.XT; rw.sizes = w.sizes; rw.key = reinterpret_cast<double *>(base + L.key); rw.pair_a = w.pair_a; rw.pair_b = w.pair_b; rw.height_sq = w.height_sq;
+    rw.Z = reinterpret_cast<double *>(base + L.z); rw.node = w.node; rw.slot_of = w.slot_of; rw.nghbr = w.nghbr; rw.flags = w.flags;
+    rw.N = w.N; rw.Np = w.Np; rw.d = w.d; rw.nblk = w.nblk;
+    Ws gw{};     // ... and the Gram-form start-up of the filter-based rounds its own (its non-finite flag lands in flags[2])
+    gw.state = reinterpret_cast<AhcState *>(base + L.state); gw.flags = w.flags + 2; gw.node = w.node; gw.XT = w.XT; gw.M = w.M; gw.C = w.C;
+    gw.N = w.N; gw.Np = w.Np; gw.d = w.d; gw.nblk = w.nblk;
+    double *d_norms = reinterpret_cast<double *>(base + L.norms);
+    return RomViews{w, rw, gw, d_norms};
+}
+
+// The start-up up to the Gram-form matrix of all pairs (rom_run_device; fa_debug_ahc_startup stops behind it): cleared records and flags, the points, node ids
+// and sizes, transpose, norms, matrix.
+static fa_status rom_start_matrix(fa_ctx *ctx, hipStream_t st, char *base, const RomLayout &L, const RomViews &v, const double *d_data, const size_t N, const size_t Np,
+                                  const size_t d, const bool matrix_ready) {
+    FA_HIP_TRY(ctx, hipMemsetAsync(base + L.dev, 0, L.part - L.dev, st));              // RomDev, the profile counters
+    FA_HIP_TRY(ctx, hipMemsetAsync(base + L.flags, 0, 16, st));
+    // matrix_ready (AUTO's attempt halted before its first merge, in these very arrays): points, transpose, norms, Gram-form matrix and the start-up's maxima
+    // (the cold part of state[0], which the rounds never write) are what this start-up would compute again — 10.6 of its 14 ms at 43 200 x 256
+    if (!matrix_ready) {
+        FA_HIP_TRY(ctx, hipMemsetAsync(base + L.state, 0, sizeof(AhcState) * 2, st));  // the two state records (the start-up's maxima start at 0)
+        FA_HIP_TRY(ctx, hipMemcpyAsync(v.w.C, d_data, sizeof(double) * N * d, hipMemcpyDeviceToDevice, st));
+    }
+    ro_launch_init(st, v.rw, std::max(Np, 2 * N));
+    if (!matrix_ready) startup_transpose(st, d_data, v.w.XT, v.w.N, v.w.Np, v.w.d);
+    if (!matrix_ready) FA_TRY(startup_gram(ctx, st, v.gw, v.d_norms));
+    return FA_SUCCESS;
+}
+
+fa_status rom_debug_startup(fa_ctx *ctx, char *base, const double *d_data, size_t N, size_t Np, size_t d, Ws &view, const double *&d_norms) {
+    const RomLayout L = rom_layout(N, Np, d);
+    const RomViews v = rom_bind(base, L, N, Np, d);
+    FA_TRY(rom_start_matrix(ctx, ctx->stream, base, L, v, d_data, N, Np, d, /* matrix_ready = */ false));
+    view = v.gw; d_norms = v.d_norms;
+    return FA_SUCCESS;
+}
+
 // The whole problem in the reference's selection order with the matrix as the filter of its scans.  `declined` (no error recorded): the matrix cannot be
 // had, or the Gram-form start-up met a non-finite entry (infinite coordinates: the sums of the matrix-free run decide what they mean) — the caller runs
 // the matrix-free form instead.
@@ -595,40 +646,16 @@ fa_status rom_run_device(fa_ctx *ctx, const double *d_data, size_t N, size_t d, 
     const RomLayout L = rom_layout(N, Np, d);
     if (fa::ws_acquire(ctx, L.total) != FA_SUCCESS) { ctx->last_error.clear(); return FA_SUCCESS; }
     char *base = static_cast<char *>(ctx->ahc_ws);
-    RomWs w{};
-    w.dev = reinterpret_cast<RomDev *>(base + L.dev); w.flags = reinterpret_cast<int32_t *>(base + L.flags);
-    w.part = reinterpret_cast<RomPart *>(base + L.part); w.part2 = reinterpret_cast<double *>(base + L.part2);
-    w.prof = reinterpret_cast<unsigned long long *>(base + L.prof);
-    w.node = reinterpret_cast<int32_t *>(base + L.node); w.slot_of = reinterpret_cast<int32_t *>(base + L.slot); w.sizes = reinterpret_cast<double *>(base + L.sizes);
-    w.ent = reinterpret_cast<fa_ro::Ent *>(base + L.ent); w.pos = reinterpret_cast<int32_t *>(base + L.pos);
-    w.nghbr = reinterpret_cast<int32_t *>(base + L.ngh); w.next = reinterpret_cast<int32_t *>(base + L.next); w.prev = reinterpret_cast<int32_t *>(base + L.prev);
-    w.pair_a = reinterpret_cast<double *>(base + L.pa); w.pair_b = reinterpret_cast<double *>(base + L.pb); w.height_sq = reinterpret_cast<double *>(base + L.hs);
-    w.C = reinterpret_cast<double *>(base + L.c); w.XT = reinterpret_cast<double *>(base + L.xt); w.M = reinterpret_cast<double *>(base + L.m);
-    w.N = static_cast<int32_t>(N); w.Np = static_cast<int32_t>(Np); w.d = static_cast<int32_t>(d); w.nblk = static_cast<int32_t>(nblk);
-    RoWs rw{};   // the kernels shared with the matrix-free run (ro_init, ro_finish) see their own view of the same arrays
-    rw.C = w.C; rw.XT = w.XT; rw.sizes = w.sizes; rw.key = reinterpret_cast<double *>(base + L.key); rw.pair_a = w.pair_a; rw.pair_b = w.pair_b; rw.height_sq = w.height_sq;
-    rw.Z = reinterpret_cast<double *>(base + L.z); rw.node = w.node; rw.slot_of = w.slot_of; rw.nghbr = w.nghbr; rw.flags = w.flags;
-    rw.N = w.N; rw.Np = w.Np; rw.d = w.d; rw.nblk = w.nblk;
-    Ws gw{};     // ... and the Gram-form start-up of the filter-based rounds its own (its non-finite flag lands in flags[2])
-    gw.state = reinterpret_cast<AhcState *>(base + L.state); gw.flags = w.flags + 2; gw.node = w.node; gw.XT = w.XT; gw.M = w.M; gw.C = w.C;
-    gw.N = w.N; gw.Np = w.Np; gw.d = w.d; gw.nblk = w.nblk;
-    double *d_norms = reinterpret_cast<double *>(base + L.norms);
+    const RomViews v = rom_bind(base, L, N, Np, d);
+    const RomWs w = v.w;
+    const RoWs rw = v.rw;
+    const Ws gw = v.gw;   // (its non-finite flag lands in flags[2])
     hipStream_t st = ctx->stream;
     hipEvent_t ev[3];
     FA_TRY(ctx_events(ctx, ev));                // the context's own three events (created once, destroyed with the context)
     FA_HIP_TRY(ctx, hipEventRecord(ev[0], st));
     // ---- start-up: the reference's nearest lower-indexed neighbours (exact sums), and the Gram-form matrix of all pairs
-    FA_HIP_TRY(ctx, hipMemsetAsync(base + L.dev, 0, L.part - L.dev, st));              // RomDev, the profile counters
-    FA_HIP_TRY(ctx, hipMemsetAsync(base + L.flags, 0, 16, st));
-    // matrix_ready (AUTO's attempt halted before its first merge, in these very arrays): points, transpose, norms, Gram-form matrix and the start-up's maxima
-    // (the cold part of state[0], which the rounds never write) are what this start-up would compute again — 10.6 of its 14 ms at 43 200 x 256
-    if (!matrix_ready) {
-        FA_HIP_TRY(ctx, hipMemsetAsync(base + L.state, 0, sizeof(AhcState) * 2, st));  // the two state records (the start-up's maxima start at 0)
-        FA_HIP_TRY(ctx, hipMemcpyAsync(w.C, d_data, sizeof(double) * N * d, hipMemcpyDeviceToDevice, st));
-    }
-    ro_launch_init(st, rw, std::max(Np, 2 * N));
-    if (!matrix_ready) startup_transpose(st, d_data, w.XT, w.N, w.Np, w.d);
-    if (!matrix_ready) FA_TRY(startup_gram(ctx, st, gw, d_norms));
+    FA_TRY(rom_start_matrix(ctx, st, base, L, v, d_data, N, Np, d, matrix_ready));
     hipLaunchKernelGGL(rom_lower_minima, dim3(static_cast<unsigned>(N - 1)), dim3(kBlk), 0, st, w, gw.state, rw.key);
     FA_HIP_TRY(ctx, hipGetLastError());
     // ---- the heap over points 1 .. N-1, the list, the first pair: host (the selection logic is the same header on both sides)

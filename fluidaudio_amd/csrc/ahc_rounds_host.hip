@@ -41,7 +41,8 @@ void prob_bind(Prob &p, char *base) {
     w.N = static_cast<int32_t>(N); w.Np = static_cast<int32_t>(Np); w.d = static_cast<int32_t>(d); w.nblk = static_cast<int32_t>(Np / (static_cast<size_t>(kBlk) * p.cpt));
 }
 
-fa_status prob_setup(fa_ctx *ctx, Prob &p, char *base) {
+// prob_bind, the points, the start-up kernels: everything of prob_setup that tests/test_gpu_ahc_startup.py looks at through fa_debug_ahc_startup
+fa_status prob_startup(fa_ctx *ctx, Prob &p, char *base) {
     prob_bind(p, base);
     const size_t N = p.N, d = p.d, Np = p.Np;
     const Layout &L = p.L;
@@ -49,6 +50,12 @@ fa_status prob_setup(fa_ctx *ctx, Prob &p, char *base) {
     const int dev_mode = p.mode == FA_AHC_MODE_EXACT ? FA_AHC_MODE_EXACT : FA_AHC_MODE_AUTO;
     FA_HIP_TRY(ctx, hipMemcpyAsync(w.C, p.d_data, sizeof(double) * N * d, hipMemcpyDeviceToDevice, ctx->stream));
     startup_filter(ctx->stream, w, L, base, dev_mode, p.d_data, N, Np, d);   // ahc_startup.hip: state, rows, transpose, matrix, row minima, eps
+    return FA_SUCCESS;
+}
+
+fa_status prob_setup(fa_ctx *ctx, Prob &p, char *base) {
+    FA_TRY(prob_startup(ctx, p, base));
+    const Ws &w = p.w;
     launch_records(ctx->stream, p.cpt, w);   // window counts need eps
     FA_HIP_TRY(ctx, hipGetLastError());
     FA_HIP_TRY(ctx, hipMemsetAsync(spec_of(w.state), 0, sizeof(AhcSpec), ctx->stream));   // no merge speculated yet: the first round takes the one-merge path
@@ -233,5 +240,57 @@ fa_status fa::ahc_run_device(fa_ctx *ctx, const double *d_data, size_t N, size_t
         fprintf(stderr, "ahc: N %zu rounds %lld merges %d speculated merges committed %lld forced re-scans %lld piggy-backed re-scans %lld windows %lld fallback %lld (kPiggy %d)\n",
                 N, p.h.rounds, p.h.step, p.spec_hits, p.h.rescans, p.h.piggy, p.h.windows, p.fallback, kPiggy);
     if (stats) stats_fill(*stats, p, intervals_of(ev));
+    return FA_SUCCESS;
+}
+
+// fa_debug_ahc_startup: the workspace prob_setup takes (one slot per thread), the points, the start-up kernels — and no round.  Route 0 is prob_startup itself,
+// route 1 the start of the matrix-filtered reference-order run (ahc_rom.hip); what they left is copied out behind ONE synchronisation.
+fa_status fa::ahc_debug_startup(fa_ctx *ctx, const double *data, size_t N, size_t d, int mode, int route, fa_ahc_startup_info *info, size_t capacity, double *m,
+                                double *norms, int32_t *node, double *d1, int32_t *nn, int32_t *nnnode, double *e2) {
+    Prob p;
+    p.cpt = 1;
+    p.N = N; p.d = d; p.Np = route::padded(N, p.cpt); p.mode = mode;
+    const size_t Np = p.Np;
+    info->slots = static_cast<int64_t>(Np);
+    if (Np > 2048) return fa::set_error(ctx, FA_INVALID_ARGUMENT, "fa_debug_ahc_startup: %zu slots, at most 2048 are copied out", Np);
+    if (capacity < Np) return fa::set_error(ctx, FA_OUTPUT_TOO_SMALL, "fa_debug_ahc_startup: %zu slots, the arrays hold %zu", Np, capacity);
+    FA_TRY(prob_check_shape(ctx, N, d));
+    p.L = make_layout(N, Np, d, route::blocks(N, p.cpt));
+    fa::WsUse ws_use(ctx);
+    FA_TRY(fa::ws_acquire(ctx, p.L.total));
+    FA_TRY(fa::ensure_scratch(ctx, sizeof(double) * N * d));   // the points staged as fa_ahc_linkage stages them
+    FA_HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch, data, sizeof(double) * N * d, hipMemcpyHostToDevice, ctx->stream));
+    p.d_data = static_cast<const double *>(ctx->scratch);
+    char *base = static_cast<char *>(ctx->ahc_ws);
+    Ws view{};                   // where the route's kernels wrote; row / e2 stay null on the route without minima
+    const double *d_norms = nullptr;
+    if (route == 0) {
+        FA_TRY(prob_startup(ctx, p, base));
+        view = p.w;
+        if (mode == FA_AHC_MODE_AUTO) d_norms = reinterpret_cast<const double *>(base + p.L.norms);
+    } else
+        FA_TRY(rom_debug_startup(ctx, base, p.d_data, N, Np, d, view, d_norms));
+    FA_HIP_TRY(ctx, hipGetLastError());
+    hipStream_t st = ctx->stream;
+    AhcState hstate{};
+    int32_t hflag = 0;
+    std::vector<RowSt> rows(view.row ? Np : 0);
+    FA_HIP_TRY(ctx, hipMemcpyAsync(&hstate, view.state, sizeof(hstate), hipMemcpyDeviceToHost, st));
+    FA_HIP_TRY(ctx, hipMemcpyAsync(&hflag, view.flags, sizeof(hflag), hipMemcpyDeviceToHost, st));
+    if (m) FA_HIP_TRY(ctx, hipMemcpyAsync(m, view.M, sizeof(double) * Np * Np, hipMemcpyDeviceToHost, st));
+    if (norms && d_norms) FA_HIP_TRY(ctx, hipMemcpyAsync(norms, d_norms, sizeof(double) * Np, hipMemcpyDeviceToHost, st));
+    if (node) FA_HIP_TRY(ctx, hipMemcpyAsync(node, view.node, sizeof(int32_t) * Np, hipMemcpyDeviceToHost, st));
+    if (view.row) FA_HIP_TRY(ctx, hipMemcpyAsync(rows.data(), view.row, sizeof(RowSt) * Np, hipMemcpyDeviceToHost, st));
+    if (e2 && view.e2) FA_HIP_TRY(ctx, hipMemcpyAsync(e2, view.e2, sizeof(double) * Np, hipMemcpyDeviceToHost, st));
+    FA_HIP_TRY(ctx, hipStreamSynchronize(st));
+    for (size_t i = 0; i < rows.size(); ++i) {
+        if (d1) d1[i] = rows[i].d1;
+        if (nn) nn[i] = rows[i].nn;
+        if (nnnode) nnnode[i] = rows[i].nnnode;
+    }
+    info->dmax = __builtin_bit_cast(double, hstate.dmax_bits);
+    info->nmax = __builtin_bit_cast(double, hstate.nmax_bits);
+    info->eps = hstate.eps;
+    info->nan_flag = hflag;
     return FA_SUCCESS;
 }

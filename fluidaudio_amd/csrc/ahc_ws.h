@@ -329,7 +329,8 @@ fa_status startup_gram(fa_ctx *ctx, hipStream_t st, const Ws &gw, double *d_norm
 void window_counter_init(WinCounters (&c)[4]);
 fa_status prob_check_shape(fa_ctx *ctx, size_t N, size_t d);
 void prob_bind(Prob &p, char *base);                      // p.w = the arrays of p.L at `base` (no device work)
-fa_status prob_setup(fa_ctx *ctx, Prob &p, char *base);   // prob_bind + the start-up kernels
+fa_status prob_startup(fa_ctx *ctx, Prob &p, char *base); // prob_bind + the points + the start-up kernels (startup_filter)
+fa_status prob_setup(fa_ctx *ctx, Prob &p, char *base);   // prob_startup + the block records and an empty speculation record
 // The rounds of a problem whose workspace is bound and whose device state is ready (prob_setup, or prob_adopt): replays of the round graph until the device
 // reports the end or halts, then the exact heights and the dendrogram to p.d_Z — unless p.needs_ro (an exact tie: the caller recomputes in reference order).
 fa_status prob_run_rounds(fa_ctx *ctx, Prob &p);
@@ -348,6 +349,9 @@ fa_status ro_run_device_mf(fa_ctx *ctx, const double *d_data, size_t N, size_t d
 fa_status ro_run_device(fa_ctx *ctx, const double *d_data, size_t N, size_t d, double *d_Z, fa_ahc_stats *stats, bool z_on_host = false, bool may_hand_over = false,
                         bool matrix_ready = false);
 size_t rom_total_bytes(size_t N, size_t Np, size_t d);   // workspace of the matrix-filtered reference-order run
+// fa_debug_ahc_startup, route 1: the start-up of the matrix-filtered reference-order run up to its Gram-form matrix, enqueued on the context's stream in the
+// workspace at `base`; view / d_norms: where it wrote (state, flags, node, M of a Ws; the norms)
+fa_status rom_debug_startup(fa_ctx *ctx, char *base, const double *d_data, size_t N, size_t Np, size_t d, Ws &view, const double *&d_norms);
 void ro_launch_init(hipStream_t st, const RoWs &w, size_t threads);
 void ro_launch_finish(hipStream_t st, const RoWs &w);
 // ahc_batch_host.hip: ahc_route.h's answers under the process's switches

@@ -236,6 +236,9 @@ struct WsUse {   // scope of one linkage call
 // d_Z: device pointer, or (z_on_host) the caller's host buffer the dendrogram is copied to directly
 fa_status ahc_run_device(fa_ctx *ctx, const double *d_data, size_t N, size_t d, double *d_Z, int mode, fa_ahc_stats *stats, bool z_on_host = false);   // ahc.hip
 fa_status ahc_normalize_dev(fa_ctx *ctx, const double *d_x, double *d_out, int64_t n, int32_t d);                              // ahc.hip (:70-105)
+// test hook (fa_debug_ahc_startup): the start-up of one problem and nothing behind it; HOST points in, HOST arrays out (ahc_rounds_host.hip; route 1: ahc_rom.hip)
+fa_status ahc_debug_startup(fa_ctx *ctx, const double *data, size_t N, size_t d, int mode, int route, fa_ahc_startup_info *info, size_t capacity, double *m,
+                            double *norms, int32_t *node, double *d1, int32_t *nn, int32_t *nnnode, double *e2);
 // count independent problems advanced by the same round launches; d_data / d_Z: HOST arrays of device pointers; statuses, stats: per problem (nullable)
 fa_status ahc_run_device_batch(fa_ctx *ctx, int count, const double *const *d_data, const size_t *n, size_t d, double *const *d_Z, int mode,
                                fa_ahc_stats *stats, fa_status *statuses);

@@ -121,6 +121,25 @@ fa_status fa_debug_ahc_adopted(const fa_ctx *ctx, int64_t *row, int32_t *kind, d
  * launch that merges a pair also evaluates the merge most likely to follow; the next launch commits it when its records certify exactly that merge).
  * 0 when the run used the one-merge round, -1 when nothing was recorded.  RUNTIME_ERROR without FLUIDAUDIO_HIP_DEBUG_HOOKS=1. */
 fa_status fa_debug_ahc_spec_hits(const fa_ctx *ctx, int64_t *hits);
+/* Test hook: the start-up of a linkage problem and nothing behind it — no round is launched.  data: HOST, n x d row-major, n >= 2.  The workspace is the
+ * one a linkage call takes for the problem (one slot per thread: slots = n rounded up to the round's block of 256), the points are copied and
+ *   route 0: the start-up of the filter-based rounds runs as a linkage call of `mode` (FA_AHC_MODE_AUTO or FA_AHC_MODE_EXACT) runs it: initial state and
+ *            rows, transpose, the matrix (AUTO: Gram form, EXACT: the reference's sequential sums), row minima, eps;
+ *   route 1: the start of the matrix-filtered reference-order run: norms and the Gram-form matrix, no row minima (mode must be FA_AHC_MODE_AUTO).
+ * One synchronisation, then everything is copied out.  info: slots, the start-up's maxima (dmax: largest finite matrix entry, nmax: largest squared norm;
+ * 0 when the route does not compute one), eps as the device computed it (route 1: 0 — that run derives its own on the host) and nan_flag, the flag the
+ * start-up kernels raise when a live entry is NaN.  The arrays (each nullable) hold `capacity` slots, m capacity * capacity doubles; they are written as
+ * [slots] and [slots][slots]: m (the matrix, +inf on the diagonal and at empty slots), norms (route 0 AUTO and route 1; negative: empty slot), node
+ * (INT32_MAX: empty slot) and — route 0 only — the row record (d1, nn, nnnode) and e2 as in fa_debug_ahc_adopted.  An array its route does not produce
+ * is left untouched.  INVALID_ARGUMENT: a NULL ctx / data / info, n < 2, d == 0, another mode or route, or more than 2048 slots (the copy stays within
+ * 32 MB; info->slots is set); OUTPUT_TOO_SMALL: capacity < slots (info->slots is set).  RUNTIME_ERROR without FLUIDAUDIO_HIP_DEBUG_HOOKS=1. */
+typedef struct fa_ahc_startup_info {
+    int64_t slots;
+    double dmax, nmax, eps;
+    int32_t nan_flag, reserved;
+} fa_ahc_startup_info;
+fa_status fa_debug_ahc_startup(fa_ctx *ctx, const double *data, size_t n, size_t d, int32_t mode, int32_t route, fa_ahc_startup_info *info, size_t capacity,
+                               double *m, double *norms, int32_t *node, double *d1, int32_t *nn, int32_t *nnnode, double *e2);
 /* Test hook: the next `count` passes through `site` fail the way the real failure would (count 0 disarms).  Process-wide; one relaxed
  * atomic load on the paths that carry a site.  Inert unless the process was started with FLUIDAUDIO_HIP_DEBUG_HOOKS=1.  Used by the
  * fault-injection tests of the degrade contracts:

@@ -29,6 +29,7 @@ RECORDS = {
     ("online", "SPEAKER_ASSIGNMENT_DTYPE", "SpeakerAssignment"): (16, [("id", "<i4", 0), ("slot", "<i4", 4), ("kind", "<i4", 8), ("distance", "<f4", 12)]),
     ("online", "SPEAKER_PAIR_DTYPE", "SpeakerPair"): (20, [("source_id", "<i4", 0), ("destination_id", "<i4", 4), ("source_slot", "<i4", 8), ("destination_slot", "<i4", 12), ("distance", "<f4", 16)]),
     ("online", "ONLINE_RUN_DTYPE", "OnlineRun"): (12, [("stream", "<i4", 0), ("chunk", "<i4", 4), ("local_speaker", "<i4", 8)]),
+    ("ahc", "AHC_STARTUP_INFO_DTYPE", "AhcStartupInfo"): (40, [("slots", "<i8", 0), ("dmax", "<f8", 8), ("nmax", "<f8", 16), ("eps", "<f8", 24), ("nan_flag", "<i4", 32), ("reserved", "<i4", 36)]),
     ("online", "ONLINE_SEGMENT_DTYPE", "OnlineSegment"): (36, [("stream", "<i4", 0), ("chunk", "<i4", 4), ("local_speaker", "<i4", 8), ("id", "<i4", 12), ("start_frame", "<i4", 16), ("end_frame", "<i4", 20), ("start", "<f4", 24), ("end", "<f4", 28), ("quality", "<f4", 32)]),
 }
 # the names the package exports at its top level
