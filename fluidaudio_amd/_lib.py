@@ -95,6 +95,10 @@ EXPORTED_SYMBOLS = [
     "fa_luxtts_session_destroy", "fa_luxtts_session_slabs", "fa_luxtts_session_begin", "fa_luxtts_session_get", "fa_luxtts_prompt_dev", "fa_luxtts_inputs_dev",
     "fa_luxtts_text_condition_dev", "fa_luxtts_step_dev", "fa_luxtts_vocoder_input_dev", "fa_luxtts_finish_dev", "fa_luxtts_prompt", "fa_luxtts_inputs",
     "fa_luxtts_text_condition", "fa_luxtts_step", "fa_luxtts_vocoder_input", "fa_luxtts_finish",
+    "fa_styletts2_default_config", "fa_styletts2_plan", "fa_styletts2_karras_sigmas", "fa_styletts2_window", "fa_styletts2_filterbank", "fa_styletts2_session_create",
+    "fa_styletts2_session_destroy", "fa_styletts2_session_slabs", "fa_styletts2_session_begin", "fa_styletts2_session_get", "fa_styletts2_reference_mel_dev",
+    "fa_styletts2_inputs_dev", "fa_styletts2_blend_dev", "fa_styletts2_durations_dev", "fa_styletts2_align_dev", "fa_styletts2_finish_dev", "fa_styletts2_reference_mel",
+    "fa_styletts2_inputs", "fa_styletts2_blend", "fa_styletts2_durations", "fa_styletts2_align", "fa_styletts2_finish",
 ]
 
 
@@ -152,6 +156,21 @@ class LuxTtsRecord(C.Structure):                                       # fa_luxt
 
 class LuxTtsSlabs(C.Structure):                                        # fa_luxtts_slabs: device addresses
     _fields_ = [(name, C.c_void_p) for name in ("tokens", "token_mask", "text_condition", "speech_condition", "x", "frame_mask", "records")]
+
+
+class StyleTts2Config(C.Structure):                                    # fa_styletts2_config
+    _fields_ = [("sigma_min", C.c_double), ("sigma_max", C.c_double), ("rho", C.c_double), ("n_fft", C.c_int32), ("win", C.c_int32), ("hop", C.c_int32), ("n_mels", C.c_int32),
+                ("filter_rate", C.c_int32), ("max_ref_frames", C.c_int32), ("default_tokens", C.c_int32), ("n_buckets", C.c_int32), ("buckets", C.c_int32 * 4),
+                ("style_dim", C.c_int32), ("diffusion_steps", C.c_int32), ("d_channels", C.c_int32), ("asr_channels", C.c_int32), ("max_frames", C.c_int32),
+                ("tail_trim", C.c_int32), ("log_eps", C.c_float), ("log_mean", C.c_float), ("log_std", C.c_float)]
+
+
+class StyleTts2ItemPlan(C.Structure):                                  # fa_styletts2_item_plan
+    _fields_ = [("samples", C.c_int64), ("ref_frames", C.c_int32), ("tokens", C.c_int32), ("bucket", C.c_int32), ("status", C.c_int32)]
+
+
+class StyleTts2Slabs(C.Structure):                                     # fa_styletts2_slabs: device addresses
+    _fields_ = [(name, C.c_void_p) for name in ("mel", "tokens", "attention_mask", "noise_init", "noises_aux", "ref", "s", "durations", "starts", "total_frames", "status")]
 
 
 class TdtConfig(C.Structure):
@@ -566,6 +585,23 @@ def lib() -> C.CDLL:
                        "fa_luxtts_step": [vp, vp, i32, vp, i64, i64], "fa_luxtts_vocoder_input": [vp, vp, i32, vp, i32, vp],
                        "fa_luxtts_finish": [vp, vp, vp, i64, vp, vp]}.items():       # the host-pointer form and its device form take the same list
         getattr(L, name).argtypes = getattr(L, name + "_dev").argtypes = args
+    yc = C.POINTER(StyleTts2Config)
+    L.fa_styletts2_default_config.argtypes = [yc]
+    L.fa_styletts2_default_config.restype = None
+    L.fa_styletts2_plan.argtypes = [yc, i32, vp, vp, vp]
+    L.fa_styletts2_karras_sigmas.argtypes = [yc, i32, vp]
+    L.fa_styletts2_window.argtypes = L.fa_styletts2_filterbank.argtypes = [yc, vp]
+    L.fa_styletts2_session_create.argtypes = [vp, yc, i32, C.POINTER(vp)]
+    L.fa_styletts2_session_destroy.argtypes = [vp]
+    L.fa_styletts2_session_destroy.restype = None
+    L.fa_styletts2_session_slabs.argtypes = [vp, C.POINTER(StyleTts2Slabs)]
+    L.fa_styletts2_session_begin.argtypes = [vp, vp, vp, vp, vp]
+    L.fa_styletts2_session_get.argtypes = [vp, vp, i32, vp]
+    for name, args in {"fa_styletts2_reference_mel": [vp, vp, vp, vp], "fa_styletts2_inputs": [vp, vp, vp, vp, vp], "fa_styletts2_blend": [vp, vp, vp, i64, vp, i64, vp, vp],
+                       "fa_styletts2_durations": [vp, vp, vp, i32, i64, i64, i64, vp, vp], "fa_styletts2_align": [vp, vp, vp, i64, i64, vp, i64, i64, i32, vp, vp, i32]}.items():
+        getattr(L, name).argtypes = getattr(L, name + "_dev").argtypes = args              # the host-pointer form and its device form take the same list
+    L.fa_styletts2_finish.argtypes = [vp, vp, vp, i64, vp, vp, i64, vp]
+    L.fa_styletts2_finish_dev.argtypes = [vp, vp, vp, i64, vp, vp, vp]
     L.fa_ctc_greedy_batch_dev.argtypes = [vp, vp, i32, i32, i32, i32, i64, i64, vp, i32, vp, vp, vp]
     L.fa_ctc_log_softmax_batch_dev.argtypes = [vp, vp, i32, i32, i32, i32, i64, i64, f32, f32, i32, vp]
     L.fa_ctc_greedy_batch.argtypes = [vp, vp, i32, i32, i32, i32, i64, i64, vp, i32, vp, vp, vp]

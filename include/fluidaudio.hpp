@@ -2444,4 +2444,71 @@ class LuxTtsSession {
     fa_luxtts_session *s_ = nullptr;
 };
 
+// The StyleTTS2 session (StyleTTS2Synthesizer.synthesize, StyleTTS2Synthesizer.swift:33-133, between its eight networks): `batch`
+// (reference clip, text) pairs whose mel, BERT inputs, noises, styles and durations stay in HBM.  d* are device pointers, vectors are
+// host data.  Only durations() waits for the device.
+class StyleTts2Session {
+  public:
+    static fa_styletts2_config defaultConfig() { fa_styletts2_config c; fa_styletts2_default_config(&c); return c; }
+    static std::vector<double> karrasSigmas(const fa_styletts2_config &cfg, int32_t steps) {
+        std::vector<double> t(static_cast<size_t>(steps > 0 ? steps : 0) + 1);
+        const fa_status st = fa_styletts2_karras_sigmas(&cfg, steps, t.data());
+        if (st != FA_SUCCESS) throw Error(st, "fa_styletts2_karras_sigmas", "");
+        return t;
+    }
+    StyleTts2Session(Context &ctx, const fa_styletts2_config &cfg, int32_t batch) : ctx_(ctx), batch_(batch) {
+        ctx_.check(fa_styletts2_session_create(ctx_.handle(), &cfg, batch, &s_), "fa_styletts2_session_create");
+    }
+    ~StyleTts2Session() { fa_styletts2_session_destroy(s_); }
+    StyleTts2Session(const StyleTts2Session &) = delete;
+    StyleTts2Session &operator=(const StyleTts2Session &) = delete;
+    fa_styletts2_slabs slabs() const { fa_styletts2_slabs out{}; fa_styletts2_session_slabs(s_, &out); return out; }
+    // one entry per item; the plans say which items were refused and which BERT / sampler bucket the others take
+    std::vector<fa_styletts2_item_plan> begin(const std::vector<int64_t> &samples, const std::vector<int32_t> &tokens) {
+        need(samples.size(), 0, "StyleTts2Session::begin"); need(tokens.size(), 0, "StyleTts2Session::begin");
+        std::vector<fa_styletts2_item_plan> plans(static_cast<size_t>(batch_));
+        ctx_.check(fa_styletts2_session_begin(ctx_.handle(), s_, samples.data(), tokens.data(), plans.data()), "fa_styletts2_session_begin");
+        return plans;
+    }
+    void referenceMel(const float *dPcm, const std::vector<int64_t> &offsets) {
+        need(offsets.size(), 1, "StyleTts2Session::referenceMel");
+        ctx_.check(fa_styletts2_reference_mel_dev(ctx_.handle(), s_, dPcm, offsets.data()), "fa_styletts2_reference_mel_dev");
+    }
+    void inputs(const int32_t *dTokenIds, const std::vector<int64_t> &tokenOffsets, const std::vector<uint64_t> &seeds) {
+        need(tokenOffsets.size(), 1, "StyleTts2Session::inputs"); need(seeds.size(), 0, "StyleTts2Session::inputs");
+        ctx_.check(fa_styletts2_inputs_dev(ctx_.handle(), s_, dTokenIds, tokenOffsets.data(), seeds.data()), "fa_styletts2_inputs_dev");
+    }
+    void blend(const float *dSPred, int64_t sPredStride, const float *dRefS, int64_t refSStride, const std::vector<float> &alphas, const std::vector<float> &betas) {
+        need(alphas.size(), 0, "StyleTts2Session::blend"); need(betas.size(), 0, "StyleTts2Session::blend");
+        ctx_.check(fa_styletts2_blend_dev(ctx_.handle(), s_, dSPred, sPredStride, dRefS, refSStride, alphas.data(), betas.data()), "fa_styletts2_blend_dev");
+    }
+    // the frames of every item (synchronises the stream); statuses receives FA_STYLETTS2_* per item when given
+    std::vector<int32_t> durations(const float *dLogits, int32_t channels, int64_t itemStride, int64_t tokenStride, int64_t channelStride, std::vector<int32_t> *statuses = nullptr) {
+        std::vector<int32_t> totals(static_cast<size_t>(batch_));
+        if (statuses) statuses->resize(static_cast<size_t>(batch_));
+        ctx_.check(fa_styletts2_durations_dev(ctx_.handle(), s_, dLogits, channels, itemStride, tokenStride, channelStride, totals.data(), statuses ? statuses->data() : nullptr),
+                   "fa_styletts2_durations_dev");
+        return totals;
+    }
+    void align(const float *dD, int64_t dRowStride, int64_t dItemStride, const float *dTEn, int64_t tRowStride, int64_t tItemStride, bool shift, float *dEn, float *dAsr,
+               int32_t frameStride) {
+        ctx_.check(fa_styletts2_align_dev(ctx_.handle(), s_, dD, dRowStride, dItemStride, dTEn, tRowStride, tItemStride, shift ? 1 : 0, dEn, dAsr, frameStride), "fa_styletts2_align_dev");
+    }
+    // where item b lies in dOut: [offsets[b], offsets[b + 1])
+    std::vector<int64_t> finish(const float *dAudio, int64_t rowStride, const std::vector<int64_t> &lengths, float *dOut) {
+        need(lengths.size(), 0, "StyleTts2Session::finish");
+        std::vector<int64_t> offsets(static_cast<size_t>(batch_) + 1);
+        ctx_.check(fa_styletts2_finish_dev(ctx_.handle(), s_, dAudio, rowStride, lengths.data(), dOut, offsets.data()), "fa_styletts2_finish_dev");
+        return offsets;
+    }
+
+  private:
+    void need(size_t have, size_t extra, const char *where) const {
+        if (have != static_cast<size_t>(batch_) + extra) throw Error(FA_INVALID_ARGUMENT, where, "one entry per item (offsets: one more)");
+    }
+    Context &ctx_;
+    int32_t batch_;
+    fa_styletts2_session *s_ = nullptr;
+};
+
 }  // namespace fluidaudio

@@ -501,6 +501,117 @@ fa_status fa_luxtts_step(fa_ctx *ctx, fa_luxtts_session *s, int32_t step, const 
 fa_status fa_luxtts_vocoder_input(fa_ctx *ctx, fa_luxtts_session *s, int32_t bucket, const int32_t *items, int32_t n, float *mel);
 fa_status fa_luxtts_finish(fa_ctx *ctx, fa_luxtts_session *s, const float *audio, int64_t row_stride, const int64_t *sample_offsets, float *out);
 
+/* ------------------------------------------------------------------ StyleTTS2 session */
+/* The host arithmetic of StyleTTS2Synthesizer.synthesize (FluidAudio/TTS/StyleTTS2/Pipeline/Synthesize/StyleTTS2Synthesizer.swift,
+ * StyleTTS2GlueOps.swift, Preprocess/StyleTTS2MelExtractor.swift, Sampler/StyleTTS2DiffusionSchedule.swift, StyleTTS2Constants.swift)
+ * between its eight networks, batched over (reference clip, text) pairs on device slabs the networks read in place.  The networks, the
+ * phonemizer, the text cleaner and the chunker stay the caller's.  Order of a batch: fa_styletts2_session_begin (the plan),
+ * fa_styletts2_reference_mel_dev, fa_styletts2_inputs_dev, the encoders and the sampler, fa_styletts2_blend_dev, the duration predictor,
+ * fa_styletts2_durations_dev (the session's one wait), fa_styletts2_align_dev, the decoders, fa_styletts2_finish_dev.
+ *   plan       per item: ref_frames = samples / hop + 1 (MelExtractor :79-84; an empty clip is one frame of the floor value); bucket =
+ *              default_tokens for tokens <= default_tokens, else the first bucket that holds them (Synthesizer :45-53).  Statuses: no
+ *              tokens, tokens beyond the largest bucket (textTooLong), more reference frames than max_ref_frames.  A refused item has its
+ *              status and zeros; later entries write zeros for it.
+ *   mel        mel[b, m, f] = (log(HTK mel of |STFT|^2 + log_eps) - log_mean) / log_std for f < ref_frames, zeros behind, row stride
+ *              max_ref_frames: periodic Hann of `win` centred in n_fft, hop, torch reflect padding with the reference's clamps, the bank
+ *              built in float32 for filter_rate (16 kHz on 24 kHz audio: the reference's documented quirk).  n_fft has to be 2048.
+ *   inputs     tokens zero-padded and attention_mask (1 below the item's token count), both with the largest bucket's stride; per item
+ *              one stream of diffusion_steps * 256 draws of StyleTTS2NoiseSource(seed) (DiffusionSchedule :45-80; seed 0 is
+ *              0xdeadbeefcafebabe): draws 0..255 into noise_init[b], the rest into noises_aux[s, b, :].
+ *   blend      ref[b, i] = a s_pred[i] + (1 - a) ref_s[i], s[b, i] = be s_pred[128 + i] + (1 - be) ref_s[128 + i]: two rounded
+ *              products and one add, no contraction (csrc/styletts2_core.h).
+ *   durations  per token the float32 sum over c ascending of 1 / (1 + expf(-x)), rounded half away from zero, at least 1; starts = the
+ *              exclusive scan, total_frames the sum; an item whose total passes max_frames gets FA_STYLETTS2_TOO_MANY_FRAMES in the
+ *              status slab and no alignment.
+ *   align      en[b, c, f] = d[b, tok(f'), c] and asr[b, c, f] = t_en[b, c, tok(f')], f' = max(f - 1, 0) with the shift on (GlueOps
+ *              :121-134), tok(f) the token whose frames hold f; zeros from total_frames up to frame_stride.  For finite features this
+ *              is the reference's sgemm against the one-hot matrix value for value; a -0.0 feature comes out as -0.0 where BLAS
+ *              gives +0.0, and a non-finite feature is copied to its own frames, not spread over the row.
+ *   finish     the item's vocoder row without its last min(tail_trim, len) samples, the items back to back in their order (the chunks
+ *              of one long text as synthesizeChunked concatenates them). */
+typedef struct {
+    double sigma_min, sigma_max, rho;   /* 0.0001, 3, 9 */
+    int32_t n_fft;               /* 2048 */
+    int32_t win;                 /* 1200 */
+    int32_t hop;                 /* 300 */
+    int32_t n_mels;              /* 80 */
+    int32_t filter_rate;         /* 16000 */
+    int32_t max_ref_frames;      /* 2400 (30 s): the mel slab's row stride, a multiple of 4 */
+    int32_t default_tokens;      /* 57 */
+    int32_t n_buckets;           /* 3 (1..4) */
+    int32_t buckets[4];          /* 64, 128, 256: ascending, at most 256 */
+    int32_t style_dim;           /* 256 */
+    int32_t diffusion_steps;     /* 5 */
+    int32_t d_channels;          /* 640 */
+    int32_t asr_channels;        /* 512 */
+    int32_t max_frames;          /* 4096: the most frames the durations of one item may sum to */
+    int32_t tail_trim;           /* 50 */
+    float log_eps, log_mean, log_std;   /* 1e-5, -4, 4 */
+} fa_styletts2_config;
+enum { FA_STYLETTS2_OK = 0, FA_STYLETTS2_NO_TOKENS = 1, FA_STYLETTS2_TEXT_TOO_LONG = 2, FA_STYLETTS2_CLIP_TOO_LONG = 3,
+       FA_STYLETTS2_TOO_MANY_FRAMES = 4 /* in the status slab only */ };
+typedef struct {
+    int64_t samples;
+    int32_t ref_frames, tokens, bucket, status;
+} fa_styletts2_item_plan;
+typedef struct {                 /* DEVICE pointers, fixed for the session's lifetime; T = the largest bucket */
+    float *mel;                  /* [batch][n_mels][max_ref_frames] */
+    int32_t *tokens;             /* [batch][T] */
+    int32_t *attention_mask;     /* [batch][T] */
+    float *noise_init;           /* [batch][256] */
+    float *noises_aux;           /* [diffusion_steps - 1][batch][256] */
+    float *ref, *s;              /* [batch][128] */
+    int32_t *durations, *starts; /* [batch][T]; starts behind the item's tokens hold its total */
+    int32_t *total_frames;       /* [batch] */
+    int32_t *status;             /* [batch], written by the durations */
+} fa_styletts2_slabs;
+enum { FA_STYLETTS2_SLAB_MEL = 0, FA_STYLETTS2_SLAB_TOKENS = 1, FA_STYLETTS2_SLAB_ATTENTION_MASK = 2, FA_STYLETTS2_SLAB_NOISE_INIT = 3,
+       FA_STYLETTS2_SLAB_NOISES_AUX = 4, FA_STYLETTS2_SLAB_REF = 5, FA_STYLETTS2_SLAB_S = 6, FA_STYLETTS2_SLAB_DURATIONS = 7,
+       FA_STYLETTS2_SLAB_STARTS = 8, FA_STYLETTS2_SLAB_TOTAL_FRAMES = 9, FA_STYLETTS2_SLAB_STATUS = 10 };
+void fa_styletts2_default_config(fa_styletts2_config *cfg);
+/* Pure host functions.  karras_sigmas: the steps + 1 doubles of StyleTTS2DiffusionSchedule.karrasSigmas (steps >= 2).  window: the `win`
+ * non-zero samples of the centred Hann.  filterbank: float[n_mels][n_fft / 2 + 1]. */
+fa_status fa_styletts2_plan(const fa_styletts2_config *cfg, int32_t batch, const int64_t *samples, const int32_t *tokens, fa_styletts2_item_plan *items);
+fa_status fa_styletts2_karras_sigmas(const fa_styletts2_config *cfg, int32_t steps, double *out);
+fa_status fa_styletts2_window(const fa_styletts2_config *cfg, float *out);
+fa_status fa_styletts2_filterbank(const fa_styletts2_config *cfg, float *out);
+/* The session owns the slabs; after creation nothing is allocated, and no _dev entry but the durations waits for the device. */
+typedef struct fa_styletts2_session fa_styletts2_session;
+fa_status fa_styletts2_session_create(fa_ctx *ctx, const fa_styletts2_config *cfg, int32_t batch, fa_styletts2_session **out);
+void fa_styletts2_session_destroy(fa_styletts2_session *s);
+fa_status fa_styletts2_session_slabs(fa_styletts2_session *s, fa_styletts2_slabs *out);
+/* Plans the batch (as fa_styletts2_plan; items may be NULL) and queues the plan's upload.  Every entry below works on this plan. */
+fa_status fa_styletts2_session_begin(fa_ctx *ctx, fa_styletts2_session *s, const int64_t *samples, const int32_t *tokens, fa_styletts2_item_plan *items);
+/* One whole slab (FA_STYLETTS2_SLAB_*) into host memory; synchronises the stream. */
+fa_status fa_styletts2_session_get(fa_ctx *ctx, fa_styletts2_session *s, int32_t slab, void *out);
+/* d_* are DEVICE pointers, every other array is a HOST array of batch (offsets: batch + 1) entries.  d_pcm: item b's clip at offsets[b].
+ * d_token_ids int32: item b's ids at token_offsets[b].  d_s_pred / d_ref_s: float [batch][>= 256], the given floats apart.  d_logits:
+ * element (b, n, c) at b item_stride + n token_stride + c channel_stride, channels <= 64; total_frames / statuses (may be NULL) receive
+ * the slabs of the same names.  d_d: float [batch][tokens][d_row_stride >= d_channels]; d_t_en: float [batch][asr_channels]
+ * [t_row_stride >= tokens]; d_en float[batch][d_channels][frame_stride], d_asr float[batch][asr_channels][frame_stride], frame_stride at
+ * least every accepted item's total.  finish: d_audio float[batch][row_stride], lengths[b] samples of row b are valid; out_offsets
+ * (batch + 1, written) says where item b lies in d_out. */
+fa_status fa_styletts2_reference_mel_dev(fa_ctx *ctx, fa_styletts2_session *s, const float *d_pcm, const int64_t *offsets);
+fa_status fa_styletts2_inputs_dev(fa_ctx *ctx, fa_styletts2_session *s, const int32_t *d_token_ids, const int64_t *token_offsets, const uint64_t *seeds);
+fa_status fa_styletts2_blend_dev(fa_ctx *ctx, fa_styletts2_session *s, const float *d_s_pred, int64_t s_pred_stride, const float *d_ref_s, int64_t ref_s_stride,
+                                 const float *alphas, const float *betas);
+fa_status fa_styletts2_durations_dev(fa_ctx *ctx, fa_styletts2_session *s, const float *d_logits, int32_t channels, int64_t item_stride, int64_t token_stride, int64_t channel_stride,
+                                     int32_t *total_frames, int32_t *statuses);
+fa_status fa_styletts2_align_dev(fa_ctx *ctx, fa_styletts2_session *s, const float *d_d, int64_t d_row_stride, int64_t d_item_stride, const float *d_t_en, int64_t t_row_stride,
+                                 int64_t t_item_stride, int32_t shift, float *d_en, float *d_asr, int32_t frame_stride);
+fa_status fa_styletts2_finish_dev(fa_ctx *ctx, fa_styletts2_session *s, const float *d_audio, int64_t row_stride, const int64_t *lengths, float *d_out, int64_t *out_offsets);
+/* The same with host pointers: upload, run, fetch (en, asr, out), one synchronisation each.  finish: out holds out_capacity floats. */
+fa_status fa_styletts2_reference_mel(fa_ctx *ctx, fa_styletts2_session *s, const float *pcm, const int64_t *offsets);
+fa_status fa_styletts2_inputs(fa_ctx *ctx, fa_styletts2_session *s, const int32_t *token_ids, const int64_t *token_offsets, const uint64_t *seeds);
+fa_status fa_styletts2_blend(fa_ctx *ctx, fa_styletts2_session *s, const float *s_pred, int64_t s_pred_stride, const float *ref_s, int64_t ref_s_stride, const float *alphas,
+                             const float *betas);
+fa_status fa_styletts2_durations(fa_ctx *ctx, fa_styletts2_session *s, const float *logits, int32_t channels, int64_t item_stride, int64_t token_stride, int64_t channel_stride,
+                                 int32_t *total_frames, int32_t *statuses);
+fa_status fa_styletts2_align(fa_ctx *ctx, fa_styletts2_session *s, const float *d, int64_t d_row_stride, int64_t d_item_stride, const float *t_en, int64_t t_row_stride,
+                             int64_t t_item_stride, int32_t shift, float *en, float *asr, int32_t frame_stride);
+fa_status fa_styletts2_finish(fa_ctx *ctx, fa_styletts2_session *s, const float *audio, int64_t row_stride, const int64_t *lengths, float *out, int64_t out_capacity,
+                              int64_t *out_offsets);
+
 /* ------------------------------------------------------------------ argmax / CTC ---- */
 /* Replaces LogitsArgmax.argmaxPerFrame (FluidAudio/ASR/Shared/LogitsArgmax.swift:16-55) and the
  * greedy collapse of ctcGreedyDecode (FluidAudio/ASR/Parakeet/SlidingWindow/CTC/CtcDecoder.swift:15-36,
