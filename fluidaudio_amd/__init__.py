@@ -21,6 +21,7 @@ from .lseend import (LseendFeatures, LseendStream, lseend_config, lseend_feature
                      lseend_plan_file, lseend_plan_push)
 from .luxtts import (LuxTtsSession, luxtts_anchor_euler, luxtts_config, luxtts_plan, luxtts_prompt_loudness,  # noqa: F401
                      luxtts_time_steps)
+from .pockettts import PocketTtsSession, pockettts_clone_plan, pockettts_config  # noqa: F401
 from .styletts2 import (StyleTts2Session, styletts2_config, styletts2_filterbank, styletts2_karras_sigmas, styletts2_plan,  # noqa: F401
                         styletts2_window)
 from .formats import AudioWAV, RTTMParser, RTTMParserError, TimedSpeakerSegment, export_embeddings_json  # noqa: F401

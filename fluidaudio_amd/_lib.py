@@ -99,6 +99,11 @@ EXPORTED_SYMBOLS = [
     "fa_styletts2_session_destroy", "fa_styletts2_session_slabs", "fa_styletts2_session_begin", "fa_styletts2_session_get", "fa_styletts2_reference_mel_dev",
     "fa_styletts2_inputs_dev", "fa_styletts2_blend_dev", "fa_styletts2_durations_dev", "fa_styletts2_align_dev", "fa_styletts2_finish_dev", "fa_styletts2_reference_mel",
     "fa_styletts2_inputs", "fa_styletts2_blend", "fa_styletts2_durations", "fa_styletts2_align", "fa_styletts2_finish",
+    "fa_pockettts_default_config", "fa_pockettts_clone_plan", "fa_pockettts_session_create", "fa_pockettts_session_destroy", "fa_pockettts_session_slabs",
+    "fa_pockettts_session_get", "fa_pockettts_session_put", "fa_pockettts_projection_set", "fa_pockettts_constants_set", "fa_pockettts_voice_add",
+    "fa_pockettts_encoder_input_dev", "fa_pockettts_encoder_input", "fa_pockettts_clone_dev", "fa_pockettts_clone", "fa_pockettts_kv_reset", "fa_pockettts_kv_capture",
+    "fa_pockettts_plan", "fa_pockettts_prefill_inputs", "fa_pockettts_position_set", "fa_pockettts_step_begin", "fa_pockettts_step_dev", "fa_pockettts_step",
+    "fa_pockettts_append_audio_dev", "fa_pockettts_append_audio",
 ]
 
 
@@ -171,6 +176,20 @@ class StyleTts2ItemPlan(C.Structure):                                  # fa_styl
 
 class StyleTts2Slabs(C.Structure):                                     # fa_styletts2_slabs: device addresses
     _fields_ = [(name, C.c_void_p) for name in ("mel", "tokens", "attention_mask", "noise_init", "noises_aux", "ref", "s", "durations", "starts", "total_frames", "status")]
+
+
+class PocketTtsConfig(C.Structure):                                    # fa_pockettts_config
+    _fields_ = [(name, C.c_int32) for name in ("layers", "kv_format", "streams", "voices", "voice_seq", "projections", "vocab", "windows", "clones", "max_frames",
+                                               "bos_sequence")]
+
+
+class PocketTtsWindow(C.Structure):                                    # fa_pockettts_window
+    _fields_ = [(name, C.c_int32) for name in ("stream", "block", "first", "n", "voice", "ids_at", "before", "pad")]
+
+
+class PocketTtsSlabs(C.Structure):                                     # fa_pockettts_slabs: device addresses
+    _fields_ = [(name, C.c_void_p) for name in ("kv", "positions", "voice_rows", "voice_kv", "encoder_input", "windows", "valid_len", "window_position", "sequence",
+                                                "state", "running", "n_running", "audio")]
 
 
 class TdtConfig(C.Structure):
@@ -602,6 +621,27 @@ def lib() -> C.CDLL:
         getattr(L, name).argtypes = getattr(L, name + "_dev").argtypes = args              # the host-pointer form and its device form take the same list
     L.fa_styletts2_finish.argtypes = [vp, vp, vp, i64, vp, vp, i64, vp]
     L.fa_styletts2_finish_dev.argtypes = [vp, vp, vp, i64, vp, vp, vp]
+    pc = C.POINTER(PocketTtsConfig)
+    L.fa_pockettts_default_config.argtypes = [pc]
+    L.fa_pockettts_default_config.restype = None
+    L.fa_pockettts_clone_plan.argtypes = [i32, vp, vp, vp, vp]
+    L.fa_pockettts_session_create.argtypes = [vp, pc, C.POINTER(vp)]
+    L.fa_pockettts_session_destroy.argtypes = [vp]
+    L.fa_pockettts_session_destroy.restype = None
+    L.fa_pockettts_session_slabs.argtypes = [vp, C.POINTER(PocketTtsSlabs)]
+    L.fa_pockettts_session_get.argtypes = L.fa_pockettts_session_put.argtypes = [vp, vp, i32, i64, i64, vp]
+    L.fa_pockettts_projection_set.argtypes = [vp, vp, i32, vp, vp]
+    L.fa_pockettts_constants_set.argtypes = [vp, vp, vp, vp, vp, i32]
+    L.fa_pockettts_voice_add.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp]
+    L.fa_pockettts_kv_reset.argtypes = [vp, vp, i32, vp, vp]
+    L.fa_pockettts_kv_capture.argtypes = [vp, vp, i32, i32, i32]
+    L.fa_pockettts_plan.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+    L.fa_pockettts_prefill_inputs.argtypes = [vp, vp, vp]
+    L.fa_pockettts_position_set.argtypes = [vp, vp, i32, f32]
+    L.fa_pockettts_step_begin.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+    for name, args in {"fa_pockettts_encoder_input": [vp, vp, i32, vp, vp, vp, vp], "fa_pockettts_clone": [vp, vp, i32, vp, vp, vp, vp, i32, i64, i64, i64],
+                       "fa_pockettts_step": [vp, vp, vp, vp], "fa_pockettts_append_audio": [vp, vp, vp]}.items():
+        getattr(L, name).argtypes = getattr(L, name + "_dev").argtypes = args              # the host-pointer form and its device form take the same list
     L.fa_ctc_greedy_batch_dev.argtypes = [vp, vp, i32, i32, i32, i32, i64, i64, vp, i32, vp, vp, vp]
     L.fa_ctc_log_softmax_batch_dev.argtypes = [vp, vp, i32, i32, i32, i32, i64, i64, f32, f32, i32, vp]
     L.fa_ctc_greedy_batch.argtypes = [vp, vp, i32, i32, i32, i32, i64, i64, vp, i32, vp, vp, vp]

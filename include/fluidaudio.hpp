@@ -2511,4 +2511,86 @@ class StyleTts2Session {
     fa_styletts2_session *s_ = nullptr;
 };
 
+// The PocketTTS session (PocketTtsVoiceCloner, PocketTtsSynthesizer+KVCache, PocketTtsStateEngine, the generation loop of
+// PocketTtsSynthesizer): the streams' KV caches, the voice table, the prefill windows and the loop's scalars stay in HBM.  d* are device
+// pointers, vectors are host data; lists that go together have one length.  No call waits for the device.
+class PocketTtsSession {
+  public:
+    static fa_pockettts_config defaultConfig() { fa_pockettts_config c; fa_pockettts_default_config(&c); return c; }
+    PocketTtsSession(Context &ctx, const fa_pockettts_config &cfg) : ctx_(ctx) {
+        ctx_.check(fa_pockettts_session_create(ctx_.handle(), &cfg, &s_), "fa_pockettts_session_create");
+    }
+    ~PocketTtsSession() { fa_pockettts_session_destroy(s_); }
+    PocketTtsSession(const PocketTtsSession &) = delete;
+    PocketTtsSession &operator=(const PocketTtsSession &) = delete;
+    fa_pockettts_slabs slabs() const { fa_pockettts_slabs out{}; fa_pockettts_session_slabs(s_, &out); return out; }
+    void setProjection(int32_t index, const std::vector<float> &pinv, const std::vector<float> &w) {
+        if (pinv.size() != 1024 * 32 || w.size() != 1024 * 32) throw Error(FA_INVALID_ARGUMENT, "PocketTtsSession::setProjection", "two matrices of 1024 x 32");
+        ctx_.check(fa_pockettts_projection_set(ctx_.handle(), s_, index, pinv.data(), w.data()), "fa_pockettts_projection_set");
+    }
+    // bosBeforeVoice / bosEmbedding may be empty (the pack has none)
+    void setConstants(const std::vector<float> &bosBeforeVoice, const std::vector<float> &bosEmbedding, const std::vector<float> &table) {
+        if ((!bosBeforeVoice.empty() && bosBeforeVoice.size() != 1024) || (!bosEmbedding.empty() && bosEmbedding.size() != 32) || table.size() % 1024)
+            throw Error(FA_INVALID_ARGUMENT, "PocketTtsSession::setConstants", "1024, 32 and vocab x 1024 floats");
+        ctx_.check(fa_pockettts_constants_set(ctx_.handle(), s_, bosBeforeVoice.empty() ? nullptr : bosBeforeVoice.data(), bosEmbedding.empty() ? nullptr : bosEmbedding.data(),
+                                              table.data(), static_cast<int32_t>(table.size() / 1024)), "fa_pockettts_constants_set");
+    }
+    // a shipped voice: the layers' caches back to back; returns FA_POCKETTTS_* (a refused voice leaves the slot empty)
+    int32_t addVoice(int32_t voice, int32_t srcSeq, const std::vector<float> &caches, const std::vector<int64_t> &floatCounts, const std::vector<int64_t> &offsets) {
+        same(floatCounts.size(), offsets.size(), "PocketTtsSession::addVoice");
+        int32_t status = 0;
+        ctx_.check(fa_pockettts_voice_add(ctx_.handle(), s_, voice, static_cast<int32_t>(offsets.size()), srcSeq, caches.data(), floatCounts.data(), offsets.data(), &status),
+                   "fa_pockettts_voice_add");
+        return status;
+    }
+    // clips -> the encoder's rows; usable and statuses per clip
+    std::vector<int32_t> encoderInput(const float *dPcm, const std::vector<int64_t> &offsets, std::vector<int32_t> &statuses) {
+        const size_t n = offsets.empty() ? 0 : offsets.size() - 1;
+        std::vector<int32_t> usable(n);
+        statuses.resize(n);
+        ctx_.check(fa_pockettts_encoder_input_dev(ctx_.handle(), s_, static_cast<int32_t>(n), dPcm, offsets.data(), usable.data(), statuses.data()), "fa_pockettts_encoder_input_dev");
+        return usable;
+    }
+    void clone(const std::vector<int32_t> &voices, const std::vector<int32_t> &projections, const std::vector<int32_t> &usable, const void *dCond, int32_t dtype, int64_t itemStride,
+               int64_t frameStride, int64_t dimStride) {
+        same(voices.size(), projections.size(), "PocketTtsSession::clone"); same(voices.size(), usable.size(), "PocketTtsSession::clone");
+        ctx_.check(fa_pockettts_clone_dev(ctx_.handle(), s_, static_cast<int32_t>(voices.size()), voices.data(), projections.data(), usable.data(), dCond, dtype, itemStride, frameStride,
+                                          dimStride), "fa_pockettts_clone_dev");
+    }
+    void kvReset(const std::vector<int32_t> &streams, const std::vector<int32_t> &voices) {
+        same(streams.size(), voices.size(), "PocketTtsSession::kvReset");
+        ctx_.check(fa_pockettts_kv_reset(ctx_.handle(), s_, static_cast<int32_t>(streams.size()), streams.data(), voices.data()), "fa_pockettts_kv_reset");
+    }
+    void kvCapture(int32_t stream, int32_t voice, int32_t seq) { ctx_.check(fa_pockettts_kv_capture(ctx_.handle(), s_, stream, voice, seq), "fa_pockettts_kv_capture"); }
+    // the windows of the listed streams (host only); statuses receives FA_POCKETTTS_* per stream
+    std::vector<fa_pockettts_window> plan(const std::vector<int32_t> &streams, const std::vector<int32_t> &voices, const std::vector<int32_t> &tokenCounts, std::vector<int32_t> &statuses,
+                                          int32_t capacity) {
+        same(streams.size(), voices.size(), "PocketTtsSession::plan"); same(streams.size(), tokenCounts.size(), "PocketTtsSession::plan");
+        std::vector<fa_pockettts_window> windows(static_cast<size_t>(capacity > 0 ? capacity : 0));   // capacity: the configuration's `windows`
+        statuses.resize(streams.size());
+        int32_t n = 0;
+        ctx_.check(fa_pockettts_plan(s_, static_cast<int32_t>(streams.size()), streams.data(), voices.data(), tokenCounts.data(), &n, windows.data(), statuses.data()), "fa_pockettts_plan");
+        windows.resize(static_cast<size_t>(n));
+        return windows;
+    }
+    void prefillInputs(const std::vector<int32_t> &tokenIds) { ctx_.check(fa_pockettts_prefill_inputs(ctx_.handle(), s_, tokenIds.data()), "fa_pockettts_prefill_inputs"); }
+    void setPosition(int32_t stream, float position) { ctx_.check(fa_pockettts_position_set(ctx_.handle(), s_, stream, position), "fa_pockettts_position_set"); }
+    std::vector<int32_t> stepBegin(const std::vector<int32_t> &streams, const std::vector<int32_t> &maxGenLen, const std::vector<int32_t> &framesAfterEos) {
+        same(streams.size(), maxGenLen.size(), "PocketTtsSession::stepBegin"); same(streams.size(), framesAfterEos.size(), "PocketTtsSession::stepBegin");
+        std::vector<int32_t> statuses(streams.size());
+        ctx_.check(fa_pockettts_step_begin(ctx_.handle(), s_, static_cast<int32_t>(streams.size()), streams.data(), maxGenLen.data(), framesAfterEos.data(), statuses.data()),
+                   "fa_pockettts_step_begin");
+        return statuses;
+    }
+    void step(const float *dEosLogit, const float *dLatent) { ctx_.check(fa_pockettts_step_dev(ctx_.handle(), s_, dEosLogit, dLatent), "fa_pockettts_step_dev"); }
+    void appendAudio(const float *dSamples) { ctx_.check(fa_pockettts_append_audio_dev(ctx_.handle(), s_, dSamples), "fa_pockettts_append_audio_dev"); }
+
+  private:
+    static void same(size_t a, size_t b, const char *where) {
+        if (a != b) throw Error(FA_INVALID_ARGUMENT, where, "the lists of one call have one length");
+    }
+    Context &ctx_;
+    fa_pockettts_session *s_ = nullptr;
+};
+
 }  // namespace fluidaudio

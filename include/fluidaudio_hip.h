@@ -612,6 +612,126 @@ fa_status fa_styletts2_align(fa_ctx *ctx, fa_styletts2_session *s, const float *
 fa_status fa_styletts2_finish(fa_ctx *ctx, fa_styletts2_session *s, const float *audio, int64_t row_stride, const int64_t *lengths, float *out, int64_t out_capacity,
                               int64_t *out_offsets);
 
+/* ------------------------------------------------------------------ PocketTTS session */
+/* The host work of PocketTTS round its networks (FluidAudio/TTS/PocketTTS/Pipeline/PocketTtsVoiceCloner.swift,
+ * PocketTtsSynthesizer+KVCache.swift, PocketTtsStateEngine.swift, PocketTtsSynthesizer.swift, PocketTtsConstants.swift), for `streams`
+ * concurrent streams on device slabs the networks read and write in place.  Fixed by the model: embedding width 1024, latent width 32,
+ * prefill windows of 256 tokens, a KV cache of 512 x 16 x 64 per layer and side, EOS threshold -4, 2 extra frames after detection, 1920
+ * samples a frame, 240 000 encoder samples, at most 125 voice frames.  The networks, the tokenizer, text normalisation and chunking,
+ * audio file loading, generatePipelined's scheduling and the start noise z_0 (the caller supplies latent_init) stay the caller's.
+ *   clone      encoder rows: a clip truncated or zero-padded to 240 000 samples; a clip under 1 s is FA_POCKETTTS_CLIP_TOO_SHORT; usable =
+ *              min(available, ceil(min(samples, 240 000) / 1920), 125).  Voice rows: out[f, :] = (cond[f, :] Pinv) W^T for f < usable,
+ *              cond the encoder's [B, frames, 1024] output in fp32 or fp16 with frame and dim strides, Pinv and W [1024, 32] row-major
+ *              of the item's projection; projection -1 stores the extracted (widened) rows unchanged.  fp32 matrix instructions, the
+ *              sums in a fixed order; rows from usable on are not written.
+ *   voices     a shipped voice: per layer [2, 1, srcSeq, 16, 64] fp32 (K then V) and an offset; the guards of kvCacheStateFromSnapshot
+ *              are statuses.  A cloned voice: the rows above and promptLength = usable.
+ *   kv_reset   each listed stream's cache from its voice's snapshot: rows below srcSeq copied (fp16: round to nearest even), zeros up
+ *              to 512, in one launch; positions = the layers' offsets (fp16: layer 0's, one position).  A voice without a snapshot
+ *              gives zeros and position 0.  kv_capture stores rows [0, seq) of a stream's cache and its positions as the voice's snapshot.
+ *   prefill    per stream the voice block [bos_before_voice, voice rows] (cloned voices without a snapshot, promptLength > 0), then the
+ *              text block table[clamp(id, 0, vocab - 1)], each cut into windows of at most 256 rows, zero rows behind; valid_len = n,
+ *              window_position = the stream's position before the window; the stream's positions advance by its rows.
+ *   step       per running stream, in the reference's order: a first eosLogit > -4 sets eos_step; step >= eos_step + frames_after_eos
+ *              + 2 ends the stream (FA_POCKETTTS_END_EOS) before this step's frame; otherwise emit = 1, sequence <- latent, positions
+ *              + 1, frames + 1, and reaching max_gen_len ends it (FA_POCKETTTS_END_MAX_LEN).  running / n_running: the streams still
+ *              running, ascending.  append_audio copies an emitting stream's 1920 samples to row frames - 1 of its audio slab. */
+typedef struct {
+    int32_t layers;              /* 6 (1..24) */
+    int32_t kv_format;           /* FA_POCKETTTS_KV_* */
+    int32_t streams;             /* 4 */
+    int32_t voices;              /* 4: slots of the voice table */
+    int32_t voice_seq;           /* 512: positions a voice's snapshot may hold (<= 512) */
+    int32_t projections;         /* 2: slots of the projection table (may be 0) */
+    int32_t vocab;               /* 4001: rows the text embedding table may hold */
+    int32_t windows;             /* 16: prefill windows of one plan */
+    int32_t clones;              /* 4: clips of one clone call */
+    int32_t max_frames;          /* 256: frames of a stream's audio slab */
+    int32_t bos_sequence;        /* 0: step_begin writes NaNs; 1: the BOS latent (split-KV and fused models) */
+} fa_pockettts_config;
+enum { FA_POCKETTTS_KV_COMBINED = 0 /* fp32 [2, 1, 512, 16, 64] per (stream, layer) */, FA_POCKETTTS_KV_SPLIT = 1 /* fp32 K slab, then V slab */,
+       FA_POCKETTTS_KV_FP16 = 2 /* as split, in fp16 */ };
+enum { FA_POCKETTTS_OK = 0, FA_POCKETTTS_CLIP_TOO_SHORT = 1, FA_POCKETTTS_LAYER_COUNT = 2, FA_POCKETTTS_SEQ_TOO_LONG = 3, FA_POCKETTTS_FLOAT_COUNT = 4,
+       FA_POCKETTTS_NO_BOS_BEFORE_VOICE = 5, FA_POCKETTTS_NO_VOICE = 6, FA_POCKETTTS_TOO_MANY_WINDOWS = 7, FA_POCKETTTS_TOO_MANY_FRAMES = 8 };
+enum { FA_POCKETTTS_IDLE = 0, FA_POCKETTTS_RUNNING = 1, FA_POCKETTTS_END_EOS = 2, FA_POCKETTTS_END_MAX_LEN = 3 };
+typedef struct {
+    int32_t stream, block, first, n;     /* block 0: voice, 1: text; rows [first, first + n) of the block */
+    int32_t voice, ids_at, before, pad;  /* the voice; the stream's first token id; rows of this plan in front of the window */
+} fa_pockettts_window;
+typedef struct {
+    int32_t step, eos_step, max_gen, after, frames, reason, emit, pad;
+} fa_pockettts_stream_state;
+typedef struct {                 /* DEVICE pointers, fixed for the session's lifetime; L layers, S streams, P = 1 (fp16) or L positions */
+    void *kv;                    /* combined: [S][L][2][512*1024] fp32; split / fp16: [2][S][L][512*1024] */
+    float *positions;            /* [S][P] */
+    float *voice_rows;           /* [voices][125][1024] */
+    float *voice_kv;             /* [voices][L][2][voice_seq*1024] */
+    float *encoder_input;        /* [clones][240000] */
+    float *windows;              /* [windows][256][1024] */
+    float *valid_len;            /* [windows] */
+    float *window_position;      /* [windows] */
+    float *sequence;             /* [S][32] */
+    fa_pockettts_stream_state *state;   /* [S] */
+    int32_t *running;            /* [S], the first n_running[0] entries */
+    int32_t *n_running;          /* [1] */
+    float *audio;                /* [S][max_frames][1920] */
+} fa_pockettts_slabs;
+enum { FA_POCKETTTS_SLAB_KV = 0, FA_POCKETTTS_SLAB_POSITIONS = 1, FA_POCKETTTS_SLAB_VOICE_ROWS = 2, FA_POCKETTTS_SLAB_VOICE_KV = 3,
+       FA_POCKETTTS_SLAB_ENCODER_INPUT = 4, FA_POCKETTTS_SLAB_WINDOWS = 5, FA_POCKETTTS_SLAB_VALID_LEN = 6, FA_POCKETTTS_SLAB_WINDOW_POSITION = 7,
+       FA_POCKETTTS_SLAB_SEQUENCE = 8, FA_POCKETTTS_SLAB_STATE = 9, FA_POCKETTTS_SLAB_RUNNING = 10, FA_POCKETTTS_SLAB_N_RUNNING = 11,
+       FA_POCKETTTS_SLAB_AUDIO = 12 };
+void fa_pockettts_default_config(fa_pockettts_config *cfg);
+/* Pure host function: per clip the status and the usable frame count out of `available` encoder frames. */
+fa_status fa_pockettts_clone_plan(int32_t n, const int64_t *samples, const int32_t *available, int32_t *usable, int32_t *statuses);
+/* The session owns the slabs; after creation nothing is allocated, and no entry below waits for the device but session_get and the
+ * host-pointer forms.  Host arrays are copied (or queued from pageable memory) before an entry returns. */
+typedef struct fa_pockettts_session fa_pockettts_session;
+fa_status fa_pockettts_session_create(fa_ctx *ctx, const fa_pockettts_config *cfg, fa_pockettts_session **out);
+void fa_pockettts_session_destroy(fa_pockettts_session *s);
+fa_status fa_pockettts_session_slabs(fa_pockettts_session *s, fa_pockettts_slabs *out);
+/* `bytes` of a slab (FA_POCKETTTS_SLAB_*) from byte `offset` on, to / from host memory; get synchronises the stream. */
+fa_status fa_pockettts_session_get(fa_ctx *ctx, fa_pockettts_session *s, int32_t slab, int64_t offset, int64_t bytes, void *out);
+fa_status fa_pockettts_session_put(fa_ctx *ctx, fa_pockettts_session *s, int32_t slab, int64_t offset, int64_t bytes, const void *src);
+/* Uploads, once each: projection `index` (pinv, w: float [1024][32]); the constants: bos_before_voice float[1024] (NULL: the pack has
+ * none), bos_embedding float[32] (NULL: zeros), the text embedding table float[vocab][1024] (the vocabulary size is this table's). */
+fa_status fa_pockettts_projection_set(fa_ctx *ctx, fa_pockettts_session *s, int32_t index, const float *pinv, const float *w);
+fa_status fa_pockettts_constants_set(fa_ctx *ctx, fa_pockettts_session *s, const float *bos_before_voice, const float *bos_embedding, const float *table, int32_t vocab);
+/* A shipped voice into slot `voice`: caches = the layers' [2][src_seq][1024] floats back to back, float_counts / offsets per layer.
+ * *status (FA_POCKETTTS_*) says what refused it; a refused voice leaves the slot empty. */
+fa_status fa_pockettts_voice_add(fa_ctx *ctx, fa_pockettts_session *s, int32_t voice, int32_t layers, int32_t src_seq, const float *caches, const int64_t *float_counts,
+                                 const int64_t *offsets, int32_t *status);
+/* Clip b = pcm[offsets[b], offsets[b + 1]) -> encoder_input row b; statuses / usable as fa_pockettts_clone_plan with available = 125. */
+fa_status fa_pockettts_encoder_input_dev(fa_ctx *ctx, fa_pockettts_session *s, int32_t n, const float *d_pcm, const int64_t *offsets, int32_t *usable, int32_t *statuses);
+fa_status fa_pockettts_encoder_input(fa_ctx *ctx, fa_pockettts_session *s, int32_t n, const float *pcm, const int64_t *offsets, int32_t *usable, int32_t *statuses);
+/* n clones in one launch: item b's conditioning element (f, d) at d_cond + b item_stride + f frame_stride + d dim_stride (elements of
+ * dtype FA_DTYPE_F32 / FA_DTYPE_F16), usable[b] <= 125 frames of it into voice slot voices[b] through projection projections[b] (-1:
+ * none).  The slot becomes a cloned voice with promptLength usable[b] and no snapshot. */
+fa_status fa_pockettts_clone_dev(fa_ctx *ctx, fa_pockettts_session *s, int32_t n, const int32_t *voices, const int32_t *projections, const int32_t *usable, const void *d_cond,
+                                 int32_t dtype, int64_t item_stride, int64_t frame_stride, int64_t dim_stride);
+fa_status fa_pockettts_clone(fa_ctx *ctx, fa_pockettts_session *s, int32_t n, const int32_t *voices, const int32_t *projections, const int32_t *usable, const void *cond,
+                             int32_t dtype, int64_t item_stride, int64_t frame_stride, int64_t dim_stride);
+/* streams[i]'s cache and positions from voices[i]; kv_capture: rows [0, seq) of `stream`'s cache and its positions become voice's snapshot. */
+fa_status fa_pockettts_kv_reset(fa_ctx *ctx, fa_pockettts_session *s, int32_t n, const int32_t *streams, const int32_t *voices);
+fa_status fa_pockettts_kv_capture(fa_ctx *ctx, fa_pockettts_session *s, int32_t stream, int32_t voice, int32_t seq);
+/* Host only: the windows of streams[i] with voices[i] and token_counts[i] text tokens, kept by the session for prefill_inputs.  statuses[i]
+ * refuses a stream (it gets no window); windows (may be NULL) holds the config's `windows` records, *n_windows of them written. */
+fa_status fa_pockettts_plan(fa_pockettts_session *s, int32_t n, const int32_t *streams, const int32_t *voices, const int32_t *token_counts, int32_t *n_windows,
+                            fa_pockettts_window *windows, int32_t *statuses);
+/* Fills the planned windows; token_ids: the accepted and refused streams' ids back to back in plan order (token_counts[i] each). */
+fa_status fa_pockettts_prefill_inputs(fa_ctx *ctx, fa_pockettts_session *s, const int32_t *token_ids);
+/* A network that reports new_position overrides the stream's positions. */
+fa_status fa_pockettts_position_set(fa_ctx *ctx, fa_pockettts_session *s, int32_t stream, float position);
+/* streams[i] starts a chunk: sequence, the EOS machine with max_gen_len[i] = Int((words + 2) * 12.5) and frames_after_eos[i].  statuses
+ * (may be NULL): FA_POCKETTTS_TOO_MANY_FRAMES leaves the stream idle. */
+fa_status fa_pockettts_step_begin(fa_ctx *ctx, fa_pockettts_session *s, int32_t n, const int32_t *streams, const int32_t *max_gen_len, const int32_t *frames_after_eos,
+                                  int32_t *statuses);
+/* One generation step of every stream: d_eos_logit float[S], d_latent float[S][32], indexed by stream; idle and ended streams are not read. */
+fa_status fa_pockettts_step_dev(fa_ctx *ctx, fa_pockettts_session *s, const float *d_eos_logit, const float *d_latent);
+fa_status fa_pockettts_step(fa_ctx *ctx, fa_pockettts_session *s, const float *eos_logit, const float *latent);
+/* d_samples float[S][1920], indexed by stream: the frame of every stream whose last step emitted. */
+fa_status fa_pockettts_append_audio_dev(fa_ctx *ctx, fa_pockettts_session *s, const float *d_samples);
+fa_status fa_pockettts_append_audio(fa_ctx *ctx, fa_pockettts_session *s, const float *samples);
+
 /* ------------------------------------------------------------------ argmax / CTC ---- */
 /* Replaces LogitsArgmax.argmaxPerFrame (FluidAudio/ASR/Shared/LogitsArgmax.swift:16-55) and the
  * greedy collapse of ctcGreedyDecode (FluidAudio/ASR/Parakeet/SlidingWindow/CTC/CtcDecoder.swift:15-36,
